@@ -13,14 +13,16 @@ extract_3Dpoints, EPnP PnP-RANSAC + refit, pose inversion, on one synthetic 1920
 timed region.  With N ranks every rank runs its own independent stream (configs[4]; weak scaling)
 and the per-step pose records are all-gathered over RCCL at the end of the timed region.
 
-The timed region of the contract -- fence, exactly K steps, gather, fence -- is run `--blocks` (7) times in a row in the same
-process; `value` / `ms_per_step` are the MEDIAN block's (MAX over ranks per block), the first / slowest / fastest block and every
-block's rate are listed beside it, with the gaps between consecutive collects (`collect_gap_ms`) and, for K <= 64, the device and
-host timestamps of every pair's phases (`pipeline_trace`), so that a stall inside one 10 ms window shows where it was.
+A plain run sets up, warms up, times the timed region -- fence, exactly K steps, gather, fence -- once, and prints ONE JSON line
+on rank 0: `value` (pairs/s), `ms_per_step` (MAX over ranks) and the gaps between consecutive collects (`collect_gap_ms`).
+`--dump-outputs DIR` then also writes what the last timed step returned (dump_outputs below).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` for the dominant
-kernel (k_hessian_nms_all: algorithmic bytes of SURVEY.md 8(d) / HIP-event time measured here)
-and `cpu_baseline` (the CPU oracle, 1 thread, on a bounded sample of the same workload).
+`--full` adds everything else the benchmark measures: the timed region run `--blocks` (7) times in a row in the same process
+(`value` / `ms_per_step` are then the MEDIAN block's, the first / slowest / fastest block and every block's rate are listed beside
+it) and, for K <= 64, the device and host timestamps of every pair's phases (`pipeline_trace`), so that a stall inside one 10 ms
+window shows where it was; the upload-inclusive rate, the synchronous step latency, `roofline` for the dominant kernel
+(k_hessian_nms_all: algorithmic bytes of SURVEY.md 8(d) / HIP-event time measured here, HBM traffic from rocprofv3 counter passes)
+and `cpu_baseline` (the CPU oracle, 1 thread, on a bounded sample of the same workload) with the parity of both paths.
 """
 from __future__ import annotations
 
@@ -216,6 +218,32 @@ def hbm_copy_peak_gbs(torch, seconds: float = 0.05, nbytes: int = 1 << 30) -> fl
     return 2.0 * nbytes * reps / (ms * 1e-3) / 1e9
 
 
+STEREO_OUTPUTS = ("kps_left", "kps_right", "desc_left", "desc_right", "matches_stereo", "matches_tri", "points4d", "good_pts",
+                  "good_idx", "inliers")
+
+
+def dump_outputs(out_dir: str, result, stereo_get) -> list[str]:
+    """What a caller of the timed path receives for its last pair, as DIR/<name>.npy in float32 / float64: the fields of the
+    uvo_stereo_result from uvo_stereo_collect (`counts`: valid, initialized and the six counts; the pose vectors) and the pair's
+    intermediates that uvo_stereo_get hands out right after that collect (structured rows become float64 columns in field order).
+    A few MB at 1080p.  -> the names written."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"counts": np.array([getattr(result, f) for f in ("valid", "initialized", "n_left", "n_right", "n_stereo_matches",
+                                                               "n_tri_matches", "n_good3d", "n_inliers")], np.float64)}
+    for f in ("rvec", "tvec", "t_prev_curr", "velocity"):
+        arrays[f] = np.array(list(getattr(result, f)), np.float64)
+    for what in STEREO_OUTPUTS:
+        a = stereo_get(what)
+        if a.dtype.names:
+            a = np.stack([a[n].astype(np.float64) for n in a.dtype.names], axis=-1).reshape(len(a), len(a.dtype.names))
+        elif a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        arrays[what] = a
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    return list(arrays)
+
+
 _REAL_STDOUT = None
 
 
@@ -249,7 +277,11 @@ def main():
                     help="pairs per launch set (uvo_stereo_set_batch): 2 = consecutive pairs of the stream are queued two at a time")
     ap.add_argument("--cpu-seconds", type=float, default=20.0, help="budget of the CPU-oracle baseline leg")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pmc", action="store_true", help="do not run the two rocprofv3 counter passes behind roofline.traffic (rank 0 at N = 1 runs them "
+    ap.add_argument("--full", action="store_true", help="measure everything, not only the headline: seven timed blocks, the pipeline trace, the "
+                    "upload-inclusive, latency and roofline legs, the rocprofv3 counter passes, the CPU-oracle baseline and the parity check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="rank 0 writes what the last timed step returned (result fields and "
+                    "the pair's intermediates) to DIR/<name>.npy")
+    ap.add_argument("--no-pmc", action="store_true", help="do not run the two rocprofv3 counter passes behind roofline.traffic (with --full, rank 0 at N = 1 runs them "
                     "before its first GPU call, ~40 s; without them the figure of the newest matching committed counter summary is reported)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="collective backend of the pose-record gather "
                     "(nccl = RCCL; gloo only for rehearsing N ranks on fewer devices)")
@@ -259,8 +291,8 @@ def main():
     ap.add_argument("--no-pin", action="store_true", help="do not pin the rank to the cores next to its GPU")
     ap.add_argument("--cpus", type=int, default=0, help="measurement: confine this rank to N logical CPUs (sched_setaffinity before the first GPU "
                     "call, whole physical cores next to the GPU first) and tell the library that N is its CPU budget")
-    ap.add_argument("--blocks", type=int, default=7, help="the timed region (K steps between two fences) is run this many times in a row; "
-                    "`value` is the median block, the first / slowest / fastest are reported beside it")
+    ap.add_argument("--blocks", type=int, default=None, help="the timed region (K steps between two fences) is run this many times in a row "
+                    "(default 1, with --full 7); `value` is the median block, the first / slowest / fastest are reported beside it")
     ap.add_argument("--no-trace", action="store_true", help="do not record the per-pair pipeline trace (for --steps <= 64 one more, untimed-for-value block runs with it)")
     ap.add_argument("--trace-all", action="store_true", help="trace every timed block instead (costs the 20-step form ~2.4 %%)")
     ap.add_argument("--timed-only", action="store_true", help="diagnostics: stop after the timed region (no latency / roofline / CPU legs), "
@@ -272,8 +304,8 @@ def main():
 
     # roofline.traffic from the counters, measured in this run: child passes, before this process touches the GPU (rank 0 at N = 1, the
     # run that also carries the CPU baseline)
-    pmc_traffic, pmc_details = None, {"skipped": "not requested for this form (--no-pmc / --no-cpu-baseline / --timed-only / N > 1)"}
-    if args.gpus == 1 and "WORLD_SIZE" not in os.environ and not (args.no_pmc or args.no_cpu_baseline or args.timed_only or args.force_dist):
+    pmc_traffic, pmc_details = None, {"skipped": "not requested for this form (no --full / --no-pmc / --no-cpu-baseline / --timed-only / N > 1)"}
+    if args.full and args.gpus == 1 and "WORLD_SIZE" not in os.environ and not (args.no_pmc or args.no_cpu_baseline or args.timed_only or args.force_dist):
         pmc_traffic, pmc_details = measure_hbm_traffic()
 
     import torch
@@ -361,7 +393,7 @@ def main():
     # same submit/collect pipeline as the timed region, so every lane's buffers, streams and worker thread have been used
     # device-to-device copy rate of this GPU (roofline.peak_measured), before the warm-up (placing it here rather than at process
     # start was measured not to matter for a 20-step run: 3500 vs 3515 pairs/s -- the clocks are not what a short run waits for)
-    hbm_measured = hbm_copy_peak_gbs(torch)
+    hbm_measured = hbm_copy_peak_gbs(torch) if args.full else None
     import gc
 
     def fence():
@@ -400,6 +432,9 @@ def main():
     n_pipe_warm = max(n_warm - 2, 2 * args.depth)
     warm_results = (uvo.StereoResult * n_pipe_warm)()
     warm_stamps = [0.0] * (n_pipe_warm + 1)
+    # the collector runs once and is then held off until the timed blocks are over: no collector pause inside a 10 ms window, and
+    # none between the warm-up and the first timed block either (the GPU idling there made a 20-step block ~5 % slower than the later ones)
+    gc.collect(); gc.freeze(); gc.disable()
     timed_block(n_pipe_warm, warm_results, warm_stamps)
     multirank.max_over_ranks(0.0, dev)
     del warm_results
@@ -408,13 +443,12 @@ def main():
     # 2.4 % of the driver's 20-step form (3830 with it, 3920 without, same box) -- so the timed blocks run WITHOUT it (their stalls, if
     # any, are located by the per-collect host stamps, collect_gap_ms) and one more block of the same shape, not part of `value`, runs
     # with it for runs of <= 64 steps (--trace-all: every block traced, as round 4's first bench lines were)
-    trace_on = (not args.no_trace) and args.steps <= 64 and not args.timed_only
+    trace_on = args.full and (not args.no_trace) and args.steps <= 64 and not args.timed_only
     if trace_on and args.trace_all:
         ctx.trace_enable(True)
-    n_blocks = max(args.blocks, 1)
+    n_blocks = max(args.blocks if args.blocks is not None else (7 if args.full else 1), 1)
     block_dt, block_local, block_cpu, block_stamps = [], [], [], []
     all_results, all_records, all_allrec, block_first_k = [], [], [], []
-    gc.collect(); gc.freeze(); gc.disable()                                # no collector pause inside a 10 ms window
     try:
         for b in range(n_blocks):
             res_b = (uvo.StereoResult * max(args.steps, 1))()              # the block's results land here in place
@@ -428,6 +462,8 @@ def main():
             block_stamps.append(stamps); all_results.append(res_b); all_records.append(records); all_allrec.append(allrec)
     finally:
         gc.enable()
+    if rank == 0 and args.dump_outputs:                                    # before any later submit reuses the last pair's lane
+        dump_outputs(args.dump_outputs, all_results[-1][args.steps - 1], ctx.stereo_get)
     order_b = sorted(range(n_blocks), key=lambda b: block_dt[b])
     med = order_b[(n_blocks - 1) // 2]                                     # the median block (lower median when the count is even)
     dt, dt_local = block_dt[med], block_local[med]
@@ -473,7 +509,7 @@ def main():
             trace_summary["traced_block_value"] = round(total_pairs / dt_t, 3)
         if trace_summary.get("dev_detection_launch_ms"):
             det_pipelined_ms = trace_summary["dev_detection_launch_ms"]["p50"]
-    elif not args.no_trace and not args.timed_only:                        # long blocks: one traced block of 64 pairs for the pipelined launch duration alone
+    elif args.full and not args.no_trace and not args.timed_only:          # long blocks: one traced block of 64 pairs for the pipelined launch duration alone
         ctx.trace_enable(True)
         res_t = (uvo.StereoResult * 64)()
         timed_block(64, res_t, [0.0] * 65)
@@ -500,7 +536,7 @@ def main():
     # ---- the same K steps with the images in (pageable) host memory: upload of both images inside the timed region ----
     # (SURVEY 8(d) figure (ii); reported beside `value`, never as `value`)
     h2d_value = None
-    if world == 1:
+    if world == 1 and args.full:
         ctx.stereo_set_rig(rig.K_left, rig.K_right, rig.R_right, rig.t_right)       # fresh VO state
         order_h = ping_pong(args.frames)
         ctx.stereo_step(*host_frames[next(order_h)], 0.05)                          # init pair
@@ -515,8 +551,8 @@ def main():
         torch.cuda.synchronize()
         h2d_value = n_h / (time.perf_counter() - th)
 
-    out = None
-    if rank == 0:
+    out, full = None, {}
+    if rank == 0 and args.full:
         # ---- latency leg: synchronous uvo_stereo_step, one pair in flight, wall clock per call ----
         lat = []
         for _ in range(200):
@@ -595,8 +631,8 @@ def main():
             if pinned:
                 os.sched_setaffinity(0, aff)
             t_each.sort()
-            med = t_each[len(t_each) // 2]
-            cpu = {"value": round(1.0 / med, 4), "unit": "pairs/s", "cores": 1, "kind": "port", "pinned": pinned,
+            med_s = t_each[len(t_each) // 2]
+            cpu = {"value": round(1.0 / med_s, 4), "unit": "pairs/s", "cores": 1, "kind": "port", "pinned": pinned,
                    "sample": f"median of {len(t_each)} consecutive pairs of the same 1920x1080 sequence through oracle/ (C restatement, "
                              f"gcc -O2, 1 thread; not OpenCV)"}
             # ---- parity of the timed configuration: the same pairs through the HIP path, compared with the oracle's results ----
@@ -642,24 +678,8 @@ def main():
                       "max_pose_rel_diff": max_rel, "timed_loop_records_checked": timed_checked, "timed_loop_max_pose_rel_diff": timed_rel,
                       "mismatches": bad[:8]}}
 
-        out = {
-            "metric": "stereo frame-pairs/sec (detect+match+pose) @1920x1080, 3k kpts",
-            "value": round(value, 3), "unit": "pairs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f32+f64", "data": "synthetic",
-            "config": {"workload": "C3: stereo UVO synthetic 1920x1080 pair, ~3000 SURF kpts/image, EPnP PnP-RANSAC"
-                                   if world == 1 else "C5: one independent 1920x1080 stereo stream per GPU",
-                       "min_hessian": min_hessian, "kpts_per_image": round(kp_sum / max(args.steps, 1), 1),
-                       "valid_steps": n_valid, "valid_steps_all_blocks": [n_valid_all, args.steps * n_blocks], "frames": args.frames, "parallelism": f"streams{world}", "pipeline": f"submit/collect, {args.depth} pairs in flight per image stream"},
-            "value_device_resident": round(value, 3),
-            # the timed region (fence, K steps, gather, fence) run `blocks` times in a row in this process: `value` / `ms_per_step` are
-            # the MEDIAN block's, every block's rate is listed in run order
-            "blocks": n_blocks, "value_is": "median block", "value_first_block": round(block_values[0], 3),
-            "value_min": round(min(block_values), 3), "value_max": round(max(block_values), 3), "block_values": [round(v, 1) for v in block_values],
-            "warmup_pipelined_pairs": n_pipe_warm, "median_block": med, "pairs_before_median_block": n_before_timed,
-            "collect_gap_ms": collect_gap_ms, "pipeline_trace": trace_summary,
-            "per_rank_value": [v / 1000.0 for v in per_rank], "ranks_seen": sorted(who[:, 0].tolist()),
-            "rccl_ranks_seen": (len(set(who[:, 0].tolist())) if (dist_on and args.backend == "nccl") else 0),
+        full = {
+            "pipeline_trace": trace_summary,
             "value_h2d_inclusive": None if h2d_value is None else round(h2d_value, 3),
             "roofline": {"bound": "hbm", "kernel": "k_hessian_nms_all (the four octaves, 3 middle layers each, 2 images per launch)",
                          "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -686,6 +706,28 @@ def main():
             "algorithmic_bytes_per_pair": int(algorithmic_bytes_pair(WIDTH, HEIGHT, 3000, b_desc)),
             "stage_ms": stage_ms, "stage_launches_per_step": stage_calls,
             "cpu_baseline": cpu,
+        }
+        full.update(parity)
+
+    if rank == 0:
+        out = {
+            "metric": "stereo frame-pairs/sec (detect+match+pose) @1920x1080, 3k kpts",
+            "value": round(value, 3), "unit": "pairs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "f32+f64", "data": "synthetic",
+            "config": {"workload": "C3: stereo UVO synthetic 1920x1080 pair, ~3000 SURF kpts/image, EPnP PnP-RANSAC"
+                                   if world == 1 else "C5: one independent 1920x1080 stereo stream per GPU",
+                       "min_hessian": min_hessian, "kpts_per_image": round(kp_sum / max(args.steps, 1), 1),
+                       "valid_steps": n_valid, "valid_steps_all_blocks": [n_valid_all, args.steps * n_blocks], "frames": args.frames, "parallelism": f"streams{world}", "pipeline": f"submit/collect, {args.depth} pairs in flight per image stream"},
+            "value_device_resident": round(value, 3),
+            # the timed region (fence, K steps, gather, fence) run `blocks` times in a row in this process: `value` / `ms_per_step` are
+            # the MEDIAN block's, every block's rate is listed in run order
+            "blocks": n_blocks, "value_is": "median block", "value_first_block": round(block_values[0], 3),
+            "value_min": round(min(block_values), 3), "value_max": round(max(block_values), 3), "block_values": [round(v, 1) for v in block_values],
+            "warmup_pipelined_pairs": n_pipe_warm, "median_block": med, "pairs_before_median_block": n_before_timed,
+            "collect_gap_ms": collect_gap_ms,
+            "per_rank_value": [v / 1000.0 for v in per_rank], "ranks_seen": sorted(who[:, 0].tolist()),
+            "rccl_ranks_seen": (len(set(who[:, 0].tolist())) if (dist_on and args.backend == "nccl") else 0),
             "host": {"cores_visible": host_cores_all, "cores_of_this_rank": len(my_cores), "pinned": len(my_cores) < host_cores_all and bool(my_cores),
                      "pin_source": pin.get("source"), "cgroup_cpu_quota": pin.get("cpu_quota"), "cpu_quota_share_of_this_rank": pin.get("quota_share"),
                      "worker_wait": os.environ.get("UVO_WORKER_WAIT", "auto"), "stage_b": os.environ.get("UVO_STAGE_B", "auto"), "policy": host_policy,
@@ -697,7 +739,7 @@ def main():
                      "busy_host_threads_rank0": round(busy_threads, 2),
                      "collectives": ("none (single process)" if not dist_on else f"{args.backend}: all_gather_into_tensor of the pose records, all_reduce(MAX) of the time, barriers; {world} rank(s)")},
         }
-        out.update(parity)
+        out.update(full)
     if dist_on:
         multirank.barrier()
         dist.destroy_process_group()

@@ -1,7 +1,7 @@
 // UVO_node_hip.cpp -- the node's bootstrap (uvo/src/UVO_node.cpp:9-29) over this directory's visual_odometry.h.
 //
 // The reference's own UVO_node.cpp compiles against that header unchanged (same class, constructor and workflow method:
-// tests/test_node.py compiles it where it lies); this file is the same bootstrap for a workspace that does not carry the
+// tests/cpp/node_main_contract.cpp pins what it needs); this file is the same bootstrap for a workspace that does not carry the
 // reference's sources, with one difference: it waits for /visual_odometry_node to exist before it enters the workflow, and
 // turns an error of the hot path into an exit code for the launch file's respawn instead of an uncaught exception.
 // Built only where roscpp exists (CMakeLists.txt next to this file).

@@ -232,7 +232,7 @@ def _bench_ranks_vs_single_gpu_streams(tmp_path, n, extra, base_seed_key):
     rec_path = str(tmp_path / "records.npy")
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "UVO_RDZV_FILE")}
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(n), "--steps", str(steps), "--warmup", str(warm),
-                        "--frames", str(frames), "--no-cpu-baseline", "--dump-records", rec_path] + extra,
+                        "--frames", str(frames), "--full", "--no-cpu-baseline", "--dump-records", rec_path] + extra,
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1100)
     assert p.returncode == 0, p.stderr[-2000:]
     line = json.loads(p.stdout.strip().splitlines()[-1])
@@ -291,6 +291,54 @@ def test_c5_five_ranks_on_one_device_match_single_gpu_streams(tmp_path):
     # card at once (this test process + 5 ranks), and a ninth would have the run killed ("process guard").
     assert line["ranks_seen"] == [0, 1, 2, 3, 4] and line["rccl_ranks_seen"] == 0 and len(set(line["host"]["numa_nodes_of_ranks"])) == 1
     assert sum(line["host"]["cores_of_ranks"]) <= line["host"]["cores_visible"]         # the five ranks split the card's NUMA node
+
+
+def test_plain_bench_run_dumps_what_its_last_timed_pair_returned(tmp_path):
+    """`python bench.py --steps K --warmup W --dump-outputs DIR` without --full: one timed block of exactly K pairs, the headline keys
+    and none of the legs --full adds, and DIR/<name>.npy in float32 / float64 holding the result fields and intermediates of the last
+    timed pair -- bit for bit what a synchronous run of the same pair sequence returns for that pair."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import ergo_uvo_amd as uvo
+    from ergo_uvo_amd import synth
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    steps, warm, frames = 6, 3, 2
+    out_dir = tmp_path / "outputs"
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "UVO_RDZV_FILE")}
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warm),
+                        "--frames", str(frames), "--dump-outputs", str(out_dir)], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    line = json.loads(p.stdout.strip().splitlines()[-1])
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(line)
+    assert line["steps"] == steps and line["blocks"] == 1 and line["config"]["valid_steps"] == steps
+    assert abs(line["ms_per_step"] - 1e3 / line["value"]) <= 1e-3 * line["ms_per_step"] + 1e-4
+    assert not {"roofline", "cpu_baseline", "step_latency_ms", "pipeline_trace", "value_h2d_inclusive", "parity_checked"} & set(line)
+    got = {f[:-len(".npy")]: np.load(out_dir / f) for f in os.listdir(out_dir)}
+    assert set(got) == {"counts", "rvec", "tvec", "t_prev_curr", "velocity"} | set(bench.STEREO_OUTPUTS)
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values()) and sum(a.nbytes for a in got.values()) <= 64 << 20
+    # the same pair sequence synchronously: the init pairs, the warm-up and the timed block; the last pair is the one dumped
+    n_pairs = line["pairs_before_median_block"] + steps
+    W, H = bench.WIDTH, bench.HEIGHT
+    scene = synth.Scene(synth.SEEDS["C3"], W)
+    pairs = [synth.stereo_pair(scene, k, W, H) for k in range(frames)]
+    rig = synth.stereo_rig(W)
+    ctx = uvo.Context(uvo.Params.stereo(SURF_MIN_HESSIAN=bench.MIN_HESSIAN_C3), 0, W, H, 8192)
+    try:
+        ctx.stereo_set_rig(rig.K_left, rig.K_right, rig.R_right, rig.t_right)
+        order = bench.ping_pong(frames)
+        for _ in range(n_pairs):
+            r = ctx.stereo_step(*pairs[next(order)], 0.05)
+        bench.dump_outputs(str(tmp_path / "want"), r, ctx.stereo_get)
+    finally:
+        ctx.close()
+    for name, a in got.items():
+        b = np.load(tmp_path / "want" / (name + ".npy"))
+        assert a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a.view(np.uint8), b.view(np.uint8)), name
+    assert got["counts"][0] == 1 and got["counts"][7] >= 100 and len(got["inliers"]) == got["counts"][7]
 
 
 @pytest.mark.parametrize("stream", range(8))

@@ -445,16 +445,15 @@ def test_ros_adapter_meets_a_compiler():
     assert res.returncode != 0 and "range_calback" in res.stderr
 
 
-def test_reference_main_compiles_against_the_adapter_unchanged():
+def test_node_bootstrap_compiles_against_the_adapter_unchanged():
     """the reference's bootstrap (uvo/src/UVO_node.cpp:9-29) names `visual_odometry_node`, its default constructor
-    and `visual_odometry_workflow(string)` from `<visual_odometry.h>`.  With ergo_uvo_amd/ros first on the include path that file -- compiled
-    WHERE IT LIES under /root/reference, not copied -- must meet the adapter's class without an edit.  (Skipped where the reference is absent.)"""
-    ref_main = "/root/reference/uvo/src/UVO_node.cpp"
-    if not os.path.exists(ref_main):
-        pytest.skip("the reference checkout is not on this machine")
+    and `visual_odometry_workflow(string)` from `<visual_odometry.h>`, with `string` unqualified at file scope.  tests/cpp/node_main_contract.cpp
+    is a bootstrap of that shape kept in this repository; with ergo_uvo_amd/ros first on the include path it must meet the adapter's class
+    without an edit."""
+    main_src = os.path.join(ROOT, "tests", "cpp", "node_main_contract.cpp")
     ros_dir = os.path.join(ROOT, "ergo_uvo_amd", "ros")
     cmd = ["g++", "-std=c++17", "-fsyntax-only", "-DUVO_NO_OPENCV", "-I", ros_dir, "-I", os.path.join(ROOT, "include"),
-           "-I", os.path.join(ROOT, "tests", "cpp", "ros_stub"), ref_main]
+           "-I", os.path.join(ROOT, "tests", "cpp", "ros_stub"), main_src]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=120)
     assert res.returncode == 0, res.stderr
     # and it is the adapter's class it met: without ergo_uvo_amd/ros on the path the same file does not find its header

@@ -39,7 +39,7 @@ MODES = {
 def run_cell(mode: str, cpus: int, steps: int, warmup: int, extra: list[str]) -> dict:
     env = {k: v for k, v in os.environ.items() if k not in ("UVO_STAGE_B", "UVO_WORKER_WAIT", "UVO_CPU_BUDGET")}
     env.update(MODES[mode])
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", str(warmup), "--timed-only", "--cpus", str(cpus)] + extra
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", str(warmup), "--timed-only", "--full", "--cpus", str(cpus)] + extra
     t0 = time.time()
     p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     if p.returncode != 0:

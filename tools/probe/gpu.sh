@@ -22,7 +22,7 @@
 #   sift-pmc                    counter passes of the SIFT detector (one per group) -> tools/pmc_summary_sift.py
 #   binary <tag>                the AKAZE and ORB detectors: timing (CPU oracle beside it), kernel stats of each
 #   budget [host_budget args]   tools/host_budget.py: {spin, sleep, block-all, device} x {2, 4, 16 CPUs}, both bench forms
-#   final <tag>                 the closing pass of a round: bench (600 steps and the driver's form), kernel stats, counters, configs
+#   final <tag>                 the closing pass of a round: bench --full (600 steps and the driver's form; the lines go to $OUT), kernel stats, counters, configs
 # TAG=<name> prefixes the output files (default r05).
 set -o pipefail
 cd /tmp && export TMPDIR=/tmp && cd ${GRAFT_REPO_ROOT:-$(dirname $0)/../..}
@@ -37,7 +37,7 @@ step() {
     tests)   if [ $# -eq 0 ]; then set -- tests -m gpu; fi
              timeout -k 10 1100 python -m pytest "$@" -x -q > gpurun_out/${TAG}_tests.log 2>&1; rc=$?; tail -4 gpurun_out/${TAG}_tests.log; return $rc ;;
     bench)   python bench.py "$@" ;;
-    bench20) n=${1:-3}; shift; for i in $(seq $n); do python bench.py --steps 20 --warmup 5 --no-cpu-baseline "$@" 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('20/5:', d['value'], 'first', d['value_first_block'], d['block_values'], 'gap max', d['collect_gap_ms']['max'], d['collect_gap_ms']['argmax'])" || return 1; done ;;
+    bench20) n=${1:-3}; shift; for i in $(seq $n); do python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline "$@" 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('20/5:', d['value'], 'first', d['value_first_block'], d['block_values'], 'gap max', d['collect_gap_ms']['max'], d['collect_gap_ms']['argmax'])" || return 1; done ;;
     ab)      for rep in 1 2; do UVO_HIP_LIB=$OLD LBL=old brun --steps ${1:-300} || return 1; LBL=new brun --steps ${1:-300} || return 1; done ;;
     sweep)   n=${1:-300}
              LBL=default brun --steps $n --depth 6; UVO_A_OVERLAP=3 LBL="A_OVERLAP=3 depth 6" brun --steps $n --depth 6; UVO_A_OVERLAP=3 LBL="A_OVERLAP=3 depth 8" brun --steps $n --depth 8
@@ -97,10 +97,10 @@ step() {
              python3 tools/prof_binary.py both 20 --cpu > gpurun_out/${t}_binary_time.log 2>&1 || { tail -5 gpurun_out/${t}_binary_time.log; return 1; }; cat gpurun_out/${t}_binary_time.log
              for d in akaze orb; do rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_${t}_$d -- python3 tools/prof_binary.py $d 5 > gpurun_out/prof_${t}_$d.log 2>&1 || return 1; echo "== $d"; python tools/probe/kstats.py prof_${t}_$d 24; done ;;
     budget)  python tools/host_budget.py --out gpurun_out/${TAG}_host_budget.json "$@" ;;
-    final)   t=${1:-$TAG}
-             python bench.py > gpurun_out/bench_${t}_final.json 2> gpurun_out/bench_${t}_final.err || return 1; tail -c 300 gpurun_out/bench_${t}_final.json; echo
-             python bench.py --steps 20 --warmup 5 > gpurun_out/bench_${t}_20steps.json 2> gpurun_out/bench_${t}_20steps.err || return 1
-             python bench.py --gpus 1 --backend nccl --force-dist --steps 200 --no-cpu-baseline > gpurun_out/bench_${t}_1rank_rccl.json 2> gpurun_out/bench_${t}_1rank_rccl.err || return 1
+    final)   t=${1:-$TAG}; out=${OUT:?"final: set OUT to the directory that receives the bench lines"}
+             python bench.py --full > $out/bench_${t}_final.json 2> $out/bench_${t}_final.err || return 1; tail -c 300 $out/bench_${t}_final.json; echo
+             python bench.py --full --steps 20 --warmup 5 > $out/bench_${t}_20steps.json 2> $out/bench_${t}_20steps.err || return 1
+             python bench.py --full --gpus 1 --backend nccl --force-dist --steps 200 --no-cpu-baseline > $out/bench_${t}_1rank_rccl.json 2> $out/bench_${t}_1rank_rccl.err || return 1
              step prof $t sync || return 1; step prof $t pipe || return 1
              step pmc $t k_hessian_nms_all || return 1 ;;
     *) echo "unknown step $s"; return 2 ;;
