@@ -183,9 +183,11 @@ class Context:
             self._check(self._lib.uvo_ctx_set_producer_stream(self._h, C.c_void_p(torch.cuda.current_stream().cuda_stream or None), 1))
 
     def set_feature_detector(self, name: str):
-        """The reference's global FEATURE_DETECTOR: "SURF" (default) or "SIFT" for the fused steps and detect_features; "AKAZE" for
-        detect_features / match_features alone (the fused steps refuse it)."""
+        """The reference's global FEATURE_DETECTOR: "SURF" (default), "SIFT", "AKAZE" or "ORB", for the fused steps (stereo_step / submit,
+        mono_step / submit) and detect_features alike.  ORB's descriptors need orb_set_pattern, before the first step that runs on it.
+        Refused while pairs are in flight, and a change while a VO sequence runs (reset first)."""
         if name in ("AKAZE", "ORB"):
+            self._check(self._lib.uvo_ctx_set_loop_detector(self._h, name.encode()))
             self._feature_akaze, self._feature_orb, self._feature_sift = name == "AKAZE", name == "ORB", False
             return
         self._check(self._lib.uvo_ctx_set_feature_detector(self._h, name.encode()))
@@ -347,6 +349,17 @@ class Context:
         m = C.c_int(prev)
         self._check(self._lib.uvo_match_knn2_ratio_hamming(self._h, _p(d1), len(d1), _p(d2), len(d2), d1.shape[1], 0, C.c_float(ratio), _p(out), len(out), C.byref(m)))
         return out[:m.value].copy()
+
+    def loop_knn_match_binary(self, descriptors1, descriptors2, metric="hamming"):
+        """Test hook (uvo_match_loop_knn2): the fused steps' kNN-2 on uint8 rows -- metric "hamming" (stereo loop) or "l2" (mono loop's
+        NORM_L2 on CV_8U rows).  Returns (idx, dist), n x 2 each."""
+        d1, d2 = _np(descriptors1, np.uint8), _np(descriptors2, np.uint8)
+        if d1.ndim != 2 or d2.ndim != 2 or d1.shape[1] != d2.shape[1]:
+            raise ValueError("binary descriptors: two uint8 matrices with the same number of columns")
+        idx = np.empty((len(d1), 2), np.int32)
+        dist = np.empty((len(d1), 2), np.float32)
+        self._check(self._lib.uvo_match_loop_knn2(self._h, _p(d1), len(d1), _p(d2), len(d2), d1.shape[1], {"hamming": 0, "l2": 1}[metric], _p(idx), _p(dist)))
+        return idx, dist
 
     def knn_match_hamming(self, descriptors1, descriptors2):
         d1, d2 = _np(descriptors1, np.uint8), _np(descriptors2, np.uint8)
@@ -526,6 +539,14 @@ class Context:
         return r
 
     def stereo_get(self, what: str):
+        """Intermediates of the last collected pair; desc_left / desc_right are float rows (SURF, SIFT) or uint8 rows of 61 (AKAZE) / 32 (ORB) bytes."""
+        binary = np.dtype(("u1", 61)) if getattr(self, "_feature_akaze", False) else (np.dtype(("u1", 32)) if getattr(self, "_feature_orb", False) else None)
+        if binary is not None and what in ("desc_left", "desc_right"):
+            buf = np.zeros(self.max_kpts, binary)
+            n = self._lib.uvo_stereo_get(self._h, what.encode(), _p(buf), buf.nbytes)
+            if n < 0:
+                raise UvoError(3, "stereo_get buffer too small")
+            return buf[:n].copy()
         spec = {"kps_left": KP_DTYPE, "kps_right": KP_DTYPE, "desc_left": np.dtype(("f4", 128 if (self.params.SURF_EXTENDED or getattr(self, "_feature_sift", False)) else 64)),
                 "desc_right": np.dtype(("f4", 128 if (self.params.SURF_EXTENDED or getattr(self, "_feature_sift", False)) else 64)), "matches_stereo": DM_DTYPE, "matches_tri": DM_DTYPE,
                 "points4d": np.dtype(("f4", 4)), "good_pts": np.dtype(("f8", 3)), "good_idx": np.dtype("i4"),

@@ -54,6 +54,7 @@ struct AkazeWs {
     std::vector<uint8_t> mask[kAkMaxLevels]; std::vector<float> val[kAkMaxLevels];               // host: keypoint mask and Ldet at candidates
     std::vector<std::vector<AkCand>> cands;
     std::vector<uint64_t> keys;                               // host: sort keys of the candidate list
+    std::vector<uvo_keypoint> out;                            // host: the refined keypoints (source of an asynchronous copy: kept until the next call)
 };
 
 // ---- fed.cpp: fed_tau_by_process_time(T, 1, 0.25f, true, tau) ----
@@ -559,13 +560,73 @@ static bool find_neighbor_point(int x, int y, const std::vector<uint8_t>& mask, 
     return false;
 }
 
-uvo_status akaze_detect(Ctx* c, const uint8_t* gray, int w, int h, int stride, int mem, uvo_keypoint* kps, uint8_t* desc, int cap, int* n_out)
+static uvo_status akaze_record(Ctx* c, AkazeWs* s, hipStream_t st)
+{
+    const dim3 blk(256);
+    auto grid = [](int ww, int hh) { return dim3((ww + 255) / 256, hh); };
+    AkKernel k5;
+    gauss_kernel(5, (double)1.0f, &k5);
+        for (int i = 1; i < s->n; i++) {
+        const AkLevel& lv = s->lv[i];
+        const int lw = lv.w, lh = lv.h;
+        if (lv.octave > s->lv[i - 1].octave) {
+            const int sw = s->lv[i - 1].w;
+            if (!s->xtab[i]) hipLaunchKernelGGL(k_ak_half, grid(lw, lh), blk, 0, st, s->Lt[i - 1], sw, lw, lh, s->Lt[i]);
+            else hipLaunchKernelGGL(k_ak_area, grid(lw, lh), blk, 0, st, s->Lt[i - 1], sw, lw, lh, s->xtab[i], s->xofs[i], s->ytab[i], s->yofs[i], s->Lt[i]);
+        } else UVO_HIP_TRY(c, hipMemcpyAsync(s->Lt[i], s->Lt[i - 1], sizeof(float) * (size_t)lw * lh, hipMemcpyDeviceToDevice, st));
+        hipLaunchKernelGGL(k_ak_blur_rows, grid(lw, lh), blk, 0, st, s->Lt[i], lw, lh, k5, s->s[0]);
+        hipLaunchKernelGGL(k_ak_blur_cols, grid(lw, lh), blk, 0, st, s->s[0], lw, lh, k5, s->Lsmooth[i]);
+        hipLaunchKernelGGL(k_ak_scharr, grid(lw, lh), blk, 0, st, s->Lsmooth[i], lw, lh, 1, s->s[0]);
+        hipLaunchKernelGGL(k_ak_scharr, grid(lw, lh), blk, 0, st, s->Lsmooth[i], lw, lh, 0, s->s[1]);
+        hipLaunchKernelGGL(k_ak_pm_g2, dim3((lw * lh + 255) / 256), blk, 0, st, s->s[0], s->s[1], lw * lh, s->d_kc, lv.octave, s->s[2]);
+        // Fast Explicit Diffusion: the cycle's steps, ping-pong between Lt[i] and a scratch plane
+        float* cur = s->Lt[i]; float* nxt = s->s[3];
+        for (int j = 0; j < lv.nsteps; j++) {
+            hipLaunchKernelGGL(k_ak_nld_step, grid(lw, lh), blk, 0, st, cur, s->s[2], lw, lh, lv.tau[j] * 0.5f, nxt);
+            std::swap(cur, nxt);
+        }
+        if (cur != s->Lt[i]) UVO_HIP_TRY(c, hipMemcpyAsync(s->Lt[i], cur, sizeof(float) * (size_t)lw * lh, hipMemcpyDeviceToDevice, st));
+    }
+    UVO_HIP_TRY(c, hipMemsetAsync(s->cand_n, 0, sizeof(int) * kAkMaxLevels, st));
+    for (int i = 0; i < s->n; i++) {
+        const AkLevel& lv = s->lv[i];
+        const int lw = lv.w, lh = lv.h, r = lv.sigma_size;
+        hipLaunchKernelGGL(k_ak_sep_deriv, grid(lw, lh), blk, 0, st, s->Lsmooth[i], lw, lh, 1, r, s->Lx[i]);
+        hipLaunchKernelGGL(k_ak_sep_deriv, grid(lw, lh), blk, 0, st, s->Lx[i], lw, lh, 1, r, s->s[0]);        // Lxx
+        hipLaunchKernelGGL(k_ak_sep_deriv, grid(lw, lh), blk, 0, st, s->Lx[i], lw, lh, 0, r, s->s[1]);        // Lxy
+        hipLaunchKernelGGL(k_ak_sep_deriv, grid(lw, lh), blk, 0, st, s->Lsmooth[i], lw, lh, 0, r, s->Ly[i]);
+        hipLaunchKernelGGL(k_ak_sep_deriv, grid(lw, lh), blk, 0, st, s->Ly[i], lw, lh, 0, r, s->s[2]);        // Lyy
+        hipLaunchKernelGGL(k_ak_det, dim3((lw * lh + 255) / 256), blk, 0, st, s->s[0], s->s[1], s->s[2], lw * lh, (float)(r * r * r * r), s->Ldet[i]);
+        if (lv.border + 1 >= lh || lw - 2 * lv.border <= 0 || lh - 2 * lv.border <= 0) continue;              // "if border is too big we shouldn't search any keypoints"
+        // every level appends to one list (the record carries its level); cand_n[0] counts them all
+        hipLaunchKernelGGL(k_ak_candidates, grid(lw - 2 * lv.border, lh - 2 * lv.border), blk, 0, st, s->Ldet[i], lw, lh, lv.border, 0.001f, i, s->cand, s->cand_n, kAkCandCap);
+    }
+    return UVO_OK;
+}
+static bool akaze_use_graph()
+{
+    static const bool on = !(getenv("UVO_AKAZE_GRAPH") && atoi(getenv("UVO_AKAZE_GRAPH")) == 0);      // UVO_AKAZE_GRAPH=0: launch by launch (measurement)
+    return on;
+}
+// the chain captured on stream st (thread-local capture mode) and instantiated, once per workspace
+static uvo_status akaze_capture(Ctx* c, AkazeWs* s, hipStream_t st)
+{
+    if (s->exec) return UVO_OK;
+    UVO_HIP_TRY(c, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+    const uvo_status rs = akaze_record(c, s, st);
+    hipGraph_t g = nullptr;
+    const hipError_t ee = hipStreamEndCapture(st, &g);
+    if (rs != UVO_OK || ee != hipSuccess || !g) { if (g) (void)hipGraphDestroy(g); if (rs == UVO_OK) c->err = std::string("AKAZE: graph capture: ") + hipGetErrorString(ee); return rs != UVO_OK ? rs : UVO_HIP_ERROR; }
+    s->graph = g;
+    UVO_HIP_TRY(c, hipGraphInstantiate(&s->exec, s->graph, nullptr, nullptr, 0));
+    return UVO_OK;
+}
+
+// detectAndCompute on `gray` (device or host): the keypoints and their M-LDB rows are left in s->d_kps / s->d_desc, *n_out = the count; when it
+// exceeds the workspace's capacity (max_kpts) nothing past the host stages is computed and the call still returns UVO_OK
+static uvo_status akaze_run(Ctx* c, AkazeWs* s, hipStream_t st, const uint8_t* gray, int w, int h, int stride, int mem, int* n_out)
 {
     *n_out = 0;
-    if (w < 16 || h < 16 || w > c->max_w || h > c->max_h || stride < w) { c->err = "uvo_akaze_detect: image size outside the context's limits"; return UVO_INVALID_ARG; }
-    AkazeWs* s = akaze_ws(c, w, h);
-    if (!s) { c->err = "AKAZE workspace allocation failed"; return UVO_HIP_ERROR; }
-    hipStream_t st = c->stream;
     const dim3 blk(256);
     auto grid = [](int ww, int hh) { return dim3((ww + 255) / 256, hh); };
     static const bool dbg = getenv("UVO_DBG_PHASE") != nullptr;                                            // host wall clock of the call's phases
@@ -623,57 +684,10 @@ uvo_status akaze_detect(Ctx* c, const uint8_t* gray, int w, int h, int stride, i
     // and replayed with one call per frame.  Measured: the chain is bound by the DEVICE (600 kernels of 3-6 us back to back: 3.2 ms at
     // 1080p either way; whole call 1.46 ms as a graph against 1.56 ms launch by launch at 640 x 360, level at 1080p); what the graph
     // buys is the host thread, idle instead of issuing launches for 3 ms. ----
-    auto record = [&]() -> uvo_status {
-        for (int i = 1; i < s->n; i++) {
-            const AkLevel& lv = s->lv[i];
-            const int lw = lv.w, lh = lv.h;
-            if (lv.octave > s->lv[i - 1].octave) {
-                const int sw = s->lv[i - 1].w;
-                if (!s->xtab[i]) hipLaunchKernelGGL(k_ak_half, grid(lw, lh), blk, 0, st, s->Lt[i - 1], sw, lw, lh, s->Lt[i]);
-                else hipLaunchKernelGGL(k_ak_area, grid(lw, lh), blk, 0, st, s->Lt[i - 1], sw, lw, lh, s->xtab[i], s->xofs[i], s->ytab[i], s->yofs[i], s->Lt[i]);
-            } else UVO_HIP_TRY(c, hipMemcpyAsync(s->Lt[i], s->Lt[i - 1], sizeof(float) * (size_t)lw * lh, hipMemcpyDeviceToDevice, st));
-            hipLaunchKernelGGL(k_ak_blur_rows, grid(lw, lh), blk, 0, st, s->Lt[i], lw, lh, k5, s->s[0]);
-            hipLaunchKernelGGL(k_ak_blur_cols, grid(lw, lh), blk, 0, st, s->s[0], lw, lh, k5, s->Lsmooth[i]);
-            hipLaunchKernelGGL(k_ak_scharr, grid(lw, lh), blk, 0, st, s->Lsmooth[i], lw, lh, 1, s->s[0]);
-            hipLaunchKernelGGL(k_ak_scharr, grid(lw, lh), blk, 0, st, s->Lsmooth[i], lw, lh, 0, s->s[1]);
-            hipLaunchKernelGGL(k_ak_pm_g2, dim3((lw * lh + 255) / 256), blk, 0, st, s->s[0], s->s[1], lw * lh, s->d_kc, lv.octave, s->s[2]);
-            // Fast Explicit Diffusion: the cycle's steps, ping-pong between Lt[i] and a scratch plane
-            float* cur = s->Lt[i]; float* nxt = s->s[3];
-            for (int j = 0; j < lv.nsteps; j++) {
-                hipLaunchKernelGGL(k_ak_nld_step, grid(lw, lh), blk, 0, st, cur, s->s[2], lw, lh, lv.tau[j] * 0.5f, nxt);
-                std::swap(cur, nxt);
-            }
-            if (cur != s->Lt[i]) UVO_HIP_TRY(c, hipMemcpyAsync(s->Lt[i], cur, sizeof(float) * (size_t)lw * lh, hipMemcpyDeviceToDevice, st));
-        }
-        UVO_HIP_TRY(c, hipMemsetAsync(s->cand_n, 0, sizeof(int) * kAkMaxLevels, st));
-        for (int i = 0; i < s->n; i++) {
-            const AkLevel& lv = s->lv[i];
-            const int lw = lv.w, lh = lv.h, r = lv.sigma_size;
-            hipLaunchKernelGGL(k_ak_sep_deriv, grid(lw, lh), blk, 0, st, s->Lsmooth[i], lw, lh, 1, r, s->Lx[i]);
-            hipLaunchKernelGGL(k_ak_sep_deriv, grid(lw, lh), blk, 0, st, s->Lx[i], lw, lh, 1, r, s->s[0]);        // Lxx
-            hipLaunchKernelGGL(k_ak_sep_deriv, grid(lw, lh), blk, 0, st, s->Lx[i], lw, lh, 0, r, s->s[1]);        // Lxy
-            hipLaunchKernelGGL(k_ak_sep_deriv, grid(lw, lh), blk, 0, st, s->Lsmooth[i], lw, lh, 0, r, s->Ly[i]);
-            hipLaunchKernelGGL(k_ak_sep_deriv, grid(lw, lh), blk, 0, st, s->Ly[i], lw, lh, 0, r, s->s[2]);        // Lyy
-            hipLaunchKernelGGL(k_ak_det, dim3((lw * lh + 255) / 256), blk, 0, st, s->s[0], s->s[1], s->s[2], lw * lh, (float)(r * r * r * r), s->Ldet[i]);
-            if (lv.border + 1 >= lh || lw - 2 * lv.border <= 0 || lh - 2 * lv.border <= 0) continue;              // "if border is too big we shouldn't search any keypoints"
-            // every level appends to one list (the record carries its level); cand_n[0] counts them all
-            hipLaunchKernelGGL(k_ak_candidates, grid(lw - 2 * lv.border, lh - 2 * lv.border), blk, 0, st, s->Ldet[i], lw, lh, lv.border, 0.001f, i, s->cand, s->cand_n, kAkCandCap);
-        }
-        return UVO_OK;
-    };
-    static const bool use_graph = !(getenv("UVO_AKAZE_GRAPH") && atoi(getenv("UVO_AKAZE_GRAPH")) == 0);      // UVO_AKAZE_GRAPH=0: launch by launch (measurement)
-    if (use_graph) {
-        if (!s->exec) {
-            UVO_HIP_TRY(c, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-            const uvo_status rs = record();
-            hipGraph_t g = nullptr;
-            const hipError_t ee = hipStreamEndCapture(st, &g);
-            if (rs != UVO_OK || ee != hipSuccess || !g) { if (g) (void)hipGraphDestroy(g); if (rs == UVO_OK) c->err = std::string("AKAZE: graph capture: ") + hipGetErrorString(ee); return rs != UVO_OK ? rs : UVO_HIP_ERROR; }
-            s->graph = g;
-            UVO_HIP_TRY(c, hipGraphInstantiate(&s->exec, s->graph, nullptr, nullptr, 0));
-        }
+    if (akaze_use_graph()) {
+        UVO_TRY(akaze_capture(c, s, st));
         UVO_HIP_TRY(c, hipGraphLaunch(s->exec, st));
-    } else UVO_TRY(record());
+    } else UVO_TRY(akaze_record(c, s, st));
     int n_cand = 0;
     UVO_HIP_TRY(c, hipMemcpyAsync(s->h_hist, s->cand_n, sizeof(int), hipMemcpyDeviceToHost, st));
     UVO_HIP_TRY(c, hipStreamSynchronize(st));
@@ -728,7 +742,8 @@ uvo_status akaze_detect(Ctx* c, const uint8_t* gray, int w, int h, int stride, i
         }
     }
     // ---- Do_Subpixel_Refinement (host: a 2 x 2 solve per keypoint on the neighbourhood the candidate record carries) ----
-    std::vector<uvo_keypoint> out;
+    std::vector<uvo_keypoint>& out = s->out;
+    out.clear();
     for (int i = 0; i < s->n; i++) {
         const AkLevel& e = s->lv[i];
         const float ratio = e.octave_ratio;
@@ -758,9 +773,7 @@ uvo_status akaze_detect(Ctx* c, const uint8_t* gray, int w, int h, int stride, i
     const int n = (int)out.size();
     *n_out = n;
     stamp();
-    if (n > s->cap) { c->err = "AKAZE found more keypoints than the context's max_kpts"; return UVO_CAPACITY; }
-    if ((kps || desc) && n > cap) { c->err = "uvo_akaze_detect: output capacity too small"; return UVO_CAPACITY; }
-    if (n == 0) return UVO_OK;
+    if (n > s->cap || n == 0) return UVO_OK;
     // ---- Compute_Keypoints_Orientation, MLDB descriptors ----
     AkPlanes pl;
     memset(&pl, 0, sizeof(pl));
@@ -769,13 +782,51 @@ uvo_status akaze_detect(Ctx* c, const uint8_t* gray, int w, int h, int stride, i
     hipLaunchKernelGGL(k_ak_orientation, dim3((n + 3) / 4), dim3(256), 0, st, pl, s->d_kps, n);
     hipLaunchKernelGGL(k_ak_mldb, dim3((n + 7) / 8), dim3(256), 0, st, pl, s->d_kps, n, s->d_desc);
     UVO_HIP_TRY(c, hipGetLastError());
+    if (dbg) UVO_HIP_TRY(c, hipStreamSynchronize(st));
+    stamp();
+    if (dbg && nph == 5) fprintf(stderr, "[uvo] akaze phases (ms): contrast %.3f | evolution + responses + candidates (%d) %.3f | host suppression + refinement %.3f | orientation + M-LDB (%d keypoints) %.3f\n",
+                                 (tph[1] - tph[0]) * 1e-3, n_cand, (tph[2] - tph[1]) * 1e-3, (tph[3] - tph[2]) * 1e-3, n, (tph[4] - tph[3]) * 1e-3);
+    return UVO_OK;
+}
+uvo_status akaze_detect(Ctx* c, const uint8_t* gray, int w, int h, int stride, int mem, uvo_keypoint* kps, uint8_t* desc, int cap, int* n_out)
+{
+    *n_out = 0;
+    if (w < 16 || h < 16 || w > c->max_w || h > c->max_h || stride < w) { c->err = "uvo_akaze_detect: image size outside the context's limits"; return UVO_INVALID_ARG; }
+    AkazeWs* s = akaze_ws(c, w, h);
+    if (!s) { c->err = "AKAZE workspace allocation failed"; return UVO_HIP_ERROR; }
+    hipStream_t st = c->stream;
+    UVO_TRY(akaze_run(c, s, st, gray, w, h, stride, mem, n_out));
+    const int n = *n_out;
+    if (n > s->cap) { c->err = "AKAZE found more keypoints than the context's max_kpts"; return UVO_CAPACITY; }
+    if ((kps || desc) && n > cap) { c->err = "uvo_akaze_detect: output capacity too small"; return UVO_CAPACITY; }
+    if (n == 0) return UVO_OK;
     if (kps) UVO_HIP_TRY(c, hipMemcpyAsync(kps, s->d_kps, sizeof(uvo_keypoint) * n, hipMemcpyDeviceToHost, st));
     if (desc) UVO_HIP_TRY(c, hipMemcpyAsync(desc, s->d_desc, (size_t)kAkDescBytes * n, hipMemcpyDeviceToHost, st));
     UVO_HIP_TRY(c, hipStreamSynchronize(st));
-    stamp();
-    if (dbg && nph == 5) fprintf(stderr, "[uvo] akaze phases (ms): contrast %.3f | evolution + responses + candidates (%d) %.3f | host suppression + refinement %.3f | orientation + M-LDB + copies (%d keypoints) %.3f\n",
-                                 (tph[1] - tph[0]) * 1e-3, n_cand, (tph[2] - tph[1]) * 1e-3, (tph[3] - tph[2]) * 1e-3, n, (tph[4] - tph[3]) * 1e-3);
     return UVO_OK;
+}
+
+// ---- detect_features' AKAZE branch inside the fused steps.  The lane's workspace is made (and its evolution graph captured on the
+// lane's stream) when a sequence starts, not in it; both images of a pair go through it in turn -- the host stages between the launches
+// (contrast factor, duplicate suppression, refinement) wait for the device, so nothing is gained by a second one.
+uvo_status akaze_prepare_lane(Ctx* c, int w, int h)
+{
+    AkazeWs* s = akaze_ws(c, w, h);
+    if (!s) { c->err = "AKAZE workspace allocation failed"; return UVO_HIP_ERROR; }
+    if (akaze_use_graph()) UVO_TRY(akaze_capture(c, s, c->stream));
+    return UVO_OK;
+}
+uvo_status akaze_detect_lane(Ctx* c, int slot, int* n)
+{
+    const int w = c->img_w, h = c->img_h;
+    *n = 0;
+    if (w < 16 || h < 16) { c->err = "AKAZE: image too small"; return UVO_INVALID_ARG; }
+    UVO_TRY(akaze_prepare_lane(c, w, h));                                    // (a no-op once the lane is primed)
+    AkazeWs* s = static_cast<AkazeWs*>(c->akaze_ws);
+    UVO_TRY(akaze_run(c, s, c->stream, c->img[slot], w, h, w, UVO_MEM_DEVICE, n));
+    if (*n > c->cap || *n == 0) return UVO_OK;
+    UVO_HIP_TRY(c, hipMemcpyAsync(c->det[slot].kps, s->d_kps, sizeof(uvo_keypoint) * (size_t)*n, hipMemcpyDeviceToDevice, c->stream));
+    return pad_binary_rows(c, c->stream, s->d_desc, *n, kAkDescBytes, reinterpret_cast<uint8_t*>(c->det[slot].desc));
 }
 // intermediates for the parity tests: what = 0 Lt, 1 Lsmooth, 2 Lx, 3 Ly, 4 Ldet of `level` after the last akaze_detect
 uvo_status akaze_plane(Ctx* c, int level, int what, float* out, int cap_floats, int* ow, int* oh)

@@ -559,10 +559,75 @@ static uvo_status check_cand_overflow(uvo_ctx* c, int nimg)
     return UVO_OK;
 }
 
-// detect_features inside the fused steps: the SURF branch (VOU:114-119) or, when the context's feature detector is "SIFT", VOU:107-112
+// detect_features' AKAZE / ORB branch (VOU:93-105) inside the fused steps: each image through the lane's detector in turn (their host stages
+// -- AKAZE's contrast factor and duplicate suppression, ORB's retainBest rankings -- run on this thread and wait for the device), then the
+// counts are published where the SURF detector leaves its own: min(n, max_kpts) in d_counts[CN_NL + i], n in d_counts[CN_CAND0 + i] (more
+// than max_kpts is reported by the caller's overflow check; no list is cut), and the VO:556 gate evaluated on the device
+__global__ void k_binary_publish(int n0, int n1, int* cn, int cap, int nimg, int gate_min_features)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    for (int i = 0; i < nimg; i++) {
+        const int n = i ? n1 : n0;
+        cn[CN_CAND0 + i] = n;
+        cn[CN_NL + i] = n < cap ? n : cap;
+    }
+    cn[CN_ORI_DROP] = 0;
+    if (gate_min_features >= 0 && nimg == 2)                           // VO:556: both images need >= MIN_NUM_FEATURES keypoints, else no stereo matching
+        cn[CN_NQA] = (cn[CN_NL] >= gate_min_features && cn[CN_NR] >= gate_min_features) ? cn[CN_NL] : 0;
+}
+static uvo_status binary_detect_lane(Ctx* c, int nimg, int gate_min_features)
+{
+    int n[2] = {0, 0};
+    for (int i = 0; i < nimg; i++) UVO_TRY(c->loop_detector() == 2 ? akaze_detect_lane(c, i, &n[i]) : orb_detect_lane(c, i, &n[i]));
+    hipLaunchKernelGGL(k_binary_publish, dim3(1), dim3(64), 0, c->stream, n[0], n[1], c->d_counts, c->cap, nimg, gate_min_features);
+    UVO_HIP_TRY(c, hipGetLastError());
+    return UVO_OK;
+}
+
+// detect_features inside the fused steps: the SURF branch (VOU:114-119), or the branch of the context's feature detector: SIFT (VOU:107-112),
+// AKAZE (VOU:93-98), ORB (VOU:100-105)
 static uvo_status detect_dispatch(Ctx* c, int nimg, int gate_min_features = -1)
 {
+    if (c->use_binary()) return binary_detect_lane(c, nimg, gate_min_features);
     return c->use_sift() ? sift_detect_lane(c, nimg, gate_min_features) : surf_detect(c, nimg, gate_min_features);
+}
+// the detector's per-lane workspaces at the sequence's image size (allocation synchronises the device: done when a sequence starts, not in it)
+static uvo_status prepare_lane_detectors(uvo_ctx* c, int w, int h, int nimg)
+{
+    for (Ctx* l : c->lanes) {
+        uvo_status st = UVO_OK;
+        if (c->use_sift()) st = sift_prepare_lane(l, w, h, nimg);
+        else if (c->loop_detector() == 2) st = akaze_prepare_lane(l, w, h);
+        else if (c->loop_detector() == 3) st = orb_prepare_lane(l, w, h);
+        if (st != UVO_OK) { if (l != c) c->err = l->err; return st; }
+    }
+    return UVO_OK;
+}
+// ORB's sampling table is the caller's to give (uvo_orb_set_pattern): a step that needs descriptors without it is refused before anything is queued
+static uvo_status need_loop_table(uvo_ctx* c)
+{
+    if (c->loop_detector() == 3 && !orb_has_pattern(c)) return fail(c, UVO_INVALID_ARG, kOrbLoopNoTable);
+    return UVO_OK;
+}
+
+static uvo_status set_loop_detector(uvo_ctx* c, int det)
+{
+    if (c->n_pending != 0) return fail(c, UVO_INVALID_ARG, "the feature detector cannot change while pairs are in flight");
+    if (det != c->detector && (c->vo_initialized || c->mono_initialized))
+        return fail(c, UVO_INVALID_ARG, "the feature detector changes the descriptors: the previous frame's set held by the running VO loop would not match (uvo_stereo_reset / uvo_mono_reset first)");
+    if (det != c->detector) {                                           // the lanes' workspaces of the detector left behind go (SIFT: 0.5 GB per image slot)
+        (void)hipSetDevice(c->device);
+        for (Ctx* l : c->lanes) {
+            if (l->stream) (void)hipStreamSynchronize(l->stream);
+            if (l->pnp_stream) (void)hipStreamSynchronize(l->pnp_stream);
+            if (c->detector == 1) sift_ws_free(l);
+            // lane 0's AKAZE / ORB workspaces are also the operators' (uvo_akaze_detect / uvo_orb_detect): they, and the ORB table, stay
+            if (l != c && c->detector == 2) akaze_ws_free(l);
+            if (l != c && c->detector == 3) orb_ws_free(l);
+        }
+    }
+    c->detector = det;
+    return UVO_OK;
 }
 
 extern "C" uvo_status uvo_ctx_set_feature_detector(uvo_ctx* c, const char* name)
@@ -570,15 +635,17 @@ try {
     if (!c || !name) return UVO_INVALID_ARG;
     const bool sift = strcmp(name, "SIFT") == 0;
     if (!sift && strcmp(name, "SURF") != 0) return fail(c, UVO_INVALID_ARG, "uvo_ctx_set_feature_detector: the fused steps run on \"SURF\" or \"SIFT\" (AKAZE and ORB are the operators uvo_akaze_detect / uvo_orb_detect + the Hamming matcher)");
-    if (c->n_pending != 0) return fail(c, UVO_INVALID_ARG, "the feature detector cannot change while pairs are in flight");
-    if ((sift ? 1 : 0) != c->feature_sift && (c->vo_initialized || c->mono_initialized))
-        return fail(c, UVO_INVALID_ARG, "the feature detector changes the descriptors: the previous frame's set held by the running VO loop would not match (uvo_stereo_reset / uvo_mono_reset first)");
-    if (!sift && c->feature_sift) {                                     // back to SURF: the lanes' scale-space workspaces (0.5 GB per image slot) go
-        (void)hipSetDevice(c->device);
-        for (Ctx* l : c->lanes) { if (l->stream) (void)hipStreamSynchronize(l->stream); if (l->pnp_stream) (void)hipStreamSynchronize(l->pnp_stream); sift_ws_free(l); }
-    }
-    c->feature_sift = sift ? 1 : 0;
-    return UVO_OK;
+    return set_loop_detector(c, sift ? 1 : 0);
+} UVO_ABI_CATCH(c)
+
+extern "C" uvo_status uvo_ctx_set_loop_detector(uvo_ctx* c, const char* name)
+try {
+    if (!c || !name) return UVO_INVALID_ARG;
+    static const char* const kNames[4] = { "SURF", "SIFT", "AKAZE", "ORB" };
+    int det = -1;
+    for (int i = 0; i < 4; i++) if (strcmp(name, kNames[i]) == 0) det = i;
+    if (det < 0) return fail(c, UVO_INVALID_ARG, "uvo_ctx_set_loop_detector: \"SURF\", \"SIFT\", \"AKAZE\" or \"ORB\"");
+    return set_loop_detector(c, det);
 } UVO_ABI_CATCH(c)
 
 extern "C" uvo_status uvo_surf_detect(uvo_ctx* c, const uint8_t* gray, int w, int h, int stride, int mem,
@@ -792,6 +859,33 @@ try {
     UVO_HIP_TRY(c, hipStreamSynchronize(c->stream));
     return UVO_OK;
 } UVO_ABI_CATCH(c)
+// test hook: the fused steps' matchers on binary rows (match_knn2_bin) -- the rows padded to 64 bytes as the detectors leave them, the counts
+// read on the device and the grid sized from max_kpts, as inside the steps
+extern "C" uvo_status uvo_match_loop_knn2(uvo_ctx* c, const uint8_t* d1, int n1, const uint8_t* d2, int n2, int bytes, int metric, int* idx, float* dist)
+try {
+    if (!c || n1 < 0 || n2 < 0 || (n1 && !d1) || (n2 && !d2) || (n1 && (!idx || !dist))) return UVO_INVALID_ARG;
+    if (bytes < 1 || bytes > 4 * kBinRowWords || (metric != BIN_HAMMING && metric != BIN_L2)) return fail(c, UVO_INVALID_ARG, "uvo_match_loop_knn2: rows of 1..64 bytes, metric 0 (Hamming) or 1 (L2)");
+    if (n1 > c->cap || n2 > c->cap) return fail(c, UVO_CAPACITY, "descriptor count exceeds the context's max_kpts");
+    (void)hipSetDevice(c->device);
+    UVO_TRY(need_idle(c, "uvo_match_loop_knn2"));
+    uint8_t* rows[2];
+    const uint8_t* src[2] = { d1, d2 }; const int n[2] = { n1, n2 };
+    for (int i = 0; i < 2; i++) {                      // raw rows in the upper half of the staging buffer (cap x 512 bytes), padded rows in the lower
+        rows[i] = reinterpret_cast<uint8_t*>(c->d_tmp_desc[i]);
+        uint8_t* raw = rows[i] + (size_t)c->cap * 256;
+        if (n[i]) UVO_HIP_TRY(c, hipMemcpyAsync(raw, src[i], (size_t)bytes * n[i], hipMemcpyHostToDevice, c->stream));
+        UVO_TRY(pad_binary_rows(c, c->stream, raw, n[i], bytes, rows[i]));
+    }
+    UVO_HIP_TRY(c, hipMemcpyAsync(c->d_tmp_idx, n, sizeof(n), hipMemcpyHostToDevice, c->stream));
+    UVO_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    UVO_TRY(match_knn2_bin(c, metric, rows[0], c->d_tmp_idx, c->cap, rows[1], c->d_tmp_idx + 1, c->cap));
+    if (n1) {
+        UVO_HIP_TRY(c, hipMemcpyAsync(idx, c->d_knn_idx, sizeof(int) * 2 * n1, hipMemcpyDeviceToHost, c->stream));
+        UVO_HIP_TRY(c, hipMemcpyAsync(dist, c->d_knn_dist, sizeof(float) * 2 * n1, hipMemcpyDeviceToHost, c->stream));
+    }
+    UVO_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return UVO_OK;
+} UVO_ABI_CATCH(c)
 extern "C" uvo_status uvo_match_knn2_ratio_hamming(uvo_ctx* c, const uint8_t* d1, int n1, const uint8_t* d2, int n2, int bytes, int mem,
                                                    float ratio, uvo_dmatch* out, int cap, int* m)
 try {
@@ -922,7 +1016,7 @@ __device__ __forceinline__ void gather_after_stereo(int bx, const uvo_dmatch* m,
     const int row = bx * 16 + (threadIdx.x >> 4), sub = threadIdx.x & 15;
     if (row >= meff) return;
     const int q = m[row].queryIdx, t = m[row].trainIdx;
-    for (int v = sub; v < dim / 4; v += 16) reinterpret_cast<float4*>(odL + (size_t)row * dim)[v] = reinterpret_cast<const float4*>(dL + (size_t)q * dim)[v];
+    for (int v = sub; v < dim / 4; v += 16) reinterpret_cast<uint4*>(odL + (size_t)row * dim)[v] = reinterpret_cast<const uint4*>(dL + (size_t)q * dim)[v];   // rows as words
     if (sub == 0) { okL[row] = kL[q]; okR[row] = kR[t]; }
 }
 // VO:601-617, 637-640: points of the triangular matches (prev left / prev right by queryIdx, curr left by trainIdx).  pmap (two-pair
@@ -957,15 +1051,16 @@ __global__ void k_gather_kps_idx(const uvo_keypoint* src, const int* idx, int n,
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) dst[i] = src[idx[i]];
 }
+// rows of `dim` 32-bit words (floats, or the words of binary rows), moved as words
 __global__ void k_gather_desc_idx(const float* src, int nsrc, const int* idx, int n, float* dst, int dim)
 {
     int row = blockIdx.x * 16 + (threadIdx.x >> 4), sub = threadIdx.x & 15;
     if (row >= n) return;
     int q = idx[row];
     for (int e = sub; e < dim / 4; e += 16) {
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);      // the reference leaves an out-of-range row uninitialised (VOU:690)
-        if (q >= 0 && q < nsrc) v = reinterpret_cast<const float4*>(src + (size_t)q * dim)[e];
-        reinterpret_cast<float4*>(dst + (size_t)row * dim)[e] = v;
+        uint4 v = make_uint4(0u, 0u, 0u, 0u);            // the reference leaves an out-of-range row uninitialised (VOU:690)
+        if (q >= 0 && q < nsrc) v = reinterpret_cast<const uint4*>(src + (size_t)q * dim)[e];
+        reinterpret_cast<uint4*>(dst + (size_t)row * dim)[e] = v;
     }
 }
 
@@ -1023,7 +1118,9 @@ static uvo_status stereo_init_step(uvo_ctx* c, uvo_stereo_result* out)
     c->last_nL = nL; c->last_nR = nR; c->last_M = c->last_T = c->last_G = c->last_ninl = 0;
     c->kp_hint = nL > nR ? nL : nR;
     if (nL >= p.MIN_NUM_FEATURES && nR >= p.MIN_NUM_FEATURES) {                         // VO:489
-        UVO_TRY(match_knn2(c, c->det[0].desc, nullptr, nL, c->det[1].desc, nullptr, nR));
+        if (c->use_binary()) UVO_TRY(match_knn2_bin(c, BIN_HAMMING, reinterpret_cast<const uint8_t*>(c->det[0].desc), nullptr, nL,
+                                                    reinterpret_cast<const uint8_t*>(c->det[1].desc), nullptr, nR));                // VOU:520-524
+        else UVO_TRY(match_knn2(c, c->det[0].desc, nullptr, nL, c->det[1].desc, nullptr, nR));
         UVO_TRY(match_ratio_compact(c, nullptr, nL, (float)p.LOWE_RATIO_THRESHOLD, c->d_matches[0], c->d_nmatch, c->cap));
         UVO_TRY(read_counts(c));
         int m = c->h_counts[CN_M];
@@ -1049,7 +1146,7 @@ static uvo_status stereo_init_step(uvo_ctx* c, uvo_stereo_result* out)
         c->as_w ^= 1; c->prev_lane = 0; c->prev_buf = b; c->prev_sync = true;
         int* d_idx = c->d_tmp_idx;     // scratch
         UVO_HIP_TRY(c, hipMemcpyAsync(d_idx, iL.data(), sizeof(int) * total, hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(k_gather_desc_idx, dim3((total + 15) / 16), dim3(256), 0, c->stream, c->det[0].desc, nL, d_idx, total, c->d_as_descL[b], c->desc_dim());
+        hipLaunchKernelGGL(k_gather_desc_idx, dim3((total + 15) / 16), dim3(256), 0, c->stream, c->det[0].desc, nL, d_idx, total, c->d_as_descL[b], c->loop_words());
         hipLaunchKernelGGL(k_gather_kps_idx, dim3((total + 255) / 256), dim3(256), 0, c->stream, c->det[0].kps, d_idx, total, c->d_as_kpsL[b]);
         UVO_HIP_TRY(c, hipStreamSynchronize(c->stream));
         UVO_HIP_TRY(c, hipMemcpyAsync(d_idx, iR.data(), sizeof(int) * total, hipMemcpyHostToDevice, c->stream));
@@ -1110,6 +1207,7 @@ extern "C" uvo_status uvo_stereo_submit(uvo_ctx* c, const uint8_t* left, const u
 try {
     if (!c || !left || !right) return UVO_INVALID_ARG;
     if (!c->rig_set) return fail(c, UVO_INVALID_ARG, "uvo_stereo_set_rig has not been called");
+    UVO_TRY(need_loop_table(c));
     const int depth = (int)c->lanes.size();
     if (c->n_pending >= depth) return fail(c, UVO_INVALID_ARG, "uvo_stereo_submit: the pipeline is full; collect a pair first (uvo_stereo_set_depth)");
     if (c->timing && c->n_pending > 0) return fail(c, UVO_INVALID_ARG, "timing mode measures one pair at a time: collect before submitting");
@@ -1125,7 +1223,7 @@ try {
         UVO_TRY(detect_dispatch(c, 2));
         UVO_TRY(stereo_init_step(c, &res));
         UVO_TRY(prime_lanes(c, w, h));
-        if (c->use_sift()) for (Ctx* l : c->lanes) { uvo_status st_ = sift_prepare_lane(l, w, h, 2); if (st_ != UVO_OK) { if (l != c) c->err = l->err; return st_; } }
+        UVO_TRY(prepare_lane_detectors(c, w, h, 2));
         c->stereo_init_results.push_back(res);
         c->inflight[c->n_pending++] = Ctx::kInflightStereoInit; c->n_submitted++;
         c->next_lane = 0;
@@ -1150,7 +1248,7 @@ try {
     }
     // a pair joins a two-pair launch when the mode is on and the pair can take that path: upright SURF, not the synchronous step,
     // no per-stage timing, two lanes at least
-    const bool may_batch = c->batch == 2 && depth >= 2 && !c->in_sync_step && !c->timing && !c->use_sift() && p.SURF_UPRIGHT && p.SURF_OCTAVES_NUMBER == 4;
+    const bool may_batch = c->batch == 2 && depth >= 2 && !c->in_sync_step && !c->timing && c->loop_detector() == 0 && p.SURF_UPRIGHT && p.SURF_OCTAVES_NUMBER == 4;
     uvo_ctx* S = c->stashed_lane >= 0 ? static_cast<uvo_ctx*>(c->lanes[c->stashed_lane]) : nullptr;      // the pair before, waiting for this one
     // uploads: a pair's images go to its own lane's buffers (or are read in place); the copies of a two-pair launch are ordered on the
     // stream that will run the kernels -- the first lane's
@@ -1233,11 +1331,16 @@ static uvo_status queue_stage_a(uvo_ctx* c, uvo_ctx* A, uvo_ctx* B)
     if (!pa.prev_sync && P != A) UVO_HIP_TRY(c, hipStreamWaitEvent(st, P->evAS, 0));
     GatherPair gp;
     gp.g[0] = GatherArgs{ A->d_matches[0], A->d_matches[1], cn, A->det[0].kps, A->det[1].kps, A->det[0].desc,
-                          A->d_as_kpsL[curr], A->d_as_kpsR[curr], A->d_as_descL[curr], A->desc_dim(), P->d_as_kpsL[prev], P->d_as_kpsR[prev],
+                          A->d_as_kpsL[curr], A->d_as_kpsR[curr], A->d_as_descL[curr], A->loop_words(), P->d_as_kpsL[prev], P->d_as_kpsR[prev],
                           A->d_x1, A->d_x2, A->d_xc, (cap + 15) / 16, nullptr };
     if (!B) {
-        LANE_TRY(match_knn2_two(A, A->det[0].desc, cn + CN_NQA, A->det[1].desc, cn + CN_NR,
-                                P->d_as_descL[prev], P->d_as_n + prev, A->det[0].desc, cn + CN_NL, cap));
+        if (A->use_binary()) {                                                             // VOU:520-524: Hamming on the padded rows
+            auto u8 = [](const float* d) { return reinterpret_cast<const uint8_t*>(d); };
+            LANE_TRY(match_knn2_bin_two(A, BIN_HAMMING, u8(A->det[0].desc), cn + CN_NQA, u8(A->det[1].desc), cn + CN_NR,
+                                        u8(P->d_as_descL[prev]), P->d_as_n + prev, u8(A->det[0].desc), cn + CN_NL, cap));
+        } else
+            LANE_TRY(match_knn2_two(A, A->det[0].desc, cn + CN_NQA, A->det[1].desc, cn + CN_NR,
+                                    P->d_as_descL[prev], P->d_as_n + prev, A->det[0].desc, cn + CN_NL, cap));
         const GateArgs gate_b = { 1, cn, p.MIN_NUM_FEATURES, cap, A->d_as_n + curr, P->d_as_n + prev };       // VO:567
         const GateArgs gate_c = { 2, cn, p.MIN_NUM_FEATURES, cap, nullptr, nullptr };                           // VO:626
         LANE_TRY(match_ratio_compact2(A, ratio, cn + CN_NQA, A->d_matches[0], cn + CN_M, gate_b,
@@ -1248,7 +1351,7 @@ static uvo_status queue_stage_a(uvo_ctx* c, uvo_ctx* A, uvo_ctx* B)
         LANE_TRY(match_two_pairs(A, B, P->d_as_descL[prev], P->d_as_n + prev, P->d_as_n + prev, curr, currB, ratio, p.MIN_NUM_FEATURES));
         // the second pair's triangular points: rows of the first pair's set, through its stereo matches, from its keypoint lists
         gp.g[1] = GatherArgs{ B->d_matches[0], B->d_matches[1], B->d_counts, B->det[0].kps, B->det[1].kps, B->det[0].desc,
-                              B->d_as_kpsL[currB], B->d_as_kpsR[currB], B->d_as_descL[currB], B->desc_dim(), A->det[0].kps, A->det[1].kps,
+                              B->d_as_kpsL[currB], B->d_as_kpsR[currB], B->d_as_descL[currB], B->loop_words(), A->det[0].kps, A->det[1].kps,
                               B->d_x1, B->d_x2, B->d_xc, (cap + 15) / 16, A->d_matches[0] };
     }
     const double I[9] = {1,0,0,0,1,0,0,0,1}, z[3] = {0,0,0};
@@ -1532,6 +1635,12 @@ try {
     const Ctx* c = m->lanes.empty() ? m : m->lanes[m->last_lane];    // the lane of the last collected pair
     const void* src = nullptr; int count = 0; size_t esz = 0;
     std::string w(what);
+    if (c->use_binary() && (w == "desc_left" || w == "desc_right")) {        // AKAZE / ORB: the rows' bytes, without the padding
+        const int bytes = c->desc_bytes(), n = w == "desc_left" ? c->last_nL : c->last_nR;
+        if ((size_t)n * bytes > (size_t)cap_bytes) return -n;
+        if (n && hipMemcpy2D(out, bytes, c->det[w == "desc_left" ? 0 : 1].desc, 4 * kBinRowWords, bytes, n, hipMemcpyDeviceToHost) != hipSuccess) return 0;
+        return n;
+    }
     if (w == "kps_left") { src = c->det[0].kps; count = c->last_nL; esz = sizeof(uvo_keypoint); }
     else if (w == "kps_right") { src = c->det[1].kps; count = c->last_nR; esz = sizeof(uvo_keypoint); }
     else if (w == "desc_left") { src = c->det[0].desc; count = c->last_nL; esz = c->desc_dim() * sizeof(float); }
@@ -1967,6 +2076,7 @@ try {
     if (!c || !img || !out) return UVO_INVALID_ARG;
     if (!c->mono_cam_set) return fail(c, UVO_INVALID_ARG, "uvo_mono_set_camera has not been called");
     if (c->mono_pipelined) return fail(c, UVO_INVALID_ARG, "uvo_mono_step after uvo_mono_submit: call uvo_mono_reset first (the previous frame is held by the pipeline)");
+    UVO_TRY(need_loop_table(c));
     (void)hipSetDevice(c->device);
     const uvo_params& p = c->p;
     Range r_step("uvo:mono_step");
@@ -1981,7 +2091,9 @@ try {
     // is decided below, from the counts
     c->mono_matched = c->mono_initialized && c->mono_n_prev > 0;
     if (c->mono_matched) {
-        UVO_TRY(match_knn2(c, c->d_as_descL[0], nullptr, c->mono_n_prev, c->det[0].desc, c->det[0].n, c->cap));
+        if (c->use_binary()) UVO_TRY(match_knn2_bin(c, BIN_L2, reinterpret_cast<const uint8_t*>(c->d_as_descL[0]), nullptr, c->mono_n_prev,     // NORM_L2 on CV_8U rows
+                                                    reinterpret_cast<const uint8_t*>(c->det[0].desc), c->det[0].n, c->cap));
+        else UVO_TRY(match_knn2(c, c->d_as_descL[0], nullptr, c->mono_n_prev, c->det[0].desc, c->det[0].n, c->cap));
         UVO_TRY(match_ratio_compact(c, nullptr, c->mono_n_prev, (float)p.LOWE_RATIO_THRESHOLD, c->d_matches[0], c->d_nmatch, c->cap));
         hipLaunchKernelGGL(k_gather_mono_pairs, dim3((c->cap + 255) / 256), dim3(256), 0, c->stream, c->d_matches[0], c->d_counts + CN_M, c->cap,
                            c->d_as_kpsL[0], c->det[0].kps, c->d_x1, c->d_x2);
@@ -1998,7 +2110,7 @@ try {
     c->mono_dev_n = n;
     auto roll_state = [&]() -> uvo_status {                                                // VO:279-282 / VO:392-395 (stream-ordered: the next frame's kernels follow)
         if (n) {
-            UVO_HIP_TRY(c, hipMemcpyAsync(c->d_as_descL[0], c->det[0].desc, sizeof(float) * c->desc_dim() * (size_t)n, hipMemcpyDeviceToDevice, c->stream));
+            UVO_HIP_TRY(c, hipMemcpyAsync(c->d_as_descL[0], c->det[0].desc, sizeof(float) * c->loop_words() * (size_t)n, hipMemcpyDeviceToDevice, c->stream));
             UVO_HIP_TRY(c, hipMemcpyAsync(c->d_as_kpsL[0], c->det[0].kps, sizeof(uvo_keypoint) * (size_t)n, hipMemcpyDeviceToDevice, c->stream));
         }
         c->mono_n_prev = n;
@@ -2022,6 +2134,7 @@ try {
     if (!c->mono_cam_set) return fail(c, UVO_INVALID_ARG, "uvo_mono_set_camera has not been called");
     const int depth = (int)c->lanes.size();
     if (depth < 2) return fail(c, UVO_INVALID_ARG, "uvo_mono_submit needs at least two lanes (uvo_stereo_set_depth): a frame is matched against the previous lane's buffers");
+    UVO_TRY(need_loop_table(c));
     if (c->n_pending >= depth) return fail(c, UVO_INVALID_ARG, "uvo_mono_submit: the pipeline is full; collect a frame first (uvo_stereo_set_depth)");
     (void)hipSetDevice(c->device);
     Range r_submit("uvo:mono_submit");
@@ -2036,7 +2149,7 @@ try {
         c->prev_lane = 0; c->next_lane = 1 % depth;
         UVO_HIP_TRY(c, hipEventRecord(c->evDet, c->stream));                               // lane 0 holds the frame the next one matches against
         UVO_TRY(prime_lanes(c, w, h));
-        if (c->use_sift()) for (Ctx* l : c->lanes) { uvo_status st_ = sift_prepare_lane(l, w, h, 1); if (st_ != UVO_OK) { if (l != c) c->err = l->err; return st_; } }
+        UVO_TRY(prepare_lane_detectors(c, w, h, 1));
         return UVO_OK;
     }
     const int li = c->next_lane;
@@ -2059,7 +2172,9 @@ try {
     const int cap = c->cap;
     if (P != L) UVO_HIP_TRY(c, hipStreamWaitEvent(st, P->evDet, 0));
     // match_features 7-arg (VO:287 -> VOU:551-573): query = previous frame, train = this frame; the counts stay on the device
-    LANE_TRY(match_knn2(L, P->det[0].desc, P->det[0].n, cap, L->det[0].desc, L->det[0].n, cap));
+    if (L->use_binary()) LANE_TRY(match_knn2_bin(L, BIN_L2, reinterpret_cast<const uint8_t*>(P->det[0].desc), P->det[0].n, cap,
+                                                 reinterpret_cast<const uint8_t*>(L->det[0].desc), L->det[0].n, cap));
+    else LANE_TRY(match_knn2(L, P->det[0].desc, P->det[0].n, cap, L->det[0].desc, L->det[0].n, cap));
     LANE_TRY(match_ratio_compact(L, P->det[0].n, cap, (float)p.LOWE_RATIO_THRESHOLD, L->d_matches[0], cn + CN_M, cap));
     hipLaunchKernelGGL(k_gather_mono_pairs, dim3((cap + 255) / 256), dim3(256), 0, st, L->d_matches[0], cn + CN_M, cap,
                        P->det[0].kps, L->det[0].kps, L->d_x1, L->d_x2);

@@ -617,3 +617,161 @@ uvo_status match_knn2_hamming(Ctx* c, const uint8_t* d_q, int nq, const uint8_t*
 }
 
 }  // namespace uvo
+
+namespace uvo {
+
+// ------------------------------------------------------------------------------------------
+// The matchers of the fused steps on AKAZE / ORB rows.  The detector leaves every row as kBinRowWords 32-bit words (64 bytes, zero past
+// the descriptor's 61 or 32), so a row is four 16-byte loads and the zero tail adds nothing to either distance.  The counts are the
+// device's (the detector's, the gates'), so the grid is sized from the capacity and a workgroup whose queries or train chunk lie past
+// the counts returns at once.
+//   k_bin_partial : a thread per query, blockIdx.y = a chunk of 512 train rows staged in LDS, blockIdx.z = the problem: the chunk's best two
+//   k_bin_merge   : a thread per query merges the chunks' pairs in chunk order -> the kNN buffers k_match_compact reads
+// Metrics.  BIN_HAMMING: popcount of the XOR (the stereo loop, VOU:520-524).  BIN_L2: the mono loop's BFMatcher(NORM_L2) on CV_8U rows
+// (VOU:551-573), which sums the squared byte differences in integers and takes sqrtf: here |a|^2 + |b|^2 - 2 a.b with v_dot4_u32_u8,
+// exact in int32 (64 * 255^2 < 2^22).  Both keep the top two by (integer distance, train index) -- BatchDistInvoker's order: below 2^22
+// two different integers never share a float square root (their roots lie more than one float ulp apart), so comparing the integers is
+// comparing OpenCV's float distances.
+// ------------------------------------------------------------------------------------------
+static const int kBinChunk = 512;
+struct BinProb { const uint4* dq; const int* nq_p; int nq_max; const uint4* dt; const int* nt_p; int nt_max; Ham2* part; int* knn_idx; float* knn_dist; };
+struct BinBatch { BinProb p[2]; int cap; };
+
+__device__ __forceinline__ int bin_count(const int* p, int mx) { return p ? max(0, min(*p, mx)) : mx; }
+template <int METRIC>
+__device__ __forceinline__ int bin_dist(const uint4 (&q)[4], int qn, const uint4* __restrict__ t, int tn)
+{
+    if (METRIC == BIN_HAMMING) {
+        int d = 0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) { const uint4 v = t[k]; d += __popc(q[k].x ^ v.x) + __popc(q[k].y ^ v.y) + __popc(q[k].z ^ v.z) + __popc(q[k].w ^ v.w); }
+        return d;
+    }
+    unsigned dot = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const uint4 v = t[k];
+        dot = __builtin_amdgcn_udot4(q[k].x, v.x, dot, false); dot = __builtin_amdgcn_udot4(q[k].y, v.y, dot, false);
+        dot = __builtin_amdgcn_udot4(q[k].z, v.z, dot, false); dot = __builtin_amdgcn_udot4(q[k].w, v.w, dot, false);
+    }
+    return qn + tn - 2 * (int)dot;
+}
+__device__ __forceinline__ int bin_norm(const uint4 (&r)[4])
+{
+    unsigned s = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        s = __builtin_amdgcn_udot4(r[k].x, r[k].x, s, false); s = __builtin_amdgcn_udot4(r[k].y, r[k].y, s, false);
+        s = __builtin_amdgcn_udot4(r[k].z, r[k].z, s, false); s = __builtin_amdgcn_udot4(r[k].w, r[k].w, s, false);
+    }
+    return (int)s;
+}
+
+template <int METRIC>
+__global__ __launch_bounds__(256) void k_bin_partial(BinBatch bb)
+{
+    const BinProb& P = bb.p[blockIdx.z];
+    const int nq = bin_count(P.nq_p, P.nq_max), nt = bin_count(P.nt_p, P.nt_max);
+    const int q = blockIdx.x * 256 + threadIdx.x, t0 = blockIdx.y * kBinChunk;
+    if ((int)blockIdx.x * 256 >= nq || t0 >= nt) return;                  // the whole workgroup: past the device's counts
+    const int cnt = min(kBinChunk, nt - t0);
+    __shared__ uint4 s_rows[kBinChunk * 4];                                // 512 rows x 64 bytes
+    __shared__ int s_tn[kBinChunk];                                        // |t|^2 (BIN_L2)
+    const uint4* __restrict__ src = P.dt + (size_t)t0 * 4;
+    for (int e = threadIdx.x; e < cnt * 4; e += 256) s_rows[e] = src[e];
+    uint4 qv[4];
+    const uint4* qrow = P.dq + (size_t)min(q, nq - 1) * 4;
+#pragma unroll
+    for (int k = 0; k < 4; k++) qv[k] = qrow[k];
+    const int qn = METRIC == BIN_L2 ? bin_norm(qv) : 0;
+    __syncthreads();
+    if (METRIC == BIN_L2) {
+        for (int r = threadIdx.x; r < cnt; r += 256) { uint4 rv[4]; for (int k = 0; k < 4; k++) rv[k] = s_rows[r * 4 + k]; s_tn[r] = bin_norm(rv); }
+        __syncthreads();
+    }
+    Ham2 best = { 0x7FFFFFFF, -1, 0x7FFFFFFF, -1 };
+    for (int r = 0; r < cnt; r++)                                          // rows in index order: the same address on every lane, a broadcast
+        ham_top2(bin_dist<METRIC>(qv, qn, s_rows + r * 4, METRIC == BIN_L2 ? s_tn[r] : 0), t0 + r, best);
+    if (q < nq) P.part[(size_t)blockIdx.y * bb.cap + q] = best;
+}
+template <int METRIC>
+__global__ __launch_bounds__(256) void k_bin_merge(BinBatch bb)
+{
+    const BinProb& P = bb.p[blockIdx.y];
+    const int nq = bin_count(P.nq_p, P.nq_max), nt = bin_count(P.nt_p, P.nt_max);
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= nq) return;
+    Ham2 best = { 0x7FFFFFFF, -1, 0x7FFFFFFF, -1 };
+    const int nchunks = (nt + kBinChunk - 1) / kBinChunk;
+    for (int c = 0; c < nchunks; c++) {
+        const Ham2 p = P.part[(size_t)c * bb.cap + q];
+        if (p.i0 >= 0) ham_top2(p.d0, p.i0, best);
+        if (p.i1 >= 0) ham_top2(p.d1, p.i1, best);
+    }
+    auto dist = [](int d) { return METRIC == BIN_L2 ? sqrtf((float)d) : (float)d; };
+    P.knn_idx[2*q] = best.i0; P.knn_idx[2*q + 1] = best.i1;
+    P.knn_dist[2*q] = best.i0 >= 0 ? dist(best.d0) : FLT_MAX; P.knn_dist[2*q + 1] = best.i1 >= 0 ? dist(best.d1) : FLT_MAX;
+}
+__global__ void k_pad_binary_rows(const uint8_t* __restrict__ src, int n, int bytes, unsigned* __restrict__ dst)
+{
+    const int e = blockIdx.x * 256 + threadIdx.x, r = e / kBinRowWords, w = e % kBinRowWords;
+    if (r >= n) return;
+    unsigned v = 0;
+    for (int b = 0; b < 4; b++) { const int o = 4 * w + b; if (o < bytes) v |= (unsigned)src[(size_t)r * bytes + o] << (8 * b); }
+    dst[e] = v;
+}
+
+uvo_status pad_binary_rows(Ctx* c, hipStream_t st, const uint8_t* src, int n, int bytes, uint8_t* dst)
+{
+    if (n <= 0) return UVO_OK;
+    if (bytes < 1 || bytes > 4 * kBinRowWords || n > c->cap) { c->err = "binary rows: 1..64 bytes, at most max_kpts rows"; return UVO_INVALID_ARG; }
+    hipLaunchKernelGGL(k_pad_binary_rows, dim3((n * kBinRowWords + 255) / 256), dim3(256), 0, st, src, n, bytes, reinterpret_cast<unsigned*>(dst));
+    UVO_HIP_TRY(c, hipGetLastError());
+    return UVO_OK;
+}
+
+static BinProb make_bin_prob(Ctx* c, int slot, const uint8_t* d_q, const int* d_nq, int nq_max, const uint8_t* d_t, const int* d_nt, int nt_max)
+{
+    BinProb p;
+    p.dq = reinterpret_cast<const uint4*>(d_q); p.nq_p = d_nq; p.nq_max = nq_max;
+    p.dt = reinterpret_cast<const uint4*>(d_t); p.nt_p = d_nt; p.nt_max = nt_max;
+    p.part = reinterpret_cast<Ham2*>(c->d_mpart + (size_t)slot * mpart_elems(c));      // (cap / 512) x cap x 16 B inside the (cap / 128) x cap x 16 B shortlist
+    p.knn_idx = c->d_knn_idx + (size_t)slot * 2 * c->cap; p.knn_dist = c->d_knn_dist + (size_t)slot * 2 * c->cap;
+    return p;
+}
+static uvo_status bin_launch(Ctx* c, int metric, const BinBatch& bb, int np, int nq_max, int nt_max)
+{
+    if (nq_max <= 0 || nt_max <= 0) return UVO_OK;
+    if (nq_max > c->cap || nt_max > c->cap) { c->err = "match: descriptor count exceeds the context's max_kpts"; return UVO_CAPACITY; }
+    const dim3 gp((nq_max + 255) / 256, (nt_max + kBinChunk - 1) / kBinChunk, np), gm((nq_max + 255) / 256, np);
+    {
+        StageTimer t(c, ST_MATCH);
+        if (metric == BIN_L2) hipLaunchKernelGGL(k_bin_partial<BIN_L2>, gp, dim3(256), 0, c->stream, bb);
+        else hipLaunchKernelGGL(k_bin_partial<BIN_HAMMING>, gp, dim3(256), 0, c->stream, bb);
+        UVO_HIP_TRY(c, hipGetLastError());
+    }
+    {
+        StageTimer t(c, ST_MATCH_MERGE);
+        if (metric == BIN_L2) hipLaunchKernelGGL(k_bin_merge<BIN_L2>, gm, dim3(256), 0, c->stream, bb);
+        else hipLaunchKernelGGL(k_bin_merge<BIN_HAMMING>, gm, dim3(256), 0, c->stream, bb);
+        UVO_HIP_TRY(c, hipGetLastError());
+    }
+    return UVO_OK;
+}
+uvo_status match_knn2_bin(Ctx* c, int metric, const uint8_t* d_q, const int* d_nq, int nq_max, const uint8_t* d_t, const int* d_nt, int nt_max)
+{
+    BinBatch bb;
+    bb.p[0] = bb.p[1] = make_bin_prob(c, 0, d_q, d_nq, nq_max, d_t, d_nt, nt_max); bb.cap = c->cap;
+    return bin_launch(c, metric, bb, 1, nq_max, nt_max);
+}
+uvo_status match_knn2_bin_two(Ctx* c, int metric, const uint8_t* d_q0, const int* d_nq0, const uint8_t* d_t0, const int* d_nt0,
+                              const uint8_t* d_q1, const int* d_nq1, const uint8_t* d_t1, const int* d_nt1, int n_max)
+{
+    BinBatch bb;
+    bb.p[0] = make_bin_prob(c, 0, d_q0, d_nq0, n_max, d_t0, d_nt0, n_max);
+    bb.p[1] = make_bin_prob(c, 1, d_q1, d_nq1, n_max, d_t1, d_nt1, n_max);
+    bb.cap = c->cap;
+    return bin_launch(c, metric, bb, 2, n_max, n_max);
+}
+
+}  // namespace uvo

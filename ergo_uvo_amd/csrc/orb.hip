@@ -58,7 +58,10 @@ struct OrbWs {
     int* d_sel = nullptr; float* d_resp = nullptr; int* d_fin = nullptr;
     uvo_keypoint* d_kps = nullptr; uint8_t* d_desc = nullptr;
     int* h_int = nullptr; float* h_f = nullptr;                     // pinned
+    std::vector<int> fin;                                           // host: the final ranking (source of an asynchronous copy: kept until the next call)
 };
+static const char* const kOrbNoTable = "uvo_orb_detect: descriptors need the sampling table -- OpenCV's bit_pattern_31_ (orb.cpp), 256 x (x0, y0, x1, y1) -- through uvo_orb_set_pattern; pass desc = NULL for keypoints only";
+const char* const kOrbLoopNoTable = "ORB in the fused steps: the descriptors need the sampling table -- OpenCV's bit_pattern_31_ (orb.cpp), 256 x (x0, y0, x1, y1) -- through uvo_orb_set_pattern";
 
 // ------------------------------------------------------------------------------------------------ kernels
 __global__ __launch_bounds__(256) void k_orb_resize(const uint8_t* __restrict__ src, int sw, int sh, int sstride, uint8_t* __restrict__ dst, int dw, int dh,
@@ -521,17 +524,12 @@ uvo_status orb_set_pattern(Ctx* c, const int* pattern)
     return UVO_OK;
 }
 
-uvo_status orb_detect(Ctx* c, const uint8_t* gray, int w, int h, int stride, int mem, uvo_keypoint* kps, uint8_t* desc, int cap, int* n_out)
+// detectAndCompute on `gray` (device or host) with workspace s (planned for w x h) and the sampling table `pattern` (device; null: keypoints
+// only): the keypoints and their rows are left in s->d_kps / s->d_desc, *n_out = the count; when it exceeds the list's capacity nothing
+// past the host ranking is computed and the call still returns UVO_OK
+static uvo_status orb_run(Ctx* c, OrbWs* s, hipStream_t st, const uint8_t* gray, int w, int h, int stride, int mem, const int8_t* pattern, int* n_out)
 {
     *n_out = 0;
-    if (w < 16 || h < 16 || w > c->max_w || h > c->max_h || stride < w || w > 65535 || h > 65535) { c->err = "uvo_orb_detect: image size outside the context's limits"; return UVO_INVALID_ARG; }
-    OrbWs* s = orb_state(c);
-    if (desc && !s->has_pattern) {
-        c->err = "uvo_orb_detect: descriptors need the sampling table -- OpenCV's bit_pattern_31_ (orb.cpp), 256 x (x0, y0, x1, y1) -- through uvo_orb_set_pattern; pass desc = NULL for keypoints only";
-        return UVO_INVALID_ARG;
-    }
-    UVO_TRY(orb_plan(c, s, w, h));
-    hipStream_t st = c->stream;
     OrbLevels L = s->L;
     const OrbParams& p = s->p;
     // ---- the pyramid ----
@@ -567,7 +565,8 @@ uvo_status orb_detect(Ctx* c, const uint8_t* gray, int w, int h, int stride, int
     }
     P1.start[L.n] = (int)sel.size();
     const int n1 = (int)sel.size();
-    std::vector<int> fin;
+    std::vector<int>& fin = s->fin;
+    fin.clear();
     if (n1 > 0) {
         UVO_HIP_TRY(c, hipMemcpyAsync(s->d_sel, sel.data(), sizeof(int) * n1, hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(k_orb_harris, dim3((n1 + 255) / 256), dim3(256), 0, st, L, P1, s->d_sel, n1, s->d_pos, s->d_resp);
@@ -579,14 +578,12 @@ uvo_status orb_detect(Ctx* c, const uint8_t* gray, int w, int h, int stride, int
     UVO_HIP_TRY(c, hipGetLastError());
     const int n = (int)fin.size();
     *n_out = n;
-    if (n > s->cap) { c->err = "ORB: more keypoints tie at the per-level cuts than the output list has room for"; return UVO_CAPACITY; }
-    if ((kps || desc) && n > cap) { c->err = "uvo_orb_detect: output capacity too small"; return UVO_CAPACITY; }
-    if (n == 0) return UVO_OK;
+    if (n > s->cap || n == 0) return UVO_OK;
     // ---- ICAngles + the KeyPoint fields; blur; descriptors ----
     OrbUmax um; memcpy(um.u, s->umax, sizeof(um.u));
     UVO_HIP_TRY(c, hipMemcpyAsync(s->d_fin, fin.data(), sizeof(int) * n, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_orb_keypoints, dim3((n + 7) / 8), dim3(256), 0, st, L, P1, um, p.patchSize / 2, p.patchSize, s->d_fin, n, s->d_sel, s->d_pos, s->d_resp, s->d_kps);
-    if (desc) {
+    if (pattern) {
         OrbTaps kk;
         {   // getGaussianKernel(7, 2, CV_32F) x 2^8 rounded: the 8-bit filter engine's integer taps
             double t[7], sum = 0;
@@ -595,13 +592,61 @@ uvo_status orb_detect(Ctx* c, const uint8_t* gray, int w, int h, int stride, int
         }
         for (int l = 0; l < L.n; l++)
             hipLaunchKernelGGL(k_orb_blur, dim3((L.w[l] + 63) / 64, (L.h[l] + 15) / 16), dim3(256), 0, st, L.img[l], L.w[l], L.h[l], L.stride[l], kk, L.blur[l]);
-        hipLaunchKernelGGL(k_orb_describe, dim3((n + 7) / 8), dim3(256), 0, st, L, s->d_pattern, s->d_kps, n, s->d_desc);
+        hipLaunchKernelGGL(k_orb_describe, dim3((n + 7) / 8), dim3(256), 0, st, L, pattern, s->d_kps, n, s->d_desc);
     }
     UVO_HIP_TRY(c, hipGetLastError());
+    return UVO_OK;
+}
+
+uvo_status orb_detect(Ctx* c, const uint8_t* gray, int w, int h, int stride, int mem, uvo_keypoint* kps, uint8_t* desc, int cap, int* n_out)
+{
+    *n_out = 0;
+    if (w < 16 || h < 16 || w > c->max_w || h > c->max_h || stride < w || w > 65535 || h > 65535) { c->err = "uvo_orb_detect: image size outside the context's limits"; return UVO_INVALID_ARG; }
+    OrbWs* s = orb_state(c);
+    if (desc && !s->has_pattern) { c->err = kOrbNoTable; return UVO_INVALID_ARG; }
+    UVO_TRY(orb_plan(c, s, w, h));
+    hipStream_t st = c->stream;
+    UVO_TRY(orb_run(c, s, st, gray, w, h, stride, mem, desc ? s->d_pattern : nullptr, n_out));
+    const int n = *n_out;
+    if (n > s->cap) { c->err = "ORB: more keypoints tie at the per-level cuts than the output list has room for"; return UVO_CAPACITY; }
+    if ((kps || desc) && n > cap) { c->err = "uvo_orb_detect: output capacity too small"; return UVO_CAPACITY; }
+    if (n == 0) return UVO_OK;
     if (kps) UVO_HIP_TRY(c, hipMemcpyAsync(kps, s->d_kps, sizeof(uvo_keypoint) * n, hipMemcpyDeviceToHost, st));
     if (desc) UVO_HIP_TRY(c, hipMemcpyAsync(desc, s->d_desc, (size_t)kOrbDescBytes * n, hipMemcpyDeviceToHost, st));
     UVO_HIP_TRY(c, hipStreamSynchronize(st));
     return UVO_OK;
+}
+
+// ---- detect_features' ORB branch inside the fused steps.  The parameters and the sampling table are the master context's (uvo_orb_configure /
+// uvo_orb_set_pattern); each lane keeps its own level buffers, made when a sequence starts.  Both images of a pair go through them in turn:
+// the two retainBest rankings between the launches wait for the device.
+bool orb_has_pattern(Ctx* c)
+{
+    Ctx* m = c->master ? c->master : c;
+    const OrbWs* s = static_cast<const OrbWs*>(m->orb_ws);
+    return s && s->has_pattern;
+}
+uvo_status orb_prepare_lane(Ctx* c, int w, int h)
+{
+    Ctx* m = c->master ? c->master : c;
+    const OrbWs* ms = orb_state(m);
+    OrbWs* s = orb_state(c);
+    if (s != ms && memcmp(&s->p, &ms->p, sizeof(OrbParams)) != 0) { s->p = ms->p; orb_free_sized(s); }     // the master's configuration
+    return orb_plan(c, s, w, h);
+}
+uvo_status orb_detect_lane(Ctx* c, int slot, int* n)
+{
+    const int w = c->img_w, h = c->img_h;
+    *n = 0;
+    if (w < 16 || h < 16 || w > 65535 || h > 65535) { c->err = "ORB: image size outside the detector's limits"; return UVO_INVALID_ARG; }
+    if (!orb_has_pattern(c)) { c->err = kOrbLoopNoTable; return UVO_INVALID_ARG; }
+    UVO_TRY(orb_prepare_lane(c, w, h));                                       // (a no-op once the lane is primed)
+    OrbWs* s = static_cast<OrbWs*>(c->orb_ws);
+    const OrbWs* ms = static_cast<const OrbWs*>((c->master ? c->master : c)->orb_ws);
+    UVO_TRY(orb_run(c, s, c->stream, c->img[slot], w, h, w, UVO_MEM_DEVICE, ms->d_pattern, n));
+    if (*n > c->cap || *n == 0) return UVO_OK;
+    UVO_HIP_TRY(c, hipMemcpyAsync(c->det[slot].kps, s->d_kps, sizeof(uvo_keypoint) * (size_t)*n, hipMemcpyDeviceToDevice, c->stream));
+    return pad_binary_rows(c, c->stream, s->d_desc, *n, kOrbDescBytes, reinterpret_cast<uint8_t*>(c->det[slot].desc));
 }
 // intermediates for the parity tests: what = 0 the level's image, 1 its blurred copy (after a detect with descriptors), 2 its FAST score map
 uvo_status orb_level_plane(Ctx* c, int level, int what, uint8_t* out, int cap_bytes, int* ow, int* oh)

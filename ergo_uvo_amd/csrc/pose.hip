@@ -484,7 +484,7 @@ __device__ __forceinline__ void tail_gather_rows(const TailArgs& a, int first_ro
     const int row = first_row + (threadIdx.x >> 4), sub = threadIdx.x & 15;
     if (row >= meff) return;
     const int q = a.m_s[row].queryIdx, t = a.m_s[row].trainIdx;
-    for (int v = sub; v < a.dim / 4; v += 16) reinterpret_cast<float4*>(a.odL + (size_t)row * a.dim)[v] = reinterpret_cast<const float4*>(a.dL + (size_t)q * a.dim)[v];
+    for (int v = sub; v < a.dim / 4; v += 16) reinterpret_cast<uint4*>(a.odL + (size_t)row * a.dim)[v] = reinterpret_cast<const uint4*>(a.dL + (size_t)q * a.dim)[v];   // rows as words
     if (sub == 0) { a.okL[row] = a.kL[q]; a.okR[row] = a.kR[t]; }
 }
 // workgroup 0 (when a.fused): extract_3Dpoints; then tri_blocks workgroups of kTriThreads rows to triangulate, p4_blocks that leave
@@ -991,7 +991,7 @@ uvo_status pose_stereo_tail(Ctx* a, Ctx* p, int prev, int curr, int slot, const 
     int* cn = a->d_counts;
     TailArgs ta;
     ta.m_s = a->d_matches[0]; ta.cn = cn; ta.kL = a->det[0].kps; ta.kR = a->det[1].kps; ta.dL = a->det[0].desc;
-    ta.okL = a->d_as_kpsL[curr]; ta.okR = a->d_as_kpsR[curr]; ta.odL = a->d_as_descL[curr]; ta.dim = a->desc_dim();
+    ta.okL = a->d_as_kpsL[curr]; ta.okR = a->d_as_kpsR[curr]; ta.odL = a->d_as_descL[curr]; ta.dim = a->loop_words();
     ta.as_pts4 = a->d_as_pts4[curr]; ta.as_cam1 = a->d_as_cam1[curr]; ta.as_flag = a->d_as_flag[curr];
     // rows to expect: the keypoints of the last pair whose counts reached the host, plus a quarter (max_kpts before that)
     const Ctx* hm = a->master ? a->master : a;

@@ -44,7 +44,8 @@ enum { CN_T = 0, CN_G = 1, CN_NINL = 2, CN_NQA = 3, CN_NQB = 4, CN_MEFF = 5, CN_
 struct GateArgs { int mode; int* cn; int min_features, cap; int* as_curr_n; const int* as_prev_n; };
 
 static const int kSumPad = 256;      // ints of slack before and after each integral image (see Ctx::d_sum_base)
-static const int kMaxHyp = 2048;      // RANSAC hypotheses evaluated per call (>= ITERATIONS_COUNT)
+static const int kMaxHyp = 2048;
+static const int kBinRowWords = 16;   // a binary descriptor row in the fused steps: 64 bytes, zero past the detector's 61 (AKAZE) or 32 (ORB)      // RANSAC hypotheses evaluated per call (>= ITERATIONS_COUNT)
 
 // A sample of a middle layer (1..3) that beat the Hessian threshold, its eight in-layer neighbours and every adjacent layer
 // the detection kernel computes (surf.hip): n9 = the 3 x 3 x 3 neighbourhood, layer L-1 first; the row of an outer layer
@@ -53,7 +54,7 @@ struct Survivor { int im, octave, L, i, j; float n9[27]; };
 
 struct DetectSet {                    // one image's detector outputs (device)
     uvo_keypoint* kps;                // sorted, cap
-    float* desc;                      // cap x 64
+    float* desc;                      // cap rows of 512 bytes: 64 / 128 floats, or a binary row as kBinRowWords words
     int* n;                           // device count (clamped to cap)
 };
 
@@ -249,7 +250,8 @@ struct Ctx {
     void* orb_ws = nullptr;                      // OrbWs* (uvo_orb_detect): parameters, sampling table, buffers of the last image size
     void* akaze_ws = nullptr;                    // AkazeWs* (uvo_akaze_detect), allocated on first use per image size
     void* sift_ws[2] = {nullptr, nullptr};       // SiftWs* per image slot (uvo_sift_detect uses slot 0), allocated on first use
-    int feature_sift = 0;                        // the reference's global FEATURE_DETECTOR == "SIFT" (uvo_ctx_set_feature_detector); read from the master context
+    int detector = 0;                            // the reference's global FEATURE_DETECTOR for the fused steps: 0 SURF, 1 SIFT, 2 AKAZE, 3 ORB
+                                                 // (uvo_ctx_set_loop_detector / uvo_ctx_set_feature_detector); read from the master context
     double mono_K[9]; bool mono_cam_set = false, mono_initialized = false, mono_pipelined = false;
     int mono_use_essential = 1;                  // the reference's global `use_essential` (VOH:89)
     double mono_R[9] = {1,0,0,0,1,0,0,0,1}, mono_t[3] = {0,0,0}, mono_SF = 1.0;
@@ -272,8 +274,12 @@ struct Ctx {
     bool trace_on = false;                       // UVO_TRACE=<file> at creation, or uvo_trace_enable (the events are created at first use)
 
     int match_dim = 0;                           // uvo_match_knn2*_dim: row width of the standalone matcher for the duration of one call (0 = SURF's)
-    bool use_sift() const { return (master ? master : this)->feature_sift != 0; }
+    int loop_detector() const { return (master ? master : this)->detector; }
+    bool use_sift() const { return loop_detector() == 1; }
+    bool use_binary() const { return loop_detector() >= 2; }      // AKAZE / ORB: CV_8U rows, kept as 64-byte zero-padded rows in det[].desc
+    int desc_bytes() const { return loop_detector() == 2 ? 61 : 32; }     // bytes of a binary row: AKAZE's M-LDB 61, ORB's rBRIEF 32
     int desc_dim() const { return match_dim ? match_dim : (use_sift() || p.SURF_EXTENDED ? 128 : 64); }      // SURF::descriptorSize(): floats per descriptor row
+    int loop_words() const { return use_binary() ? kBinRowWords : desc_dim(); }   // 32-bit words per row of the fused steps' descriptor buffers
 
     // ---- timing ----
     bool timing = false;
@@ -320,6 +326,15 @@ uvo_status surf_hessian_layer_debug(Ctx* c, int octave, int layer, float* det, f
 // match.hip
 uvo_status match_knn2(Ctx* c, const float* d_q, const int* d_nq, int nq_max, const float* d_t, const int* d_nt, int nt_max);
 uvo_status match_knn2_hamming(Ctx* c, const uint8_t* d_q, int nq, const uint8_t* d_t, int nt, int bytes);
+// kNN-2 on the fused steps' binary rows (kBinRowWords words each, zero-padded), counts on the device (d_n*: device pointer or null,
+// then n*_max): metric 0 Hamming (stereo loop: VOU:520-524), 1 exact L2 of the bytes (mono loop: BFMatcher(NORM_L2) on CV_8U, VOU:551-573).
+// Results in slot 0 (and 1) of the kNN buffers, as match_knn2 / match_knn2_two leave them.
+enum { BIN_HAMMING = 0, BIN_L2 = 1 };
+uvo_status match_knn2_bin(Ctx* c, int metric, const uint8_t* d_q, const int* d_nq, int nq_max, const uint8_t* d_t, const int* d_nt, int nt_max);
+uvo_status match_knn2_bin_two(Ctx* c, int metric, const uint8_t* d_q0, const int* d_nq0, const uint8_t* d_t0, const int* d_nt0,
+                              const uint8_t* d_q1, const int* d_nq1, const uint8_t* d_t1, const int* d_nt1, int n_max);
+// rows of `bytes` bytes (src, n rows) -> rows of kBinRowWords words, zero-padded (dst), on stream st
+uvo_status pad_binary_rows(Ctx* c, hipStream_t st, const uint8_t* src, int n, int bytes, uint8_t* dst);
 uvo_status match_knn2_two(Ctx* c, const float* d_q0, const int* d_nq0, const float* d_t0, const int* d_nt0,
                           const float* d_q1, const int* d_nq1, const float* d_t1, const int* d_nt1, int n_max);
 uvo_status match_ratio_compact2(Ctx* c, float ratio, const int* d_nq0, uvo_dmatch* d_out0, int* d_nout0, const GateArgs& g0,
@@ -372,10 +387,18 @@ uvo_status orb_configure(Ctx* c, int nfeatures, float scaleFactor, int nlevels, 
 uvo_status orb_set_pattern(Ctx* c, const int* pattern);
 uvo_status orb_detect(Ctx* c, const uint8_t* gray, int w, int h, int stride, int mem, uvo_keypoint* kps, uint8_t* desc, int cap, int* n_out);
 uvo_status orb_level_plane(Ctx* c, int level, int what, uint8_t* out, int cap_bytes, int* ow, int* oh);
+bool orb_has_pattern(Ctx* c);
+extern const char* const kOrbLoopNoTable;
+// detect_features' ORB / AKAZE branch inside the fused steps, image `slot` of the lane (c->img[slot]): keypoints to det[slot].kps, rows
+// to det[slot].desc (kBinRowWords words each); *n = the detector's count (> max_kpts: nothing is copied, the caller reports it)
+uvo_status orb_prepare_lane(Ctx* c, int w, int h);
+uvo_status orb_detect_lane(Ctx* c, int slot, int* n);
 // akaze.hip
 void akaze_ws_free(Ctx* c);
 uvo_status akaze_detect(Ctx* c, const uint8_t* gray, int w, int h, int stride, int mem, uvo_keypoint* kps, uint8_t* desc, int cap, int* n_out);
 uvo_status akaze_plane(Ctx* c, int level, int what, float* out, int cap_floats, int* ow, int* oh);
+uvo_status akaze_prepare_lane(Ctx* c, int w, int h);
+uvo_status akaze_detect_lane(Ctx* c, int slot, int* n);
 uvo_status sift_detect(Ctx* c, const uint8_t* gray, int w, int h, int stride, int mem, int nfeatures, int nL, double contrastThreshold,
                        double edgeThreshold, double sigma, uvo_keypoint* kps, float* desc, int cap, int* n_out);
 uvo_status sift_layer(Ctx* c, int octave, int layer, int dog, float* out, int cap_floats, int* ow, int* oh);

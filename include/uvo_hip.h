@@ -93,12 +93,24 @@ int         uvo_ctx_pending(const uvo_ctx* c);
  * one host thread busy.  Results do not depend on the choice.  Valid until the next call. */
 const char* uvo_ctx_host_policy(uvo_ctx* c);
 
-/* The reference's global FEATURE_DETECTOR (VO_utility.h:25, /vo_params/feature_detector) for the fused steps: "SURF" (default) or
- * "SIFT" -- uvo_stereo_step / submit and uvo_mono_step / submit then take detect_features' SIFT branch (VO_utility.cpp:107-112,
- * SIFT::create(10000, 3, 0.03, 10, 1.6)) and match 128-float rows (VO_utility.cpp:525-529); everything after the matcher is unchanged.
- * Refused while pairs are in flight or a VO sequence is running (reset first).  A frame with more than max_kpts SIFT keypoints is a
- * UVO_CAPACITY error, as for SURF: create the context with max_kpts >= 10000 + ties for 1080p frames. */
+/* The float-row subset of uvo_ctx_set_loop_detector: "SURF" or "SIFT" only; any other name, "AKAZE" and "ORB" included, is refused
+ * (callers that route the binary detectors through the operators rely on that refusal). */
 uvo_status uvo_ctx_set_feature_detector(uvo_ctx* c, const char* name);
+/* The reference's global FEATURE_DETECTOR (VO_utility.h:25, /vo_params/feature_detector) for the fused steps: "SURF" (default), "SIFT",
+ * "AKAZE" or "ORB".  uvo_stereo_step / submit and uvo_mono_step / submit then take detect_features' branch of that name (VO_utility.cpp:
+ * 93-119) and everything after the matcher is unchanged:
+ *   SIFT  -- SIFT::create(10000, 3, 0.03, 10, 1.6), 128-float rows, the L2 matcher (VO_utility.cpp:525-529);
+ *   AKAZE -- as uvo_akaze_detect, 61-byte rows;  ORB -- as uvo_orb_detect with the master context's uvo_orb_configure / uvo_orb_set_pattern,
+ *            32-byte rows.  The stereo loop matches them by Hamming distance (VO_utility.cpp:520-524); the mono loop's 7-argument
+ *            match_features builds BFMatcher(NORM_L2) whatever the detector (VO_utility.cpp:551-573): exact L2 of the bytes.
+ *   "ORB" is accepted without a sampling table; the first step then fails with UVO_INVALID_ARG (the message names bit_pattern_31_).
+ * The binary detectors' host stages (AKAZE's contrast factor and sequential duplicate suppression, ORB's retainBest rankings) run on the
+ * thread that calls uvo_stereo_submit / uvo_mono_submit: with several pairs in flight they serialise the submissions' detection.  Each
+ * lane keeps its own detector workspace, made by the first (synchronous) pair of a sequence; uvo_stereo_get("desc_left" / "desc_right")
+ * returns the rows' bytes (61 or 32 per row).  Refused while pairs are in flight, and a change of detector while a VO sequence is running
+ * (reset first).  A frame with more than max_kpts keypoints is a UVO_CAPACITY error, as for SURF: create the context with max_kpts >=
+ * 10000 + ties for SIFT / ORB on 1080p frames.  NULL c or name: UVO_INVALID_ARG. */
+uvo_status uvo_ctx_set_loop_detector(uvo_ctx* c, const char* name);
 
 /* ---- detect_features, SURF branch (VO_utility.h:100 -> VO_utility.cpp:114-119) ----
  * gray: 8-bit single channel, `stride` bytes per row.  kps/desc are host buffers of capacity `cap`, either may be NULL;
@@ -113,15 +125,15 @@ uvo_status uvo_surf_detect(uvo_ctx* c, const uint8_t* gray, int w, int h, int st
  * the five arguments of SIFT::create are passed through (nfeatures <= 0 keeps every keypoint).  gray as for uvo_surf_detect.
  * kps / desc: host buffers (desc: cap x 128 floats, the integer-valued rows cv::SIFT writes as CV_32F); keypoints come out in
  * KeyPoint_LessThan order (x, y, size, angle ...) after duplicate removal, with OpenCV's packed octave / layer / offset in
- * `octave`.  A standalone operator: the stereo / mono steps of this library run on SURF (the shipped parameter files). */
+ * `octave`.  The fused steps take the same detector after uvo_ctx_set_loop_detector(c, "SIFT"). */
 uvo_status uvo_sift_detect(uvo_ctx* c, const uint8_t* gray, int w, int h, int stride, int mem, int nfeatures, int n_octave_layers,
                            double contrast_threshold, double edge_threshold, double sigma, uvo_keypoint* kps, float* desc, int cap, int* n);
 /* detect_features, FEATURE_DETECTOR == "AKAZE" (VO_utility.cpp:93-98): AKAZE::create()->detectAndCompute(img, noArray(), keypoints,
  * descriptors) -- DESCRIPTOR_MLDB at full length (486 bits: rows of 61 bytes, for uvo_match_knn2_ratio_hamming), 3 channels, threshold
  * 0.001, 4 octaves of 4 sublevels, DIFF_PM_G2.  Keypoints in OpenCV's order (evolution level by level, row-major), `size` the diameter,
  * `angle` in degrees, `class_id` the evolution level.  The non-linear scale space, the Hessian response, orientation and descriptors run
- * on the device; the sequential duplicate suppression of Find_Scale_Space_Extrema runs on the host over the candidate list.  A
- * standalone operator: the fused stereo / mono steps run on SURF or SIFT. */
+ * on the device; the sequential duplicate suppression of Find_Scale_Space_Extrema runs on the host over the candidate list.  The fused
+ * steps take the same detector after uvo_ctx_set_loop_detector(c, "AKAZE"). */
 uvo_status uvo_akaze_detect(uvo_ctx* c, const uint8_t* gray, int w, int h, int stride, int mem, uvo_keypoint* kps, uint8_t* desc, int cap, int* n);
 /* test hook: plane `what` (0 Lt, 1 Lsmooth, 2 Lx, 3 Ly -- the multiscale derivatives --, 4 Ldet) of evolution level `level` of the last
  * uvo_akaze_detect, row-major floats to a host buffer */
@@ -139,7 +151,7 @@ uvo_status uvo_akaze_plane(uvo_ctx* c, int level, int what, float* out, int cap_
  * layout -- x0, y0, x1, y1 per descriptor bit, |coordinate| <= patchSize / 2 -- and keeps it for the context (NULL forgets it).  Without a
  * table uvo_orb_detect returns keypoints only (desc = NULL) and refuses descriptors with UVO_INVALID_ARG.  (For patch sizes other than
  * 31 OpenCV draws the table itself with cv::RNG(0x34985739): INTEGRATION.md shows the eight lines.)
- * A standalone operator: the fused stereo / mono steps run on SURF or SIFT. */
+ * The fused steps take the same detector after uvo_ctx_set_loop_detector(c, "ORB"), with this context's parameters and table. */
 uvo_status uvo_orb_configure(uvo_ctx* c, int nfeatures, float scale_factor, int nlevels, int edge_threshold, int patch_size, int fast_threshold);
 uvo_status uvo_orb_set_pattern(uvo_ctx* c, const int* pattern /* 1024 ints or NULL */);
 uvo_status uvo_orb_detect(uvo_ctx* c, const uint8_t* gray, int w, int h, int stride, int mem, uvo_keypoint* kps, uint8_t* desc, int cap, int* n);
@@ -176,6 +188,11 @@ uvo_status uvo_match_knn2_ratio_hamming(uvo_ctx* c, const uint8_t* d1, int n1, c
                                         float ratio, uvo_dmatch* out, int cap, int* m);
 uvo_status uvo_match_knn2_hamming(uvo_ctx* c, const uint8_t* d1, int n1, const uint8_t* d2, int n2, int bytes, int mem,
                                   int* idx, float* dist);
+/* test hook: the kNN-2 matchers the fused steps run on AKAZE / ORB rows, on host rows of `bytes` bytes (1..64) -- padded to 64 bytes and
+ * matched with the counts read on the device, as inside the steps.  metric 0: Hamming (the stereo loop), 1: exact L2 of the bytes,
+ * sqrtf of the integer sum (the mono loop's BFMatcher(NORM_L2) on CV_8U rows).  idx / dist as uvo_match_knn2 (-1 / FLT_MAX when the
+ * train set has fewer than two rows). */
+uvo_status uvo_match_loop_knn2(uvo_ctx* c, const uint8_t* d1, int n1, const uint8_t* d2, int n2, int bytes, int metric, int* idx, float* dist);
 
 /* ---- cv::triangulatePoints as called at visual_odometry.h:355, 631 and VO_utility.cpp:595 ----
  * P1, P2: 3x4 f64 row-major; x1, x2: n Point2f (host); out: 4 x n f32 (host). */
