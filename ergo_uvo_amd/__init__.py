@@ -26,6 +26,7 @@ DM_DTYPE = np.dtype([("queryIdx", "i4"), ("trainIdx", "i4"), ("imgIdx", "i4"), (
 
 MEM_HOST, MEM_DEVICE = 0, 1
 _STATUS = {1: "UVO_INVALID_ARG", 2: "UVO_TOO_FEW_POINTS", 3: "UVO_CAPACITY", 4: "UVO_HIP_ERROR", 5: "UVO_NO_DEVICE"}
+_UVO_CAPACITY = 3
 
 
 class UvoError(RuntimeError):
@@ -203,7 +204,12 @@ class Context:
         """detect_features(img, keypoints, descriptors): the SURF branch (VO_utility.cpp:114-119), or the SIFT branch (VO_utility.cpp:107-112)
         when set_feature_detector("SIFT") was called -- the reference switches on its global FEATURE_DETECTOR."""
         if getattr(self, "_feature_akaze", False):
-            return self.akaze_detect(img)                  # VO_utility.cpp:93-98
+            try:
+                return self.akaze_detect(img)              # VO_utility.cpp:93-98
+            except UvoError as e:                          # AKAZE's count has no bound (17 850 keypoints on a 1080p frame): a frame with
+                if e.status != _UVO_CAPACITY:              # more than max_kpts runs again with room for all of them
+                    raise
+            return self.akaze_detect(img, cap=self._akaze_last_n)
         if getattr(self, "_feature_orb", False):
             return self.orb_detect(img)                    # VO_utility.cpp:100-105
         if getattr(self, "_feature_sift", False):
@@ -220,7 +226,9 @@ class Context:
         kps = np.empty(cap, KP_DTYPE)
         desc = np.empty((cap, 61), np.uint8)
         self._order_after_producer(img)
-        self._check(self._lib.uvo_akaze_detect(self._h, p, w, h, w, mem, _p(kps), _p(desc), cap, C.byref(n)))
+        st = self._lib.uvo_akaze_detect(self._h, p, w, h, w, mem, _p(kps), _p(desc), cap, C.byref(n))
+        self._akaze_last_n = n.value                       # (the count, also when `cap` was too small for it)
+        self._check(st)
         return kps[:n.value], desc[:n.value]
 
     def akaze_plane(self, level: int, what: int):

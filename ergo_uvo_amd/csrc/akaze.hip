@@ -47,7 +47,7 @@ struct AkazeWs {
     int* hist = nullptr;                                      // [0] max bits, [1..300] histogram
     AkCand* cand = nullptr; int* cand_n = nullptr;            // candidates of one level (device), count
     AkCand* h_cand = nullptr; int* h_hist = nullptr;          // pinned
-    uvo_keypoint* d_kps = nullptr; uint8_t* d_desc = nullptr; // outputs (cap)
+    uvo_keypoint* d_kps = nullptr; uint8_t* d_desc = nullptr; // outputs (cap: max_kpts, grown by the single-image path when a frame has more)
     AkTab* xtab[kAkMaxLevels] = {nullptr}; AkTab* ytab[kAkMaxLevels] = {nullptr}; int* xofs[kAkMaxLevels] = {nullptr}; int* yofs[kAkMaxLevels] = {nullptr};   // general INTER_AREA tables of the octave changes that are not exact halvings (built with the workspace)
     float* d_kc = nullptr; float* h_kc = nullptr;             // compute_kcontrast's result: pinned source, device copy the conductance kernels read
     hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; // the launch chain from the first evolution step to the last level's candidates, captured once per image size
@@ -622,9 +622,11 @@ static uvo_status akaze_capture(Ctx* c, AkazeWs* s, hipStream_t st)
     return UVO_OK;
 }
 
-// detectAndCompute on `gray` (device or host): the keypoints and their M-LDB rows are left in s->d_kps / s->d_desc, *n_out = the count; when it
-// exceeds the workspace's capacity (max_kpts) nothing past the host stages is computed and the call still returns UVO_OK
-static uvo_status akaze_run(Ctx* c, AkazeWs* s, hipStream_t st, const uint8_t* gray, int w, int h, int stride, int mem, int* n_out)
+// detectAndCompute on `gray` (device or host): the keypoints and their M-LDB rows are left in s->d_kps / s->d_desc, *n_out = the count.  When
+// the count exceeds the workspace's capacity, `grow` reallocates the two output buffers to hold it (the single-image operator: AKAZE has no
+// upper bound on its count -- 17 850 on a 1080p frame); without it nothing past the host stages is computed and the call still returns
+// UVO_OK (the fused steps, whose lane buffers max_kpts sizes)
+static uvo_status akaze_run(Ctx* c, AkazeWs* s, hipStream_t st, const uint8_t* gray, int w, int h, int stride, int mem, bool grow, int* n_out)
 {
     *n_out = 0;
     const dim3 blk(256);
@@ -759,9 +761,11 @@ static uvo_status akaze_run(Ctx* c, AkazeWs* s, hipStream_t st, const uint8_t* g
             const float Dxx = v[5] + v[3] - 2.0f * v[4];
             const float Dyy = v[7] + v[1] - 2.0f * v[4];
             const float Dxy = 0.25f * (v[8] + v[0] - v[2] - v[6]);
-            float dx = 0.0f, dy = 0.0f;                              // solve(Matx22f, Vec2f, DECOMP_LU): Cramer in float
-            const float det = Dxx * Dyy - Dxy * Dxy;
-            if (det != 0) { const float d = 1 / det; dx = d * ((-Dx) * Dyy - (-Dy) * Dxy); dy = d * ((-Dy) * Dxx - (-Dx) * Dxy); }
+            // solve(Matx22f, Vec2f, DECOMP_LU): lapack.cpp's 2 x 2 CV_32F branch -- determinant and numerators in double, the result
+            // cast to float; a zero determinant leaves dst = 0
+            float dx = 0.0f, dy = 0.0f;
+            double det = (double)Dxx * Dyy - (double)Dxy * Dxy;
+            if (det != 0) { det = 1. / det; dx = (float)(((double)(-Dx) * Dyy - (double)(-Dy) * Dxy) * det); dy = (float)(((double)(-Dy) * Dxx - (double)(-Dx) * Dxy) * det); }
             if (fabsf(dx) > 1.0f || fabsf(dy) > 1.0f) continue;
             k.x += dx * ratio + .5f * (ratio - 1.f);
             k.y += dy * ratio + .5f * (ratio - 1.f);
@@ -773,7 +777,15 @@ static uvo_status akaze_run(Ctx* c, AkazeWs* s, hipStream_t st, const uint8_t* g
     const int n = (int)out.size();
     *n_out = n;
     stamp();
-    if (n > s->cap || n == 0) return UVO_OK;
+    if (n == 0 || (n > s->cap && !grow)) return UVO_OK;
+    if (n > s->cap) {                                                // (the stream is idle here: synchronised after the candidate copy; the
+        (void)hipFree(s->d_kps); (void)hipFree(s->d_desc);          // outputs are not part of the captured graph)
+        s->d_kps = nullptr; s->d_desc = nullptr; s->cap = 0;
+        const int ncap = (n + 4095) & ~4095;
+        if (hipMalloc(reinterpret_cast<void**>(&s->d_kps), sizeof(uvo_keypoint) * (size_t)ncap) != hipSuccess ||
+            hipMalloc(reinterpret_cast<void**>(&s->d_desc), (size_t)kAkDescBytes * ncap) != hipSuccess) { c->err = "AKAZE: growing the output buffers failed"; return UVO_HIP_ERROR; }
+        s->cap = ncap;
+    }
     // ---- Compute_Keypoints_Orientation, MLDB descriptors ----
     AkPlanes pl;
     memset(&pl, 0, sizeof(pl));
@@ -795,9 +807,8 @@ uvo_status akaze_detect(Ctx* c, const uint8_t* gray, int w, int h, int stride, i
     AkazeWs* s = akaze_ws(c, w, h);
     if (!s) { c->err = "AKAZE workspace allocation failed"; return UVO_HIP_ERROR; }
     hipStream_t st = c->stream;
-    UVO_TRY(akaze_run(c, s, st, gray, w, h, stride, mem, n_out));
+    UVO_TRY(akaze_run(c, s, st, gray, w, h, stride, mem, true, n_out));
     const int n = *n_out;
-    if (n > s->cap) { c->err = "AKAZE found more keypoints than the context's max_kpts"; return UVO_CAPACITY; }
     if ((kps || desc) && n > cap) { c->err = "uvo_akaze_detect: output capacity too small"; return UVO_CAPACITY; }
     if (n == 0) return UVO_OK;
     if (kps) UVO_HIP_TRY(c, hipMemcpyAsync(kps, s->d_kps, sizeof(uvo_keypoint) * n, hipMemcpyDeviceToHost, st));
@@ -823,7 +834,7 @@ uvo_status akaze_detect_lane(Ctx* c, int slot, int* n)
     if (w < 16 || h < 16) { c->err = "AKAZE: image too small"; return UVO_INVALID_ARG; }
     UVO_TRY(akaze_prepare_lane(c, w, h));                                    // (a no-op once the lane is primed)
     AkazeWs* s = static_cast<AkazeWs*>(c->akaze_ws);
-    UVO_TRY(akaze_run(c, s, c->stream, c->img[slot], w, h, w, UVO_MEM_DEVICE, n));
+    UVO_TRY(akaze_run(c, s, c->stream, c->img[slot], w, h, w, UVO_MEM_DEVICE, false, n));
     if (*n > c->cap || *n == 0) return UVO_OK;
     UVO_HIP_TRY(c, hipMemcpyAsync(c->det[slot].kps, s->d_kps, sizeof(uvo_keypoint) * (size_t)*n, hipMemcpyDeviceToDevice, c->stream));
     return pad_binary_rows(c, c->stream, s->d_desc, *n, kAkDescBytes, reinterpret_cast<uint8_t*>(c->det[slot].desc));

@@ -347,12 +347,19 @@ void detect_features(Mat img, vector<KeyPoint>& keypoints, Mat& descriptors)
         return;
     }
     if (akaze) {
-        const int cap = g.max_kpts;
+        // AKAZE has no cap on its count (17 850 keypoints on a 1080p frame): a frame with more than max_kpts is run again with room for all
+        int cap = g.max_kpts;
         vector<uvo_keypoint> kps((size_t)cap);
         vector<uint8_t> desc((size_t)cap * 61);
         int n = 0;
         const int stride = img.rows > 1 ? (int)(img.ptr<uint8_t>(1) - img.ptr<uint8_t>(0)) : img.cols;
-        SHIM_TRY(uvo_akaze_detect(c, img.ptr<uint8_t>(0), img.cols, img.rows, stride, UVO_MEM_HOST, kps.data(), desc.data(), cap, &n), "uvo_akaze_detect");
+        uvo_status st = uvo_akaze_detect(c, img.ptr<uint8_t>(0), img.cols, img.rows, stride, UVO_MEM_HOST, kps.data(), desc.data(), cap, &n);
+        if (st == UVO_CAPACITY && n > cap) {
+            cap = n;
+            kps.resize((size_t)cap); desc.resize((size_t)cap * 61);
+            st = uvo_akaze_detect(c, img.ptr<uint8_t>(0), img.cols, img.rows, stride, UVO_MEM_HOST, kps.data(), desc.data(), cap, &n);
+        }
+        SHIM_TRY(st, "uvo_akaze_detect");
         keypoints.resize((size_t)n);
         if (n) memcpy(static_cast<void*>(keypoints.data()), kps.data(), sizeof(uvo_keypoint) * n);
         descriptors.create(n, 61, CV_8UC1);                                  // AKAZE::descriptorType() == CV_8U, descriptorSize() == 61

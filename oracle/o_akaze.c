@@ -605,10 +605,11 @@ int orc_akaze_detect_and_compute(const uint8_t* img, int w, int h, int stride, o
                 const float Dxx = ldet[y * cols + x + 1] + ldet[y * cols + x - 1] - 2.0f * ldet[y * cols + x];
                 const float Dyy = ldet[(y + 1) * cols + x] + ldet[(y - 1) * cols + x] - 2.0f * ldet[y * cols + x];
                 const float Dxy = 0.25f * (ldet[(y + 1) * cols + x + 1] + ldet[(y - 1) * cols + x - 1] - ldet[(y - 1) * cols + x + 1] - ldet[(y + 1) * cols + x - 1]);
-                /* solve(Matx22f(Dxx, Dxy, Dxy, Dyy), Vec2f(-Dx, -Dy), dst, DECOMP_LU): Cramer in float; a singular matrix leaves dst = 0 */
+                /* solve(Matx22f(Dxx, Dxy, Dxy, Dyy), Vec2f(-Dx, -Dy), dst, DECOMP_LU): the 2 x 2 CV_32F branch of lapack.cpp's solve --
+                 * determinant and numerators in double, the result cast to float; a zero determinant leaves dst = 0 */
                 float dx = 0.0f, dy = 0.0f;
-                const float det = Dxx * Dyy - Dxy * Dxy;
-                if (det != 0) { const float d = 1 / det; dx = d * ((-Dx) * Dyy - (-Dy) * Dxy); dy = d * ((-Dy) * Dxx - (-Dx) * Dxy); }
+                double det = (double)Dxx * Dyy - (double)Dxy * Dxy;
+                if (det != 0) { det = 1. / det; dx = (float)(((double)(-Dx) * Dyy - (double)(-Dy) * Dxy) * det); dy = (float)(((double)(-Dy) * Dxx - (double)(-Dx) * Dxy) * det); }
                 if (fabsf(dx) > 1.0f || fabsf(dy) > 1.0f) continue;
                 k.x += dx * ratio + .5f * (ratio - 1.f);
                 k.y += dy * ratio + .5f * (ratio - 1.f);

@@ -77,6 +77,52 @@ def test_akaze_rows_through_the_hamming_matcher_and_the_mirror(oracle):
         ctx.close()
 
 
+def _shim_detect(tmp_path, img):
+    from ergo_uvo_amd import KP_DTYPE
+    subprocess.check_call(["make", "-C", os.path.join(ROOT, "ergo_uvo_amd", "shim"), "-s"])
+    h, w = img.shape
+    inp, outp = tmp_path / "in.bin", tmp_path / "out.bin"
+    inp.write_bytes(struct.pack("<iii8s", w, h, 1500, b"AKAZE") + img.tobytes())
+    res = subprocess.run([os.path.join(ROOT, "tests", "cpp", "build", "shim_detect"), str(inp), str(outp)], capture_output=True, text=True, timeout=300)
+    assert res.returncode == 0, res.stderr
+    raw = outp.read_bytes()
+    n, cols = struct.unpack("<ii", raw[:8])
+    return np.frombuffer(raw[8:8 + 28 * n], KP_DTYPE), np.frombuffer(raw[8 + 28 * n:], np.uint8).reshape(n, cols)
+
+
+def test_shim_detect_features_akaze_1080p_beyond_max_kpts(tmp_path, oracle):
+    """The C++ surface at 1920 x 1080 with configure()'s default max_kpts (8192): AKAZE::create()->detectAndCompute returns every keypoint
+    (about 18 500 here), not a capacity error."""
+    img = _scene(1920, 1080, 81)
+    kps, desc = _shim_detect(tmp_path, img)
+    ko, do = oracle.akaze_detect(img, cap=1 << 17)
+    assert len(ko) > 8192 and desc.shape == (len(ko), 61)
+    _same_kps(kps, ko)
+    assert np.array_equal(desc, do)
+
+
+def test_mirror_detect_features_akaze_1080p_beyond_max_kpts(oracle):
+    """Context.detect_features with the AKAZE switch returns every keypoint of a frame with more than max_kpts; akaze_detect keeps its
+    contract (a capacity error when `cap`, by default max_kpts, is too small)."""
+    import ergo_uvo_amd as uvo
+    img = _scene(1920, 1080, 81)
+    ctx = uvo.Context(uvo.Params.stereo(), 0, 1920, 1080, 8192)
+    try:
+        ctx.set_feature_detector("AKAZE")
+        kps, desc = ctx.detect_features(img)
+        ko, do = oracle.akaze_detect(img, cap=1 << 17)
+        assert len(ko) > 8192
+        _same_kps(kps, ko)
+        assert np.array_equal(desc, do)
+        with pytest.raises(uvo.UvoError):
+            ctx.akaze_detect(img)
+        k2, d2 = ctx.akaze_detect(img, cap=len(ko))
+        _same_kps(k2, ko)
+        assert np.array_equal(d2, do)
+    finally:
+        ctx.close()
+
+
 def test_shim_detect_features_akaze_branch(tmp_path, oracle):
     """detect_features(img, keypoints, descriptors) with FEATURE_DETECTOR = "AKAZE" through the C++ surface: CV_8U rows of 61 bytes."""
     from ergo_uvo_amd import KP_DTYPE
