@@ -8,7 +8,8 @@
 //                             3x3x3 NMS + quadratic interpolation; box patterns compile-time; the integral tile is
 //                             staged in LDS (octaves 0-1) or read from the planes (2-3); det planes never leave LDS;
 //                             candidates are appended with one atomic per keypoint
-//   rank_partial / rank_scatter : deterministic ordering (OpenCV's KeypointGreater) by counting rank
+//   order (rank_partial / rank_scatter / big_sort above 8192 candidates) : deterministic ordering (OpenCV's
+//                             KeypointGreater) and the large-window list
 //   descriptor64_small / _big (+ _big_tabs, _big_finish) : INTER_AREA window resample + Haar gradients + 4x4x4 sums
 // All float arithmetic keeps OpenCV's operation order (int box sum * float weight accumulated in
 // double; no FMA contraction) so results are bit-identical to the CPU restatement.
@@ -1069,16 +1070,29 @@ __device__ __forceinline__ SortKey make_sort_key(const uvo_keypoint& kp)
 
 static const int kSmallWin = 128;       // descriptor windows up to this size use the small-LDS kernel
 static const int kMaxWin = 740;         // (int)(21 * 264 * 1.2f / 9) = 739: the window of the largest octave-3 keypoint
-// Large windows are listed in append order by k_rank_scatter and then sorted by descending window size (a (keypoint,
+// Large windows (fallback path) are listed in append order by k_rank_scatter and then sorted by descending window size (a (keypoint,
 // column) task of descriptor64_big costs about ceil(win/256) lane passes x ceil((win/21 + 2)/16) tap batches, 1..9 units),
 // which the task dealing of that kernel relies on.  Counting sort, one workgroup per image.
 static const int kBigBins = 1024;
 static const int kTripleWin = 246;     // windows up to this size: three destination columns per task (3 x 246 floats share the 740-float row buffer)
+// k_order (below) and its capacity: one workgroup orders up to kOrderCap candidates in LDS
+static const int kOrderThreads = 1024;
+static const int kOrderPer = 8;                                  // candidates per thread
+static const int kOrderCap = kOrderThreads * kOrderPer;          // 8192: the default max_kpts orders in one launch
+static const int kOrderBucketBits = 12;
+static const int kOrderBuckets = 1 << kOrderBucketBits;          // 4096
+static const int kOrderBinsPer = kOrderBuckets / kOrderThreads;  // buckets per thread in the scan
+// LDS: k1 and candidate index in bucket order, 8192 x (8 + 2) B (80 KiB) + bucket starts 4096 x 4 B (16 KiB) + window bins
+// kBigBins x 4 B (4 KiB) + 2 x 16 wave totals = 100.1 KiB of the 160 KiB a workgroup may hold on gfx950
+static_assert(kOrderBuckets % kOrderThreads == 0 && kBigBins == kOrderThreads, "k_order scans kOrderBinsPer buckets and one window bin per thread");
+static_assert(kOrderCap <= 65536, "bucket members are 16-bit candidate indices");
+
 __global__ __launch_bounds__(1024) void k_big_sort(LanePair lp, int cap, const int* __restrict__ iscale_tab)
 {
     const LaneArgs& LA = UVO_LANE_OF(lp, blockIdx.x);
     const int4* __restrict__ in = LA.big_in; int4* __restrict__ out = LA.big_out; const int* __restrict__ big_n = LA.da.big_n; int* __restrict__ big_large = LA.big_large;
     const int im = UVO_LANE_IM(blockIdx.x), tid = threadIdx.x;
+    if (min(LA.sa.cand_n[im], cap) <= kOrderCap) return;       // k_order's image
     const int n = min(big_n[im], cap);
     __shared__ int hist[kBigBins], scan[kBigBins];
     hist[tid] = 0;
@@ -1109,11 +1123,152 @@ __global__ __launch_bounds__(1024) void k_big_sort(LanePair lp, int cap, const i
 }
 static const int kSortChunk = 128;     // compared-against keypoints per workgroup: small, so that ~600 workgroups share the work
 
+// ------------------------------------------------------------------------------------------
+// k_order: the whole ordering of one image in ONE workgroup when its candidates fit in LDS (n <= kOrderCap; a 1080p frame has
+// ~2900).  Bucket sort on the response, then exact ranks inside each bucket:
+//   1. every candidate in registers; the range [lo, hi] of the order-preserving response bits
+//   2. bucket = kOrderBuckets - 1 - ((ord(response) - lo) >> sh), sh chosen so that the range fits kOrderBuckets: a bucket
+//      holds a contiguous range of responses, higher responses in lower buckets (linear in float bits = logarithmic in value)
+//   3. exclusive scan of the bucket counts; k1 (response, size) and the candidate index scattered to LDS in bucket order (any
+//      order inside a bucket)
+//   4. rank = bucket start + number of bucket members that sort before the candidate under the full KeypointGreater key with the
+//      candidate index last -- exactly the rank k_rank_partial counts, so the output is the same array.  (Members with equal
+//      k1 are rare; their k2 / k3 are read back from the candidate list.  Fully equal records are identical keypoints: their
+//      relative order could not change the output either.)  A bucket of b members costs O(b) per candidate: ~1-10 at 1080p,
+//      every candidate at once only if all responses are equal.
+// The large-window list is counted in the same pass (k_big_sort's bins: descending window size, iscale in .y's high bits).
+// Larger n: k_order returns at once and k_rank_partial / k_rank_scatter / k_big_sort do the work; they return at once when n
+// fits here, so each image is ordered by exactly one path and the rank scratch (touched only by the fallback) stays zero.
+__device__ __forceinline__ int wave_incl_scan(int v)
+{
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) { const int t = __shfl_up(v, d); if (lane >= d) v += t; }
+    return v;
+}
+
+__global__ __launch_bounds__(kOrderThreads) void k_order(LanePair lp, const int* __restrict__ iscale_tab)
+{
+    const LaneArgs& LA = UVO_LANE_OF(lp, blockIdx.y);
+    const SortArgs& a = LA.sa;
+    const int im = UVO_LANE_IM(blockIdx.y), tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int n = min(a.cand_n[im], a.cap);
+    if (n > kOrderCap) return;                                   // (uniform) the fallback launches order this image
+    __shared__ unsigned long long s_k1[kOrderCap];
+    __shared__ unsigned short s_mem[kOrderCap];
+    __shared__ int s_bin[kOrderBuckets];
+    __shared__ int s_win[kBigBins];
+    __shared__ int s_wave[2][kOrderThreads / 64];
+    __shared__ unsigned s_lo, s_hi;
+#pragma unroll
+    for (int k = 0; k < kOrderBinsPer; k++) s_bin[tid * kOrderBinsPer + k] = 0;
+    s_win[tid] = 0;
+    if (tid == 0) { s_lo = 0xFFFFFFFFu; s_hi = 0; }
+    __syncthreads();
+
+    // 1. response range, window bins (candidate e = k * kOrderThreads + tid).  The loads are unconditional (clamped to the
+    // last candidate) so that all of them are in flight at once, not one round trip per guarded load.
+    uvo_keypoint kp[kOrderPer];
+    unsigned long long k1[kOrderPer];
+    int wbin[kOrderPer];
+    unsigned lo = 0xFFFFFFFFu, hi = 0;
+#pragma unroll
+    for (int k = 0; k < kOrderPer; k++) kp[k] = a.cand[im][min(k * kOrderThreads + tid, max(n - 1, 0))];
+#pragma unroll
+    for (int k = 0; k < kOrderPer; k++) {
+        const int e = k * kOrderThreads + tid;
+        wbin[k] = -1;
+        k1[k] = make_sort_key(kp[k]).k1;
+        if (e < n) {
+            const unsigned r = ord_f32(kp[k].response);
+            lo = min(lo, r); hi = max(hi, r);
+            const float sc = kp[k].size * 1.2f / 9.0f;          // k_rank_scatter's window size
+            const int win_size = (int)((20 + 1) * sc);
+            if (win_size > kSmallWin) { wbin[k] = min(kBigBins - 1, max(0, kBigBins - 1 - win_size)); atomicAdd(&s_win[wbin[k]], 1); }
+        }
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) { lo = min(lo, (unsigned)__shfl_xor((int)lo, d)); hi = max(hi, (unsigned)__shfl_xor((int)hi, d)); }
+    if (lane == 0) { atomicMin(&s_lo, lo); atomicMax(&s_hi, hi); }
+    __syncthreads();
+
+    // 2. buckets
+    lo = s_lo; hi = s_hi;
+    const int bits = hi > lo ? 32 - __clz((int)(hi - lo)) : 0;
+    const int sh = bits > kOrderBucketBits ? bits - kOrderBucketBits : 0;
+    int bkt[kOrderPer];
+#pragma unroll
+    for (int k = 0; k < kOrderPer; k++) {
+        const int e = k * kOrderThreads + tid;
+        bkt[k] = -1;
+        if (e < n) { bkt[k] = kOrderBuckets - 1 - (int)((ord_f32(kp[k].response) - lo) >> sh); atomicAdd(&s_bin[bkt[k]], 1); }
+    }
+    __syncthreads();
+
+    // 3. exclusive scans: kOrderBinsPer buckets and one window bin per thread
+    int cnt[kOrderBinsPer], sb = 0;
+#pragma unroll
+    for (int k = 0; k < kOrderBinsPer; k++) { cnt[k] = s_bin[tid * kOrderBinsPer + k]; sb += cnt[k]; }
+    const int wcnt = s_win[tid];
+    const int ib = wave_incl_scan(sb), iw = wave_incl_scan(wcnt);
+    if (lane == 63) { s_wave[0][wv] = ib; s_wave[1][wv] = iw; }
+    __syncthreads();
+    int xb = ib - sb, xw = iw - wcnt, wtot = 0;
+    for (int v = 0; v < kOrderThreads / 64; v++) { if (v < wv) { xb += s_wave[0][v]; xw += s_wave[1][v]; } wtot += s_wave[1][v]; }
+#pragma unroll
+    for (int k = 0; k < kOrderBinsPer; k++) { s_bin[tid * kOrderBinsPer + k] = xb; xb += cnt[k]; }
+    s_win[tid] = xw;
+    if (tid == kBigBins - 1 - kTripleWin) LA.big_large[im] = xw;  // entries before this bin are wider than kTripleWin
+    if (tid == 0) {
+        a.big_n[im] = wtot;
+        *a.out_n[im] = n;
+        if (im == 0 && a.gate_nqa) {                             // VO:556, as k_rank_scatter
+            const int nL = n, nR = min(a.cand_n[1], a.cap);
+            *a.gate_nqa = (nL >= a.gate_min_features && nR >= a.gate_min_features) ? nL : 0;
+        }
+    }
+    __syncthreads();
+    int slot[kOrderPer];
+#pragma unroll
+    for (int k = 0; k < kOrderPer; k++)
+        if (bkt[k] >= 0) { slot[k] = atomicAdd(&s_bin[bkt[k]], 1); s_mem[slot[k]] = (unsigned short)(k * kOrderThreads + tid); s_k1[slot[k]] = k1[k]; }
+    __syncthreads();
+
+    // 4. ranks; s_bin[b] is now the end of bucket b, the start of b + 1; s_k1 / s_mem hold k1 and the candidate index in bucket order
+#pragma unroll
+    for (int k = 0; k < kOrderPer; k++) {
+        if (bkt[k] < 0) continue;
+        const int e = k * kOrderThreads + tid;
+        const int beg = bkt[k] > 0 ? s_bin[bkt[k] - 1] : 0, end = s_bin[bkt[k]];
+        int rank = beg;
+#pragma unroll 4
+        for (int q = beg; q < end; q++) {
+            const unsigned long long o1 = s_k1[q];
+            rank += o1 > k1[k] ? 1 : 0;
+            if (o1 == k1[k] && q != slot[k]) {
+                const int f = s_mem[q];
+                const SortKey mine = make_sort_key(kp[k]), o = make_sort_key(a.cand[im][f]);
+                rank += (o.k2 > mine.k2 || (o.k2 == mine.k2 && (o.k3 > mine.k3 || (o.k3 == mine.k3 && f < e)))) ? 1 : 0;
+            }
+        }
+        a.out[im][rank] = kp[k];
+        if (wbin[k] >= 0) {
+            const float sc = kp[k].size * 1.2f / 9.0f;
+            const int win_size = (int)((20 + 1) * sc);
+            const float win_offset = -(float)(win_size - 1) / 2;
+            const int pos = atomicAdd(&s_win[wbin[k]], 1);
+            LA.big_out[im * a.cap + pos] = make_int4(rank, win_size | (iscale_tab[min(win_size, kMaxWin)] << 16),
+                                                     cv_round_f(kp[k].x + win_offset), cv_round_f(kp[k].y - win_offset));
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void k_rank_partial(LanePair lp)
 {
     const SortArgs& a = UVO_LANE_OF(lp, blockIdx.y).sa;
     const int im = UVO_LANE_IM(blockIdx.y), tid = threadIdx.x;
     const int n = min(a.cand_n[im], a.cap);
+    if (n <= kOrderCap) return;                                  // k_order's image
     __shared__ SortKey tile[kSortChunk];
     __shared__ unsigned long long tile_k1[kSortChunk];
     // the count lives on the device: a fixed grid walks the (256 keypoints) x (kSortChunk compared-against) tiles that exist
@@ -1152,6 +1307,7 @@ __global__ __launch_bounds__(256) void k_rank_scatter(LanePair lp)
     const SortArgs& a = UVO_LANE_OF(lp, blockIdx.y).sa;
     const int im = UVO_LANE_IM(blockIdx.y);
     const int n = min(a.cand_n[im], a.cap);
+    if (n <= kOrderCap) return;                                  // k_order's image
     const int me = blockIdx.x * 256 + threadIdx.x;
     bool big = false;
     int4 par = make_int4(0, 0, 0, 0);
@@ -2244,15 +2400,18 @@ uvo_status surf_detect_lanes(Ctx* c, Ctx* c2, int nimg, int gate_min_features)
     }
     {
         StageTimer t(c, ST_SORT);
-        const int tiles_max = ((c->cap + 255) / 256) * ((c->cap + kSortChunk - 1) / kSortChunk);
-        hipLaunchKernelGGL(k_rank_partial, dim3(tiles_max < 512 ? tiles_max : 512, nim), dim3(256), 0, c->stream, lp);
-        hipLaunchKernelGGL(k_rank_scatter, dim3((c->cap + 255) / 256, nim), dim3(256), 0, c->stream, lp);
+        hipLaunchKernelGGL(k_order, dim3(1, nim), dim3(kOrderThreads), 0, c->stream, lp, c->d_area_iscale);
+        if (c->cap > kOrderCap) {                              // the counts live on the device: each of these returns at once for an image k_order ordered
+            const int tiles_max = ((c->cap + 255) / 256) * ((c->cap + kSortChunk - 1) / kSortChunk);
+            hipLaunchKernelGGL(k_rank_partial, dim3(tiles_max < 512 ? tiles_max : 512, nim), dim3(256), 0, c->stream, lp);
+            hipLaunchKernelGGL(k_rank_scatter, dim3((c->cap + 255) / 256, nim), dim3(256), 0, c->stream, lp);
+            hipLaunchKernelGGL(k_big_sort, dim3(nim), dim3(1024), 0, c->stream, lp, c->cap, c->d_area_iscale);
+        }
         UVO_HIP_TRY(c, hipGetLastError());
     }
     {
         StageTimer t(c, ST_DESCRIPTOR);
         const size_t lds_small = sizeof(float) * 21 * ((kSmallWin + 3) | 1), lds_big = sizeof(float) * 4 * kBigRow;
-        hipLaunchKernelGGL(k_big_sort, dim3(nim), dim3(1024), 0, c->stream, lp, c->cap, c->d_area_iscale);
         if (c->p.SURF_UPRIGHT) {
             const int nbig = 1024;                             // 8192 persistent waves for the large-window tasks (512: 80 us, 768..2048: 66-69 us)
             static const int desc_part = getenv("UVO_DESC_PART") ? atoi(getenv("UVO_DESC_PART")) : 0;      // measurement only
