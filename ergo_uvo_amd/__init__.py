@@ -117,7 +117,8 @@ class Context:
         h = C.c_void_p()
         st = self._lib.uvo_ctx_create(C.byref(params), device, max_w, max_h, max_kpts, C.byref(h))
         if st != 0:
-            raise UvoError(st, "uvo_ctx_create failed (no usable HIP device?)" if st == 5 else "uvo_ctx_create failed")
+            why = (self._lib.uvo_last_error(None) or b"").decode()
+            raise UvoError(st, "uvo_ctx_create failed (no usable HIP device?)" if st == 5 else "uvo_ctx_create failed" + (f": {why}" if why != "null context" else ""))
         self._h = h
         self._inflight = collections.deque()       # tensors handed to submit: kept alive until the matching collect
         self._producer = None
@@ -194,6 +195,12 @@ class Context:
         self._check(self._lib.uvo_ctx_set_feature_detector(self._h, name.encode()))
         self._feature_sift = name == "SIFT"
         self._feature_akaze = self._feature_orb = False
+
+    def set_pnp_method(self, flag: int):
+        """cv::solvePnPRansac's `flags` (the reference's PNP_METHOD_FLAG) for solvePnPRansac, stereo_step and stereo_submit / collect:
+        1 EPnP (default), 2 P3P (four-point RANSAC kernel, EPnP refit), 3 DLS and 4 UPNP (EPnP, as in OpenCV 4.5).  Any other value
+        raises UvoError, as does a call with pairs in flight.  Survives set_params."""
+        self._check(self._lib.uvo_ctx_set_pnp_method(self._h, int(flag)))
 
     def set_params(self, params: Params):
         self.params = params

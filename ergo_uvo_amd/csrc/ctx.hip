@@ -141,16 +141,21 @@ void stream_release(int device, int role, int lane, hipStream_t s)
 static const char* unsupported_params(const uvo_params* p)
 {
     if (p->ITERATIONS_COUNT > 0 && p->PNP_METHOD_FLAG != 1)
-        return "PNP_METHOD_FLAG: only 1 (cv::SOLVEPNP_EPNP, the value shipped in stereo_VO_parameters.yaml) is implemented";
+        return "PNP_METHOD_FLAG: uvo_params takes only 1 (cv::SOLVEPNP_EPNP, the value shipped in stereo_VO_parameters.yaml); 2 (P3P), 3 (DLS) and 4 (UPNP) "
+               "are set with uvo_ctx_set_pnp_method, 0 (ITERATIVE), 5 (AP3P) and above are not implemented";
     if (p->USE_EXTRINSIC_GUESS != 0) return "USE_EXTRINSIC_GUESS: only false is implemented (EPnP ignores the guess)";
     return nullptr;
 }
+
+// why the calling thread's last uvo_ctx_create refused its parameters: there is no context to hold the message, uvo_last_error(NULL) hands it out
+static thread_local const char* t_create_refusal = nullptr;
 
 static uvo_status create_one(const uvo_params* p, int device, int max_w, int max_h, int max_kpts, uvo_ctx** out, int lane = 0)
 {
     if (!out) return UVO_INVALID_ARG;
     *out = nullptr;
-    if (!p || max_w < 16 || max_h < 16 || max_kpts < 16 || unsupported_params(p)) return UVO_INVALID_ARG;
+    t_create_refusal = p ? unsupported_params(p) : nullptr;
+    if (!p || max_w < 16 || max_h < 16 || max_kpts < 16 || t_create_refusal) return UVO_INVALID_ARG;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return UVO_NO_DEVICE;
     if (hipSetDevice(device) != hipSuccess) return UVO_HIP_ERROR;
@@ -468,7 +473,7 @@ static void destroy_one(uvo_ctx* c)
     delete c;
 }
 
-extern "C" const char* uvo_last_error(const uvo_ctx* c) { return c ? c->err.c_str() : "null context"; }
+extern "C" const char* uvo_last_error(const uvo_ctx* c) { return c ? c->err.c_str() : (t_create_refusal ? t_create_refusal : "null context"); }
 extern "C" void* uvo_ctx_stream(uvo_ctx* c) { return c ? (void*)c->stream : nullptr; }
 extern "C" uvo_status uvo_ctx_set_params(uvo_ctx* c, const uvo_params* p)
 try {
@@ -646,6 +651,19 @@ try {
     for (int i = 0; i < 4; i++) if (strcmp(name, kNames[i]) == 0) det = i;
     if (det < 0) return fail(c, UVO_INVALID_ARG, "uvo_ctx_set_loop_detector: \"SURF\", \"SIFT\", \"AKAZE\" or \"ORB\"");
     return set_loop_detector(c, det);
+} UVO_ABI_CATCH(c)
+
+// cv::solvePnPRansac's `flags` (visual_odometry.h:647-648; the values of stereo_VO_parameters.yaml:32) for every PnP stage of the
+// context: the operator, the synchronous step and all pipeline lanes read it from the master context (Ctx::pnp_p3p).
+extern "C" uvo_status uvo_ctx_set_pnp_method(uvo_ctx* c, int flag)
+try {
+    if (!c) return UVO_INVALID_ARG;
+    if (c->n_pending != 0) return fail(c, UVO_INVALID_ARG, "uvo_ctx_set_pnp_method: the PnP method cannot change while pairs are in flight (collect them first)");
+    if (flag < 1 || flag > 4)
+        return fail(c, UVO_INVALID_ARG, "uvo_ctx_set_pnp_method: served are 1 (cv::SOLVEPNP_EPNP), 2 (SOLVEPNP_P3P), 3 (SOLVEPNP_DLS) and 4 (SOLVEPNP_UPNP; 3 and 4 run EPnP, as in OpenCV 4.5); "
+                                         "0 (SOLVEPNP_ITERATIVE), 5 (SOLVEPNP_AP3P) and above are not implemented");
+    c->pnp_method = flag;
+    return UVO_OK;
 } UVO_ABI_CATCH(c)
 
 extern "C" uvo_status uvo_surf_detect(uvo_ctx* c, const uint8_t* gray, int w, int h, int stride, int mem,
@@ -1392,7 +1410,8 @@ static uvo_status queue_stage_a(uvo_ctx* c, uvo_ctx* A, uvo_ctx* B)
     const bool dev_b = !B && !A->inline_b && !c->timing && stage_b_on_device(c);
     A->dev_b = dev_b;
     if (B) B->dev_b = false;
-    A->spec_queued = !B && spec_env != 0 && (A->inline_b || dev_b) && !c->timing && p.ITERATIONS_COUNT >= 1;
+    // (the speculative round is EPnP with a five-point draw table: under SOLVEPNP_P3P the host-replayed stage serves the pair)
+    A->spec_queued = !B && spec_env != 0 && (A->inline_b || dev_b) && !c->timing && p.ITERATIONS_COUNT >= 1 && !c->pnp_p3p();
     if (B) B->spec_queued = false;
     hipStream_t sb = st;
     if (dev_b) { sb = A->pnp_stream; UVO_HIP_TRY(c, hipStreamWaitEvent(sb, A->evA[1], 0)); }

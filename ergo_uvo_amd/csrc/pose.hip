@@ -16,6 +16,7 @@
 #include <atomic>
 #include <chrono>
 #include "uvo_epnp.h"
+#include "uvo_p3p.h"
 #include "uvo_epnp_fast.h"
 #include <string.h>
 #include <stdlib.h>
@@ -550,6 +551,7 @@ struct PnpJob {
     int* ninl_host;                          // pinned host mirrors (hcount, pose and ninl_host are written straight into host memory: no copies to queue)
     int G, nhyp, best;
     int n_best, seq;                         // inliers of the winning hypothesis; refit by the sequential (OpenCV-ordered) kernel
+    int mp;                                  // points per hypothesis: 5 = EPnP (k_pnp_hyp), 4 = P3P (k_pnp_hyp_p3p)
 };
 struct PnpBatch { int n, cap; double fx, fy, cx, cy; float thr2; int dbg; PnpJob job[kMaxPnpBatch]; };
 
@@ -559,7 +561,7 @@ __global__ __launch_bounds__(64) void k_pnp_hyp(PnpBatch b)
     const float* opts = jb.opts; const uvo_point2f* ipts = jb.ipts; const int* subsets = jb.subsets; double* models = jb.models;
     const int nhyp = jb.nhyp;
     const double fx = b.fx, fy = b.fy, cx = b.cx, cy = b.cy;
-    if ((int)blockIdx.x * kHypGroups >= nhyp) return;
+    if ((int)blockIdx.x * kHypGroups >= nhyp || jb.mp != 5) return;      // (a four-point job of the batch is k_pnp_hyp_p3p's)
     extern __shared__ __align__(16) unsigned char smem[];
     double* lds = reinterpret_cast<double*>(smem);
     const int group = threadIdx.x >> 3, lane = threadIdx.x & 7;
@@ -587,6 +589,35 @@ __global__ __launch_bounds__(64) void k_pnp_hyp(PnpBatch b)
         double* m = models + (size_t)hyp * 6;
         m[0] = rvec[0]; m[1] = rvec[1]; m[2] = rvec[2]; m[3] = tvec[0]; m[4] = tvec[1]; m[5] = tvec[2];
     }
+}
+
+// The RANSAC kernel of SOLVEPNP_P3P (and of any solvePnPRansac call on exactly four points): one lane per four-point hypothesis, P3P on
+// the subset's first three points, the fourth point choosing among the up to four poses (uvo_p3p.h).  fp64 in registers, no LDS, no
+// barriers: the result of a hypothesis does not depend on where it runs.  A subset without a pose -- PnPRansacCallback::runKernel
+// returning 0, RANSAC's `nmodels <= 0 -> continue` -- leaves NaNs as its model: k_pnp_score reports such a hypothesis as -1 inliers.
+static const int kP3pThreads = 64;
+__global__ __launch_bounds__(kP3pThreads) void k_pnp_hyp_p3p(PnpBatch b)
+{
+    const PnpJob& jb = b.job[blockIdx.y];
+    const int hyp = blockIdx.x * kP3pThreads + threadIdx.x;
+    if (jb.mp != 4 || hyp >= jb.nhyp) return;
+    const double fx = b.fx, fy = b.fy, cx = b.cx, cy = b.cy;
+    const double ifx = 1. / fx, ify = 1. / fy;
+    double obj[4][3], img[4][2];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const int id = jb.subsets[hyp * 4 + i];
+        obj[i][0] = jb.opts[3*id]; obj[i][1] = jb.opts[3*id + 1]; obj[i][2] = jb.opts[3*id + 2];
+        // undistortPoints with zero distortion onto the camera matrix, stored CV_32FC2 (as k_pnp_hyp); P3P normalises again
+        const double x = (double)(float)((jb.ipts[id].x - cx) * ifx), y = (double)(float)((jb.ipts[id].y - cy) * ify);
+        img[i][0] = ifx * (x * fx + cx) - cx * ifx; img[i][1] = ify * (y * fy + cy) - cy * ify;
+    }
+    double rvec[3], tvec[3];
+    const bool ok = p3p_solve4(obj, img, rvec, tvec);
+    double* m = jb.models + (size_t)hyp * 6;
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    m[0] = ok ? rvec[0] : nan; m[1] = ok ? rvec[1] : nan; m[2] = ok ? rvec[2] : nan;
+    m[3] = ok ? tvec[0] : nan; m[4] = ok ? tvec[1] : nan; m[5] = ok ? tvec[2] : nan;
 }
 
 // PnPRansacCallback::computeError + findInliers for one model: projectPoints (double, stored float),
@@ -622,6 +653,7 @@ __global__ __launch_bounds__(256) void k_pnp_score(PnpBatch b)
     double R[9], t[3];
     for (int k = 0; k < 9; k++) R[k] = sR[k];
     t[0] = st[0]; t[1] = st[1]; t[2] = st[2];
+    if (jb.mp == 4 && t[0] != t[0]) { if (tid == 0) hcount[hyp] = -1; return; }     // k_pnp_hyp_p3p's "no model": a count the scan never accepts
     int cnt = 0;
     for (int i = tid; i < n; i += 256) cnt += pnp_is_inlier(opts, ipts, i, R, t, fx, fy, cx, cy, thr2) ? 1 : 0;
     for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off);
@@ -1149,7 +1181,9 @@ bool pose_pnp_spec_accept(Ctx* c, int G, int iters, double confidence, PnpResult
 uvo_status pose_pnp_ransac_batch(Ctx* m, int n, Ctx* const* lanes, const int* G, const double* K, int iterationsCount,
                                  float reprojectionError, double confidence, PnpResult* res)
 {
-    const int modelPoints = 5;
+    // solvePnPRansac: model_points = 5 and an EPnP kernel, unless flags is SOLVEPNP_P3P or npoints == 4: then model_points = 4 and a P3P
+    // kernel.  npoints == model_points is one direct solve with every point an inlier (no solution: false, no inliers).
+    const bool p3p_method = m->pnp_p3p();
     hipStream_t st = m->pnp_stream;
     double t_b0 = g_bdbg ? now_us() : 0;
     if (n < 1 || n > kMaxPnpBatch) { m->err = "pnp batch size"; return UVO_INVALID_ARG; }
@@ -1167,7 +1201,7 @@ uvo_status pose_pnp_ransac_batch(Ctx* m, int n, Ctx* const* lanes, const int* G,
     // way, so the chosen model is the one a single launch of all ITERATIONS_COUNT hypotheses would give; with the
     // inlier ratios of a working odometry the count drops to a handful after the first good hypothesis and one round of
     // 8 workgroups replaces 63 (whose 54 KB of LDS each would otherwise sit beside other pairs' stage-A kernels).
-    struct Scan { int job, G, niters, maxGood, best, last, iter, computed; uint64_t rng; bool active; };
+    struct Scan { int job, G, mp, niters, maxGood, best, last, iter, computed; uint64_t rng; bool active; };
     Scan sc[kMaxPnpBatch];
     PnpJob base[kMaxPnpBatch];                // full-range pointers of each active job
     int ns = 0;
@@ -1176,16 +1210,16 @@ uvo_status pose_pnp_ransac_batch(Ctx* m, int n, Ctx* const* lanes, const int* G,
         r.st = UVO_OK; r.wrote = r.ok = r.ninl = 0;
         Ctx* c = lanes[i];
         if (G[i] < 4) { c->err = "solvePnPRansac needs at least 4 points (OpenCV asserts)"; r.st = UVO_TOO_FEW_POINTS; continue; }
-        if (G[i] == 4) { c->err = "solvePnPRansac with exactly 4 points takes OpenCV's P3P path, which the reference never reaches; not implemented"; r.st = UVO_TOO_FEW_POINTS; continue; }
         if (niters0 > kMaxHyp) { c->err = "iterations_count exceeds the compiled hypothesis capacity (2048)"; r.st = UVO_CAPACITY; continue; }
         // subsets are read from, and the per-hypothesis counts, the pose and the inlier count written to, pinned host memory
         // by the kernels themselves: the queue holds launches only (each small copy costs ~10 us of stage-B latency)
         PnpJob& j = base[ns];
         j.opts = c->d_opts[0]; j.ipts = c->d_ipts[0]; j.subsets = c->h_subsets; j.models = c->d_models; j.hcount = c->h_hcount;
         j.inliers = c->d_inliers; j.ws = c->d_refit; j.countsB = c->d_countsB; j.pose = c->h_pose; j.ninl_host = c->h_countsB;
-        j.G = G[i]; j.nhyp = 0; j.best = 0; j.n_best = 0; j.seq = 0;
+        const int modelPoints = (p3p_method || G[i] == 4) ? 4 : 5;
+        j.G = G[i]; j.nhyp = 0; j.best = 0; j.n_best = 0; j.seq = 0; j.mp = modelPoints;
         Scan& q = sc[ns++];
-        q.job = i; q.G = G[i]; q.niters = G[i] == modelPoints ? 1 : niters0; q.maxGood = 0; q.best = -1; q.last = 0; q.iter = 0; q.computed = 0;
+        q.job = i; q.G = G[i]; q.mp = modelPoints; q.niters = G[i] == modelPoints ? 1 : niters0; q.maxGood = 0; q.best = -1; q.last = -1; q.iter = 0; q.computed = 0;
         q.rng = (uint64_t)-1;                 // getSubset (ptsetreg.cpp): cv::RNG((uint64)-1)
         q.active = true;
     }
@@ -1194,17 +1228,18 @@ uvo_status pose_pnp_ransac_batch(Ctx* m, int n, Ctx* const* lanes, const int* G,
     if (tr) { tr->b_used = true; (void)hipEventRecord(tr->ev[3], st); (void)hipEventRecord(tr->ev[4], st); (void)hipEventRecord(tr->ev[5], st); }
     const int kFirstHyp = 64;
     for (int round = 0; ; round++) {
-        int slot_of[kMaxPnpBatch], nb = 0, max_hyp = 0;
+        int slot_of[kMaxPnpBatch], nb = 0, max_hyp5 = 0, max_hyp4 = 0;
         for (int k = 0; k < ns; k++) {
             Scan& q = sc[k];
             if (!q.active) continue;
             Ctx* c = lanes[q.job];
+            const int modelPoints = q.mp;
             const int count = round == 0 ? (q.niters < kFirstHyp ? q.niters : kFirstHyp) : q.niters - q.computed;
-            if (q.G == modelPoints) { for (int t = 0; t < 5; t++) c->h_subsets[t] = t; }
+            if (q.G == modelPoints) { for (int t = 0; t < modelPoints; t++) c->h_subsets[t] = t; }
             else {
                 // getSubset: uniform(0, count), redraw while duplicate; the generator runs on from round to round
                 for (int it = q.computed; it < q.computed + count; it++) {
-                    int* sub = c->h_subsets + it * 5;
+                    int* sub = c->h_subsets + it * modelPoints;
                     for (int t = 0; t < modelPoints; t++) {
                         int idx_k;
                         for (;;) {
@@ -1219,28 +1254,30 @@ uvo_status pose_pnp_ransac_batch(Ctx* m, int n, Ctx* const* lanes, const int* G,
             }
             PnpJob& j = b.job[nb];
             j = base[k];
-            j.subsets = base[k].subsets + (size_t)q.computed * 5; j.models = base[k].models + (size_t)q.computed * 6; j.hcount = base[k].hcount + q.computed;
+            j.subsets = base[k].subsets + (size_t)q.computed * modelPoints; j.models = base[k].models + (size_t)q.computed * 6; j.hcount = base[k].hcount + q.computed;
             j.nhyp = count;
-            if (count > max_hyp) max_hyp = count;
+            if (modelPoints == 5 && count > max_hyp5) max_hyp5 = count;
+            if (modelPoints == 4 && count > max_hyp4) max_hyp4 = count;
             slot_of[nb++] = k;
         }
         if (nb == 0) break;
         b.n = nb;
         {
             StageTimer t(m, ST_PNP_HYP, st);
-            hipLaunchKernelGGL(k_pnp_hyp, dim3((max_hyp + kHypGroups - 1) / kHypGroups, nb), dim3(64), hyp_lds, st, b);
+            if (max_hyp5 > 0) hipLaunchKernelGGL(k_pnp_hyp, dim3((max_hyp5 + kHypGroups - 1) / kHypGroups, nb), dim3(64), hyp_lds, st, b);
+            if (max_hyp4 > 0) hipLaunchKernelGGL(k_pnp_hyp_p3p, dim3((max_hyp4 + kP3pThreads - 1) / kP3pThreads, nb), dim3(kP3pThreads), 0, st, b);
             UVO_HIP_TRY(m, hipGetLastError());
         }
         bool any_scored = false;
-        for (int s_ = 0; s_ < nb; s_++) any_scored = any_scored || sc[slot_of[s_]].G != modelPoints;
+        for (int s_ = 0; s_ < nb; s_++) any_scored = any_scored || sc[slot_of[s_]].G != sc[slot_of[s_]].mp;
         if (any_scored) {
             StageTimer t(m, ST_PNP_SCORE, st);
-            hipLaunchKernelGGL(k_pnp_score, dim3(max_hyp, nb), dim3(256), 0, st, b);
+            hipLaunchKernelGGL(k_pnp_score, dim3(max_hyp5 > max_hyp4 ? max_hyp5 : max_hyp4, nb), dim3(256), 0, st, b);
             UVO_HIP_TRY(m, hipGetLastError());
         }
         for (int s_ = 0; s_ < nb; s_++) {
             Ctx* c = lanes[sc[slot_of[s_]].job];
-            if (sc[slot_of[s_]].G == modelPoints) UVO_HIP_TRY(m, hipMemcpyAsync(c->h_pose, c->d_models, sizeof(double) * 6, hipMemcpyDeviceToHost, st));
+            if (sc[slot_of[s_]].G == sc[slot_of[s_]].mp) UVO_HIP_TRY(m, hipMemcpyAsync(c->h_pose, c->d_models, sizeof(double) * 6, hipMemcpyDeviceToHost, st));
         }
         if (tr) (void)hipEventRecord(tr->ev[4], st);
         UVO_HIP_TRY(m, host_sync(m, st));
@@ -1248,11 +1285,13 @@ uvo_status pose_pnp_ransac_batch(Ctx* m, int n, Ctx* const* lanes, const int* G,
         for (int s_ = 0; s_ < nb; s_++) {
             Scan& q = sc[slot_of[s_]];
             Ctx* c = lanes[q.job];
+            const int modelPoints = q.mp;
             q.computed += b.job[s_].nhyp;
             if (q.G == modelPoints) { q.active = false; continue; }
             for (; q.iter < q.niters && q.iter < q.computed; q.iter++) {
-                q.last = q.iter;
                 const int goodCount = c->h_hcount[q.iter];
+                if (goodCount < 0) continue;       // P3P found no pose for the subset: the iteration is spent, nothing is scored
+                q.last = q.iter;
                 if (goodCount > (q.maxGood > modelPoints - 1 ? q.maxGood : modelPoints - 1)) {
                     q.best = q.iter; q.maxGood = goodCount;
                     q.niters = ransac_update_num_iters(confidence, (double)(q.G - goodCount) / q.G, modelPoints, q.niters);
@@ -1270,16 +1309,20 @@ uvo_status pose_pnp_ransac_batch(Ctx* m, int n, Ctx* const* lanes, const int* G,
         const Scan& q = sc[k];
         Ctx* c = lanes[q.job];
         PnpResult& r = res[q.job];
-        if (q.G == modelPoints) {              // npoints == model_points: the single model, all five points inliers
+        if (q.G == q.mp) {                     // npoints == model_points: the single model, all its points inliers
+            if (q.mp == 4 && c->h_pose[0] != c->h_pose[0]) continue;      // P3P without a solution: solvePnP returned false -- ok = 0, no inliers, no pose
             memcpy(r.rvec, c->h_pose, sizeof(double) * 3); memcpy(r.tvec, c->h_pose + 3, sizeof(double) * 3);
             int ids[5] = {0, 1, 2, 3, 4};
-            UVO_HIP_TRY(m, hipMemcpyAsync(c->d_inliers, ids, sizeof(ids), hipMemcpyHostToDevice, st));
+            UVO_HIP_TRY(m, hipMemcpyAsync(c->d_inliers, ids, sizeof(int) * q.mp, hipMemcpyHostToDevice, st));
             UVO_HIP_TRY(m, hipStreamSynchronize(st));
-            r.wrote = 1; r.ok = 1; r.ninl = 5;
+            r.wrote = 1; r.ok = 1; r.ninl = q.mp;
             continue;
         }
         if (q.best < 0) {
-            // RANSAC failed: OpenCV hands back the last hypothesis' rvec/tvec and no inliers
+            // RANSAC failed: OpenCV hands back the last hypothesis' rvec/tvec and no inliers.  Under P3P a hypothesis without a model
+            // leaves the callback's rvec/tvec as they were, so "the last" is the last hypothesis of the scan that HAD a model; when none
+            // had, OpenCV returns an uninitialised pose and this library writes none (ok = 0, rvec/tvec untouched).
+            if (q.last < 0) continue;
             UVO_HIP_TRY(m, hipMemcpyAsync(c->h_pose, c->d_models + (size_t)q.last * 6, sizeof(double) * 6, hipMemcpyDeviceToHost, st));
             need_sync = true;
             r.wrote = 2;                      // pose arrives with the final sync

@@ -275,6 +275,10 @@ struct Ctx {
 
     int match_dim = 0;                           // uvo_match_knn2*_dim: row width of the standalone matcher for the duration of one call (0 = SURF's)
     int loop_detector() const { return (master ? master : this)->detector; }
+    // cv::solvePnPRansac's `flags` (uvo_ctx_set_pnp_method): 1 EPnP; 3 DLS and 4 UPNP run EPnP in OpenCV 4.5; 2 P3P: a four-point RANSAC
+    // kernel (k_pnp_hyp_p3p), the final refit stays EPnP.  Read from the master context; uvo_ctx_set_params leaves it alone.
+    int pnp_method = 1;
+    bool pnp_p3p() const { return (master ? master : this)->pnp_method == 2; }
     bool use_sift() const { return loop_detector() == 1; }
     bool use_binary() const { return loop_detector() >= 2; }      // AKAZE / ORB: CV_8U rows, kept as 64-byte zero-padded rows in det[].desc
     int desc_bytes() const { return loop_detector() == 2 ? 61 : 32; }     // bytes of a binary row: AKAZE's M-LDB 61, ORB's rBRIEF 32

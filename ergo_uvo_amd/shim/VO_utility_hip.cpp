@@ -58,7 +58,9 @@ uvo_params globals_to()
     p.REPROJECTION_TOLERANCE = REPROJECTION_TOLERANCE; p.MIN_NUM_FEATURES = MIN_NUM_FEATURES;
     p.MIN_NUM_3DPOINTS = MIN_NUM_3DPOINTS; p.MIN_NUM_INLIERS = MIN_NUM_INLIERS; p.ITERATIONS_COUNT = ITERATIONS_COUNT;
     p.REPROJECTION_ERROR_THRESHOLD = REPROJECTION_ERROR_THRESHOLD; p.CONFIDENCE = CONFIDENCE;
-    p.USE_EXTRINSIC_GUESS = USE_EXTRINSIC_GUESS; p.PNP_METHOD_FLAG = PNP_METHOD_FLAG;
+    // PNP_METHOD_FLAG 2 (P3P), 3 (DLS), 4 (UPNP) go to the context through uvo_ctx_set_pnp_method (ctx_now); the struct, which accepts 1
+    // only, then carries 1.  Every other value goes through the struct and is refused by the library with its own message.
+    p.USE_EXTRINSIC_GUESS = USE_EXTRINSIC_GUESS; p.PNP_METHOD_FLAG = (PNP_METHOD_FLAG >= 2 && PNP_METHOD_FLAG <= 4) ? 1 : PNP_METHOD_FLAG;
     p.SURF_MIN_HESSIAN = SURF_MIN_HESSIAN; p.SURF_OCTAVES_NUMBER = SURF_OCTAVES_NUMBER;
     p.SURF_OCTAVES_LAYERS = SURF_OCTAVES_LAYERS; p.SURF_EXTENDED = SURF_EXTENDED; p.SURF_UPRIGHT = SURF_UPRIGHT;
     return p;
@@ -69,6 +71,7 @@ struct State {
     std::mutex mu;
     uvo_ctx* ctx = nullptr;
     uvo_params applied;
+    int pnp_method = 1;                           // what uvo_ctx_set_pnp_method was last given (a context starts on 1)
     int device = 0, max_w = 1920, max_h = 1200, max_kpts = 8192;
     std::vector<int> orb_pattern;                 // OpenCV's bit_pattern_31_ (set_orb_pattern / UVO_ORB_PATTERN_FILE); empty = not supplied
     bool orb_pattern_sent = false;                // ... and handed to the current context
@@ -76,10 +79,19 @@ struct State {
 
 [[noreturn]] void raise(uvo_status st, const char* where)
 {
-    const char* msg = g.ctx ? uvo_last_error(g.ctx) : "";
+    const char* msg = uvo_last_error(g.ctx);             // no context: the reason uvo_ctx_create gave for refusing the parameters
+    if (!g.ctx && msg && strcmp(msg, "null context") == 0) msg = "";
     throw uvo_hip::Error(st, std::string(where) + ": uvo_status " + std::to_string((int)st) + (msg && *msg ? std::string(" (") + msg + ")" : ""));
 }
 #define SHIM_TRY(expr, where) do { uvo_status st_ = (expr); if (st_ != UVO_OK) raise(st_, where); } while (0)
+
+// cv::solvePnPRansac's flags on the context (g.mu held): the global PNP_METHOD_FLAG, or the argument of uvo_hip::solvePnPRansac
+void set_method_locked(int flag)
+{
+    if (flag == g.pnp_method) return;
+    SHIM_TRY(uvo_ctx_set_pnp_method(g.ctx, flag), "uvo_ctx_set_pnp_method");
+    g.pnp_method = flag;
+}
 
 // the context with the current value of the parameter globals applied
 uvo_ctx* ctx_now()
@@ -94,6 +106,7 @@ uvo_ctx* ctx_now()
         SHIM_TRY(uvo_ctx_set_params(g.ctx, &p), "uvo_ctx_set_params");
         g.applied = p;
     }
+    if (PNP_METHOD_FLAG >= 1 && PNP_METHOD_FLAG <= 4) set_method_locked(PNP_METHOD_FLAG);
     return g.ctx;
 }
 
@@ -149,7 +162,7 @@ void shutdown()
 {
     std::lock_guard<std::mutex> lk(g.mu);
     if (g.ctx) { uvo_ctx_destroy(g.ctx); g.ctx = nullptr; }
-    g.orb_pattern_sent = false;
+    g.orb_pattern_sent = false; g.pnp_method = 1;
 }
 void set_orb_pattern(const int* pattern1024)
 {
@@ -176,8 +189,8 @@ bool solvePnPRansac(const Mat& objectPoints, const vector<Point2f>& imagePoints,
                     Mat& rvec, Mat& tvec, bool useExtrinsicGuess, int iterationsCount, float reprojectionError, double confidence,
                     Mat& inliers, int flags)
 {
-    (void)useExtrinsicGuess;                              // SOLVEPNP_EPNP ignores the guess (calib3d solvepnp.cpp)
-    require(flags == 1, "solvePnPRansac: only SOLVEPNP_EPNP (1) is provided (visual_odometry.h:647-648)");
+    (void)useExtrinsicGuess;                              // EPnP and P3P ignore the guess (calib3d solvepnp.cpp)
+    require(flags >= 1 && flags <= 4, "solvePnPRansac: flags 1 (SOLVEPNP_EPNP), 2 (SOLVEPNP_P3P), 3 (SOLVEPNP_DLS) and 4 (SOLVEPNP_UPNP) are provided (visual_odometry.h:647-648)");
     if (!distCoeffs.empty())
         for (int i = 0; i < distCoeffs.rows; i++) for (int j = 0; j < distCoeffs.cols; j++)
             require(distCoeffs.at<double>(i, j) == 0.0, "solvePnPRansac: distortion must be zero (images are undistorted by get_image)");
@@ -189,7 +202,9 @@ bool solvePnPRansac(const Mat& objectPoints, const vector<Point2f>& imagePoints,
     double rv[3] = {0, 0, 0}, tv[3] = {0, 0, 0};
     vector<int> inl((size_t)(n > 0 ? n : 1));
     int ni = 0, ok = 0;
-    SHIM_TRY(uvo_solve_pnp_ransac(ctx_now(), obj.data(), pts_of(imagePoints), n, K, iterationsCount, reprojectionError, confidence,
+    uvo_ctx* c = ctx_now();
+    { std::lock_guard<std::mutex> lk(g.mu); set_method_locked(flags); }
+    SHIM_TRY(uvo_solve_pnp_ransac(c, obj.data(), pts_of(imagePoints), n, K, iterationsCount, reprojectionError, confidence,
                                   rv, tv, inl.data(), &ni, &ok), "uvo_solve_pnp_ransac");
     if (ok) { rvec = mat_from(rv, 3, 1); tvec = mat_from(tv, 3, 1); }
     inliers.create(ni, 1, CV_32SC1);

@@ -73,7 +73,8 @@ void uvo_params_default_mono(uvo_params* p);
 /* ---- context ---- */
 uvo_status  uvo_ctx_create(const uvo_params* p, int device, int max_w, int max_h, int max_kpts, uvo_ctx** out);
 void        uvo_ctx_destroy(uvo_ctx* c);
-const char* uvo_last_error(const uvo_ctx* c);           /* message of the last non-OK status */
+const char* uvo_last_error(const uvo_ctx* c);           /* message of the last non-OK status; c == NULL: why this thread's last
+                                                           uvo_ctx_create refused its parameters, if it did */
 void*       uvo_ctx_stream(uvo_ctx* c);                 /* the context's hipStream_t */
 uvo_status  uvo_ctx_set_params(uvo_ctx* c, const uvo_params* p);
 /* The hipStream_t on which the caller produces its UVO_MEM_DEVICE inputs (NULL = the default stream): while `enabled`,
@@ -111,6 +112,19 @@ uvo_status uvo_ctx_set_feature_detector(uvo_ctx* c, const char* name);
  * (reset first).  A frame with more than max_kpts keypoints is a UVO_CAPACITY error, as for SURF: create the context with max_kpts >=
  * 10000 + ties for SIFT / ORB on 1080p frames.  NULL c or name: UVO_INVALID_ARG. */
 uvo_status uvo_ctx_set_loop_detector(uvo_ctx* c, const char* name);
+
+/* The `flags` argument of cv::solvePnPRansac at visual_odometry.h:647-648 (the reference's global PNP_METHOD_FLAG; the values documented in
+ * stereo_VO_parameters.yaml:32), for uvo_solve_pnp_ransac, uvo_stereo_step and uvo_stereo_submit / collect on every pipeline lane:
+ *   1  SOLVEPNP_EPNP (default)  five-point EPnP hypotheses, EPnP refit on the winner's inliers;
+ *   3  SOLVEPNP_DLS, 4  SOLVEPNP_UPNP  OpenCV 4.5's solvePnPGeneric runs EPnP for both: every output is bit-identical to flag 1;
+ *   2  SOLVEPNP_P3P  model_points = 4: P3P (Gao et al. 2003) on the first three points of a subset, the fourth point picks among its
+ *      solutions; a subset without a solution spends its iteration unscored.  The final refit on the winner's inliers is EPnP, as in
+ *      OpenCV.  If RANSAC fails, rvec / tvec are those of the last hypothesis that had a solution (untouched when none had).
+ *   anything else (0 SOLVEPNP_ITERATIVE, 5 SOLVEPNP_AP3P, ...) is UVO_INVALID_ARG: no method is ever replaced silently.
+ * Under every method a problem of exactly four points is the single P3P solve OpenCV runs there (all four points inliers; *ok = 0 and
+ * no inliers when P3P has no solution).  The value survives uvo_ctx_set_params: uvo_params.PNP_METHOD_FLAG is validated on its own
+ * and still accepts 1 only.  Refused while pairs are in flight.  NULL c: UVO_INVALID_ARG. */
+uvo_status uvo_ctx_set_pnp_method(uvo_ctx* c, int flag);
 
 /* ---- detect_features, SURF branch (VO_utility.h:100 -> VO_utility.cpp:114-119) ----
  * gray: 8-bit single channel, `stride` bytes per row.  kps/desc are host buffers of capacity `cap`, either may be NULL;
@@ -211,9 +225,9 @@ uvo_status uvo_extract_3d_points(uvo_ctx* c, const uvo_point2f* k1, const uvo_po
 uvo_status uvo_reproject_errors(uvo_ctx* c, const double* world, int n, const double* R, const double* t,
                                 const double* K, const uvo_point2f* img, double* err);
 
-/* ---- cv::solvePnPRansac(..., SOLVEPNP_EPNP) as called at visual_odometry.h:647-648 ----
+/* ---- cv::solvePnPRansac(..., flags) as called at visual_odometry.h:647-648; flags = SOLVEPNP_EPNP unless uvo_ctx_set_pnp_method ----
  * obj: n x 3 f64, img: n Point2f, K 3x3 f64 (host).  inliers: host, capacity n, ascending.
- * *ok is OpenCV's bool return. */
+ * *ok is OpenCV's bool return.  n < 4: UVO_TOO_FEW_POINTS. */
 uvo_status uvo_solve_pnp_ransac(uvo_ctx* c, const double* obj, const uvo_point2f* img, int n, const double* K,
                                 int iterations_count, float reprojection_error, double confidence,
                                 double* rvec, double* tvec, int* inliers, int* n_inliers, int* ok);
