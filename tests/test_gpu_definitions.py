@@ -16,7 +16,10 @@ Lowe's ratio test; DLT triangulation; VO_utility.cpp:188-237 for the 3-D filter;
     observations;
   * extract_3Dpoints keeps exactly the points the definition keeps (mean reprojection error below the tolerance, positive depth,
     depth within mean +- 3 sigma of those);
-  * solvePnPRansac recovers a planted pose, and its inliers reproject within the threshold under it."""
+  * solvePnPRansac recovers a planted pose, and its inliers reproject within the threshold under it.
+
+get_image, the preprocessing in front of the detectors, has its second statement in tests/preproc_definitions_np.py
+(tests/test_gpu_preproc_definitions.py holds the HIP kernels to it); AKAZE and SIFT in tests/detector_definitions_np.py."""
 import numpy as np
 import pytest
 

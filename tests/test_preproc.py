@@ -1,8 +1,12 @@
 """get_image (VO_utility.cpp:337-379): resize INTER_AREA -> RGB2GRAY -> undistort -> CLAHE.
 
 CPU: known-answer tests of the oracle restatement (oracle/o_preproc.c) -- closed forms that do not depend on the
-restatement itself.  GPU: the HIP path (ergo_uvo_amd/csrc/preproc.hip, through the C ABI uvo_get_image) must equal
-the oracle byte for byte, stage by stage and end to end."""
+restatement itself.  They are narrow: the undistortion runs with dist = 0 only, CLAHE with clipping off at one pixel, the
+fractional resize for its mean.  GPU: the HIP path (ergo_uvo_amd/csrc/preproc.hip, through the C ABI uvo_get_image) must
+equal the oracle byte for byte, end to end -- which cannot show that the two, written by one hand, read the algorithms right.
+The independent statement of every stage (the distortion polynomial, the stripes, the fixed-point split, CLAHE's clip and
+redistribute and its extension rule, the area average pixel by pixel) is tests/preproc_definitions_np.py; the oracle is held
+to it in tests/test_oracle_preproc_definitions.py, the HIP kernels in tests/test_gpu_preproc_definitions.py."""
 import numpy as np
 import pytest
 
