@@ -498,6 +498,73 @@ class Context:
         assert (ow.value, oh.value) == (desired_width, dh)
         return out
 
+    # ------------------------------------------------------------------ camera frames into the loops (uvo_*_frames)
+    def set_camera(self, cam, K, dist4, newK, desired_width, clahe=True, clip_limit=3):
+        """get_image's arguments for camera `cam` (0 = left or mono, 1 = right), kept by the context for the *_frames calls.
+        Raises UvoError with pairs / frames in flight."""
+        K, dist4, newK = _np(K, np.float64), _np(dist4, np.float64), _np(newK, np.float64)
+        self._check(self._lib.uvo_ctx_set_camera(self._h, int(cam), _p(K), _p(dist4), _p(newK), int(desired_width), int(bool(clahe)), int(clip_limit)))
+
+    @staticmethod
+    def _frame(rgb):
+        """(pointer, w, h, stride, mem, keepalive) of an HxWx3 uint8 frame: a numpy array, or a CUDA tensor whose rows may be padded."""
+        if _is_device(rgb):
+            h, w, ch = rgb.shape
+            if ch != 3 or rgb.stride(2) != 1 or rgb.stride(1) != 3:
+                raise ValueError("device frames must be HxWx3 uint8 with interleaved channels (rows may be padded)")
+            return C.c_void_p(rgb.data_ptr()), w, h, int(rgb.stride(0)), MEM_DEVICE, rgb
+        arr = _np(rgb, np.uint8)
+        h, w, ch = arr.shape
+        if ch != 3:
+            raise ValueError("frames must be HxWx3 uint8")
+        return _p(arr), w, h, 3 * w, MEM_HOST, arr
+
+    def _frame_pair(self, left_rgb, right_rgb):
+        pl, w, h, sl, ml, kl = self._frame(left_rgb)
+        pr, wr, hr, sr, mr, kr = self._frame(right_rgb)
+        if ml != mr:
+            raise ValueError("left and right must live in the same memory space")
+        if (w, h, sl) != (wr, hr, sr):
+            raise ValueError("left and right frames must have the same size and row stride")
+        return pl, pr, w, h, sl, ml, (kl, kr)
+
+    def stereo_step_frames(self, left_rgb, right_rgb, dt: float = 0.05) -> StereoResult:
+        """stereo_step on colour frames: get_image with the cameras of set_camera(0 / 1, ...) runs in front of detection, on the device."""
+        pl, pr, w, h, stride, mem, keep = self._frame_pair(left_rgb, right_rgb)
+        r = StereoResult()
+        self._order_after_producer(left_rgb, right_rgb)
+        self._check(self._lib.uvo_stereo_step_frames(self._h, pl, pr, w, h, stride, mem, C.c_double(dt), C.byref(r)))
+        return r
+
+    def stereo_submit_frames(self, left_rgb, right_rgb):
+        """stereo_submit on colour frames (collect with stereo_collect); the frames are read asynchronously until then."""
+        pl, pr, w, h, stride, mem, keep = self._frame_pair(left_rgb, right_rgb)
+        self._order_after_producer(left_rgb, right_rgb)
+        self._check(self._lib.uvo_stereo_submit_frames(self._h, pl, pr, w, h, stride, mem))
+        self._inflight.append(keep)
+
+    def mono_step_frames(self, rgb, range_=1.0, dt: float = 0.05) -> MonoResult:
+        """mono_step on a colour frame: get_image with camera 0 of set_camera runs in front of detection, on the device."""
+        p, w, h, stride, mem, keep = self._frame(rgb)
+        r = MonoResult()
+        self._order_after_producer(rgb)
+        self._check(self._lib.uvo_mono_step_frames(self._h, p, w, h, stride, mem, C.c_double(range_), C.c_double(dt), C.byref(r)))
+        return r
+
+    def mono_submit_frames(self, rgb, range_=1.0):
+        """mono_submit on a colour frame (collect with mono_collect)."""
+        p, w, h, stride, mem, keep = self._frame(rgb)
+        self._order_after_producer(rgb)
+        self._check(self._lib.uvo_mono_submit_frames(self._h, p, w, h, stride, mem, C.c_double(range_)))
+        self._inflight.append((keep,))
+
+    def _get_image_key(self, getter, what):
+        buf = np.zeros(self.max_w * self.max_h, np.uint8)
+        n = getter(self._h, what.encode(), _p(buf), buf.nbytes)
+        if n < 0:
+            raise UvoError(3, "image buffer too small")
+        return buf[:n].copy()
+
     def decode_image(self, data: bytes, fmt: str = "bgr8; jpeg compressed bgr8", device_out=False):
         """from_ros_to_cv_image (math_utility.cpp:154-173): the payload of a sensor_msgs/CompressedImage -> H x W x 3 BGR (or H x W grey);
         a format containing "bayer" is demosaiced with COLOR_BayerBGGR2BGR.  Returns a numpy array, or a CUDA tensor when device_out."""
@@ -555,6 +622,8 @@ class Context:
 
     def stereo_get(self, what: str):
         """Intermediates of the last collected pair; desc_left / desc_right are float rows (SURF, SIFT) or uint8 rows of 61 (AKAZE) / 32 (ORB) bytes."""
+        if what in ("img_left", "img_right"):       # the detector's image of the pair, flat (out_w * out_h bytes)
+            return self._get_image_key(self._lib.uvo_stereo_get, what)
         binary = np.dtype(("u1", 61)) if getattr(self, "_feature_akaze", False) else (np.dtype(("u1", 32)) if getattr(self, "_feature_orb", False) else None)
         if binary is not None and what in ("desc_left", "desc_right"):
             buf = np.zeros(self.max_kpts, binary)
@@ -668,6 +737,8 @@ class Context:
         self._drained()
 
     def mono_get(self, what: str):
+        if what == "img":                           # the detector's image of the frame, flat (out_w * out_h bytes)
+            return self._get_image_key(self._lib.uvo_mono_get, what)
         spec = {"kps": KP_DTYPE, "matches": DM_DTYPE, "mask": np.dtype("u1"), "good_pts": np.dtype(("f8", 3))}[what]
         buf = np.zeros(self.max_kpts, spec)
         n = self._lib.uvo_mono_get(self._h, what.encode(), _p(buf), buf.nbytes)

@@ -441,6 +441,7 @@ static void destroy_one(uvo_ctx* c)
     if (c->pnp_stream) (void)hipStreamSynchronize(c->pnp_stream);
     mono_ws_free(c);
     pre_ws_free(c);
+    frames_ws_free(c);
     codec_ws_free(c);
     sift_ws_free(c);
     akaze_ws_free(c);
@@ -1670,6 +1671,11 @@ try {
     else if (w == "good_pts") { src = c->d_good_pts[0]; count = c->last_G; esz = 3 * sizeof(double); }
     else if (w == "good_idx") { src = c->d_good_idx[0]; count = c->last_G; esz = sizeof(int); }
     else if (w == "inliers") { src = c->d_inliers; count = c->last_ninl; esz = sizeof(int); }
+    else if (w == "img_left" || w == "img_right") {                  // the lane's own detector image (nothing when the pair's images were read in place from the caller's memory)
+        const int s = w == "img_left" ? 0 : 1;
+        if (c->img[s] != c->d_img[s]) return 0;
+        src = c->d_img[s]; count = c->img_w * c->img_h; esz = 1;
+    }
     else return 0;
     if ((size_t)count * esz > (size_t)cap_bytes) return -count;
     if (count) {
@@ -2265,6 +2271,10 @@ try {
         else { src = f->d_good_pts[0]; count = f->mono_dev_G; on_device = true; }
         nb = (size_t)count * 3 * sizeof(double);
     }
+    else if (w == "img") {                                               // the lane's own detector image (see uvo_stereo_get)
+        if (f->img[0] != f->d_img[0]) return 0;
+        src = f->d_img[0]; count = f->img_w * f->img_h; nb = (size_t)count; on_device = true;
+    }
     else return 0;
     if (nb > (size_t)cap_bytes) return -count;
     if (nb) {
@@ -2273,6 +2283,106 @@ try {
     }
     return count;
 } UVO_ABI_CATCH_RET(c, 0)
+
+// ------------------------------------------------------------------------------------------ camera frames into the loops
+// get_image (VO:235/260, VO:482-483/542-543) inside the loop entries: the colour frames of an entry are preprocessed on the entry's
+// lane's stage-A stream, into the lane's own detector images, and the entry then goes through uvo_stereo_submit / uvo_mono_submit /
+// uvo_mono_step as a device image read in place -- so everything behind the seam is those calls' code, unchanged.  The lane is the
+// one the call below will pick: lane 0 while the loop initialises (synchronous), else next_lane, which is free because the pipeline is
+// not full.  No later entry reads a predecessor's IMAGE (queue_stage_a reads the previous lane's "after stereo match" set, the mono
+// submit the previous lane's keypoints and descriptors), so a lane's image buffers are its own from collect to collect.
+extern "C" uvo_status uvo_ctx_set_camera(uvo_ctx* c, int cam, const double* K, const double* dist4, const double* newK, int desired_width,
+                                         int clahe, int clip_limit)
+try {
+    if (!c) return UVO_INVALID_ARG;
+    if (!K || !dist4 || !newK) return fail(c, UVO_INVALID_ARG, "uvo_ctx_set_camera: NULL camera matrix / distortion pointer");
+    if (cam < 0 || cam > 1) return fail(c, UVO_INVALID_ARG, "uvo_ctx_set_camera: cam is 0 (left or mono) or 1 (right)");
+    if (desired_width <= 0) return fail(c, UVO_INVALID_ARG, "uvo_ctx_set_camera: desired_width must be positive");
+    if (c->n_pending != 0) return fail(c, UVO_INVALID_ARG, "uvo_ctx_set_camera: a camera cannot change while pairs / frames are in flight (collect first)");
+    return frames_set_camera(c, cam, K, dist4, newK, desired_width, clahe, clip_limit);
+} UVO_ABI_CATCH(c)
+
+namespace {
+// a frames entry goes alone (never into a two-pair launch set: the set's kernels run on the other lane's stream), and its producer
+// wait is queued in front of the preprocessing, not again in front of detection
+struct FramesEntryScope {
+    uvo_ctx* c; int batch; bool has_producer;
+    explicit FramesEntryScope(uvo_ctx* c_) : c(c_), batch(c_->batch), has_producer(c_->has_producer) { c->batch = 1; c->has_producer = false; }
+    ~FramesEntryScope() { c->batch = batch; c->has_producer = has_producer; }
+};
+}
+static uvo_status frames_to_lane(uvo_ctx* c, uvo_ctx* L, int ncam, const uint8_t* const* rgb, int w, int h, int stride, int mem, int dw, int dh)
+{
+    UVO_TRY(wait_for_producer(c, L, mem));
+    const uvo_status st = frames_queue(c, L, ncam, rgb, w, h, stride, mem, dw, dh);
+    if (st != UVO_OK && L != c) c->err = L->err;
+    return st;
+}
+
+extern "C" uvo_status uvo_stereo_submit_frames(uvo_ctx* c, const uint8_t* left_rgb, const uint8_t* right_rgb, int w, int h, int stride, int mem)
+try {
+    if (!c) return UVO_INVALID_ARG;
+    if (!left_rgb || !right_rgb) return fail(c, UVO_INVALID_ARG, "uvo_stereo_submit_frames: NULL frame pointer");
+    // uvo_stereo_submit's own refusals, before anything is queued on a lane
+    if (!c->rig_set) return fail(c, UVO_INVALID_ARG, "uvo_stereo_set_rig has not been called");
+    UVO_TRY(need_loop_table(c));
+    if (c->n_pending >= (int)c->lanes.size()) return fail(c, UVO_INVALID_ARG, "uvo_stereo_submit_frames: the pipeline is full; collect a pair first (uvo_stereo_set_depth)");
+    if (c->timing && c->n_pending > 0) return fail(c, UVO_INVALID_ARG, "timing mode measures one pair at a time: collect before submitting");
+    (void)hipSetDevice(c->device);
+    int dw = 0, dh = 0;
+    UVO_TRY(frames_plan(c, 2, w, h, stride, mem, &dw, &dh));
+    uvo_ctx* L = c->vo_initialized ? static_cast<uvo_ctx*>(c->lanes[c->next_lane]) : c;
+    const uint8_t* rgb[2] = { left_rgb, right_rgb };
+    UVO_TRY(frames_to_lane(c, L, 2, rgb, w, h, stride, mem, dw, dh));
+    FramesEntryScope alone(c);
+    return uvo_stereo_submit(c, L->d_img[0], L->d_img[1], dw, dh, dw, UVO_MEM_DEVICE);
+} UVO_ABI_CATCH(c)
+
+extern "C" uvo_status uvo_stereo_step_frames(uvo_ctx* c, const uint8_t* left_rgb, const uint8_t* right_rgb, int w, int h, int stride, int mem,
+                                             double dt, uvo_stereo_result* out)
+try {
+    if (!c) return UVO_INVALID_ARG;
+    if (!out) return fail(c, UVO_INVALID_ARG, "uvo_stereo_step_frames: NULL result pointer");
+    if (c->n_pending != 0) return fail(c, UVO_INVALID_ARG, "uvo_stereo_step_frames: pairs submitted with uvo_stereo_submit are still in flight");
+    c->in_sync_step = true;
+    const uvo_status st = uvo_stereo_submit_frames(c, left_rgb, right_rgb, w, h, stride, mem);
+    c->in_sync_step = false;
+    UVO_TRY(st);
+    return uvo_stereo_collect(c, dt, out);
+} UVO_ABI_CATCH(c)
+
+extern "C" uvo_status uvo_mono_step_frames(uvo_ctx* c, const uint8_t* rgb, int w, int h, int stride, int mem, double range, double dt, uvo_mono_result* out)
+try {
+    if (!c) return UVO_INVALID_ARG;
+    if (!rgb || !out) return fail(c, UVO_INVALID_ARG, "uvo_mono_step_frames: NULL frame / result pointer");
+    if (!c->mono_cam_set) return fail(c, UVO_INVALID_ARG, "uvo_mono_set_camera has not been called");
+    if (c->mono_pipelined) return fail(c, UVO_INVALID_ARG, "uvo_mono_step after uvo_mono_submit: call uvo_mono_reset first (the previous frame is held by the pipeline)");
+    UVO_TRY(need_loop_table(c));
+    (void)hipSetDevice(c->device);
+    int dw = 0, dh = 0;
+    UVO_TRY(frames_plan(c, 1, w, h, stride, mem, &dw, &dh));
+    UVO_TRY(frames_to_lane(c, c, 1, &rgb, w, h, stride, mem, dw, dh));
+    FramesEntryScope alone(c);
+    return uvo_mono_step(c, c->d_img[0], dw, dh, dw, UVO_MEM_DEVICE, range, dt, out);
+} UVO_ABI_CATCH(c)
+
+extern "C" uvo_status uvo_mono_submit_frames(uvo_ctx* c, const uint8_t* rgb, int w, int h, int stride, int mem, double range)
+try {
+    if (!c) return UVO_INVALID_ARG;
+    if (!rgb) return fail(c, UVO_INVALID_ARG, "uvo_mono_submit_frames: NULL frame pointer");
+    if (!c->mono_cam_set) return fail(c, UVO_INVALID_ARG, "uvo_mono_set_camera has not been called");
+    const int depth = (int)c->lanes.size();
+    if (depth < 2) return fail(c, UVO_INVALID_ARG, "uvo_mono_submit needs at least two lanes (uvo_stereo_set_depth): a frame is matched against the previous lane's buffers");
+    UVO_TRY(need_loop_table(c));
+    if (c->n_pending >= depth) return fail(c, UVO_INVALID_ARG, "uvo_mono_submit_frames: the pipeline is full; collect a frame first (uvo_stereo_set_depth)");
+    (void)hipSetDevice(c->device);
+    int dw = 0, dh = 0;
+    UVO_TRY(frames_plan(c, 1, w, h, stride, mem, &dw, &dh));
+    uvo_ctx* L = c->mono_initialized ? static_cast<uvo_ctx*>(c->lanes[c->next_lane]) : c;
+    UVO_TRY(frames_to_lane(c, L, 1, &rgb, w, h, stride, mem, dw, dh));
+    FramesEntryScope alone(c);
+    return uvo_mono_submit(c, L->d_img[0], dw, dh, dw, UVO_MEM_DEVICE, range);
+} UVO_ABI_CATCH(c)
 
 // ------------------------------------------------------------------------------------------ pipeline trace
 // The UVO_TRACE machinery through the ABI: device timestamps (hipEvents on the lane's streams) and host timestamps (steady clock) of

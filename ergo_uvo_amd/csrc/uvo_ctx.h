@@ -246,6 +246,7 @@ struct Ctx {
     // ---- mono stage (mono.hip) ----
     void* mono_ws = nullptr;                     // MonoWs*, allocated on first use
     void* pre_ws = nullptr;                      // PreWs* (get_image), allocated on first use
+    void* frames_ws = nullptr;                   // FramesWs* (the *_frames loop entries): the lane's get_image buffers; master: the cameras and their maps
     void* codec_ws = nullptr;                    // CodecWs* (uvo_decode_image), allocated on first use
     void* orb_ws = nullptr;                      // OrbWs* (uvo_orb_detect): parameters, sampling table, buffers of the last image size
     void* akaze_ws = nullptr;                    // AkazeWs* (uvo_akaze_detect), allocated on first use per image size
@@ -378,6 +379,11 @@ int ransac_update_num_iters(double p, double ep, int modelPoints, int maxIters);
 void pre_ws_free(Ctx* c);
 uvo_status pre_get_image(Ctx* c, const uint8_t* rgb, int w, int h, int stride, int mem, const double* K, const double* dist4, const double* newK,
                          int desired_width, int clahe_on, int clip_limit, const uint8_t** d_out, int* out_w, int* out_h);
+// camera frames into the loops' lanes (preproc.hip, "camera frames"): the master keeps the cameras, every lane its buffers
+void frames_ws_free(Ctx* c);
+uvo_status frames_set_camera(Ctx* m, int cam, const double* K, const double* dist4, const double* newK, int desired_width, int clahe, int clip_limit);
+uvo_status frames_plan(Ctx* m, int ncam, int w, int h, int stride, int mem, int* out_w, int* out_h);
+uvo_status frames_queue(Ctx* m, Ctx* L, int ncam, const uint8_t* const* rgb, int w, int h, int stride, int mem, int dw, int dh);
 // codec.hip
 void codec_ws_free(Ctx* c);
 uvo_status codec_decode(Ctx* c, const uint8_t* data, size_t n, int bayer, const uint8_t** d_out, int* w, int* h, int* channels);

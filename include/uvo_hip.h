@@ -328,6 +328,32 @@ uvo_status uvo_get_image(uvo_ctx* c, const uint8_t* rgb, int w, int h, int strid
                          const double* newK, int desired_width, int clahe, int clip_limit, uint8_t* out, int out_mem,
                          int* out_w, int* out_h);
 
+/* ---- camera frames into the loops: get_image in front of detect_features as the reference's nodes run it (visual_odometry.h:235/260
+ * mono, 482-483/542-543 stereo), inside the loop entry.  uvo_ctx_set_camera keeps get_image's arguments for camera `cam` (0 = left or
+ * mono, 1 = right) in the context; the *_frames calls take h x w x 3 interleaved u8 frames, `stride` bytes per row, host or device per
+ * `mem`, exactly as uvo_get_image does, and are otherwise uvo_stereo_step / uvo_stereo_submit / uvo_mono_step / uvo_mono_submit: same
+ * results, same collects, same lifetime rule (frames stay valid and unmodified until the matching collect), and they may be mixed
+ * with grey entries in one sequence.  The images the detector sees are byte-identical to uvo_get_image's for the same arguments.  The
+ * preprocessing of an entry is queued on its pipeline lane's stream in front of detection (at most four launches for both cameras,
+ * no host sync, no copy); init entries run on lane 0, synchronously.  The undistortion maps are kept per camera and built once per
+ * (camera, output size): a frame size or camera change while entries are in flight is refused (collect first), and so is a call
+ * that makes the lanes' workspaces grow then (the first host-memory frames after device-memory ones, a larger stride).  Refused with
+ * UVO_INVALID_ARG and a message: a camera that is not set (camera 1 is needed by the stereo calls only), get_image's geometry
+ * refusals, an output larger than the context's max_w / max_h, NULL pointers.  A frames pair never joins a two-pair launch set.
+ * uvo_stereo_get("img_left" / "img_right") and uvo_mono_get("img") return the detector's image of the last collected entry
+ * (out_w * out_h bytes; nothing when the entry's grey images were read in place from the caller's device memory).  As for every
+ * intermediate, the image is the lane's until the lane is submitted to again; init entries all run on lane 0, so when several of
+ * them are submitted before the first is collected these keys hold the image of the last one SUBMITTED.
+ * The preprocessing launches are queued in front of the loop call: they belong to no stage of uvo_timing_get and lie before the
+ * first timestamp of uvo_trace_read's stage A. */
+uvo_status uvo_ctx_set_camera(uvo_ctx* c, int cam, const double* K, const double* dist4, const double* newK,
+                              int desired_width, int clahe, int clip_limit);
+uvo_status uvo_stereo_step_frames(uvo_ctx* c, const uint8_t* left_rgb, const uint8_t* right_rgb, int w, int h, int stride, int mem,
+                                  double dt, uvo_stereo_result* out);
+uvo_status uvo_stereo_submit_frames(uvo_ctx* c, const uint8_t* left_rgb, const uint8_t* right_rgb, int w, int h, int stride, int mem);
+uvo_status uvo_mono_step_frames(uvo_ctx* c, const uint8_t* rgb, int w, int h, int stride, int mem, double range, double dt, uvo_mono_result* out);
+uvo_status uvo_mono_submit_frames(uvo_ctx* c, const uint8_t* rgb, int w, int h, int stride, int mem, double range);
+
 /* ---- compressed-image ingest: from_ros_to_cv_image (math_utility.h -> uvo_libraries/src/math_utility.cpp:154-173) =
  * cv_bridge::toCvCopy(sensor_msgs/CompressedImage) -> cv::imdecode, then cv::cvtColor(COLOR_BayerBGGR2BGR) when the message's
  * `format` contains "bayer".  data: the message payload, recognised by its signature as cv::imdecode does:
