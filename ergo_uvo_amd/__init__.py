@@ -653,6 +653,18 @@ class Context:
                                                      int(max_iters), _p(E), _p(mask), C.byref(ok)))
         return bool(ok.value), E, mask[:n].copy()
 
+    def five_point_models(self, q1, q2, subsets):
+        """Test hook (uvo_five_point_models): the five-point hypothesis kernel on normalised points q1, q2 (n x 2 float64) and index
+        subsets (nsub x 5).  Returns a list of nsub arrays, each (nmodels, 3, 3)."""
+        q1, q2, sub = _np(q1, np.float64), _np(q2, np.float64), _np(subsets, np.int32)
+        if q1.shape != q2.shape or q1.ndim != 2 or q1.shape[1] != 2 or sub.ndim != 2 or sub.shape[1] != 5:
+            raise ValueError("five_point_models: q1, q2 n x 2 and subsets nsub x 5")
+        models = np.full((len(sub), 10, 9), np.nan); nm = np.zeros(len(sub), np.int32)
+        self._check(self._lib.uvo_five_point_models(self._h, _p(q1), _p(q2), len(q1), _p(sub), len(sub), _p(models), _p(nm)))
+        if nm.min() < 0 or nm.max() > 10:           # the counts come back as the kernel wrote them; only ten models per subset have room
+            raise RuntimeError(f"five_point_models: the kernel counted {int(nm.min())}..{int(nm.max())} models for a subset, outside 0..10")
+        return [models[i, :nm[i]].reshape(-1, 3, 3).copy() for i in range(len(sub))]
+
     def recoverPose(self, E, pts1, pts2, K, mask):
         E, p1, p2, K = _np(E, np.float64), _np(pts1, np.float32), _np(pts2, np.float32), _np(K, np.float64)
         m = _np(mask, np.uint8).copy(); R = np.empty((3, 3)); t = np.empty(3); good = C.c_int(0)

@@ -1798,6 +1798,15 @@ try {
     (void)hipSetDevice(c->device);
     return mono_find_essential(c, p1, p2, n, K, method, prob, threshold, max_iters, E, mask, ok);
 } UVO_ABI_CATCH(c)
+// test hook: k_fivepoint_hyp on the caller's normalised points and subsets
+extern "C" uvo_status uvo_five_point_models(uvo_ctx* c, const double* q1, const double* q2, int n, const int* subsets, int nsub, double* models, int* nmodels)
+try {
+    if (!c || !q1 || !q2 || !subsets || !models || !nmodels || n < 1 || nsub < 1) return UVO_INVALID_ARG;
+    for (int i = 0; i < 5 * nsub; i++) if (subsets[i] < 0 || subsets[i] >= n) return fail(c, UVO_INVALID_ARG, "uvo_five_point_models: a subset index is outside the points");
+    (void)hipSetDevice(c->device);
+    UVO_TRY(need_idle(c, "uvo_five_point_models"));
+    return mono_five_point_models(c, q1, q2, n, subsets, nsub, models, nmodels);
+} UVO_ABI_CATCH(c)
 extern "C" uvo_status uvo_recover_pose(uvo_ctx* c, const double* E, const uvo_point2f* p1, const uvo_point2f* p2, int n, const double* K,
                                        double* R, double* t, uint8_t* mask, int* good)
 try {

@@ -726,6 +726,7 @@ struct MonoWs {                       // device workspace of the mono stage, own
     Pinned<int> h_prep;                            // k_mono_prep: [0] use_essential of select_estimation_method, [1] M it saw
     Pinned<int> h_pick;                            // k_mono_pick: best, good[4], n_in, valid inliers; k_mono_scale: G, n_front
     Pinned<double> h_zs;                           // z of the points convert_3Dpoints_camera keeps (cap)
+    int lds = 0;                                   // LDS bytes a workgroup may hold, once LMedS beyond 8192 points has asked (lmeds_capacity)
 };
 
 void mono_ws_free(Ctx* c);
@@ -769,6 +770,29 @@ void mono_ws_free(Ctx* c)
 }
 
 static int next_pow2(int n) { int p = 1; while (p < n) p <<= 1; return p; }
+
+// LMedS scoring (k_e_score / k_h_score in median mode) sorts next_pow2(n) float errors in dynamic LDS, beside the kernel's one static
+// word.  Up to n = 8192 that is 32 KiB, which every launch is given unasked, and nothing is done here.  Beyond it the device says how
+// much LDS a workgroup may hold (gfx950: all 160 KiB of a CU, which serves n <= 32768) and, once per context, both score kernels'
+// dynamic-LDS ceiling is raised to that figure -- the same value whichever context or thread sets it, so no call can lower it under
+// another's launch.  A larger n is refused here, before anything is launched (the launch would only fail with the runtime's bare error).
+static uvo_status lmeds_capacity(Ctx* c, MonoWs* w, int n)
+{
+    const size_t need = sizeof(float) * (size_t)next_pow2(n) + 16;      // + the static word, rounded up
+    if (need <= 32 * 1024 + 16) return UVO_OK;
+    if (!w->lds) {
+        int lds = 0;
+        if (hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, c->device) != hipSuccess || lds < 64 * 1024) lds = 64 * 1024;
+        UVO_HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_e_score), hipFuncAttributeMaxDynamicSharedMemorySize, lds - 16));
+        UVO_HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_h_score), hipFuncAttributeMaxDynamicSharedMemorySize, lds - 16));
+        w->lds = lds;
+    }
+    if (need <= (size_t)w->lds) return UVO_OK;
+    int most = 1; while (sizeof(float) * (size_t)(most * 2) + 16 <= (size_t)w->lds) most *= 2;
+    c->err = "LMedS: point count " + std::to_string(n) + " exceeds " + std::to_string(most) + ", the most errors one workgroup can sort in its " +
+             std::to_string(w->lds) + " bytes of LDS";
+    return UVO_CAPACITY;
+}
 
 // HomographyEstimatorCallback::checkSubset (host, on the sampled points)
 static bool have_collinear_points(const float* m, int count)
@@ -891,6 +915,7 @@ uvo_status mono_find_essential(Ctx* c, const uvo_point2f* p1, const uvo_point2f*
     else if (lmeds) { niters = ransac_update_num_iters(prob, 0.45, modelPoints, maxIters); niters = niters > 3 ? niters : 3; }
     else niters = maxIters > 1 ? maxIters : 1;
     if (niters > kMaxHyp) { c->err = "max_iters exceeds the compiled hypothesis capacity (2048)"; return UVO_CAPACITY; }
+    if (lmeds && n != modelPoints) UVO_TRY(lmeds_capacity(c, w, n));
     bool failed_first = false;
     int nsub;
     if (n == modelPoints) { for (int i = 0; i < 5; i++) w->h_subsets[i] = i; nsub = 1; }
@@ -964,6 +989,29 @@ uvo_status mono_find_essential(Ctx* c, const uvo_point2f* p1, const uvo_point2f*
     memcpy(mask, w->h_mask.data(), (size_t)n); memcpy(E, w->h_models.data(), sizeof(double) * 9);
     if (lmeds) { int good = 0; for (int i = 0; i < n; i++) good += mask[i]; *ok = good >= modelPoints; }
     else *ok = 1;
+    return UVO_OK;
+}
+
+// test hook (uvo_five_point_models): the hypothesis kernel alone, on normalised points and subsets of the caller's, launched as above
+uvo_status mono_five_point_models(Ctx* c, const double* q1, const double* q2, int n, const int* subsets, int nsub, double* models, int* nmodels)
+{
+    if (n > c->cap) { c->err = "point count exceeds the context's max_kpts"; return UVO_CAPACITY; }
+    if (nsub > kMaxHyp) { c->err = "subset count exceeds the compiled hypothesis capacity (2048)"; return UVO_CAPACITY; }
+    MonoWs* w = mono_ws(c);
+    if (!w) { c->err = "mono workspace allocation failed"; return UVO_HIP_ERROR; }
+    hipStream_t st = c->stream;
+    memcpy(w->h_q1.data(), q1, sizeof(double) * 2 * n); memcpy(w->h_q2.data(), q2, sizeof(double) * 2 * n);
+    memcpy(w->h_subsets.data(), subsets, sizeof(int) * 5 * nsub);
+    UVO_HIP_TRY(c, hipMemcpyAsync(w->q1, w->h_q1.data(), sizeof(double) * 2 * n, hipMemcpyHostToDevice, st));
+    UVO_HIP_TRY(c, hipMemcpyAsync(w->q2, w->h_q2.data(), sizeof(double) * 2 * n, hipMemcpyHostToDevice, st));
+    UVO_HIP_TRY(c, hipMemcpyAsync(w->subsets, w->h_subsets.data(), sizeof(int) * 5 * nsub, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_fivepoint_hyp, dim3((nsub + kFpPerWg - 1) / kFpPerWg), dim3(64), 0, st, w->q1, w->q2, w->subsets, nsub, w->models, w->nmodels);
+    UVO_HIP_TRY(c, hipGetLastError());
+    UVO_HIP_TRY(c, hipMemcpyAsync(w->h_nmodels.data(), w->nmodels, sizeof(int) * nsub, hipMemcpyDeviceToHost, st));
+    UVO_HIP_TRY(c, hipMemcpyAsync(w->h_models.data(), w->models, sizeof(double) * 90 * nsub, hipMemcpyDeviceToHost, st));
+    UVO_HIP_TRY(c, host_sync(c, st));
+    memcpy(nmodels, w->h_nmodels.data(), sizeof(int) * nsub);
+    for (int i = 0; i < nsub; i++) memcpy(models + (size_t)90 * i, w->h_models.data() + (size_t)90 * i, sizeof(double) * 9 * (nmodels[i] > 0 ? (nmodels[i] < 10 ? nmodels[i] : 10) : 0));
     return UVO_OK;
 }
 
@@ -1199,6 +1247,7 @@ uvo_status mono_find_homography(Ctx* c, const uvo_point2f* p1, const uvo_point2f
         if (lmeds) { niters = ransac_update_num_iters(confidence, 0.45, modelPoints, maxIters); niters = niters > 3 ? niters : 3; }
         else niters = maxIters > 1 ? maxIters : 1;
         if (niters > kMaxHyp) { c->err = "max_iters exceeds the compiled hypothesis capacity (2048)"; return UVO_CAPACITY; }
+        if (lmeds) UVO_TRY(lmeds_capacity(c, w, n));
         bool failed_first = false;
         int nsub = make_subsets(w->h_subsets.data(), niters, modelPoints, n, lmeds ? 1000 : 10000, src.data(), dst.data(), &failed_first);
         if (nsub > 0) {
@@ -1593,6 +1642,7 @@ uvo_status mono_essential_resident(Ctx* c, int n, const double* K, int method, d
     else if (lmeds) { niters = ransac_update_num_iters(prob, 0.45, modelPoints, maxIters); niters = niters > 3 ? niters : 3; }
     else niters = maxIters > 1 ? maxIters : 1;
     if (niters > kMaxHyp) { c->err = "max_iters exceeds the compiled hypothesis capacity (2048)"; return UVO_CAPACITY; }
+    if (lmeds && n != modelPoints) UVO_TRY(lmeds_capacity(c, w, n));
     bool failed_first = false;
     int nsub;
     if (n == modelPoints) { for (int i = 0; i < 5; i++) w->h_subsets[i] = i; nsub = 1; }

@@ -275,6 +275,10 @@ int        uvo_stereo_get(uvo_ctx* c, const char* what, void* out, int cap_bytes
 /* cv::findEssentialMat(p1, p2, K, method, prob, threshold, maxIters, mask)  (VO_utility.cpp:147); *ok = 0: OpenCV's empty E */
 uvo_status uvo_find_essential_mat(uvo_ctx* c, const uvo_point2f* p1, const uvo_point2f* p2, int n, const double* K, int method,
                                   double prob, double threshold, int max_iters, double* E, uint8_t* mask, int* ok);
+/* test hook: the five-point hypothesis kernel on its own, launched as uvo_find_essential_mat launches it.  q1, q2: n x 2 f64 NORMALISED
+ * points (host), subsets: nsub x 5 indices into them (any indices in [0, n), repeats included), nsub <= 2048 (the compiled hypothesis
+ * capacity, UVO_CAPACITY beyond).  models: nsub x 10 x 9 f64, nmodels: nsub (host); only the first nmodels[i] models of row i are written. */
+uvo_status uvo_five_point_models(uvo_ctx* c, const double* q1, const double* q2, int n, const int* subsets, int nsub, double* models, int* nmodels);
 /* cv::recoverPose(E, p1, p2, K, R, t, mask), distance threshold 50 (VO_utility.cpp:149); mask is in/out */
 uvo_status uvo_recover_pose(uvo_ctx* c, const double* E, const uvo_point2f* p1, const uvo_point2f* p2, int n, const double* K,
                             double* R, double* t, uint8_t* mask, int* good);
