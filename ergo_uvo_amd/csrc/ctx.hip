@@ -494,6 +494,32 @@ try {
     c->producer_stream = static_cast<hipStream_t>(hip_stream); c->has_producer = enabled != 0;
     return UVO_OK;
 } UVO_ABI_CATCH(c)
+// device memory of the context's GPU for callers built without the HIP headers (the C++ layer over this ABI is plain C++)
+extern "C" uvo_status uvo_device_alloc(uvo_ctx* c, size_t bytes, void** out)
+try {
+    if (!c) return UVO_INVALID_ARG;
+    if (!out || bytes == 0) { c->err = "uvo_device_alloc: NULL result pointer or zero bytes"; return UVO_INVALID_ARG; }
+    *out = nullptr;
+    (void)hipSetDevice(c->device);
+    UVO_HIP_TRY(c, hipMalloc(out, bytes));
+    return UVO_OK;
+} UVO_ABI_CATCH(c)
+extern "C" uvo_status uvo_device_free(uvo_ctx* c, void* ptr)
+try {
+    if (!c) return UVO_INVALID_ARG;
+    if (!ptr) return UVO_OK;
+    (void)hipSetDevice(c->device);
+    UVO_HIP_TRY(c, hipFree(ptr));
+    return UVO_OK;
+} UVO_ABI_CATCH(c)
+extern "C" uvo_status uvo_device_download(uvo_ctx* c, void* host_dst, const void* device_src, size_t bytes)
+try {
+    if (!c) return UVO_INVALID_ARG;
+    if (!host_dst || !device_src) { c->err = "uvo_device_download: NULL pointer"; return UVO_INVALID_ARG; }
+    (void)hipSetDevice(c->device);
+    if (bytes) UVO_HIP_TRY(c, hipMemcpy(host_dst, device_src, bytes, hipMemcpyDeviceToHost));
+    return UVO_OK;
+} UVO_ABI_CATCH(c)
 extern "C" const char* uvo_ctx_warning(const uvo_ctx* c) { return c ? c->warning.c_str() : ""; }
 extern "C" int uvo_ctx_pending(const uvo_ctx* c) { return c ? c->n_pending : 0; }
 extern "C" const char* uvo_ctx_host_policy(uvo_ctx* c)

@@ -15,6 +15,8 @@
 //   publications    /estimated_linear_vel_{stereo,mono}_UVO (geometry_msgs/Vector3Stamped), /validity_{stereo,mono}_UVO
 //                   (std_msgs/Bool), queue 10                                             (visual_odometry.h:763-764, 781-782)
 //   loop            ros::Rate(NODE_FREQ): spinOnce, sleep, one loop body                  (visual_odometry.h:249-251, 528-530)
+// One parameter of this adapter's own: the private `~execution`, "operators" (default: the loop body operator by operator, as the
+// reference runs it) or "fused" (the same iteration as one call of the library's camera-frames loop entry; visual_odometry_hip.h).
 // Image decoding stays where the reference has it (cv_bridge::toCvCopy + COLOR_BayerBGGR2BGR for bayer formats,
 // uvo_libraries/src/math_utility.cpp:154-173) when OpenCV is present; without it the library's own decoder is used
 // (uvo_hip::decode_compressed_image, include/uvo_libraries_hip/image_codec.h).
@@ -49,6 +51,7 @@ class visual_odometry_node
         ros::NodeHandle node_obj;
         std::string CAMERA_NAME;
         std::unique_ptr<uvo_hip::visual_odometry_core> core;          // the two loops and what they keep between iterations
+        uvo_hip::Execution execution = uvo_hip::Execution::operators;  // ~execution
         ros::Publisher pub_estimated_linear_vel, pub_validity;
 
         // the parameter server's subtree -> ParamTree (same conversions afterwards as with the YAML loader)
@@ -90,11 +93,30 @@ class visual_odometry_node
 #endif
         }
 
+        // the library's decoder with the image left in the GPU's memory, where the fused iteration reads it in place
+        static uvo_hip::DeviceImage from_ros_to_device_image(const sensor_msgs::CompressedImage::ConstPtr& msg)
+        { return uvo_hip::decode_compressed_image_device(msg->data.data(), msg->data.size(), msg->format); }
+        bool device_ingest() const
+        {
+#ifdef UVO_HAVE_OPENCV
+            return false;                                                                              // decoding stays with cv_bridge
+#else
+            return execution == uvo_hip::Execution::fused;
+#endif
+        }
+
         // the subscribers' callbacks (visual_odometry.h:67-78, 88-95): the newest message replaces an unprocessed one
-        void mono_imgs_callback(const sensor_msgs::CompressedImage::ConstPtr& msg) { core->mono_imgs_callback(from_ros_to_cv_image(msg), msg->header.stamp.toSec()); }
+        void mono_imgs_callback(const sensor_msgs::CompressedImage::ConstPtr& msg)
+        {
+            if (device_ingest()) core->mono_imgs_callback(from_ros_to_device_image(msg), msg->header.stamp.toSec());
+            else core->mono_imgs_callback(from_ros_to_cv_image(msg), msg->header.stamp.toSec());
+        }
         void range_callback(const sensor_msgs::Range::ConstPtr& msg) { core->range_callback(msg->range); }
         void stereo_imgs_callback(const sensor_msgs::CompressedImage::ConstPtr& left_image, const sensor_msgs::CompressedImage::ConstPtr& right_image)
-        { core->stereo_imgs_callback(from_ros_to_cv_image(left_image), from_ros_to_cv_image(right_image), left_image->header.stamp.toSec()); }
+        {
+            if (device_ingest()) core->stereo_imgs_callback(from_ros_to_device_image(left_image), from_ros_to_device_image(right_image), left_image->header.stamp.toSec());
+            else core->stereo_imgs_callback(from_ros_to_cv_image(left_image), from_ros_to_cv_image(right_image), left_image->header.stamp.toSec());
+        }
 
         void publish(const uvo_hip::Published& p)                                                      // visual_odometry.h:121-133, 142-160
         {
@@ -137,8 +159,15 @@ inline void visual_odometry_node::visual_odometry_workflow(std::string VO_NODE)
     uvo_hip::ParamTree tree;
     XmlRpc::XmlRpcValue root;
     if (node_obj.getParam("/", root)) copy_param("", root, tree);
+    std::string exec_name = "operators";
+    ros::param::get("~execution", exec_name);                                                          // private: <param name="execution" value="fused"/> inside the <node>
+    if (exec_name != "operators" && exec_name != "fused") {
+        ROS_ERROR(" ################ WRONG SELECTION OF ~execution - CHOOSE BETWEEN operators AND fused ################");
+        return;
+    }
+    execution = exec_name == "fused" ? uvo_hip::Execution::fused : uvo_hip::Execution::operators;
     // get_VO_parameters + get_{stereo,mono}_camera_parameters (visual_odometry.h:757, 776, 787) run in the core's constructor
-    core.reset(new uvo_hip::visual_odometry_core(VO_NODE, tree, CAMERA_NAME));
+    core.reset(new uvo_hip::visual_odometry_core(VO_NODE, tree, CAMERA_NAME, execution));
     ros::Rate loop_rate(NODE_FREQ);                                                                    // visual_odometry.h:759
 
     if (VO_NODE == "stereo") {

@@ -632,3 +632,72 @@ bool select_estimation_method(const vector<Point2f>& keypoints1_conv, const vect
     if (essential < 0) throw std::bad_alloc();            // the C entry reports what the reference's std::vector would have thrown
     return essential != 0;
 }
+
+// ================================================================================================================
+// The fused loops for the node class: the library's loop entries on the shared context, under the current parameter globals.
+namespace uvo_hip {
+
+DeviceImage::DeviceImage(int rows_, int cols_, int channels_) : rows(rows_), cols(cols_), channels(channels_)
+{
+    require(rows > 0 && cols > 0 && channels > 0, "DeviceImage: empty size");
+    uvo_ctx* c = ctx_now();
+    void* p = nullptr;
+    SHIM_TRY(uvo_device_alloc(c, bytes(), &p), "uvo_device_alloc");
+    // the block outlives any one context only when shutdown() / configure() came first: then it is left to the process's end
+    mem_ = std::shared_ptr<void>(p, [c](void* q) { std::lock_guard<std::mutex> lk(g.mu); if (g.ctx == c) (void)uvo_device_free(c, q); });
+}
+Mat DeviceImage::download() const
+{
+    require(!empty() && (channels == 1 || channels == 3 || channels == 4), "DeviceImage::download: empty image");
+    Mat m(rows, cols, channels == 4 ? CV_8UC4 : (channels == 3 ? CV_8UC3 : CV_8UC1));
+    SHIM_TRY(uvo_device_download(ctx_now(), m.ptr<uint8_t>(0), data(), bytes()), "uvo_device_download");
+    return m;
+}
+
+void loop_set_camera(int cam, const Mat& cameraMatrix, const Mat& distortionCoeff, const Mat& newCamMatrix)
+{
+    double K[9], newK[9], d4[4] = {0, 0, 0, 0};
+    doubles_of(cameraMatrix, 3, 3, K, "loop_set_camera: cameraMatrix must be 3x3 CV_64F");
+    doubles_of(newCamMatrix, 3, 3, newK, "loop_set_camera: newCamMatrix must be 3x3 CV_64F");
+    require(!distortionCoeff.empty() && distortionCoeff.type() == CV_64FC1 && distortionCoeff.rows * distortionCoeff.cols == 4,
+            "loop_set_camera: distortion must be (k1, k2, p1, p2) CV_64F");
+    for (int i = 0, k = 0; i < distortionCoeff.rows; i++) for (int j = 0; j < distortionCoeff.cols; j++) d4[k++] = distortionCoeff.at<double>(i, j);
+    SHIM_TRY(uvo_ctx_set_camera(ctx_now(), cam, K, d4, newK, DESIRED_WIDTH, CLAHE_CORRECTION ? 1 : 0, CLIP_LIMIT), "uvo_ctx_set_camera");
+}
+void loop_set_rig(const Mat& newK_left, const Mat& newK_right, const Mat& R_right, const Mat& t_right)
+{
+    double KL[9], KR[9], R[9], t[3];
+    doubles_of(newK_left, 3, 3, KL, "loop_set_rig: newK_left must be 3x3 CV_64F"); doubles_of(newK_right, 3, 3, KR, "loop_set_rig: newK_right must be 3x3 CV_64F");
+    doubles_of(R_right, 3, 3, R, "loop_set_rig: R_right must be 3x3 CV_64F"); doubles_of(t_right, 3, 1, t, "loop_set_rig: t_right must be 3x1 CV_64F");
+    SHIM_TRY(uvo_stereo_set_rig(ctx_now(), KL, KR, R, t), "uvo_stereo_set_rig");
+}
+void loop_set_mono_camera(const Mat& newCamMatrix)
+{
+    double K[9];
+    doubles_of(newCamMatrix, 3, 3, K, "loop_set_mono_camera: newCamMatrix must be 3x3 CV_64F");
+    SHIM_TRY(uvo_mono_set_camera(ctx_now(), K), "uvo_mono_set_camera");
+}
+void loop_set_detector()
+{
+    uvo_ctx* c = ctx_now();
+    if (FEATURE_DETECTOR == "ORB") orb_pattern_to(c);                         // the table first: the loop reads the context's
+    SHIM_TRY(uvo_ctx_set_loop_detector(c, FEATURE_DETECTOR.c_str()), "uvo_ctx_set_loop_detector");
+}
+void loop_set_depth(int depth) { SHIM_TRY(uvo_stereo_set_depth(ctx_now(), depth), "uvo_stereo_set_depth"); }
+void loop_reset(bool stereo) { if (stereo) SHIM_TRY(uvo_stereo_reset(ctx_now()), "uvo_stereo_reset"); else SHIM_TRY(uvo_mono_reset(ctx_now()), "uvo_mono_reset"); }
+int  loop_pending() { return uvo_ctx_pending(ctx_now()); }
+
+void stereo_step_frames(const unsigned char* left, const unsigned char* right, int w, int h, int stride, int mem, double dt, uvo_stereo_result& out)
+{ SHIM_TRY(uvo_stereo_step_frames(ctx_now(), left, right, w, h, stride, mem, dt, &out), "uvo_stereo_step_frames"); }
+void stereo_submit_frames(const unsigned char* left, const unsigned char* right, int w, int h, int stride, int mem)
+{ SHIM_TRY(uvo_stereo_submit_frames(ctx_now(), left, right, w, h, stride, mem), "uvo_stereo_submit_frames"); }
+void stereo_collect(double dt, uvo_stereo_result& out) { SHIM_TRY(uvo_stereo_collect(ctx_now(), dt, &out), "uvo_stereo_collect"); }
+void mono_step_frames(const unsigned char* img, int w, int h, int stride, int mem, double range, double dt, uvo_mono_result& out)
+{ SHIM_TRY(uvo_mono_step_frames(ctx_now(), img, w, h, stride, mem, range, dt, &out), "uvo_mono_step_frames"); }
+void mono_submit_frames(const unsigned char* img, int w, int h, int stride, int mem, double range)
+{ SHIM_TRY(uvo_mono_submit_frames(ctx_now(), img, w, h, stride, mem, range), "uvo_mono_submit_frames"); }
+void mono_collect(double dt, uvo_mono_result& out) { SHIM_TRY(uvo_mono_collect(ctx_now(), dt, &out), "uvo_mono_collect"); }
+int  stereo_get(const char* what, void* out, int cap_bytes) { return uvo_stereo_get(ctx_now(), what, out, cap_bytes); }
+int  mono_get(const char* what, void* out, int cap_bytes) { return uvo_mono_get(ctx_now(), what, out, cap_bytes); }
+
+}  // namespace uvo_hip

@@ -80,6 +80,14 @@ uvo_status  uvo_ctx_set_params(uvo_ctx* c, const uvo_params* p);
 /* The hipStream_t on which the caller produces its UVO_MEM_DEVICE inputs (NULL = the default stream): while `enabled`,
  * every image upload first waits for the work queued on that stream so far.  May be changed between any two calls. */
 uvo_status  uvo_ctx_set_producer_stream(uvo_ctx* c, void* hip_stream, int enabled);
+/* Device memory of the context's GPU for a caller that is built without the HIP headers: what hipMalloc / hipFree give, for buffers
+ * passed with UVO_MEM_DEVICE (uvo_decode_image's `out`, the frames entries' images).  hipFree waits for the device, so free nothing that
+ * an entry in flight still reads.  bytes == 0 or NULL out: UVO_INVALID_ARG; freeing NULL is UVO_OK. */
+uvo_status  uvo_device_alloc(uvo_ctx* c, size_t bytes, void** out);
+uvo_status  uvo_device_free(uvo_ctx* c, void* ptr);
+/* blocking copy of `bytes` bytes from such memory to the host (hipMemcpy: ordered after the work queued on the default stream only, so
+ * the data must be complete, as for any UVO_MEM_DEVICE input) */
+uvo_status  uvo_device_download(uvo_ctx* c, void* host_dst, const void* device_src, size_t bytes);
 /* Non-fatal advice about the process environment noticed at context creation ("" when there is none), e.g. a pipeline
  * deeper than two lanes with GPU_MAX_HW_QUEUES left at the ROCm default of 4 (lanes then share hardware queues). */
 const char* uvo_ctx_warning(const uvo_ctx* c);

@@ -15,6 +15,7 @@
 //   * the cv:: calls the stereo/mono loops make directly (triangulatePoints, solvePnPRansac, Rodrigues) have
 //     same-signature replacements in namespace uvo_hip.
 #pragma once
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -95,5 +96,46 @@ bool solvePnPRansac(const uvocv::Mat& objectPoints /* N x 3 CV_64F */, const std
                     uvocv::Mat& rvec, uvocv::Mat& tvec, bool useExtrinsicGuess, int iterationsCount, float reprojectionError,
                     double confidence, uvocv::Mat& inliers, int flags);
 void Rodrigues(const uvocv::Mat& src, uvocv::Mat& dst);
+
+// ---- the fused loops (uvo_stereo_step / uvo_mono_step and their camera-frames entries, include/uvo_hip.h) for the node class
+// (visual_odometry_hip.h, Execution::fused).  They run on the same shared context as the functions above, with the current value
+// of the parameter globals applied first, so a global changed between two iterations reaches the loop as it reaches the operators;
+// with frames in flight such a change is the library's error ("... cannot change while pairs are in flight").  Every refusal of
+// the library becomes an Error carrying its message.
+//
+// An image in the memory of the context's GPU: what decode_compressed_image_device (image_codec.h) returns and the frames entries
+// read in place.  Copies share the block; it is freed when the last copy goes (or left to the process's end when the context went
+// first).  rows x cols x channels interleaved bytes, tight pitch.
+class DeviceImage {
+public:
+    int rows = 0, cols = 0, channels = 0;
+    DeviceImage() = default;
+    DeviceImage(int rows_, int cols_, int channels_);
+    bool empty() const { return !mem_ || rows == 0 || cols == 0; }
+    unsigned char* data() const { return static_cast<unsigned char*>(mem_.get()); }
+    size_t bytes() const { return (size_t)rows * cols * channels; }
+    uvocv::Mat download() const;                 // a host copy (CV_8UC1 / CV_8UC3 / CV_8UC4)
+private:
+    std::shared_ptr<void> mem_;
+};
+
+void loop_set_camera(int cam, const uvocv::Mat& cameraMatrix, const uvocv::Mat& distortionCoeff, const uvocv::Mat& newCamMatrix);   // + DESIRED_WIDTH, CLAHE_CORRECTION, CLIP_LIMIT
+void loop_set_rig(const uvocv::Mat& newK_left, const uvocv::Mat& newK_right, const uvocv::Mat& R_right, const uvocv::Mat& t_right);
+void loop_set_mono_camera(const uvocv::Mat& newCamMatrix);
+void loop_set_detector();                        // FEATURE_DETECTOR; "ORB": the sampling table (set_orb_pattern / UVO_ORB_PATTERN_FILE) goes first
+void loop_set_depth(int depth);                  // uvo_stereo_set_depth
+void loop_reset(bool stereo);                    // uvo_stereo_reset / uvo_mono_reset: the shared context may have run a sequence for an earlier node
+int  loop_pending();                             // uvo_ctx_pending
+// frames: h x w x 3 interleaved bytes, `stride` bytes per row, mem = UVO_MEM_HOST or UVO_MEM_DEVICE; a submitted frame stays valid and
+// unmodified until its collect
+void stereo_step_frames(const unsigned char* left, const unsigned char* right, int w, int h, int stride, int mem, double dt, uvo_stereo_result& out);
+void stereo_submit_frames(const unsigned char* left, const unsigned char* right, int w, int h, int stride, int mem);
+void stereo_collect(double dt, uvo_stereo_result& out);
+void mono_step_frames(const unsigned char* img, int w, int h, int stride, int mem, double range, double dt, uvo_mono_result& out);
+void mono_submit_frames(const unsigned char* img, int w, int h, int stride, int mem, double range);
+void mono_collect(double dt, uvo_mono_result& out);
+// uvo_stereo_get / uvo_mono_get of the last collected entry: the element count, or -(count) when cap_bytes is too small
+int  stereo_get(const char* what, void* out, int cap_bytes);
+int  mono_get(const char* what, void* out, int cap_bytes);
 
 }  // namespace uvo_hip

@@ -7,9 +7,17 @@
 // (ergo_uvo_amd/ros/UVO_node_hip.cpp, compiled only where roscpp exists) wires the topics to these methods; the tests drive
 // it directly (tests/cpp/shim_vo_node.cpp) and compare every published sample with the CPU oracle's state machines.
 //
+// Execution::operators (the default) runs the loops operator by operator through host Mats, as the reference's node does.
+// Execution::fused runs the same iteration as ONE call of the library's camera-frames loop entry (uvo_stereo_step_frames /
+// uvo_mono_step_frames, include/uvo_hip.h): get_image, detection, matching and the pose stay on the device, and the node only maps the
+// entry's result onto what it publishes.  The reference's quirks (appended init matches, state carried with empty sets after a failed
+// gate, the last t_prevCam_currCam published again) live in that entry and are not repeated here.  For recorded sequences the fused
+// mode also has a pipelined form: spin_submit() / spin_collect() keep up to set_depth() frames in flight.
+//
 // Line references: VO = uvo/include/visual_odometry.h of the reference.
 #pragma once
 #include <cmath>
+#include <deque>
 #include <string>
 #include <vector>
 #include "uvo_libraries_hip/uvo_config.h"
@@ -24,10 +32,13 @@ struct Published {
     int    n_kps = 0, n_matches = 0, n_inliers = 0, n_good3d = 0;     // diagnostics (ROS_INFO lines of the reference)
 };
 
+enum class Execution { operators, fused };
+
 class visual_odometry_core {
 public:
     // VO_NODE: "mono" or "stereo" (rosparam /visual_odometry_node, NODE:23); CAMERA_NAME: rosparam /camera_name (VO:756)
-    visual_odometry_core(const std::string& VO_NODE, const ParamTree& params, const std::string& CAMERA_NAME) : mode_(VO_NODE)
+    visual_odometry_core(const std::string& VO_NODE, const ParamTree& params, const std::string& CAMERA_NAME, Execution exec = Execution::operators)
+        : mode_(VO_NODE), exec_(exec)
     {
         if (mode_ != "mono" && mode_ != "stereo") throw Error(UVO_INVALID_ARG, "WRONG SELECTION OF VISUAL ODOMETRY NODE - CHOOSE BETWEEN mono AND stereo");   // VO:789
         get_VO_parameters(params);                                                       // VO:757
@@ -37,19 +48,82 @@ public:
         rvec_ = uvocv::Mat::zeros(3, 1, uvocv::CV_64FC1); t_prevCam_currCam_ = uvocv::Mat::zeros(3, 1, uvocv::CV_64FC1);
     }
 
+    // frames submitted and not collected are collected (their results dropped) before the node's copies of their pixels go
+    ~visual_odometry_core() { Published p; while (!fifo_.empty()) { try { spin_collect(p); } catch (...) {} } }
+    visual_odometry_core(const visual_odometry_core&) = delete;
+    visual_odometry_core& operator=(const visual_odometry_core&) = delete;
+
     // ---- the subscribers' callbacks (queue size 1: the newest message replaces an unprocessed one) ----
-    void mono_imgs_callback(const uvocv::Mat& img, double stamp) { camera_img_ = img; stamp_ = stamp; first_img_ = true; new_img_available_ = true; }   // VO:67-73
+    void mono_imgs_callback(const uvocv::Mat& img, double stamp) { camera_img_ = img; dev_img_ = DeviceImage(); stamp_ = stamp; first_img_ = true; new_img_available_ = true; }   // VO:67-73
     void range_callback(double range) { range_ = range; }                                                                                               // VO:75-78
     void stereo_imgs_callback(const uvocv::Mat& left, const uvocv::Mat& right, double stamp)                                                            // VO:88-95
-    { camera_left_ = left; camera_right_ = right; stamp_ = stamp; first_img_ = true; new_img_available_ = true; }
+    { camera_left_ = left; camera_right_ = right; dev_left_ = dev_right_ = DeviceImage(); stamp_ = stamp; first_img_ = true; new_img_available_ = true; }
+    // The same callbacks for images that are already in the GPU's memory (decode_compressed_image_device, image_codec.h): the fused
+    // iterations read them in place; the operator loops take host Mats, so Execution::operators copies them down once, here.
+    void mono_imgs_callback(const DeviceImage& img, double stamp)
+    {
+        if (exec_ == Execution::operators) { mono_imgs_callback(img.download(), stamp); return; }
+        dev_img_ = img; camera_img_ = Mat(); stamp_ = stamp; first_img_ = true; new_img_available_ = true;
+    }
+    void stereo_imgs_callback(const DeviceImage& left, const DeviceImage& right, double stamp)
+    {
+        if (exec_ == Execution::operators) { stereo_imgs_callback(left.download(), right.download(), stamp); return; }
+        dev_left_ = left; dev_right_ = right; camera_left_ = Mat(); camera_right_ = Mat(); stamp_ = stamp; first_img_ = true; new_img_available_ = true;
+    }
 
     // ---- one iteration of the node's loop (after ros::spinOnce(); loop_rate.sleep()) ----
-    Published spin_once() { return mode_ == "stereo" ? stereo_iteration() : mono_iteration(); }
+    Published spin_once()
+    {
+        if (exec_ == Execution::fused) return fused_iteration();
+        return mode_ == "stereo" ? stereo_iteration() : mono_iteration();
+    }
     bool initialized() const { return vo_initialized_; }
+    Execution execution() const { return exec_; }
+
+    // ---- pipelined replay (Execution::fused only): for recorded sequences, where throughput counts and latency does not ----
+    // Up to `depth` frames in flight (1..16, default 2; uvo_stereo_set_depth: the stereo loop is fastest at 6).  Not with frames in flight.
+    void set_depth(int depth)
+    {
+        need_fused("set_depth");
+        if (depth < 1 || depth > 16) throw Error(UVO_INVALID_ARG, "set_depth: 1..16");
+        if (!fifo_.empty()) throw Error(UVO_INVALID_ARG, "set_depth: frames are in flight (spin_collect first)");
+        loop_set_depth(mode_ == "mono" && depth < 2 ? 2 : depth);        // a mono frame is matched against the previous lane's buffers: two lanes at least
+        depth_ = depth; depth_set_ = true;
+    }
+    // Takes the frame the callbacks last delivered and queues its iteration; false when there is none.  The node keeps the frame (a
+    // cv::Mat header on the caller's pixels: they must stay unmodified until the frame's spin_collect).
+    bool spin_submit()
+    {
+        need_fused("spin_submit");
+        if (!first_img_) return false;
+        fused_setup();
+        if (!new_img_available_) return false;
+        if ((int)fifo_.size() >= depth_) throw Error(UVO_INVALID_ARG, "spin_submit: the pipeline is full (spin_collect first, or set_depth)");
+        if (!depth_set_) set_depth(depth_);
+        fifo_.push_back(take_frame());
+        const Frame& f = fifo_.back();
+        try {
+            if (mode_ == "stereo") stereo_submit_frames(f.p[0], f.p[1], f.w, f.h, f.stride, f.mem);
+            else mono_submit_frames(f.p[0], f.w, f.h, f.stride, f.mem, (double)(float)f.range);
+        } catch (...) { fifo_.pop_back(); throw; }
+        new_img_available_ = false;
+        return true;
+    }
+    // The oldest frame in flight: what spin_once() publishes for it (results come in the order of submission); false when none is.
+    bool spin_collect(Published& out)
+    {
+        if (fifo_.empty()) return false;
+        const Frame f = fifo_.front();
+        fifo_.pop_front();                                               // the library dequeues the entry whether its collect succeeds or not
+        out = fused_collect(f);
+        return true;
+    }
+    int in_flight() const { return (int)fifo_.size(); }
 
 private:
     using Mat = uvocv::Mat;
     std::string mode_;
+    Execution exec_ = Execution::operators;
     bool first_img_ = false, new_img_available_ = false, vo_initialized_ = false, cameras_ready_ = false;
     double range_ = 1.0, stamp_ = 0, prev_time_ = 0;
     Mat camera_img_, camera_left_, camera_right_;
@@ -63,6 +137,17 @@ private:
     Mat rvec_, t_prevCam_currCam_;
     std::vector<uvocv::DMatch> results_match_prev_;
     std::vector<uvocv::KeyPoint> prevL_as_, prevR_as_; Mat prevL_desc_as_;
+
+    // fused execution: the frame as the loop entry takes it, and the frames in flight in the order of their submission
+    struct Frame {
+        Mat host[2]; DeviceImage dev[2];                                 // keep the pixels alive until the collect
+        const unsigned char* p[2] = {nullptr, nullptr};
+        int w = 0, h = 0, stride = 0, mem = UVO_MEM_HOST;
+        double stamp = 0, range = 0;
+    };
+    DeviceImage dev_img_, dev_left_, dev_right_;
+    std::deque<Frame> fifo_;
+    int depth_ = 2; bool depth_set_ = false;
 
     static Mat mat33(double a, double b, double c, double d, double e, double f, double g, double h, double i)
     { Mat m(3, 3, uvocv::CV_64FC1); const double v[9] = {a, b, c, d, e, f, g, h, i}; for (int k = 0; k < 9; k++) m.at<double>(k / 3, k % 3) = v[k]; return m; }
@@ -212,6 +297,124 @@ private:
         for (int i = 0; i < 3; i++) out.v[i] = t_prevCam_currCam_.at<double>(i, 0) / deltaT;             // stereo_output_computation (VO:148-159)
         out.published = true; out.valid = valid; out.stamp = curr_time;
         prevL_as_ = currL_as; prevR_as_ = currR_as; prevL_desc_as_ = currL_desc_as.clone(); prev_time_ = curr_time;     // VO:723-733
+        return out;
+    }
+
+    // ------------------------------------------------------------------ Execution::fused
+    void need_fused(const char* who) const
+    { if (exec_ != Execution::fused) throw Error(UVO_INVALID_ARG, std::string(who) + ": the node was built with Execution::operators (pass Execution::fused)"); }
+
+    // the frame the callbacks last delivered, as the camera-frames entries take it
+    Frame take_frame() const
+    {
+        Frame f;
+        const bool stereo = mode_ == "stereo";
+        const int ncam = stereo ? 2 : 1;
+        f.stamp = stamp_; f.range = range_;
+        if (!(stereo ? dev_left_ : dev_img_).empty()) {
+            f.dev[0] = stereo ? dev_left_ : dev_img_; if (stereo) f.dev[1] = dev_right_;
+            for (int i = 0; i < ncam; i++) {
+                if (f.dev[i].empty() || f.dev[i].channels != 3 || f.dev[i].cols != f.dev[0].cols || f.dev[i].rows != f.dev[0].rows)
+                    throw Error(UVO_INVALID_ARG, "fused iteration: 3-channel device images of one size expected");
+                f.p[i] = f.dev[i].data();
+            }
+            f.w = f.dev[0].cols; f.h = f.dev[0].rows; f.stride = f.w * 3; f.mem = UVO_MEM_DEVICE;
+            return f;
+        }
+        f.host[0] = stereo ? camera_left_ : camera_img_; if (stereo) f.host[1] = camera_right_;
+        auto pitch = [](const Mat& m) { return m.rows > 1 ? (int)(m.ptr<unsigned char>(1) - m.ptr<unsigned char>(0)) : m.cols * 3; };     // rows may be padded in a real cv::Mat
+        for (int i = 0; i < ncam; i++)
+            if (f.host[i].empty() || f.host[i].type() != uvocv::CV_8UC3 || f.host[i].cols != f.host[0].cols || f.host[i].rows != f.host[0].rows)
+                throw Error(UVO_INVALID_ARG, "fused iteration: CV_8UC3 images of one size expected");
+        if (stereo && pitch(f.host[0]) != pitch(f.host[1])) { f.host[0] = f.host[0].clone(); f.host[1] = f.host[1].clone(); }       // the entry takes one pitch for the pair: clone() packs the rows
+        for (int i = 0; i < ncam; i++) f.p[i] = f.host[i].ptr<unsigned char>(0);
+        f.w = f.host[0].cols; f.h = f.host[0].rows; f.stride = pitch(f.host[0]); f.mem = UVO_MEM_HOST;
+        return f;
+    }
+
+    // once, on the first image (VO:188-189, 221-225 mono; VO:426-463 stereo): the cameras, the rig, the detector and the PnP method
+    // (PNP_METHOD_FLAG reaches the context with the other parameter globals, in every shim call) go to the context
+    void fused_setup()
+    {
+        if (cameras_ready_) return;
+        const bool stereo = mode_ == "stereo";
+        const DeviceImage& d0 = stereo ? dev_left_ : dev_img_;
+        // resize_camera_matrix reads the size of the original image only
+        auto size_of = [](const Mat& m, const DeviceImage& d) { return d.empty() ? m : Mat(d.rows, d.cols, uvocv::CV_8UC1); };
+        if (stereo) {
+            K_left_ = mat33(fx_left, 0, ccx_left, 0, fy_left, ccy_left, 0, 0, 1); K_right_ = mat33(fx_right, 0, ccx_right, 0, fy_right, ccy_right, 0, 0, 1);
+            dist_left_ = row4(k1_left, k2_left, p1_left, p2_left); dist_right_ = row4(k1_right, k2_right, p1_right, p2_right);
+            resize_camera_matrix(size_of(camera_left_, d0), K_left_, dist_left_, newK_left_);
+            resize_camera_matrix(size_of(camera_right_, dev_right_), K_right_, dist_right_, newK_right_);
+            loop_set_camera(0, K_left_, dist_left_, newK_left_);
+            loop_set_camera(1, K_right_, dist_right_, newK_right_);
+            loop_set_rig(newK_left_, newK_right_, R_right, t_right);
+        } else {
+            distortion_ = row4(k1, k2, p1, p2);
+            camera_matrix_ = mat33(fx, 0, ccx, 0, fy, ccy, 0, 0, 1);
+            resize_camera_matrix(size_of(camera_img_, d0), camera_matrix_, distortion_, new_camera_matrix_);
+            loop_set_camera(0, camera_matrix_, distortion_, new_camera_matrix_);
+            loop_set_mono_camera(new_camera_matrix_);
+        }
+        loop_reset(stereo);                                              // the shared context may hold an earlier node's sequence
+        loop_set_detector();
+        cameras_ready_ = true;
+    }
+
+    Published fused_iteration()
+    {
+        Published out;
+        if (!first_img_) return out;                                     // VO:173-177 / VO:412-416
+        fused_setup();
+        if (!new_img_available_) return out;
+        if (!fifo_.empty()) throw Error(UVO_INVALID_ARG, "spin_once: frames submitted with spin_submit are in flight (spin_collect first)");
+        new_img_available_ = false;
+        const Frame f = take_frame();
+        const double dt = f.stamp - prev_time_;
+        prev_time_ = f.stamp;
+        if (mode_ == "stereo") {
+            uvo_stereo_result r;
+            stereo_step_frames(f.p[0], f.p[1], f.w, f.h, f.stride, f.mem, dt, r);
+            return published_of(r, f.stamp);
+        }
+        uvo_mono_result r;
+        mono_step_frames(f.p[0], f.w, f.h, f.stride, f.mem, (double)(float)f.range, dt, r);      // VO:366-368 (range narrows to float)
+        return published_of(r, f.stamp);
+    }
+    // the collect of the oldest submitted frame: deltaT is its stamp minus its predecessor's, as in the synchronous loop
+    Published fused_collect(const Frame& f)
+    {
+        const double dt = f.stamp - prev_time_;
+        prev_time_ = f.stamp;
+        if (mode_ == "stereo") { uvo_stereo_result r; stereo_collect(dt, r); return published_of(r, f.stamp); }
+        uvo_mono_result r; mono_collect(dt, r); return published_of(r, f.stamp);
+    }
+
+    // what stereo_iteration() reports, from the loop entry's result: nothing is published for a pair the init loop consumed (VO:474-520)
+    Published published_of(const uvo_stereo_result& r, double stamp)
+    {
+        Published out;
+        out.n_kps = r.n_left;
+        if (!r.initialized) {
+            vo_initialized_ = r.n_left >= MIN_NUM_FEATURES && r.n_right >= MIN_NUM_FEATURES && r.n_stereo_matches > MIN_NUM_FEATURES;
+            return out;
+        }
+        vo_initialized_ = true;
+        out.n_matches = r.n_tri_matches; out.n_good3d = r.n_good3d; out.n_inliers = r.n_inliers;
+        for (int i = 0; i < 3; i++) out.v[i] = r.velocity[i];
+        out.published = true; out.valid = r.valid != 0; out.stamp = stamp;
+        return out;
+    }
+    // what mono_iteration() reports: a frame skipped with `continue` (VO:276-307) or consumed by the init loop publishes nothing
+    Published published_of(const uvo_mono_result& r, double stamp)
+    {
+        Published out;
+        out.n_kps = r.n_kps; out.n_matches = r.n_matches; out.n_inliers = r.n_inliers; out.n_good3d = r.n_good3d;
+        vo_initialized_ = vo_initialized_ || r.initialized || r.n_kps >= MIN_NUM_FEATURES;
+        if (!r.published) return out;
+        use_essential = r.used_essential != 0;                           // the reference's global: written where the operator loop writes it (VO:310-317, VOU:160-163)
+        for (int i = 0; i < 3; i++) out.v[i] = r.velocity[i];
+        out.published = true; out.valid = r.valid != 0; out.stamp = stamp;
         return out;
     }
 };
