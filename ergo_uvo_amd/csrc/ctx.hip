@@ -11,7 +11,6 @@
 #include <float.h>
 #include <new>
 #include <algorithm>
-#include <atomic>
 namespace uvo { extern bool g_bdbg; extern std::atomic<double> g_bstat[16]; double now_us(); void operator+=(std::atomic<double>& a, double v); }
 
 using namespace uvo;
@@ -46,7 +45,6 @@ uvo_status abi_caught(uvo_ctx* c) noexcept
 // variable is read when the HIP runtime initialises, so it is set when this library is loaded -- before main() when the node
 // links it -- unless the process already chose a value.
 __attribute__((constructor)) static void uvo_default_hw_queues() { setenv("GPU_MAX_HW_QUEUES", "16", 0); }
-
 
 extern "C" void uvo_params_default_stereo(uvo_params* p)
 {   // uvo/config/stereo_VO_parameters.yaml:20-47 (keys absent from that file stay zero, as the globals do)
@@ -85,13 +83,13 @@ static void make_desc_weights(float* DW)
 
 static void lane_worker(uvo_ctx* L);
 __global__ void k_prime(int* sink, int n);
-static void run_stage_b(uvo_ctx* L, bool stage_a_ok);
 static uvo_status prime_lanes(uvo_ctx* c, int w, int h);
-extern "C" uvo_status uvo_mono_collect(uvo_ctx* c, double dt, uvo_mono_result* out);
+static uvo_status stereo_collect_body(uvo_ctx* c, double dt, uvo_stereo_result* out);
+static uvo_status mono_collect_body(uvo_ctx* c, double dt, uvo_mono_result* out);
 static void run_mono_stage_b(uvo_ctx* L, bool stage_a_ok);
 static void destroy_one(uvo_ctx* c);
+static void destroy_ctx(uvo_ctx* c);
 static uvo_status queue_stage_a(uvo_ctx* c, uvo_ctx* A, uvo_ctx* B);
-struct GatherPair;
 // the ring of timing events behind UVO_TRACE / uvo_trace_enable (a lane's, created once)
 static hipError_t trace_alloc(Ctx* c)
 {
@@ -384,7 +382,7 @@ try {
     if (getenv("UVO_BATCH")) (*out)->batch = atoi(getenv("UVO_BATCH")) == 2 ? 2 : 1;
     if (getenv("UVO_A_OVERLAP_MONO")) (*out)->a_overlap_mono = std::min(8, std::max(0, atoi(getenv("UVO_A_OVERLAP_MONO"))));
     st = set_depth(*out, 2);                      // two pairs in flight by default (uvo_stereo_set_depth changes it)
-    if (st != UVO_OK) { uvo_ctx_destroy(*out); *out = nullptr; }
+    if (st != UVO_OK) { uvo_ctx* made = *out; *out = nullptr; destroy_ctx(made); }
     return st;
 } UVO_ABI_CATCH(nullptr)
 
@@ -404,9 +402,9 @@ try {
     return set_depth(c, depth);
 } UVO_ABI_CATCH(c)
 
-extern "C" void uvo_ctx_destroy(uvo_ctx* c)
-try {
-    if (!c) return;
+// the caller's context with every further lane of it
+static void destroy_ctx(uvo_ctx* c)
+{
     if (uvo::g_bdbg && uvo::g_bstat[4].load() > 0) {
         const double n = uvo::g_bstat[4].load();
         fprintf(stderr, "[uvo] stage B over %.0f calls, host wall us per call: wait-for-A %.1f | hyp+score to sync %.1f | host scan + refit launch %.1f | refit to sync %.1f | semaphore wait %.1f\n",
@@ -420,7 +418,9 @@ try {
     for (size_t i = c->lanes.size(); i > 1; i--) destroy_one(static_cast<uvo_ctx*>(c->lanes[i - 1]));
     c->lanes.clear();
     destroy_one(c);
-} UVO_ABI_CATCH_VOID(c)
+}
+extern "C" void uvo_ctx_destroy(uvo_ctx* c)
+try { if (c) destroy_ctx(c); } UVO_ABI_CATCH_VOID(c)
 
 static void destroy_one(uvo_ctx* c)
 {
@@ -642,6 +642,33 @@ static uvo_status need_loop_table(uvo_ctx* c)
     return UVO_OK;
 }
 
+// Each loop step has a grey-image entry and a camera-frames entry (uvo_*_frames) over ONE body.  What differs between them is an argument of the call, never
+// context state: the pair joins no two-pair launch (the set's kernels run on the other lane's stream); the producer wait is queued already, before the preprocessing
+struct EntryOpts { bool alone = false, producer_waited = false; };
+static const EntryOpts kFramesEntry = { true, true };
+// ... and ONE list of refusals per step, tested by both entries before anything is queued on a lane; `who` is the entry the message names
+static uvo_status stereo_submit_refusal(uvo_ctx* c, const char* who)
+{
+    if (!c->rig_set) return fail(c, UVO_INVALID_ARG, "uvo_stereo_set_rig has not been called");
+    UVO_TRY(need_loop_table(c));
+    if (c->n_pending >= (int)c->lanes.size()) { c->err = std::string(who) + ": the pipeline is full; collect a pair first (uvo_stereo_set_depth)"; return UVO_INVALID_ARG; }
+    if (c->timing && c->n_pending > 0) return fail(c, UVO_INVALID_ARG, "timing mode measures one pair at a time: collect before submitting");
+    return UVO_OK;
+}
+static uvo_status mono_step_refusal(uvo_ctx* c)
+{
+    if (!c->mono_cam_set) return fail(c, UVO_INVALID_ARG, "uvo_mono_set_camera has not been called");
+    if (c->mono_pipelined) return fail(c, UVO_INVALID_ARG, "uvo_mono_step after uvo_mono_submit: call uvo_mono_reset first (the previous frame is held by the pipeline)");
+    return need_loop_table(c);
+}
+static uvo_status mono_submit_refusal(uvo_ctx* c, const char* who)
+{
+    if (!c->mono_cam_set) return fail(c, UVO_INVALID_ARG, "uvo_mono_set_camera has not been called");
+    if (c->lanes.size() < 2) return fail(c, UVO_INVALID_ARG, "uvo_mono_submit needs at least two lanes (uvo_stereo_set_depth): a frame is matched against the previous lane's buffers");
+    UVO_TRY(need_loop_table(c));
+    if (c->n_pending >= (int)c->lanes.size()) { c->err = std::string(who) + ": the pipeline is full; collect a frame first (uvo_stereo_set_depth)"; return UVO_INVALID_ARG; }
+    return UVO_OK;
+}
 static uvo_status set_loop_detector(uvo_ctx* c, int det)
 {
     if (c->n_pending != 0) return fail(c, UVO_INVALID_ARG, "the feature detector cannot change while pairs are in flight");
@@ -802,11 +829,12 @@ try {
 } UVO_ABI_CATCH(c)
 
 // ------------------------------------------------------------------------------------------ matching
-static uvo_status stage_desc(uvo_ctx* c, int slot, const float* d, int n, int mem, const float** out)
+// one side of a standalone matcher call where the kernels read it: in place (device memory), or in the context's staging buffer (cap x 512 bytes)
+static uvo_status stage_rows(uvo_ctx* c, int slot, const void* d, int n, size_t row_bytes, int mem, const void** out)
 {
     if (n > c->cap) return fail(c, UVO_CAPACITY, "descriptor count exceeds the context's max_kpts");
     if (mem == UVO_MEM_DEVICE) { *out = d; return UVO_OK; }
-    if (n) UVO_HIP_TRY(c, hipMemcpyAsync(c->d_tmp_desc[slot], d, sizeof(float) * c->desc_dim() * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    if (n) UVO_HIP_TRY(c, hipMemcpyAsync(c->d_tmp_desc[slot], d, row_bytes * (size_t)n, hipMemcpyHostToDevice, c->stream));
     *out = c->d_tmp_desc[slot];
     return UVO_OK;
 }
@@ -816,93 +844,97 @@ static uvo_status stage_desc(uvo_ctx* c, int slot, const float* d, int n, int me
 // (uvo_ctx_set_feature_detector): their callers hand over n x 64 buffers, and the width of the loops' detector is not theirs.
 namespace { struct DimScope { uvo_ctx* c; int prev; DimScope(uvo_ctx* c_, int d) : c(c_), prev(c_->match_dim) { if (!prev) c->match_dim = d; } ~DimScope() { c->match_dim = prev; } };
             int surf_dim(const uvo_ctx* c) { return c->p.SURF_EXTENDED ? 128 : 64; } }
-extern "C" uvo_status uvo_match_knn2(uvo_ctx* c, const float* d1, int n1, const float* d2, int n2, int mem, int* idx, float* dist)
-try {
-    if (!c || n1 < 0 || n2 < 0 || (n1 && !d1) || (n2 && !d2) || !idx || !dist) return UVO_INVALID_ARG;
-    DimScope surf_rows(c, surf_dim(c));
+
+// What the six standalone matcher entries share: the check of their two sets, and behind their own checks a prologue and one of two epilogues.
+static bool match_sets_ok(const uvo_ctx* c, const void* d1, int n1, const void* d2, int n2) { return c && n1 >= 0 && n2 >= 0 && (!n1 || d1) && (!n2 || d2); }
+// The prologue: lane 0 must be idle; an empty set is answered at once (*go stays false: "no neighbour" from the k-NN entries, which give
+// idx and dist, nothing appended by the ratio entries); else both sets are staged behind the producer and the 2-NN kernels queued, on
+// float rows of the open DimScope's width (bytes == 0: match_features' L2 arm) or binary rows of `bytes` bytes (VO_utility.cpp:520-524:
+// AKAZE / ORB, Hamming distance).  `who` is the entry that the messages name.
+static uvo_status match_prologue(uvo_ctx* c, const char* who, const void* d1, int n1, const void* d2, int n2, int bytes, int mem, int* idx, float* dist, bool* go)
+{
+    *go = false;
     (void)hipSetDevice(c->device);
-    UVO_TRY(need_idle(c, "uvo_match_knn2"));
-    if (n1 == 0) return UVO_OK;
-    if (n2 == 0) { for (int i = 0; i < 2 * n1; i++) { idx[i] = -1; dist[i] = FLT_MAX; } return UVO_OK; }
+    UVO_TRY(need_idle(c, who));
+    if (idx) {
+        if (n1 == 0) return UVO_OK;
+        if (n2 == 0) { for (int i = 0; i < 2 * n1; i++) { idx[i] = -1; dist[i] = FLT_MAX; } return UVO_OK; }
+    } else if (n1 == 0 || n2 == 0) return UVO_OK;          // knnMatch on an empty query/train set yields no matches
     UVO_TRY(wait_for_producer(c, c, mem));
-    const float *q, *t;
-    UVO_TRY(stage_desc(c, 0, d1, n1, mem, &q));
-    UVO_TRY(stage_desc(c, 1, d2, n2, mem, &t));
-    UVO_TRY(match_knn2(c, q, nullptr, n1, t, nullptr, n2));
+    const size_t row_bytes = bytes ? (size_t)bytes : sizeof(float) * c->desc_dim();
+    const void *q, *t;
+    UVO_TRY(stage_rows(c, 0, d1, n1, row_bytes, mem, &q));
+    UVO_TRY(stage_rows(c, 1, d2, n2, row_bytes, mem, &t));
+    UVO_TRY(bytes ? match_knn2_hamming(c, static_cast<const uint8_t*>(q), n1, static_cast<const uint8_t*>(t), n2, bytes)
+                  : match_knn2(c, static_cast<const float*>(q), nullptr, n1, static_cast<const float*>(t), nullptr, n2));
+    *go = true;
+    return UVO_OK;
+}
+// The k-NN entries: the prologue, then both neighbours of every query row
+static uvo_status match_knn_out(uvo_ctx* c, const char* who, const void* d1, int n1, const void* d2, int n2, int bytes, int mem, int* idx, float* dist)
+{
+    bool go = false;
+    UVO_TRY(match_prologue(c, who, d1, n1, d2, n2, bytes, mem, idx, dist, &go));
+    if (!go) return UVO_OK;
     UVO_HIP_TRY(c, hipMemcpyAsync(idx, c->d_knn_idx, sizeof(int) * 2 * n1, hipMemcpyDeviceToHost, c->stream));
     UVO_HIP_TRY(c, hipMemcpyAsync(dist, c->d_knn_dist, sizeof(float) * 2 * n1, hipMemcpyDeviceToHost, c->stream));
     UVO_HIP_TRY(c, hipStreamSynchronize(c->stream));
     return UVO_OK;
-} UVO_ABI_CATCH(c)
-
-extern "C" uvo_status uvo_match_knn2_ratio(uvo_ctx* c, const float* d1, int n1, const float* d2, int n2, int mem,
-                                           float ratio, uvo_dmatch* out, int cap, int* m)
-try {
-    if (!c || n1 < 0 || n2 < 0 || (n1 && !d1) || (n2 && !d2) || !out || !m || *m < 0) return UVO_INVALID_ARG;
-    DimScope surf_rows(c, surf_dim(c));
-    (void)hipSetDevice(c->device);
-    UVO_TRY(need_idle(c, "uvo_match_knn2_ratio"));
-    if (n1 == 0 || n2 == 0) return UVO_OK;          // knnMatch on an empty query/train set yields no matches
-    UVO_TRY(wait_for_producer(c, c, mem));
-    const float *q, *t;
-    UVO_TRY(stage_desc(c, 0, d1, n1, mem, &q));
-    UVO_TRY(stage_desc(c, 1, d2, n2, mem, &t));
-    UVO_TRY(match_knn2(c, q, nullptr, n1, t, nullptr, n2));
+}
+// The ratio entries: the prologue, Lowe's test, the surviving matches appended to the caller's
+static uvo_status match_ratio_out(uvo_ctx* c, const char* who, const void* d1, int n1, const void* d2, int n2, int bytes, int mem, float ratio, uvo_dmatch* out, int cap, int* m)
+{
+    bool go = false;
+    UVO_TRY(match_prologue(c, who, d1, n1, d2, n2, bytes, mem, nullptr, nullptr, &go));
+    if (!go) return UVO_OK;
     UVO_TRY(match_ratio_compact(c, nullptr, n1, ratio, c->d_matches[0], c->d_nmatch, c->cap));
     UVO_TRY(read_counts(c));
     int cnt = c->h_counts[CN_M];
-    if (*m + cnt > cap) return fail(c, UVO_CAPACITY, "uvo_match_knn2_ratio: output capacity too small");
+    if (*m + cnt > cap) { c->err = std::string(who) + ": output capacity too small"; return UVO_CAPACITY; }
     if (cnt) UVO_HIP_TRY(c, hipMemcpyAsync(out + *m, c->d_matches[0], sizeof(uvo_dmatch) * cnt, hipMemcpyDeviceToHost, c->stream));
     UVO_HIP_TRY(c, hipStreamSynchronize(c->stream));
     *m += cnt;                                       // appended, as VOU:538
     return UVO_OK;
+}
+
+extern "C" uvo_status uvo_match_knn2(uvo_ctx* c, const float* d1, int n1, const float* d2, int n2, int mem, int* idx, float* dist)
+try {
+    if (!match_sets_ok(c, d1, n1, d2, n2) || !idx || !dist) return UVO_INVALID_ARG;
+    DimScope surf_rows(c, surf_dim(c));
+    return match_knn_out(c, "uvo_match_knn2", d1, n1, d2, n2, 0, mem, idx, dist);
+} UVO_ABI_CATCH(c)
+extern "C" uvo_status uvo_match_knn2_ratio(uvo_ctx* c, const float* d1, int n1, const float* d2, int n2, int mem,
+                                           float ratio, uvo_dmatch* out, int cap, int* m)
+try {
+    if (!match_sets_ok(c, d1, n1, d2, n2) || !out || !m || *m < 0) return UVO_INVALID_ARG;
+    DimScope surf_rows(c, surf_dim(c));
+    return match_ratio_out(c, "uvo_match_knn2_ratio", d1, n1, d2, n2, 0, mem, ratio, out, cap, m);
 } UVO_ABI_CATCH(c)
 
 // match_features' L2 arm for descriptors that are not this context's SURF rows (VO_utility.cpp:525-529 sends "SIFT" -- 128 floats
-// per row whatever SURF_EXTENDED says -- to the same BFMatcher(NORM_L2)): the row width is given per call.
+// per row whatever SURF_EXTENDED says -- to the same BFMatcher(NORM_L2)): the row width is given per call (the messages name the entries above).
 extern "C" uvo_status uvo_match_knn2_dim(uvo_ctx* c, const float* d1, int n1, const float* d2, int n2, int dim, int mem, int* idx, float* dist)
 try {
     if (!c) return UVO_INVALID_ARG;
     if (dim != 64 && dim != 128) return fail(c, UVO_INVALID_ARG, "uvo_match_knn2_dim: rows of 64 or 128 floats");
+    if (!match_sets_ok(c, d1, n1, d2, n2) || !idx || !dist) return UVO_INVALID_ARG;
     DimScope ds(c, dim);
-    return uvo_match_knn2(c, d1, n1, d2, n2, mem, idx, dist);
+    return match_knn_out(c, "uvo_match_knn2", d1, n1, d2, n2, 0, mem, idx, dist);
 } UVO_ABI_CATCH(c)
 extern "C" uvo_status uvo_match_knn2_ratio_dim(uvo_ctx* c, const float* d1, int n1, const float* d2, int n2, int dim, int mem,
                                                float ratio, uvo_dmatch* out, int cap, int* m)
 try {
     if (!c) return UVO_INVALID_ARG;
     if (dim != 64 && dim != 128) return fail(c, UVO_INVALID_ARG, "uvo_match_knn2_ratio_dim: rows of 64 or 128 floats");
+    if (!match_sets_ok(c, d1, n1, d2, n2) || !out || !m || *m < 0) return UVO_INVALID_ARG;
     DimScope ds(c, dim);
-    return uvo_match_knn2_ratio(c, d1, n1, d2, n2, mem, ratio, out, cap, m);
+    return match_ratio_out(c, "uvo_match_knn2_ratio", d1, n1, d2, n2, 0, mem, ratio, out, cap, m);
 } UVO_ABI_CATCH(c)
-
-// The AKAZE / ORB branch of match_features (VO_utility.cpp:520-524): binary descriptors, Hamming distance
-static uvo_status stage_bytes(uvo_ctx* c, int slot, const uint8_t* d, int n, int bytes, int mem, const uint8_t** out)
-{
-    if (n > c->cap) return fail(c, UVO_CAPACITY, "descriptor count exceeds the context's max_kpts");
-    if (bytes < 1 || bytes > 64) return fail(c, UVO_INVALID_ARG, "binary descriptor rows of 1..64 bytes");
-    if (mem == UVO_MEM_DEVICE) { *out = d; return UVO_OK; }
-    if (n) UVO_HIP_TRY(c, hipMemcpyAsync(c->d_tmp_desc[slot], d, (size_t)bytes * n, hipMemcpyHostToDevice, c->stream));     // cap x 512 bytes of staging
-    *out = reinterpret_cast<const uint8_t*>(c->d_tmp_desc[slot]);
-    return UVO_OK;
-}
 extern "C" uvo_status uvo_match_knn2_hamming(uvo_ctx* c, const uint8_t* d1, int n1, const uint8_t* d2, int n2, int bytes, int mem, int* idx, float* dist)
 try {
-    if (!c || n1 < 0 || n2 < 0 || (n1 && !d1) || (n2 && !d2) || !idx || !dist) return UVO_INVALID_ARG;
+    if (!match_sets_ok(c, d1, n1, d2, n2) || !idx || !dist) return UVO_INVALID_ARG;
     if (bytes < 1 || bytes > 64) return fail(c, UVO_INVALID_ARG, "uvo_match_knn2_hamming: descriptor rows of 1..64 bytes");    // before anything is staged
-    (void)hipSetDevice(c->device);
-    UVO_TRY(need_idle(c, "uvo_match_knn2_hamming"));
-    if (n1 == 0) return UVO_OK;
-    if (n2 == 0) { for (int i = 0; i < 2 * n1; i++) { idx[i] = -1; dist[i] = FLT_MAX; } return UVO_OK; }
-    UVO_TRY(wait_for_producer(c, c, mem));
-    const uint8_t *q, *t;
-    UVO_TRY(stage_bytes(c, 0, d1, n1, bytes, mem, &q));
-    UVO_TRY(stage_bytes(c, 1, d2, n2, bytes, mem, &t));
-    UVO_TRY(match_knn2_hamming(c, q, n1, t, n2, bytes));
-    UVO_HIP_TRY(c, hipMemcpyAsync(idx, c->d_knn_idx, sizeof(int) * 2 * n1, hipMemcpyDeviceToHost, c->stream));
-    UVO_HIP_TRY(c, hipMemcpyAsync(dist, c->d_knn_dist, sizeof(float) * 2 * n1, hipMemcpyDeviceToHost, c->stream));
-    UVO_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return UVO_OK;
+    return match_knn_out(c, "uvo_match_knn2_hamming", d1, n1, d2, n2, bytes, mem, idx, dist);
 } UVO_ABI_CATCH(c)
 // test hook: the fused steps' matchers on binary rows (match_knn2_bin) -- the rows padded to 64 bytes as the detectors leave them, the counts
 // read on the device and the grid sized from max_kpts, as inside the steps
@@ -934,24 +966,9 @@ try {
 extern "C" uvo_status uvo_match_knn2_ratio_hamming(uvo_ctx* c, const uint8_t* d1, int n1, const uint8_t* d2, int n2, int bytes, int mem,
                                                    float ratio, uvo_dmatch* out, int cap, int* m)
 try {
-    if (!c || n1 < 0 || n2 < 0 || (n1 && !d1) || (n2 && !d2) || !out || !m || *m < 0) return UVO_INVALID_ARG;
+    if (!match_sets_ok(c, d1, n1, d2, n2) || !out || !m || *m < 0) return UVO_INVALID_ARG;
     if (bytes < 1 || bytes > 64) return fail(c, UVO_INVALID_ARG, "uvo_match_knn2_ratio_hamming: descriptor rows of 1..64 bytes");   // before anything is staged
-    (void)hipSetDevice(c->device);
-    UVO_TRY(need_idle(c, "uvo_match_knn2_ratio_hamming"));
-    if (n1 == 0 || n2 == 0) return UVO_OK;
-    UVO_TRY(wait_for_producer(c, c, mem));
-    const uint8_t *q, *t;
-    UVO_TRY(stage_bytes(c, 0, d1, n1, bytes, mem, &q));
-    UVO_TRY(stage_bytes(c, 1, d2, n2, bytes, mem, &t));
-    UVO_TRY(match_knn2_hamming(c, q, n1, t, n2, bytes));
-    UVO_TRY(match_ratio_compact(c, nullptr, n1, ratio, c->d_matches[0], c->d_nmatch, c->cap));
-    UVO_TRY(read_counts(c));
-    int cnt = c->h_counts[CN_M];
-    if (*m + cnt > cap) return fail(c, UVO_CAPACITY, "uvo_match_knn2_ratio_hamming: output capacity too small");
-    if (cnt) UVO_HIP_TRY(c, hipMemcpyAsync(out + *m, c->d_matches[0], sizeof(uvo_dmatch) * cnt, hipMemcpyDeviceToHost, c->stream));
-    UVO_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    *m += cnt;                                       // appended, as VOU:538
-    return UVO_OK;
+    return match_ratio_out(c, "uvo_match_knn2_ratio_hamming", d1, n1, d2, n2, bytes, mem, ratio, out, cap, m);
 } UVO_ABI_CATCH(c)
 
 // ------------------------------------------------------------------------------------------ geometry operators
@@ -1109,18 +1126,6 @@ __global__ void k_gather_desc_idx(const float* src, int nsrc, const int* idx, in
     }
 }
 
-extern "C" uvo_status uvo_stereo_set_rig(uvo_ctx* c, const double* K_left, const double* K_right, const double* R_right, const double* t_right)
-try {
-    if (!c || !K_left || !K_right || !R_right || !t_right) return UVO_INVALID_ARG;
-    memcpy(c->K_left, K_left, sizeof(double) * 9); memcpy(c->K_right, K_right, sizeof(double) * 9);
-    memcpy(c->R_right, R_right, sizeof(double) * 9); memcpy(c->t_right, t_right, sizeof(double) * 3);
-    const double I[9] = {1,0,0,0,1,0,0,0,1}, z[3] = {0,0,0};
-    projection_matrix(I, z, K_left, c->P_eye_left);               // VO:460
-    projection_matrix(R_right, t_right, K_right, c->P_right);     // VO:462
-    c->rig_set = true;
-    return uvo_stereo_reset(c);
-} UVO_ABI_CATCH(c)
-
 // collect and drop every entry in flight, stereo pairs and mono frames alike (each collect dequeues its entry even when the pair failed)
 static void drain_in_flight(uvo_ctx* c)
 {
@@ -1128,15 +1133,14 @@ static void drain_in_flight(uvo_ctx* c)
         const int e = c->inflight[0];
         const bool mono = e == Ctx::kInflightMonoInit || (e >= 0 && c->lanes[e]->job.kind == 1);
         const int before = c->n_pending;
-        if (mono) { uvo_mono_result r; (void)uvo_mono_collect(c, 1.0, &r); }
-        else { uvo_stereo_result r; (void)uvo_stereo_collect(c, 1.0, &r); }
+        uvo_mono_result rm; uvo_stereo_result rs;
+        try { (void)(mono ? mono_collect_body(c, 1.0, &rm) : stereo_collect_body(c, 1.0, &rs)); } catch (...) { (void)abi_caught(c); }   // a failure is dropped with the result
         if (c->n_pending == before) break;                 // cannot happen; never spin
     }
 }
 
-extern "C" uvo_status uvo_stereo_reset(uvo_ctx* c)
-try {
-    if (!c) return UVO_INVALID_ARG;
+static uvo_status stereo_reset_body(uvo_ctx* c)
+{
     (void)hipSetDevice(c->device);
     drain_in_flight(c);                                    // results of whatever is still in flight are dropped
     for (Ctx* l : c->lanes) {
@@ -1150,6 +1154,19 @@ try {
     c->n_pending = 0; c->n_submitted = c->n_collected = 0;
     for (int i = 0; i < 3; i++) c->t_prev_curr[i] = c->rvec[i] = c->tvec[i] = 0;
     return UVO_OK;
+}
+extern "C" uvo_status uvo_stereo_reset(uvo_ctx* c)
+try { return c ? stereo_reset_body(c) : UVO_INVALID_ARG; } UVO_ABI_CATCH(c)
+extern "C" uvo_status uvo_stereo_set_rig(uvo_ctx* c, const double* K_left, const double* K_right, const double* R_right, const double* t_right)
+try {
+    if (!c || !K_left || !K_right || !R_right || !t_right) return UVO_INVALID_ARG;
+    memcpy(c->K_left, K_left, sizeof(double) * 9); memcpy(c->K_right, K_right, sizeof(double) * 9);
+    memcpy(c->R_right, R_right, sizeof(double) * 9); memcpy(c->t_right, t_right, sizeof(double) * 3);
+    const double I[9] = {1,0,0,0,1,0,0,0,1}, z[3] = {0,0,0};
+    projection_matrix(I, z, K_left, c->P_eye_left);               // VO:460
+    projection_matrix(R_right, t_right, K_right, c->P_right);     // VO:462
+    c->rig_set = true;
+    return stereo_reset_body(c);
 } UVO_ABI_CATCH(c)
 
 // init phase VO:474-520 (first pairs only; host-assisted because results_match_prev accumulates)
@@ -1209,6 +1226,33 @@ static uvo_status stereo_init_step(uvo_ctx* c, uvo_stereo_result* out)
     return UVO_OK;
 }
 
+// The hand-over of lane L's job to its worker (lane_worker is the other side): the job's fields, its state, then the state's atomic twin,
+// all under the lane's mutex; the worker is notified after the lock is released.  (`range` is a mono frame's; no other kind reads it.)
+static void lane_hand_over(uvo_ctx* L, int kind, double range = 0)
+{
+    { std::lock_guard<std::mutex> lk(L->mu); L->job.kind = kind; L->job.range = range; L->job.state = 1; L->job_state_a.store(1, std::memory_order_release); }
+    L->cv.notify_all();
+}
+static void poll_job_state(uvo_ctx* L, int want, double spin_us);
+// ... and back: the worker's answer, awaited polling the twin for up to spin_us first (0: asleep at once); the lane is idle again
+static void lane_await_done(uvo_ctx* L, double spin_us)
+{
+    if (spin_us > 0) poll_job_state(L, 2, spin_us);
+    std::unique_lock<std::mutex> lk(L->mu);
+    L->cv.wait(lk, [&] { return L->job.state == 2; });
+    L->job.state = 0; L->job_state_a.store(0, std::memory_order_release);
+}
+// The oldest entry in flight leaves the queue and is the one collected last: a lane's index (the lane holds no pending entry any more), or
+// Ctx::kInflightStereoInit / kInflightMonoInit (a synchronous init entry, which ran on lane 0)
+static int pop_oldest_inflight(uvo_ctx* c)
+{
+    const int e = c->inflight[0];
+    for (int i = 1; i < c->n_pending; i++) c->inflight[i - 1] = c->inflight[i];
+    c->n_pending--; c->n_collected++;
+    c->last_lane = e < 0 ? 0 : e;
+    if (e >= 0) c->lanes[e]->pending.used = false;
+    return e;
+}
 // First use of a pipeline lane costs what every first use costs -- the hardware queues behind its two HIP streams are created at
 // their first submission, the per-image-size detector tables are built and uploaded (two allocations, four host syncs) -- and a
 // caller that times its first pairs through a deep pipeline pays it once per lane inside that loop.  The synchronous init phase
@@ -1237,9 +1281,8 @@ static uvo_status prime_lanes(uvo_ctx* c, int w, int h)
         // (event + stream) also set up the runtime's per-thread state
         UVO_HIP_TRY(c, hipEventRecord(l->evA[0], l->stream));
         l->t_handover_us = 0;
-        { std::lock_guard<std::mutex> lk(l->mu); l->job.kind = 2; l->job.state = 1; l->job_state_a.store(1, std::memory_order_release); }
-        l->cv.notify_all();
-        { std::unique_lock<std::mutex> lk(l->mu); l->cv.wait(lk, [&] { return l->job.state == 2; }); l->job.state = 0; l->job_state_a.store(0, std::memory_order_release); }
+        lane_hand_over(static_cast<uvo_ctx*>(l), 2);
+        lane_await_done(static_cast<uvo_ctx*>(l), 0);
         l->primed_w = w; l->primed_h = h;
     }
     return UVO_OK;
@@ -1248,21 +1291,15 @@ static uvo_status prime_lanes(uvo_ctx* c, int w, int h)
 // Stage A of one pair (VO:548-632): detect, stereo match, triangular match, triangulation,
 // extract_3Dpoints -- all enqueued on the lane's stream without a host sync; the counters are copied to the
 // lane's pinned mirror, an event marks completion and the lane's worker thread takes over for stage B.
-extern "C" uvo_status uvo_stereo_submit(uvo_ctx* c, const uint8_t* left, const uint8_t* right, int w, int h, int stride, int mem)
-try {
-    if (!c || !left || !right) return UVO_INVALID_ARG;
-    if (!c->rig_set) return fail(c, UVO_INVALID_ARG, "uvo_stereo_set_rig has not been called");
-    UVO_TRY(need_loop_table(c));
+static uvo_status stereo_submit_body(uvo_ctx* c, const uint8_t* left, const uint8_t* right, int w, int h, int stride, int mem, EntryOpts o)
+{
     const int depth = (int)c->lanes.size();
-    if (c->n_pending >= depth) return fail(c, UVO_INVALID_ARG, "uvo_stereo_submit: the pipeline is full; collect a pair first (uvo_stereo_set_depth)");
-    if (c->timing && c->n_pending > 0) return fail(c, UVO_INVALID_ARG, "timing mode measures one pair at a time: collect before submitting");
-    (void)hipSetDevice(c->device);
     const uvo_params& p = c->p;
     if (!c->vo_initialized) {                                                               // VO:474-520, on lane 0, synchronous
         // (earlier init pairs may still await their collect: they are complete, only their results are queued)
         uvo_stereo_result res;
         memset(&res, 0, sizeof(res));
-        UVO_TRY(wait_for_producer(c, c, mem));
+        if (!o.producer_waited) UVO_TRY(wait_for_producer(c, c, mem));
         UVO_TRY(surf_upload(c, 0, left, w, h, stride, mem));
         UVO_TRY(surf_upload(c, 1, right, w, h, stride, mem));
         UVO_TRY(detect_dispatch(c, 2));
@@ -1292,14 +1329,14 @@ try {
         tr->host_us[0] = uvo::now_us();
     }
     // a pair joins a two-pair launch when the mode is on and the pair can take that path: upright SURF, not the synchronous step,
-    // no per-stage timing, two lanes at least
-    const bool may_batch = c->batch == 2 && depth >= 2 && !c->in_sync_step && !c->timing && c->loop_detector() == 0 && p.SURF_UPRIGHT && p.SURF_OCTAVES_NUMBER == 4;
+    // no per-stage timing, two lanes at least, not an entry that goes alone
+    const bool may_batch = c->batch == 2 && !o.alone && depth >= 2 && !c->in_sync_step && !c->timing && c->loop_detector() == 0 && p.SURF_UPRIGHT && p.SURF_OCTAVES_NUMBER == 4;
     uvo_ctx* S = c->stashed_lane >= 0 ? static_cast<uvo_ctx*>(c->lanes[c->stashed_lane]) : nullptr;      // the pair before, waiting for this one
     // uploads: a pair's images go to its own lane's buffers (or are read in place); the copies of a two-pair launch are ordered on the
     // stream that will run the kernels -- the first lane's
     hipStream_t own = L->stream;
     if (S && may_batch) L->stream = S->stream;
-    uvo_status up = wait_for_producer(c, L, mem);
+    uvo_status up = o.producer_waited ? UVO_OK : wait_for_producer(c, L, mem);
     if (up == UVO_OK) up = surf_upload(L, 0, left, w, h, stride, mem);
     if (up == UVO_OK) up = surf_upload(L, 1, right, w, h, stride, mem);
     L->stream = own;
@@ -1315,6 +1352,13 @@ try {
     if (S) return queue_stage_a(c, S, L);
     if (may_batch) { c->stashed_lane = li; return UVO_OK; }           // waits for its partner (or for the collect that needs it)
     return queue_stage_a(c, L, nullptr);
+}
+extern "C" uvo_status uvo_stereo_submit(uvo_ctx* c, const uint8_t* left, const uint8_t* right, int w, int h, int stride, int mem)
+try {
+    if (!c || !left || !right) return UVO_INVALID_ARG;
+    UVO_TRY(stereo_submit_refusal(c, "uvo_stereo_submit"));
+    (void)hipSetDevice(c->device);
+    return stereo_submit_body(c, left, right, w, h, stride, mem, EntryOpts());
 } UVO_ABI_CATCH(c)
 
 // Stage A of one pair (VO:548-632) -- or of two consecutive pairs, lanes A and B, in one set of launches on A's stream: detect,
@@ -1462,8 +1506,7 @@ static uvo_status queue_stage_a(uvo_ctx* c, uvo_ctx* A, uvo_ctx* B)
             L->job.kind = 0;                                   // nobody is woken: the round is on the device, collect finishes the pair
         } else {   // hand stage B to the lane's worker
             L->t_handover_us = uvo::now_us();
-            { std::lock_guard<std::mutex> lk(L->mu); L->job.kind = 0; L->job.state = 1; L->job_state_a.store(1, std::memory_order_release); }
-            L->cv.notify_all();
+            lane_hand_over(L, 0);
         }
     }
     seg(11);                                                                               // matcher .. extract_3Dpoints launches, hand-over
@@ -1473,7 +1516,6 @@ static uvo_status queue_stage_a(uvo_ctx* c, uvo_ctx* A, uvo_ctx* B)
 }
 
 // Stage B of one lane's pair (VO:634-648), on the lane's worker thread: wait for stage A, then solvePnPRansac.
-namespace uvo { extern bool g_bdbg; extern std::atomic<double> g_bstat[16]; double now_us(); void operator+=(std::atomic<double>& a, double v); }
 static void run_stage_b(uvo_ctx* L, bool stage_a_ok)
 {
     Ctx::BJob& j = L->job;
@@ -1581,27 +1623,21 @@ static void lane_worker(uvo_ctx* L)
 }
 
 // Result of the oldest submitted pair: gates, pose inversion and output (VO:634-717, VO:148-159), in order.
-extern "C" uvo_status uvo_stereo_collect(uvo_ctx* c, double dt, uvo_stereo_result* out)
-try {
-    if (!c || !out) return UVO_INVALID_ARG;
+static uvo_status stereo_collect_body(uvo_ctx* c, double dt, uvo_stereo_result* out)
+{
     if (c->n_pending <= 0) return fail(c, UVO_INVALID_ARG, "uvo_stereo_collect: nothing submitted");
     if (c->inflight[0] == Ctx::kInflightMonoInit || (c->inflight[0] >= 0 && c->lanes[c->inflight[0]]->job.kind != 0))
         return fail(c, UVO_INVALID_ARG, "uvo_stereo_collect: the oldest entry in flight is a mono frame (uvo_mono_collect)");
     (void)hipSetDevice(c->device);
     Range r_collect("uvo:stereo_collect");
     const uvo_params& p = c->p;
-    const int li = c->inflight[0];
-    for (int i = 1; i < c->n_pending; i++) c->inflight[i - 1] = c->inflight[i];
-    c->n_pending--; c->n_collected++;
+    const int li = pop_oldest_inflight(c);
     if (li == Ctx::kInflightStereoInit) {                       // a synchronous init pair (its state is already applied)
         *out = c->stereo_init_results.front();
         c->stereo_init_results.pop_front();
-        c->last_lane = 0;
         return UVO_OK;
     }
     uvo_ctx* L = static_cast<uvo_ctx*>(c->lanes[li]);
-    c->last_lane = li;
-    L->pending.used = false;
     if (c->stashed_lane == li) {                               // the pair was waiting for a partner that has not come: it goes alone, now
         const uvo_status qs = queue_stage_a(c, L, nullptr);
         if (qs != UVO_OK) return qs;
@@ -1619,12 +1655,7 @@ try {
         if (wtr) wtr->host_us[4] = uvo::now_us();
         run_stage_b(L, ok);
         if (wtr) wtr->host_us[5] = uvo::now_us();
-    } else {
-        poll_job_state(L, 2, 5000.0);
-        std::unique_lock<std::mutex> lk(L->mu);
-        L->cv.wait(lk, [&] { return L->job.state == 2; });
-        L->job.state = 0; L->job_state_a.store(0, std::memory_order_release);
-    }
+    } else lane_await_done(L, 5000.0);
     const Ctx::BJob& j = L->job;
     memset(out, 0, sizeof(*out));
     out->initialized = 1;
@@ -1660,18 +1691,26 @@ try {
         out->velocity[i] = c->t_prev_curr[i] / dt;                                         // VO:152
     }
     return UVO_OK;
-} UVO_ABI_CATCH(c)
+}
+extern "C" uvo_status uvo_stereo_collect(uvo_ctx* c, double dt, uvo_stereo_result* out)
+try { return c && out ? stereo_collect_body(c, dt, out) : UVO_INVALID_ARG; } UVO_ABI_CATCH(c)
 
-extern "C" uvo_status uvo_stereo_step(uvo_ctx* c, const uint8_t* left, const uint8_t* right, int w, int h, int stride,
-                                      int mem, double dt, uvo_stereo_result* out)
+// The synchronous step: one pair submitted and collected by the calling thread, which finishes stage B itself.  Ctx::in_sync_step, read
+// by the submit and by the SIFT detector, is false again however the submit ends.
+namespace { struct SyncStepScope { uvo_ctx* c; explicit SyncStepScope(uvo_ctx* c_) : c(c_) { c->in_sync_step = true; } ~SyncStepScope() { c->in_sync_step = false; } }; }
+static uvo_status stereo_step_body(uvo_ctx* c, const uint8_t* left, const uint8_t* right, int w, int h, int stride, int mem, double dt, uvo_stereo_result* out, EntryOpts o)
+{
+    { SyncStepScope sync(c); UVO_TRY(stereo_submit_body(c, left, right, w, h, stride, mem, o)); }
+    return stereo_collect_body(c, dt, out);
+}
+extern "C" uvo_status uvo_stereo_step(uvo_ctx* c, const uint8_t* left, const uint8_t* right, int w, int h, int stride, int mem, double dt, uvo_stereo_result* out)
 try {
     if (!c || !out) return UVO_INVALID_ARG;
     if (c->n_pending != 0) return fail(c, UVO_INVALID_ARG, "uvo_stereo_step: pairs submitted with uvo_stereo_submit are still in flight");
-    c->in_sync_step = true;
-    const uvo_status st = uvo_stereo_submit(c, left, right, w, h, stride, mem);
-    c->in_sync_step = false;
-    UVO_TRY(st);
-    return uvo_stereo_collect(c, dt, out);
+    if (!left || !right) return UVO_INVALID_ARG;
+    UVO_TRY(stereo_submit_refusal(c, "uvo_stereo_submit"));
+    (void)hipSetDevice(c->device);
+    return stereo_step_body(c, left, right, w, h, stride, mem, dt, out, EntryOpts());
 } UVO_ABI_CATCH(c)
 
 extern "C" int uvo_stereo_get(uvo_ctx* m, const char* what, void* out, int cap_bytes)
@@ -1709,7 +1748,6 @@ try {
     }
     return count;
 } UVO_ABI_CATCH_RET(m, 0)
-
 
 // ------------------------------------------------------------------------------------------ get_image
 // cvUndistortPointsInternal for one point, no R, no P (normalised output): five fixed-point iterations of the inverse of the
@@ -1955,16 +1993,8 @@ try {
     return UVO_OK;
 } UVO_ABI_CATCH(c)
 
-extern "C" uvo_status uvo_mono_set_camera(uvo_ctx* c, const double* K)
-try {
-    if (!c || !K) return UVO_INVALID_ARG;
-    memcpy(c->mono_K, K, sizeof(c->mono_K));
-    c->mono_cam_set = true;
-    return uvo_mono_reset(c);
-} UVO_ABI_CATCH(c)
-extern "C" uvo_status uvo_mono_reset(uvo_ctx* c)
-try {
-    if (!c) return UVO_INVALID_ARG;
+static uvo_status mono_reset_body(uvo_ctx* c)
+{
     drain_in_flight(c);                                    // results of whatever is still in flight are dropped
     c->mono_init_results.clear();
     for (Ctx* l : c->lanes) { if (l->stream) (void)hipStreamSynchronize(l->stream); l->prev_read_pending = false; l->pending = Ctx::Pending(); }
@@ -1975,7 +2005,16 @@ try {
     memcpy(c->mono_R, I, sizeof(I)); c->mono_t[0] = c->mono_t[1] = c->mono_t[2] = 0;
     c->mono_mask.clear(); c->mono_good_pts.clear(); c->mono_dev_n = c->mono_dev_M = c->mono_dev_G = 0; c->mono_good_on_host = true; c->mono_matched = false;
     return UVO_OK;
+}
+extern "C" uvo_status uvo_mono_set_camera(uvo_ctx* c, const double* K)
+try {
+    if (!c || !K) return UVO_INVALID_ARG;
+    memcpy(c->mono_K, K, sizeof(c->mono_K));
+    c->mono_cam_set = true;
+    return mono_reset_body(c);
 } UVO_ABI_CATCH(c)
+extern "C" uvo_status uvo_mono_reset(uvo_ctx* c)
+try { return c ? mono_reset_body(c) : UVO_INVALID_ARG; } UVO_ABI_CATCH(c)
 
 // ---------------------------------------------------------------------------------------------------------------------
 // mono pipeline (uvo_mono_submit / uvo_mono_collect): the loop body of uvo_mono_step split at the point where the host
@@ -2126,40 +2165,40 @@ static void apply_mono_result(uvo_ctx* c, const Ctx::BJob& j, double dt, uvo_mon
     }
 }
 
+// match_features 7-arg (VO:287 -> VOU:551-573) of a mono frame, queued on lane L's stream: query = the previous frame (its count on the
+// device, d_nprev, with nprev the bound, or on the host, nprev, with d_nprev NULL), train = the frame just detected in L (its count stays
+// on the device); ratio test, the matched point pairs, then their normalised form with select_estimation_method's decision (k_mono_prep)
+#define LANE_TRY(expr) do { uvo_status st_ = (expr); if (st_ != UVO_OK) { if (L != c) c->err = L->err; return st_; } } while (0)
+static uvo_status queue_mono_match(uvo_ctx* c, uvo_ctx* L, const float* prev_desc, const uvo_keypoint* prev_kps, const int* d_nprev, int nprev)
+{
+    const int cap = c->cap; const uvo_params& p = c->p;
+    if (L->use_binary()) LANE_TRY(match_knn2_bin(L, BIN_L2, reinterpret_cast<const uint8_t*>(prev_desc), d_nprev, nprev,               // NORM_L2 on CV_8U rows
+                                                 reinterpret_cast<const uint8_t*>(L->det[0].desc), L->det[0].n, cap));
+    else LANE_TRY(match_knn2(L, prev_desc, d_nprev, nprev, L->det[0].desc, L->det[0].n, cap));
+    LANE_TRY(match_ratio_compact(L, d_nprev, nprev, (float)p.LOWE_RATIO_THRESHOLD, L->d_matches[0], L->d_nmatch, cap));
+    hipLaunchKernelGGL(k_gather_mono_pairs, dim3((cap + 255) / 256), dim3(256), 0, L->stream, L->d_matches[0], L->d_counts + CN_M, cap,
+                       prev_kps, L->det[0].kps, L->d_x1, L->d_x2);
+    UVO_HIP_TRY(c, hipGetLastError());
+    LANE_TRY(mono_prep_launch(L, L->stream, c->mono_K, p.DISTANCE));
+    return UVO_OK;
+}
 // mono loop body, visual_odometry_node::mono_VO (visual_odometry.h:227-245 init, 247-397 main loop, 126-140 output), one frame at a
 // time on lane 0: the previous frame's keypoints and descriptors are rolled into d_as_kpsL[0] / d_as_descL[0] (VO:279-282 / 392-395).
 // Detection, matching, the point gather and select_estimation_method's kernel are queued without a host sync; the counts are read
 // once, then the pose stage runs on the calling thread (run_mono_stage_b).
-extern "C" uvo_status uvo_mono_step(uvo_ctx* c, const uint8_t* img, int w, int h, int stride, int mem, double range, double dt,
-                                    uvo_mono_result* out)
-try {
-    if (!c || !img || !out) return UVO_INVALID_ARG;
-    if (!c->mono_cam_set) return fail(c, UVO_INVALID_ARG, "uvo_mono_set_camera has not been called");
-    if (c->mono_pipelined) return fail(c, UVO_INVALID_ARG, "uvo_mono_step after uvo_mono_submit: call uvo_mono_reset first (the previous frame is held by the pipeline)");
-    UVO_TRY(need_loop_table(c));
-    (void)hipSetDevice(c->device);
+static uvo_status mono_step_body(uvo_ctx* c, const uint8_t* img, int w, int h, int stride, int mem, double range, double dt, uvo_mono_result* out, EntryOpts o)
+{
     const uvo_params& p = c->p;
     Range r_step("uvo:mono_step");
     memset(out, 0, sizeof(*out));
     c->mono_mask.clear(); c->mono_good_pts.clear();
     c->mono_dev_n = c->mono_dev_M = c->mono_dev_G = 0; c->mono_good_on_host = true;
-    UVO_TRY(wait_for_producer(c, c, mem));
+    if (!o.producer_waited) UVO_TRY(wait_for_producer(c, c, mem));
     UVO_TRY(surf_upload(c, 0, img, w, h, stride, mem));
     UVO_TRY(detect_dispatch(c, 1));                                                        // VO:238 / VO:274
-    // match_features 7-arg (VO:287 -> VOU:551-573) against the rolled previous frame: query = previous, train = this frame (its count
-    // stays on the device), ratio test, the matched point pairs, select_estimation_method -- whether the gates let the frame use them
-    // is decided below, from the counts
+    // the match against the rolled previous frame -- whether the gates let the frame use it is decided below, from the counts
     c->mono_matched = c->mono_initialized && c->mono_n_prev > 0;
-    if (c->mono_matched) {
-        if (c->use_binary()) UVO_TRY(match_knn2_bin(c, BIN_L2, reinterpret_cast<const uint8_t*>(c->d_as_descL[0]), nullptr, c->mono_n_prev,     // NORM_L2 on CV_8U rows
-                                                    reinterpret_cast<const uint8_t*>(c->det[0].desc), c->det[0].n, c->cap));
-        else UVO_TRY(match_knn2(c, c->d_as_descL[0], nullptr, c->mono_n_prev, c->det[0].desc, c->det[0].n, c->cap));
-        UVO_TRY(match_ratio_compact(c, nullptr, c->mono_n_prev, (float)p.LOWE_RATIO_THRESHOLD, c->d_matches[0], c->d_nmatch, c->cap));
-        hipLaunchKernelGGL(k_gather_mono_pairs, dim3((c->cap + 255) / 256), dim3(256), 0, c->stream, c->d_matches[0], c->d_counts + CN_M, c->cap,
-                           c->d_as_kpsL[0], c->det[0].kps, c->d_x1, c->d_x2);
-        UVO_HIP_TRY(c, hipGetLastError());
-        UVO_TRY(mono_prep_launch(c, c->stream, c->mono_K, p.DISTANCE));
-    }
+    if (c->mono_matched) UVO_TRY(queue_mono_match(c, c, c->d_as_descL[0], c->d_as_kpsL[0], nullptr, c->mono_n_prev));
     UVO_HIP_TRY(c, hipMemcpyAsync(c->h_countsA[0], c->d_counts, sizeof(int) * CN_TOTAL, hipMemcpyDeviceToHost, c->stream));
     UVO_HIP_TRY(c, host_sync(c, c->stream));
     memcpy(c->h_counts, c->h_countsA[0], sizeof(int) * CN_TOTAL);
@@ -2186,24 +2225,24 @@ try {
     if (c->job.st != UVO_OK) { const uvo_status st_ = c->job.st; c->err = c->job.err; return st_; }
     apply_mono_result(c, c->job, dt, out);
     return roll_state();
+}
+extern "C" uvo_status uvo_mono_step(uvo_ctx* c, const uint8_t* img, int w, int h, int stride, int mem, double range, double dt, uvo_mono_result* out)
+try {
+    if (!c || !img || !out) return UVO_INVALID_ARG;
+    UVO_TRY(mono_step_refusal(c));
+    (void)hipSetDevice(c->device);
+    return mono_step_body(c, img, w, h, stride, mem, range, dt, out, EntryOpts());
 } UVO_ABI_CATCH(c)
 
-extern "C" uvo_status uvo_mono_submit(uvo_ctx* c, const uint8_t* img, int w, int h, int stride, int mem, double range)
-try {
-    if (!c || !img) return UVO_INVALID_ARG;
-    if (!c->mono_cam_set) return fail(c, UVO_INVALID_ARG, "uvo_mono_set_camera has not been called");
+static uvo_status mono_submit_body(uvo_ctx* c, const uint8_t* img, int w, int h, int stride, int mem, double range, EntryOpts o)
+{
     const int depth = (int)c->lanes.size();
-    if (depth < 2) return fail(c, UVO_INVALID_ARG, "uvo_mono_submit needs at least two lanes (uvo_stereo_set_depth): a frame is matched against the previous lane's buffers");
-    UVO_TRY(need_loop_table(c));
-    if (c->n_pending >= depth) return fail(c, UVO_INVALID_ARG, "uvo_mono_submit: the pipeline is full; collect a frame first (uvo_stereo_set_depth)");
-    (void)hipSetDevice(c->device);
     Range r_submit("uvo:mono_submit");
-    const uvo_params& p = c->p;
     if (!c->mono_initialized) {                                                            // VO:227-245 on lane 0, synchronous
         // (earlier init frames may still await their collect: they are complete, only their result is queued)
         uvo_mono_result r;
         memset(&r, 0, sizeof(r));
-        UVO_TRY(uvo_mono_step(c, img, w, h, stride, mem, range, 1.0, &r));                 // nothing is published before initialisation
+        UVO_TRY(mono_step_body(c, img, w, h, stride, mem, range, 1.0, &r, o));             // nothing is published before initialisation
         c->mono_init_results.push_back(r);
         c->inflight[c->n_pending++] = Ctx::kInflightMonoInit; c->n_submitted++;                // a synchronous init frame
         c->prev_lane = 0; c->next_lane = 1 % depth;
@@ -2216,11 +2255,10 @@ try {
     uvo_ctx* L = static_cast<uvo_ctx*>(c->lanes[li]);
     Ctx* P = c->lanes[c->prev_lane];
     c->mono_pipelined = true;                  // the previous frame now lives in a lane's buffers, not in uvo_mono_step's rolled state
-#define LANE_TRY(expr) do { uvo_status st_ = (expr); if (st_ != UVO_OK) { if (L != c) c->err = L->err; return st_; } } while (0)
     hipStream_t st = L->stream;
     L->pending = Ctx::Pending(); L->pending.used = true;
     if (L->prev_read_pending) { UVO_HIP_TRY(c, hipStreamWaitEvent(st, L->evPrevRead, 0)); L->prev_read_pending = false; }   // the frame after this lane's last one has read its buffers
-    UVO_TRY(wait_for_producer(c, L, mem));
+    if (!o.producer_waited) UVO_TRY(wait_for_producer(c, L, mem));
     LANE_TRY(surf_upload(L, 0, img, w, h, stride, mem));
     if (c->a_overlap_mono > 0 && depth > c->a_overlap_mono) {                              // as uvo_stereo_submit: paced by this thread; one image per frame, so more stage As side by side
         Ctx* H = c->lanes[(li + depth - c->a_overlap_mono) % depth];
@@ -2228,18 +2266,8 @@ try {
     }
     LANE_TRY(detect_dispatch(L, 1));                                                       // VO:274
     UVO_HIP_TRY(c, hipEventRecord(L->evDet, st));
-    int* cn = L->d_counts;
-    const int cap = c->cap;
     if (P != L) UVO_HIP_TRY(c, hipStreamWaitEvent(st, P->evDet, 0));
-    // match_features 7-arg (VO:287 -> VOU:551-573): query = previous frame, train = this frame; the counts stay on the device
-    if (L->use_binary()) LANE_TRY(match_knn2_bin(L, BIN_L2, reinterpret_cast<const uint8_t*>(P->det[0].desc), P->det[0].n, cap,
-                                                 reinterpret_cast<const uint8_t*>(L->det[0].desc), L->det[0].n, cap));
-    else LANE_TRY(match_knn2(L, P->det[0].desc, P->det[0].n, cap, L->det[0].desc, L->det[0].n, cap));
-    LANE_TRY(match_ratio_compact(L, P->det[0].n, cap, (float)p.LOWE_RATIO_THRESHOLD, L->d_matches[0], cn + CN_M, cap));
-    hipLaunchKernelGGL(k_gather_mono_pairs, dim3((cap + 255) / 256), dim3(256), 0, st, L->d_matches[0], cn + CN_M, cap,
-                       P->det[0].kps, L->det[0].kps, L->d_x1, L->d_x2);
-    UVO_HIP_TRY(c, hipGetLastError());
-    LANE_TRY(mono_prep_launch(L, st, c->mono_K, p.DISTANCE));                              // normalised points, select_estimation_method, pinned mirrors
+    UVO_TRY(queue_mono_match(c, L, P->det[0].desc, P->det[0].kps, P->det[0].n, c->cap));   // against the previous lane's frame, behind its evDet
     L->mono_matched = true;
     if (P != L) { UVO_HIP_TRY(c, hipEventRecord(P->evPrevRead, st)); P->prev_read_pending = true; }
     UVO_HIP_TRY(c, hipMemcpyAsync(L->h_countsA[0], L->d_counts, sizeof(int) * CN_TOTAL, hipMemcpyDeviceToHost, st));
@@ -2248,46 +2276,40 @@ try {
     c->prev_lane = li; c->next_lane = (li + 1) % depth;
     c->inflight[c->n_pending++] = li; c->n_submitted++;
     L->t_handover_us = uvo::now_us();
-    {
-        std::lock_guard<std::mutex> lk(L->mu);
-        L->job.kind = 1; L->job.range = range; L->job.state = 1; L->job_state_a.store(1, std::memory_order_release);
-    }
-    L->cv.notify_all();
+    lane_hand_over(L, 1, range);
     return UVO_OK;
+}
 #undef LANE_TRY
+extern "C" uvo_status uvo_mono_submit(uvo_ctx* c, const uint8_t* img, int w, int h, int stride, int mem, double range)
+try {
+    if (!c || !img) return UVO_INVALID_ARG;
+    UVO_TRY(mono_submit_refusal(c, "uvo_mono_submit"));
+    (void)hipSetDevice(c->device);
+    return mono_submit_body(c, img, w, h, stride, mem, range, EntryOpts());
 } UVO_ABI_CATCH(c)
 
-extern "C" uvo_status uvo_mono_collect(uvo_ctx* c, double dt, uvo_mono_result* out)
-try {
-    if (!c || !out) return UVO_INVALID_ARG;
+static uvo_status mono_collect_body(uvo_ctx* c, double dt, uvo_mono_result* out)
+{
     if (c->n_pending <= 0) return fail(c, UVO_INVALID_ARG, "uvo_mono_collect: nothing submitted");
     if (c->inflight[0] == Ctx::kInflightStereoInit || (c->inflight[0] >= 0 && c->lanes[c->inflight[0]]->job.kind != 1))
         return fail(c, UVO_INVALID_ARG, "uvo_mono_collect: the oldest entry in flight is a stereo pair (uvo_stereo_collect)");
     (void)hipSetDevice(c->device);
-    const int li = c->inflight[0];
-    for (int i = 1; i < c->n_pending; i++) c->inflight[i - 1] = c->inflight[i];
-    c->n_pending--; c->n_collected++;
+    const int li = pop_oldest_inflight(c);
     if (li < 0) {                                          // a synchronous init frame (its state is already applied)
         *out = c->mono_init_results.front();
         c->mono_init_results.pop_front();
-        c->last_lane = 0;
         return UVO_OK;
     }
     uvo_ctx* L = static_cast<uvo_ctx*>(c->lanes[li]);
-    c->last_lane = li;
-    L->pending.used = false;
-    {
-        poll_job_state(L, 2, 5000.0);
-        std::unique_lock<std::mutex> lk(L->mu);
-        L->cv.wait(lk, [&] { return L->job.state == 2; });
-        L->job.state = 0; L->job_state_a.store(0, std::memory_order_release);
-    }
+    lane_await_done(L, 5000.0);
     const Ctx::BJob& j = L->job;
     if (j.st != UVO_OK) return fail(c, j.st, j.err.c_str());
     // (uvo_mono_get reads the frame's intermediates from this lane, c->last_lane, until the lane is submitted to again)
     apply_mono_result(c, j, dt, out);
     return UVO_OK;
-} UVO_ABI_CATCH(c)
+}
+extern "C" uvo_status uvo_mono_collect(uvo_ctx* c, double dt, uvo_mono_result* out)
+try { return c && out ? mono_collect_body(c, dt, out) : UVO_INVALID_ARG; } UVO_ABI_CATCH(c)
 
 // last frame's intermediates.  Keypoints, matches and (after the device-resident pose chain) the good points live in the frame's lane
 // until that lane is submitted to again: they are copied out here, when asked for, not once per frame.
@@ -2321,11 +2343,11 @@ try {
 
 // ------------------------------------------------------------------------------------------ camera frames into the loops
 // get_image (VO:235/260, VO:482-483/542-543) inside the loop entries: the colour frames of an entry are preprocessed on the entry's
-// lane's stage-A stream, into the lane's own detector images, and the entry then goes through uvo_stereo_submit / uvo_mono_submit /
-// uvo_mono_step as a device image read in place -- so everything behind the seam is those calls' code, unchanged.  The lane is the
-// one the call below will pick: lane 0 while the loop initialises (synchronous), else next_lane, which is free because the pipeline is
-// not full.  No later entry reads a predecessor's IMAGE (queue_stage_a reads the previous lane's "after stereo match" set, the mono
-// submit the previous lane's keypoints and descriptors), so a lane's image buffers are its own from collect to collect.
+// lane's stage-A stream, into the lane's own detector images, and the entry then runs its step's body -- the grey-image entry's -- on
+// those images, read in place as device images: the two entries of a step share its refusals and everything behind the seam (EntryOpts).
+// The lane is the one the body will pick: lane 0 while the loop initialises (synchronous), else next_lane, which is free because the
+// pipeline is not full.  No later entry reads a predecessor's IMAGE (queue_stage_a reads the previous lane's "after stereo match" set,
+// the mono submit the previous lane's keypoints and descriptors), so a lane's image buffers are its own from collect to collect.
 extern "C" uvo_status uvo_ctx_set_camera(uvo_ctx* c, int cam, const double* K, const double* dist4, const double* newK, int desired_width,
                                          int clahe, int clip_limit)
 try {
@@ -2337,86 +2359,62 @@ try {
     return frames_set_camera(c, cam, K, dist4, newK, desired_width, clahe, clip_limit);
 } UVO_ABI_CATCH(c)
 
-namespace {
-// a frames entry goes alone (never into a two-pair launch set: the set's kernels run on the other lane's stream), and its producer
-// wait is queued in front of the preprocessing, not again in front of detection
-struct FramesEntryScope {
-    uvo_ctx* c; int batch; bool has_producer;
-    explicit FramesEntryScope(uvo_ctx* c_) : c(c_), batch(c_->batch), has_producer(c_->has_producer) { c->batch = 1; c->has_producer = false; }
-    ~FramesEntryScope() { c->batch = batch; c->has_producer = has_producer; }
-};
-}
-static uvo_status frames_to_lane(uvo_ctx* c, uvo_ctx* L, int ncam, const uint8_t* const* rgb, int w, int h, int stride, int mem, int dw, int dh)
+// the entry's frames (one, or left and right) to the detector images, dw x dh, of the lane *L that the body will pick, behind the producer
+static uvo_status frames_to_lane(uvo_ctx* c, bool loop_initialized, const uint8_t* rgb0, const uint8_t* rgb1, int w, int h, int stride, int mem, uvo_ctx** L, int* dw, int* dh)
 {
-    UVO_TRY(wait_for_producer(c, L, mem));
-    const uvo_status st = frames_queue(c, L, ncam, rgb, w, h, stride, mem, dw, dh);
-    if (st != UVO_OK && L != c) c->err = L->err;
+    const uint8_t* rgb[2] = { rgb0, rgb1 };
+    const int ncam = rgb1 ? 2 : 1;
+    UVO_TRY(frames_plan(c, ncam, w, h, stride, mem, dw, dh));
+    *L = loop_initialized ? static_cast<uvo_ctx*>(c->lanes[c->next_lane]) : c;
+    UVO_TRY(wait_for_producer(c, *L, mem));
+    const uvo_status st = frames_queue(c, *L, ncam, rgb, w, h, stride, mem, *dw, *dh);
+    if (st != UVO_OK && *L != c) c->err = (*L)->err;
     return st;
 }
-
+// the front of both stereo frames entries: the submit's refusals, then the pair's frames
+static uvo_status stereo_frames_to_lane(uvo_ctx* c, const uint8_t* left_rgb, const uint8_t* right_rgb, int w, int h, int stride, int mem, uvo_ctx** L, int* dw, int* dh)
+{
+    if (!left_rgb || !right_rgb) return fail(c, UVO_INVALID_ARG, "uvo_stereo_submit_frames: NULL frame pointer");
+    UVO_TRY(stereo_submit_refusal(c, "uvo_stereo_submit_frames"));
+    (void)hipSetDevice(c->device);
+    return frames_to_lane(c, c->vo_initialized, left_rgb, right_rgb, w, h, stride, mem, L, dw, dh);
+}
 extern "C" uvo_status uvo_stereo_submit_frames(uvo_ctx* c, const uint8_t* left_rgb, const uint8_t* right_rgb, int w, int h, int stride, int mem)
 try {
     if (!c) return UVO_INVALID_ARG;
-    if (!left_rgb || !right_rgb) return fail(c, UVO_INVALID_ARG, "uvo_stereo_submit_frames: NULL frame pointer");
-    // uvo_stereo_submit's own refusals, before anything is queued on a lane
-    if (!c->rig_set) return fail(c, UVO_INVALID_ARG, "uvo_stereo_set_rig has not been called");
-    UVO_TRY(need_loop_table(c));
-    if (c->n_pending >= (int)c->lanes.size()) return fail(c, UVO_INVALID_ARG, "uvo_stereo_submit_frames: the pipeline is full; collect a pair first (uvo_stereo_set_depth)");
-    if (c->timing && c->n_pending > 0) return fail(c, UVO_INVALID_ARG, "timing mode measures one pair at a time: collect before submitting");
-    (void)hipSetDevice(c->device);
-    int dw = 0, dh = 0;
-    UVO_TRY(frames_plan(c, 2, w, h, stride, mem, &dw, &dh));
-    uvo_ctx* L = c->vo_initialized ? static_cast<uvo_ctx*>(c->lanes[c->next_lane]) : c;
-    const uint8_t* rgb[2] = { left_rgb, right_rgb };
-    UVO_TRY(frames_to_lane(c, L, 2, rgb, w, h, stride, mem, dw, dh));
-    FramesEntryScope alone(c);
-    return uvo_stereo_submit(c, L->d_img[0], L->d_img[1], dw, dh, dw, UVO_MEM_DEVICE);
+    uvo_ctx* L = nullptr; int dw = 0, dh = 0;
+    UVO_TRY(stereo_frames_to_lane(c, left_rgb, right_rgb, w, h, stride, mem, &L, &dw, &dh));
+    return stereo_submit_body(c, L->d_img[0], L->d_img[1], dw, dh, dw, UVO_MEM_DEVICE, kFramesEntry);
 } UVO_ABI_CATCH(c)
-
 extern "C" uvo_status uvo_stereo_step_frames(uvo_ctx* c, const uint8_t* left_rgb, const uint8_t* right_rgb, int w, int h, int stride, int mem,
                                              double dt, uvo_stereo_result* out)
 try {
     if (!c) return UVO_INVALID_ARG;
     if (!out) return fail(c, UVO_INVALID_ARG, "uvo_stereo_step_frames: NULL result pointer");
     if (c->n_pending != 0) return fail(c, UVO_INVALID_ARG, "uvo_stereo_step_frames: pairs submitted with uvo_stereo_submit are still in flight");
-    c->in_sync_step = true;
-    const uvo_status st = uvo_stereo_submit_frames(c, left_rgb, right_rgb, w, h, stride, mem);
-    c->in_sync_step = false;
-    UVO_TRY(st);
-    return uvo_stereo_collect(c, dt, out);
+    uvo_ctx* L = nullptr; int dw = 0, dh = 0;
+    UVO_TRY(stereo_frames_to_lane(c, left_rgb, right_rgb, w, h, stride, mem, &L, &dw, &dh));
+    return stereo_step_body(c, L->d_img[0], L->d_img[1], dw, dh, dw, UVO_MEM_DEVICE, dt, out, kFramesEntry);
 } UVO_ABI_CATCH(c)
-
 extern "C" uvo_status uvo_mono_step_frames(uvo_ctx* c, const uint8_t* rgb, int w, int h, int stride, int mem, double range, double dt, uvo_mono_result* out)
 try {
     if (!c) return UVO_INVALID_ARG;
     if (!rgb || !out) return fail(c, UVO_INVALID_ARG, "uvo_mono_step_frames: NULL frame / result pointer");
-    if (!c->mono_cam_set) return fail(c, UVO_INVALID_ARG, "uvo_mono_set_camera has not been called");
-    if (c->mono_pipelined) return fail(c, UVO_INVALID_ARG, "uvo_mono_step after uvo_mono_submit: call uvo_mono_reset first (the previous frame is held by the pipeline)");
-    UVO_TRY(need_loop_table(c));
+    UVO_TRY(mono_step_refusal(c));
     (void)hipSetDevice(c->device);
-    int dw = 0, dh = 0;
-    UVO_TRY(frames_plan(c, 1, w, h, stride, mem, &dw, &dh));
-    UVO_TRY(frames_to_lane(c, c, 1, &rgb, w, h, stride, mem, dw, dh));
-    FramesEntryScope alone(c);
-    return uvo_mono_step(c, c->d_img[0], dw, dh, dw, UVO_MEM_DEVICE, range, dt, out);
+    uvo_ctx* L = nullptr; int dw = 0, dh = 0;
+    UVO_TRY(frames_to_lane(c, false, rgb, nullptr, w, h, stride, mem, &L, &dw, &dh));       // the synchronous step runs on lane 0
+    return mono_step_body(c, L->d_img[0], dw, dh, dw, UVO_MEM_DEVICE, range, dt, out, kFramesEntry);
 } UVO_ABI_CATCH(c)
-
 extern "C" uvo_status uvo_mono_submit_frames(uvo_ctx* c, const uint8_t* rgb, int w, int h, int stride, int mem, double range)
 try {
     if (!c) return UVO_INVALID_ARG;
     if (!rgb) return fail(c, UVO_INVALID_ARG, "uvo_mono_submit_frames: NULL frame pointer");
-    if (!c->mono_cam_set) return fail(c, UVO_INVALID_ARG, "uvo_mono_set_camera has not been called");
-    const int depth = (int)c->lanes.size();
-    if (depth < 2) return fail(c, UVO_INVALID_ARG, "uvo_mono_submit needs at least two lanes (uvo_stereo_set_depth): a frame is matched against the previous lane's buffers");
-    UVO_TRY(need_loop_table(c));
-    if (c->n_pending >= depth) return fail(c, UVO_INVALID_ARG, "uvo_mono_submit_frames: the pipeline is full; collect a frame first (uvo_stereo_set_depth)");
+    UVO_TRY(mono_submit_refusal(c, "uvo_mono_submit_frames"));
     (void)hipSetDevice(c->device);
-    int dw = 0, dh = 0;
-    UVO_TRY(frames_plan(c, 1, w, h, stride, mem, &dw, &dh));
-    uvo_ctx* L = c->mono_initialized ? static_cast<uvo_ctx*>(c->lanes[c->next_lane]) : c;
-    UVO_TRY(frames_to_lane(c, L, 1, &rgb, w, h, stride, mem, dw, dh));
-    FramesEntryScope alone(c);
-    return uvo_mono_submit(c, L->d_img[0], dw, dh, dw, UVO_MEM_DEVICE, range);
+    uvo_ctx* L = nullptr; int dw = 0, dh = 0;
+    UVO_TRY(frames_to_lane(c, c->mono_initialized, rgb, nullptr, w, h, stride, mem, &L, &dw, &dh));
+    return mono_submit_body(c, L->d_img[0], dw, dh, dw, UVO_MEM_DEVICE, range, kFramesEntry);
 } UVO_ABI_CATCH(c)
 
 // ------------------------------------------------------------------------------------------ pipeline trace

@@ -39,6 +39,14 @@ def test_every_extern_c_body_is_guarded():
     assert plain == sorted(["uvo_last_error", "uvo_ctx_stream", "uvo_ctx_warning", "uvo_ctx_pending", "uvo_timing_count", "uvo_timing_name",
                             "uvo_params_default_stereo", "uvo_params_default_mono"]), plain           # (memset + stores)
     assert sum(1 for _, how in defs if how.startswith("try")) == src.count("} UVO_ABI_CATCH") >= 50
+    # No entry is re-entered from inside the library: an extern "C" function that takes the context is named once in ctx.hip's code (strings
+    # and comments apart), where it is defined -- so no extern "C" body, and no static function one of them reaches, calls uvo_*(c, ...), and
+    # a call's checks and its handler run once.  Entries share `static` bodies instead (context-free helpers such as uvo_rodrigues may be called).
+    code = re.sub(r'//[^\n]*', '', re.sub(r'"(?:\\.|[^"\\\n])*"', '""', src))
+    taking_ctx = [name for name, params in re.findall(r'^extern "C" [^;{]*?\b(uvo_\w+)\(([^;{]*?)\)\s*(?:try\s*\{|\{)', src, flags=re.M | re.S) if "uvo_ctx*" in params]
+    assert len(taking_ctx) >= 60
+    reentered = {name: n for name in taking_ctx for n in [len(re.findall(r'\b%s\s*\(' % name, code))] if n != 1}
+    assert not reentered, reentered
     for f in sorted(os.listdir(os.path.join(ROOT, "ergo_uvo_amd", "csrc"))):
         if f.endswith(".hip") and f != "ctx.hip":
             assert 'extern "C"' not in open(os.path.join(ROOT, "ergo_uvo_amd", "csrc", f)).read(), f     # the ABI lives in ctx.hip alone

@@ -355,3 +355,174 @@ def test_refusals_name_their_cause_and_leave_the_context_usable(uvo, node_cams, 
         assert got[0][1] == 0 and got[1][1] == 1 and got[1][0] == 1
     finally:
         c.close()
+
+
+# ------------------------------------------------------------------ the two entries of a step share its body and its refusals
+def test_per_call_options_of_a_frames_entry_do_not_live_in_the_context(uvo, node_cams, scene_small):
+    """Two-pair launches on (stereo_set_batch(2)) and a producer stream declared, frames entries and grey entries interleaved, three
+    pairs in flight.  A frames entry goes alone and does not wait for the producer a second time; the grey entries around it still
+    pair up -- pairs 2, 3 and 7, 8 are two consecutive grey pairs right after a frames pair -- and a grey pair that waits for a
+    partner when a frames pair arrives (pair 5) goes alone.  Every result equals the synchronous run of the same sequence on a fresh
+    context with one pair per launch, field for field (the comparison of test_frames_and_grey_entries_mix_in_one_sequence)."""
+    import torch
+    _, camL, camR = node_cams
+    kinds = "FFGGFGFGG"
+    seq = [scene_small[0]] + [scene_small[1 + k % 2] for k in range(len(kinds) - 1)]
+    pre = uvo.Context(uvo.Params.stereo(), 0, 640, 360, 8192)
+    want_c = _stereo_ctx(uvo, node_cams)
+    c = _stereo_ctx(uvo, node_cams, depth=3)
+    producer = torch.cuda.Stream()
+    try:
+        grey = [None if k == "F" else (pre.get_image(_gray3(L), 640, *camL, True, 8, device_out=True),
+                                       pre.get_image(_gray3(R), 640, *camR, True, 8, device_out=True)) for k, (L, R) in zip(kinds, seq)]
+        want = [_fields(want_c.stereo_step_frames(_gray3(L), _gray3(R), 0.05) if g is None else want_c.stereo_step(*g, 0.05))
+                for g, (L, R) in zip(grey, seq)]
+        assert sum(f[0] for f in want) >= 4, "the compared runs hold too few valid estimates"
+        with torch.cuda.stream(producer):                                # the frames entries' inputs are produced on the declared stream
+            frames = [None if k == "G" else (torch.from_numpy(_gray3(L)).cuda(), torch.from_numpy(_gray3(R)).cuda()) for k, (L, R) in zip(kinds, seq)]
+        c.stereo_set_batch(2)
+        c.set_producer_stream(producer)
+        got, sub = [], 0
+        for i in range(len(seq)):
+            while sub < len(seq) and sub - i < 3:
+                if grey[sub] is None:
+                    c.stereo_submit_frames(*frames[sub])
+                else:
+                    c.stereo_submit(*grey[sub])
+                sub += 1
+            got.append(_fields(c.stereo_collect(0.05)))
+        assert got == want
+    finally:
+        c.close(); want_c.close(); pre.close()
+
+
+# uvo_last_error after each refusal of a loop step, through the grey-image entry and through the frames entry: the literal strings of
+# ctx.hip / orb.hip at the commit before the entries were put over shared bodies (never read from the library under test)
+_RIG = "uvo_stereo_set_rig has not been called"
+_CAM = "uvo_mono_set_camera has not been called"
+_TABLE = ("ORB in the fused steps: the descriptors need the sampling table -- OpenCV's bit_pattern_31_ (orb.cpp), 256 x (x0, y0, x1, y1) -- "
+          "through uvo_orb_set_pattern")
+_TIMING = "timing mode measures one pair at a time: collect before submitting"
+_PIPELINED = "uvo_mono_step after uvo_mono_submit: call uvo_mono_reset first (the previous frame is held by the pipeline)"
+_TWO_LANES = "uvo_mono_submit needs at least two lanes (uvo_stereo_set_depth): a frame is matched against the previous lane's buffers"
+REFUSALS = {
+    ("stereo_submit", "rig"): _RIG, ("stereo_submit_frames", "rig"): _RIG,
+    ("stereo_submit", "table"): _TABLE, ("stereo_submit_frames", "table"): _TABLE,
+    ("stereo_submit", "full"): "uvo_stereo_submit: the pipeline is full; collect a pair first (uvo_stereo_set_depth)",
+    ("stereo_submit_frames", "full"): "uvo_stereo_submit_frames: the pipeline is full; collect a pair first (uvo_stereo_set_depth)",
+    ("stereo_submit", "timing"): _TIMING, ("stereo_submit_frames", "timing"): _TIMING,
+    ("stereo_step", "in flight"): "uvo_stereo_step: pairs submitted with uvo_stereo_submit are still in flight",
+    ("stereo_step_frames", "in flight"): "uvo_stereo_step_frames: pairs submitted with uvo_stereo_submit are still in flight",
+    ("stereo_step", "rig"): _RIG, ("stereo_step_frames", "rig"): _RIG,
+    ("stereo_step", "table"): _TABLE, ("stereo_step_frames", "table"): _TABLE,
+    ("mono_step", "camera"): _CAM, ("mono_step_frames", "camera"): _CAM,
+    ("mono_step", "pipelined"): _PIPELINED, ("mono_step_frames", "pipelined"): _PIPELINED,
+    ("mono_step", "table"): _TABLE, ("mono_step_frames", "table"): _TABLE,
+    ("mono_submit", "camera"): _CAM, ("mono_submit_frames", "camera"): _CAM,
+    ("mono_submit", "two lanes"): _TWO_LANES, ("mono_submit_frames", "two lanes"): _TWO_LANES,
+    ("mono_submit", "table"): _TABLE, ("mono_submit_frames", "table"): _TABLE,
+    ("mono_submit", "full"): "uvo_mono_submit: the pipeline is full; collect a frame first (uvo_stereo_set_depth)",
+    ("mono_submit_frames", "full"): "uvo_mono_submit_frames: the pipeline is full; collect a frame first (uvo_stereo_set_depth)",
+}
+
+
+@pytest.fixture(scope="module")
+def refusal_ctxs(uvo, node_cams):
+    """(a stereo context with its rig but no mono camera, a mono context with its camera but no rig); both know the frames' cameras"""
+    rig, camL, camR = node_cams
+    s = uvo.Context(uvo.Params.stereo(SURF_MIN_HESSIAN=1500), 0, 640, 360, 8192)
+    m = uvo.Context(uvo.Params.mono(SURF_MIN_HESSIAN=400, ESSENTIAL_OUTLIER_METHOD=8, HOMOGRAPHY_OUTLIER_METHOD=8, REPROJECTION_TOLERANCE=3.0,
+                                    ESSENTIAL_THRESHOLD=1.0, HOMOGRAPHY_THRESHOLD=1.0), 0, 640, 360, 8192)
+    for c in (s, m):
+        c.set_camera(0, *camL, 640, True, 8)
+        c.set_camera(1, *camR, 640, True, 8)
+    s.stereo_set_rig(camL[2], camR[2], rig.R_right, rig.t_right)
+    m.mono_set_camera(camL[2])
+    yield s, m
+    s.close(); m.close()
+
+
+@pytest.mark.parametrize("loop", ["stereo", "mono"])
+def test_both_entries_of_a_step_refuse_in_the_parents_words(uvo, refusal_ctxs, scene_small, mono_small, loop):
+    """Every refusal of every loop step, provoked through the grey-image entry and through the frames entry: uvo_last_error is REFUSALS'
+    string byte for byte, and the context completes an ordinary step afterwards.  Argument and state refusals only."""
+    s, m = refusal_ctxs
+    g, f = scene_small[0], (_gray3(scene_small[0][0]), _gray3(scene_small[0][1]))
+    mg, mf = mono_small[0], _gray3(mono_small[0])
+    entries = {                                    # entry -> (context -> the call)
+        "stereo_submit": lambda c: c.stereo_submit(*g), "stereo_submit_frames": lambda c: c.stereo_submit_frames(*f),
+        "stereo_step": lambda c: c.stereo_step(*g, 0.05), "stereo_step_frames": lambda c: c.stereo_step_frames(*f, 0.05),
+        "mono_submit": lambda c: c.mono_submit(mg, 4.0), "mono_submit_frames": lambda c: c.mono_submit_frames(mf, 4.0),
+        "mono_step": lambda c: c.mono_step(mg, 4.0, 0.2), "mono_step_frames": lambda c: c.mono_step_frames(mf, 4.0, 0.2),
+    }
+    seen = set()
+
+    def idle(c):
+        c.stereo_reset(); c.mono_reset()           # whatever is in flight is dropped
+        assert c._lib.uvo_ctx_pending(c._h) == 0
+
+    def stereo_works():
+        idle(s)
+        assert s.stereo_step(*g, 0.05).n_left > 100
+
+    def mono_works():
+        idle(m)
+        assert m.mono_step(mg, 4.0, 0.2).n_kps > 100
+
+    def refused(c, entry, cause, works):
+        with pytest.raises(uvo.UvoError):
+            entries[entry](c)
+        assert (c._lib.uvo_last_error(c._h) or b"").decode() == REFUSALS[(entry, cause)], (entry, cause)
+        seen.add((entry, cause))
+        works()
+
+    def without_table(c, entry, works):
+        idle(c)
+        c.set_feature_detector("ORB")              # ... and no uvo_orb_set_pattern
+        try:
+            refused(c, entry, "table", lambda: None)
+        finally:
+            c.set_feature_detector("SURF")
+        works()
+
+    if loop == "stereo":
+        for step in ("stereo_submit", "stereo_step"):
+            for entry in (step, step + "_frames"):
+                refused(m, entry, "rig", mono_works)                     # the mono context has no rig
+                without_table(s, entry, stereo_works)
+        for entry in ("stereo_submit", "stereo_submit_frames"):
+            idle(s)
+            entries[entry](s); entries[entry](s)                         # depth 2: an init pair and a pipelined one
+            refused(s, entry, "full", stereo_works)
+            idle(s)
+            s.timing_enable(True)
+            try:
+                entries[entry](s)
+                refused(s, entry, "timing", stereo_works)                # (a synchronous step is what timing mode measures)
+            finally:
+                s.timing_enable(False)
+        for entry in ("stereo_step", "stereo_step_frames"):
+            idle(s)
+            s.stereo_submit(*g)
+            refused(s, entry, "in flight", stereo_works)
+    else:
+        for step in ("mono_submit", "mono_step"):
+            for entry in (step, step + "_frames"):
+                refused(s, entry, "camera", stereo_works)                # the stereo context has no mono camera
+                without_table(m, entry, mono_works)
+        for entry in ("mono_submit", "mono_submit_frames"):
+            idle(m)
+            m.stereo_set_depth(1)
+            try:
+                refused(m, entry, "two lanes", mono_works)
+            finally:
+                m.stereo_set_depth(2)
+            idle(m)
+            entries[entry](m); entries[entry](m)                         # depth 2: an init frame and a pipelined one
+            refused(m, entry, "full", mono_works)
+        for entry in ("mono_step", "mono_step_frames"):
+            idle(m)
+            m.mono_submit(mg, 4.0); m.mono_submit(mono_small[1], 4.0)
+            m.mono_collect(0.2); m.mono_collect(0.2)                     # nothing in flight, but the previous frame lives in a lane
+            refused(m, entry, "pipelined", mono_works)
+    assert seen == {k for k in REFUSALS if k[0].startswith(loop)}
