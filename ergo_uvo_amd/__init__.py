@@ -582,6 +582,69 @@ class Context:
         self._check(self._lib.uvo_decode_image(self._h, _p(buf), len(buf), fmt.encode(), dst, nb, omem, C.byref(w), C.byref(h), C.byref(ch)))
         return out
 
+    # ------------------------------------------------------------------ compressed frames into the loops (uvo_*_compressed)
+    class _Compressed(C.Structure):
+        _fields_ = [("data", C.c_void_p), ("n", C.c_size_t), ("format", C.c_char_p)]
+
+    @classmethod
+    def _compressed(cls, data, fmt):
+        """(uvo_compressed_image, keepalive) of a payload: bytes-like, or a writable uint8 numpy array (read in place)."""
+        buf = data if isinstance(data, np.ndarray) else np.frombuffer(data, np.uint8)
+        if buf.dtype != np.uint8 or buf.ndim != 1 or not buf.flags.c_contiguous:
+            raise ValueError("a compressed payload is a contiguous run of bytes")
+        f = fmt.encode()
+        return cls._Compressed(buf.ctypes.data, buf.size, f), (buf, f)
+
+    def set_jpeg_entropy(self, where: int):
+        """Where decode_image decodes JPEG Huffman streams: 0 host (default), 1 device.  The compressed entries always use the device."""
+        self._check(self._lib.uvo_ctx_set_jpeg_entropy(self._h, int(where)))
+
+    def stereo_step_compressed(self, left, right, dt: float = 0.05, fmt: str = "bgr8; jpeg compressed bgr8") -> StereoResult:
+        """stereo_step_frames on the payloads of two compressed-image messages, decoded on the device in front of get_image."""
+        a, ka = self._compressed(left, fmt)
+        b, kb = self._compressed(right, fmt)
+        r = StereoResult()
+        self._check(self._lib.uvo_stereo_step_compressed(self._h, C.byref(a), C.byref(b), C.c_double(dt), C.byref(r)))
+        return r
+
+    def stereo_submit_compressed(self, left, right, fmt: str = "bgr8; jpeg compressed bgr8"):
+        """stereo_submit_frames on two payloads (collect with stereo_collect).  The payloads are consumed before this returns."""
+        a, ka = self._compressed(left, fmt)
+        b, kb = self._compressed(right, fmt)
+        self._check(self._lib.uvo_stereo_submit_compressed(self._h, C.byref(a), C.byref(b)))
+        self._inflight.append(())
+
+    def mono_step_compressed(self, data, range_=1.0, dt: float = 0.05, fmt: str = "bgr8; jpeg compressed bgr8") -> MonoResult:
+        a, ka = self._compressed(data, fmt)
+        r = MonoResult()
+        self._check(self._lib.uvo_mono_step_compressed(self._h, C.byref(a), C.c_double(range_), C.c_double(dt), C.byref(r)))
+        return r
+
+    def mono_submit_compressed(self, data, range_=1.0, fmt: str = "bgr8; jpeg compressed bgr8"):
+        """mono_submit_frames on a payload (collect with mono_collect).  The payload is consumed before this returns."""
+        a, ka = self._compressed(data, fmt)
+        self._check(self._lib.uvo_mono_submit_compressed(self._h, C.byref(a), C.c_double(range_)))
+        self._inflight.append(())
+
+    def jpeg_coefficients(self, data, where: int = 1, sub_words: int = 0):
+        """Test hook: the coefficient buffer of the host (where=0) or device (where=1) JPEG entropy decoder, int16."""
+        buf = np.frombuffer(data, np.uint8)
+        n = C.c_size_t(0)
+        out = np.empty(1 << 16, np.int16)
+        st = self._lib.uvo_jpeg_coefficients(self._h, _p(buf), buf.size, int(where), int(sub_words), _p(out), out.size, C.byref(n))
+        if st == 3 and n.value > out.size:
+            out = np.empty(n.value, np.int16)
+            st = self._lib.uvo_jpeg_coefficients(self._h, _p(buf), buf.size, int(where), int(sub_words), _p(out), out.size, C.byref(n))
+        self._check(st)
+        return out[:n.value].copy()
+
+    def jpeg_entropy_stats(self) -> dict:
+        """Figures of the last device entropy decode on lane 0 (decode_image with set_jpeg_entropy(1), or jpeg_coefficients)."""
+        v = [C.c_int(0) for _ in range(4)]
+        nb = C.c_size_t(0)
+        self._check(self._lib.uvo_jpeg_entropy_stats(self._h, C.byref(v[0]), C.byref(v[1]), C.byref(v[2]), C.byref(v[3]), C.byref(nb)))
+        return dict(n_sub=v[0].value, n_groups=v[1].value, rounds_in_group=v[2].value, rounds_across=v[3].value, scan_bytes=nb.value)
+
     def bayer_bggr2bgr(self, bayer):
         h, w = bayer.shape
         p, mem, keep = _ptr_mem(bayer, np.uint8)

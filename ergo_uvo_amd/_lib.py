@@ -23,6 +23,8 @@ EXPORTS = [
     "uvo_recover_pose_homography", "uvo_select_estimation_method", "uvo_estimate_relative_pose", "uvo_mono_set_camera",
     "uvo_mono_reset", "uvo_mono_step", "uvo_mono_submit", "uvo_mono_collect", "uvo_mono_get", "uvo_get_image",
     "uvo_ctx_set_camera", "uvo_stereo_step_frames", "uvo_stereo_submit_frames", "uvo_mono_step_frames", "uvo_mono_submit_frames",
+    "uvo_ctx_set_jpeg_entropy", "uvo_stereo_step_compressed", "uvo_stereo_submit_compressed", "uvo_mono_step_compressed", "uvo_mono_submit_compressed",
+    "uvo_jpeg_coefficients", "uvo_jpeg_entropy_stats",
     "uvo_decode_image", "uvo_bayer_bggr2bgr", "uvo_resize_camera_matrix", "uvo_timing_enable", "uvo_timing_count", "uvo_timing_name", "uvo_timing_get", "uvo_timing_reset", "uvo_trace_enable", "uvo_trace_read",
 ]
 
@@ -66,6 +68,13 @@ def lib() -> C.CDLL:
         _lib.uvo_ctx_host_policy.argtypes = [C.c_void_p]
         _lib.uvo_ctx_set_producer_stream.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         _lib.uvo_decode_image.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_char_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.uvo_ctx_set_jpeg_entropy.argtypes = [C.c_void_p, C.c_int]
+        _lib.uvo_stereo_step_compressed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]
+        _lib.uvo_stereo_submit_compressed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.uvo_mono_step_compressed.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p]
+        _lib.uvo_mono_submit_compressed.argtypes = [C.c_void_p, C.c_void_p, C.c_double]
+        _lib.uvo_jpeg_coefficients.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
+        _lib.uvo_jpeg_entropy_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.uvo_sift_detect.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         _lib.uvo_ctx_set_feature_detector.argtypes = [C.c_void_p, C.c_char_p]
         _lib.uvo_ctx_set_loop_detector.argtypes = [C.c_void_p, C.c_char_p]

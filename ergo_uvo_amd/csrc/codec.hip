@@ -2,9 +2,11 @@
 // (uvo_libraries/src/math_utility.cpp:154-173): cv_bridge::toCvCopy(CompressedImage) = cv::imdecode -> libjpeg, then
 // cv::cvtColor(COLOR_BayerBGGR2BGR) when the format string says "bayer".
 //
-// A JPEG bit stream is sequential by construction (variable-length codes, DC prediction), so the entropy decoding runs on
-// the host -- one pass over the compressed bytes into a pinned coefficient buffer -- and everything that is per-block or
-// per-pixel runs on the device, HBM-bound byte work with coalesced accesses:
+// uvo_decode_image's default entropy decoder runs on the host -- one sequential pass over the compressed bytes into a pinned
+// coefficient buffer (variable-length codes, DC prediction).  The compressed loop entries, and uvo_decode_image after
+// uvo_ctx_set_jpeg_entropy(c, 1), decode the Huffman stream on the device instead: Huffman streams self-synchronise, so subsequences
+// are decoded in parallel and stitched (the k_jh_* kernels below, uvo_jhuff.h).  Everything that is per-block or per-pixel runs on
+// the device, HBM-bound byte work with coalesced accesses:
 //   k_jpeg_idct    one thread per 8 x 8 block: dequantisation + libjpeg's jpeg_idct_islow (JDCT_ISLOW, libjpeg's and
 //                  cv::imdecode's default), the block's 64 samples written to the component plane
 //   k_jpeg_colour  one thread per pixel: libjpeg's fancy (triangle) chroma upsampling evaluated at the pixel from the
@@ -17,6 +19,7 @@
 // (uvo_png.h), k_png_expand on the device: 1 / 2 / 4 / 8-bit grey, palette and RGB(A) samples -> grey / B G R (A) bytes.
 #include "uvo_ctx.h"
 #include "uvo_png.h"
+#include "uvo_jhuff.h"
 #include <string.h>
 #include <vector>
 
@@ -109,12 +112,15 @@ struct CodecWs {
     uint8_t* d_out = nullptr; size_t out_cap = 0;                                      // decoded image (and the Bayer source)
     uint8_t* d_out2 = nullptr; size_t out2_cap = 0;                                    // demosaiced image
     uint16_t* d_quant = nullptr;                                                       // 4 x 64
+    void* jh = nullptr;                                                                // JhWs*: the device entropy decoder's workspaces
 };
+static void jh_ws_free(CodecWs* w);
 
 void codec_ws_free(Ctx* c)
 {
     CodecWs* w = static_cast<CodecWs*>(c->codec_ws);
     if (!w) return;
+    jh_ws_free(w);
     (void)hipHostFree(w->h_coef); (void)hipFree(w->d_coef); (void)hipFree(w->d_planes); (void)hipFree(w->d_out); (void)hipFree(w->d_out2); (void)hipFree(w->d_quant);
     delete w;
     c->codec_ws = nullptr;
@@ -134,7 +140,8 @@ static uvo_status grow(Ctx* c, void** p, size_t* cap, size_t need, bool pinned)
 // blocks in raster order of the MCU-padded component).  Host only.
 // headers_only: stop at the first scan header, after every check of the frame, table and scan headers (the size query of
 // uvo_decode_image): nothing is allocated and no coefficient is decoded.
-static uvo_status jpeg_entropy_decode(Ctx* c, CodecWs* ws, const uint8_t* data, size_t n, Jpeg* j, bool headers_only = false)
+// scan_off (with headers_only): where the first scan's entropy-coded bytes begin
+static uvo_status jpeg_entropy_decode(Ctx* c, CodecWs* ws, const uint8_t* data, size_t n, Jpeg* j, bool headers_only = false, size_t* scan_off = nullptr)
 {
     auto bad = [&](const char* m) { c->err = std::string("JPEG: ") + m; return UVO_INVALID_ARG; };
     if (n < 4 || data[0] != 0xFF || data[1] != 0xD8) return bad("not a JPEG stream (no SOI)");
@@ -214,7 +221,7 @@ static uvo_status jpeg_entropy_decode(Ctx* c, CodecWs* ws, const uint8_t* data, 
                     if (j->comp[k].id == s[1 + 2 * i]) { j->comp[k].td = s[2 + 2 * i] >> 4; j->comp[k].ta = s[2 + 2 * i] & 15; }
             for (int k = 0; k < j->ncomp; k++) if (j->comp[k].td > 3 || j->comp[k].ta > 3 || !j->dc[j->comp[k].td].present || !j->ac[j->comp[k].ta].present) return bad("scan refers to a missing Huffman table");
             for (int k = 0; k < j->ncomp; k++) if (!j->dc[j->comp[k].td].dc_symbols_ok()) return bad("bad DC Huffman table (category above 15)");
-            if (headers_only) return UVO_OK;
+            if (headers_only) { if (scan_off) *scan_off = pos + len; return UVO_OK; }
             BitReader b; b.p = data + pos + len; b.end = data + n;
             int left = j->restart;
             for (int my = 0; my < j->mcuy; my++)
@@ -388,6 +395,452 @@ __global__ __launch_bounds__(256) void k_bayer_bggr(const uint8_t* __restrict__ 
     o[0] = (uint8_t)B; o[1] = (uint8_t)G; o[2] = (uint8_t)R;
 }
 
+// ------------------------------------------------------------------------------------------ entropy decoding on the device
+// The scheme of uvo_jhuff.h as four launches on the lane's stream, every grid-wide seam a kernel boundary (no workgroup waits for another):
+//   k_jh_pass1  one thread per subsequence, kJhGroup subsequences per workgroup: decode from (first bit, 0, 0), then again from the
+//               left neighbour's exit state until no state in the workgroup changes (at most kJhGroup - 1 rounds: after k rounds the
+//               first k subsequences behind a final one are final)
+//   k_jh_cross  ONE workgroup, one thread per workgroup boundary: a boundary whose incoming state differs from the state its group
+//               was decoded from walks that group until a subsequence's entry state agrees again; rounds until nothing changes (at
+//               most the number of boundaries).  Then the segmented exclusive scan of the slot counts: every subsequence's first slot
+//   k_jh_emit   one thread per subsequence: decode from the final entry state and scatter the DC differences and AC coefficients
+//   k_jh_dc     one workgroup per component: DC differences -> DC values, a scan over the component's blocks in scan order,
+//               segmented at restart intervals, modulo 2^32 and narrowed to int16 as the host decoder does
+// The Huffman tables are copied to LDS by every workgroup that decodes.  Reads of the staged scan are clamped to its zero padding
+// (jhuff::peek32), writes of coefficients are tested against the interval's and the picture's slots, every loop has a trip bound.
+constexpr int kJhGroup = 256;
+constexpr int kJhWide = 1024;
+__device__ const uint8_t kNaturalDev[64] = { 0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
+                                             35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63 };
+struct JhBufs {
+    const jhuff::Table* tabs; int n_tabs;
+    const uint8_t* scan; const uint32_t* info;
+    jhuff::State* entry; jhuff::State* exit; jhuff::State* incoming;     // per subsequence, per subsequence, per workgroup
+    uint32_t* slots; uint32_t* first;
+    int* stats;                                                          // [0] rounds inside a workgroup (maximum), [1] rounds across
+};
+
+__device__ __forceinline__ void jh_tables_to_lds(jhuff::Table* dst, const jhuff::Table* src, int n_tabs)
+{
+    const int words = n_tabs * (int)(sizeof(jhuff::Table) / 4);
+    static_assert(sizeof(jhuff::Table) % 4 == 0, "tables are copied as words");
+    for (int i = threadIdx.x; i < words; i += blockDim.x) reinterpret_cast<uint32_t*>(dst)[i] = reinterpret_cast<const uint32_t*>(src)[i];
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(kJhGroup) void k_jh_pass1(jhuff::Scan s, JhBufs b)
+{
+    __shared__ jhuff::Table tabs[jhuff::kMaxTables];
+    __shared__ jhuff::State s_exit[kJhGroup];
+    jh_tables_to_lds(tabs, b.tabs, b.n_tabs);
+    const int tid = threadIdx.x;
+    const uint32_t i = blockIdx.x * kJhGroup + tid, sub_bits = s.sub_words * 32;
+    const bool live = i < s.n_sub;
+    const bool fixed = !live || tid == 0 || (b.info[i] & 1);             // a workgroup's first subsequence is k_jh_cross's
+    jhuff::State in = { i * sub_bits, 0 }, out = in;
+    uint32_t sl = 0;
+    if (live) sl = jhuff::decode_span(tabs, s, b.scan, &out, (i + 1) * sub_bits, jhuff::NoEmit());
+    s_exit[tid] = out;
+    __syncthreads();
+    int rounds = 0;
+    for (int r = 0; r < kJhGroup - 1; r++) {
+        jhuff::State prev = in;
+        if (!fixed) prev = s_exit[tid - 1];
+        const int changed = !jhuff::same(prev, in);
+        if (!__syncthreads_or(changed)) break;                           // (every thread has read its neighbour before any writes)
+        rounds++;
+        if (changed) { in = prev; out = in; sl = jhuff::decode_span(tabs, s, b.scan, &out, (i + 1) * sub_bits, jhuff::NoEmit()); s_exit[tid] = out; }
+        __syncthreads();
+    }
+    if (live) { b.entry[i] = in; b.exit[i] = out; b.slots[i] = sl; }
+    if (tid == 0) atomicMax(&b.stats[0], rounds);
+}
+
+// inclusive scan over the workgroup's (flag, value) pairs with the segmented sum: a flagged right operand replaces, else it adds
+__device__ __forceinline__ void jh_seg_scan(uint32_t* s_val, uint32_t* s_flag, uint32_t& val, uint32_t& flag)
+{
+    const int tid = threadIdx.x;
+    s_val[tid] = val; s_flag[tid] = flag;
+    __syncthreads();
+    for (int o = 1; o < kJhWide; o <<= 1) {
+        uint32_t lv = 0, lf = 0;
+        if (tid >= o) { lv = s_val[tid - o]; lf = s_flag[tid - o]; }
+        __syncthreads();
+        if (tid >= o && !flag) { val += lv; flag = lf; }
+        s_val[tid] = val; s_flag[tid] = flag;
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(kJhWide) void k_jh_cross(jhuff::Scan s, JhBufs b, uint32_t n_groups)
+{
+    __shared__ jhuff::Table tabs[jhuff::kMaxTables];
+    __shared__ uint32_t s_val[kJhWide], s_flag[kJhWide];
+    jh_tables_to_lds(tabs, b.tabs, b.n_tabs);
+    const uint32_t tid = threadIdx.x, sub_bits = s.sub_words * 32;
+    int rounds = 0;
+    for (uint32_t r = 0; r < n_groups; r++) {                            // (n_groups - 1 boundaries; the last round finds nothing)
+        int changed = 0;
+        for (uint32_t g = 1 + tid; g < n_groups; g += kJhWide) b.incoming[g] = b.exit[g * kJhGroup - 1];
+        __syncthreads();
+        for (uint32_t g = 1 + tid; g < n_groups; g += kJhWide) {
+            const uint32_t i0 = g * kJhGroup, i1 = i0 + kJhGroup < s.n_sub ? i0 + kJhGroup : s.n_sub;
+            if (b.info[i0] & 1) continue;                                // a restart interval begins here: in step from its first bit
+            jhuff::State cur = b.incoming[g];
+            if (jhuff::same(cur, b.entry[i0])) continue;
+            changed = 1;
+            for (uint32_t i = i0; i < i1; i++) {
+                if (i > i0 && ((b.info[i] & 1) || jhuff::same(cur, b.entry[i]))) break;      // from here on the group already follows
+                b.entry[i] = cur;
+                b.slots[i] = jhuff::decode_span(tabs, s, b.scan, &cur, (i + 1) * sub_bits, jhuff::NoEmit());
+                b.exit[i] = cur;
+            }
+        }
+        if (!__syncthreads_or(changed)) break;
+        rounds++;
+    }
+    if (tid == 0) b.stats[1] = rounds;
+    // first slot of every subsequence: its interval's first slot at an interval's start, else the predecessor's first + slots
+    const uint32_t per = (s.n_sub + kJhWide - 1) / kJhWide, a = tid * per, e = a + per < s.n_sub ? a + per : s.n_sub;
+    const uint32_t iv_slots = s.iv_mcus * s.bpm * 64;
+    uint32_t val = 0, flag = 0;
+    for (uint32_t i = a; i < e; i++) {
+        const uint32_t inf = b.info[i];
+        if (inf & 1) { flag = 1; val = (inf >> 1) * iv_slots; }
+        val += b.slots[i];
+    }
+    jh_seg_scan(s_val, s_flag, val, flag);
+    uint32_t cur = tid ? s_val[tid - 1] : 0;
+    for (uint32_t i = a; i < e; i++) {
+        const uint32_t inf = b.info[i];
+        if (inf & 1) cur = (inf >> 1) * iv_slots;
+        b.first[i] = cur;
+        cur += b.slots[i];
+    }
+}
+
+__global__ __launch_bounds__(kJhGroup) void k_jh_emit(jhuff::Scan s, JhBufs b, int16_t* __restrict__ coef)
+{
+    __shared__ jhuff::Table tabs[jhuff::kMaxTables];
+    jh_tables_to_lds(tabs, b.tabs, b.n_tabs);
+    const uint32_t i = blockIdx.x * kJhGroup + threadIdx.x;
+    if (i >= s.n_sub) return;
+    jhuff::State st = b.entry[i];
+    const uint32_t first = b.first[i];
+    const unsigned long long total_slots = (unsigned long long)s.total_blocks * 64, iv_end = ((unsigned long long)(b.info[i] >> 1) + 1) * s.iv_mcus * s.bpm * 64;
+    const unsigned long long slot_end = iv_end < total_slots ? iv_end : total_slots;       // slots at or beyond it are dropped
+    const size_t n_coef = (size_t)s.total_blocks * 64;
+    (void)jhuff::decode_span(tabs, s, b.scan, &st, (i + 1) * s.sub_words * 32, [&](uint32_t rel, int v) {
+        const uint32_t slot = first + rel;
+        if (slot >= slot_end) return;
+        const size_t idx = jhuff::slot_block(s, slot >> 6) * 64 + kNaturalDev[slot & 63];
+        if (idx < n_coef) coef[idx] = (int16_t)v;
+    });
+}
+
+// component k = blockIdx.x: element e of its scan order is block (e % hv) of MCU e / hv; a segment begins every iv_mcus * hv elements
+__global__ __launch_bounds__(kJhWide) void k_jh_dc(jhuff::Scan s, int16_t* __restrict__ coef)
+{
+    __shared__ uint32_t s_val[kJhWide], s_flag[kJhWide];
+    const uint32_t k = blockIdx.x, tid = threadIdx.x;
+    const uint32_t h = s.comp_h[k], hv = h * s.comp_v[k], n = s.total_mcus * hv, seg = s.iv_mcus * hv;
+    const uint32_t per = (n + kJhWide - 1) / kJhWide, a = tid * per, e = a + per < n ? a + per : n;
+    const size_t n_coef = (size_t)s.total_blocks * 64;
+    auto at = [&](uint32_t el) -> size_t {
+        const uint32_t mcu = el / hv, j = el - mcu * hv, by = j / h, bx = j - by * h, my = mcu / s.mcux, mx = mcu - my * s.mcux;
+        const size_t idx = ((size_t)s.comp_off[k] + (size_t)(my * s.comp_v[k] + by) * s.comp_bw[k] + (mx * h + bx)) * 64;
+        return idx < n_coef ? idx : n_coef;                              // (n_coef: outside the buffer -- read as zero, never written)
+    };
+    uint32_t val = 0, flag = 0;
+    for (uint32_t el = a; el < e; el++) {
+        if (el % seg == 0) { flag = 1; val = 0; }
+        const size_t idx = at(el);
+        val += idx < n_coef ? (uint32_t)(int)coef[idx] : 0u;
+    }
+    jh_seg_scan(s_val, s_flag, val, flag);
+    uint32_t cur = tid ? s_val[tid - 1] : 0;
+    for (uint32_t el = a; el < e; el++) {
+        if (el % seg == 0) cur = 0;
+        const size_t idx = at(el);
+        if (idx >= n_coef) continue;
+        cur += (uint32_t)(int)coef[idx];
+        coef[idx] = (int16_t)(int)cur;
+    }
+}
+
+// ---- host side of the device entropy decoder
+// One image's workspace.  A stereo entry decodes two images on one lane, so a lane has two; uvo_decode_image uses lane 0's first.
+// The pinned block h_stage holds what the kernels read besides their by-value arguments -- the Huffman tables, the quantisation
+// tables, the staged scan -- and is uploaded once; h_info holds the subsequences' interval words.  Nothing is copied from a stack frame.
+struct JhSlot {
+    uint8_t* h_stage = nullptr; uint8_t* d_stage = nullptr; size_t h_stage_cap = 0, d_stage_cap = 0;
+    uint32_t* h_info = nullptr; size_t h_info_cap = 0;
+    uint8_t* d_sub = nullptr; size_t d_sub_cap = 0;
+    int16_t* d_coef = nullptr; size_t coef_cap = 0;
+    uint8_t* d_planes = nullptr; size_t planes_cap = 0;
+    uint8_t* d_out = nullptr; size_t out_cap = 0;
+    uint8_t* d_out2 = nullptr; size_t out2_cap = 0;
+    int* h_stats = nullptr;                                            // pinned: rounds in group, rounds across (of the last decode with stats)
+    int n_sub = 0, n_groups = 0; size_t scan_bytes = 0; bool have_stats = false;
+};
+constexpr size_t kJhTabBytes = sizeof(jhuff::Table) * jhuff::kMaxTables, kJhQuantBytes = 4 * 64 * sizeof(uint16_t), kJhHeadBytes = (kJhTabBytes + kJhQuantBytes + 15) / 16 * 16;
+constexpr int kJhDefaultSubWords = 32;
+struct JhNeed { size_t stage = 0, subs = 0, coef = 0, planes = 0, out = 0, out2 = 0; };
+// a parsed payload between the entry's checks (nothing queued yet) and its decode
+struct JhJob { Jpeg j; const uint8_t* scan = nullptr; size_t scan_n = 0; int bayer = 0, sub_words = kJhDefaultSubWords; jhuff::Scan s; jhuff::Table tabs[jhuff::kMaxTables]; int n_tabs = 0; JhNeed need; };
+struct JhWs { JhSlot slot[2]; JhJob job[2]; int where = 0; };
+
+static size_t jh_sub_bytes(size_t subs) { const size_t groups = (subs + kJhGroup - 1) / kJhGroup; return subs * (2 * sizeof(jhuff::State) + 3 * sizeof(uint32_t)) + groups * sizeof(jhuff::State) + 64; }
+
+static JhWs* jh_ws(Ctx* c)
+{
+    if (!c->codec_ws) c->codec_ws = new CodecWs();
+    CodecWs* ws = static_cast<CodecWs*>(c->codec_ws);
+    if (!ws->jh) ws->jh = new JhWs();
+    return static_cast<JhWs*>(ws->jh);
+}
+static void jh_ws_free(CodecWs* w)
+{
+    JhWs* q = static_cast<JhWs*>(w->jh);
+    if (!q) return;
+    for (JhSlot& s : q->slot) {
+        (void)hipHostFree(s.h_stage); (void)hipHostFree(s.h_info); (void)hipHostFree(s.h_stats);
+        (void)hipFree(s.d_stage); (void)hipFree(s.d_sub); (void)hipFree(s.d_coef); (void)hipFree(s.d_planes); (void)hipFree(s.d_out); (void)hipFree(s.d_out2);
+    }
+    delete q;
+    w->jh = nullptr;
+}
+
+// headers -> job: the scan's layout, its compacted tables and what a workspace must hold.  Refuses what the host JPEG path refuses.
+static uvo_status jh_prepare(Ctx* m, const uint8_t* data, size_t n, int bayer, int sub_words, JhJob* job)
+{
+    Jpeg& j = job->j;
+    j = Jpeg();
+    memset(j.quant, 0, sizeof(j.quant));
+    size_t off = 0;
+    UVO_TRY(jpeg_entropy_decode(m, nullptr, data, n, &j, true, &off));
+    if (bayer && j.ncomp != 1) { m->err = "a bayer-format message must decode to one channel"; return UVO_INVALID_ARG; }
+    if (sub_words <= 0) sub_words = kJhDefaultSubWords;
+    if (sub_words > 4096) { m->err = "JPEG: sub_words is 1 .. 4096"; return UVO_INVALID_ARG; }
+    if (n - off > ((size_t)1 << 27)) { m->err = "JPEG: scans above 128 MB are refused (bit positions are 32-bit)"; return UVO_INVALID_ARG; }
+    job->scan = data + off; job->scan_n = n - off; job->bayer = bayer; job->sub_words = sub_words;
+    int map_dc[4] = {-1, -1, -1, -1}, map_ac[4] = {-1, -1, -1, -1}, h[3], v[3], tdc[3], tac[3];
+    job->n_tabs = 0;
+    for (int k = 0; k < j.ncomp; k++) {
+        const Comp& q = j.comp[k];
+        if (map_dc[q.td] < 0) { map_dc[q.td] = job->n_tabs; if (!jhuff::build_table(&job->tabs[job->n_tabs++], j.dc[q.td].bits, j.dc[q.td].vals)) { m->err = "JPEG: bad Huffman table"; return UVO_INVALID_ARG; } }
+        if (map_ac[q.ta] < 0) { map_ac[q.ta] = job->n_tabs; if (!jhuff::build_table(&job->tabs[job->n_tabs++], j.ac[q.ta].bits, j.ac[q.ta].vals)) { m->err = "JPEG: bad Huffman table"; return UVO_INVALID_ARG; } }
+        h[k] = q.h; v[k] = q.v; tdc[k] = map_dc[q.td]; tac[k] = map_ac[q.ta];
+    }
+    jhuff::make_scan(&job->s, j.ncomp, h, v, tdc, tac, j.mcux, j.mcuy, j.restart);
+    job->s.sub_words = (uint32_t)sub_words;
+    JhNeed& nd = job->need;
+    // bit positions and slot sums are 32-bit: the STAGED scan (every restart interval padded to a subsequence) must stay below 2^32 bits,
+    // and so must the picture's slots
+    if (jhuff::stage_bound_bytes(job->s, job->scan_n, (uint32_t)sub_words) >= ((size_t)1 << 29) || j.total_blocks >= ((size_t)1 << 25)) {
+        m->err = "JPEG: the staged scan (restart intervals padded to subsequences) or the picture exceeds the device decoder's 32-bit positions; decode on the host";
+        return UVO_INVALID_ARG;
+    }
+    nd.stage = kJhHeadBytes + jhuff::stage_bound_bytes(job->s, job->scan_n, (uint32_t)sub_words);
+    nd.subs = jhuff::stage_bound_subs(job->s, job->scan_n, (uint32_t)sub_words);
+    nd.coef = j.total_blocks * 64 * sizeof(int16_t);
+    nd.planes = j.total_blocks * 64;
+    nd.out = (size_t)j.w * j.h * j.ncomp;
+    nd.out2 = bayer ? (size_t)j.w * j.h * 3 : 0;
+    return UVO_OK;
+}
+
+static bool jh_fits(const JhSlot& s, const JhNeed& nd)
+{
+    return s.h_stats && s.h_stage_cap >= nd.stage && s.d_stage_cap >= nd.stage && s.h_info_cap >= nd.subs * sizeof(uint32_t) && s.d_sub_cap >= jh_sub_bytes(nd.subs) &&
+           s.coef_cap >= nd.coef && s.planes_cap >= nd.planes && s.out_cap >= nd.out && s.out2_cap >= nd.out2;
+}
+static uvo_status jh_grow_slot(Ctx* m, JhSlot& s, const JhNeed& nd)
+{
+    if (!s.h_stats) UVO_HIP_TRY(m, hipHostMalloc(reinterpret_cast<void**>(&s.h_stats), 4 * sizeof(int)));
+    UVO_TRY(grow(m, reinterpret_cast<void**>(&s.h_stage), &s.h_stage_cap, nd.stage, true));
+    UVO_TRY(grow(m, reinterpret_cast<void**>(&s.d_stage), &s.d_stage_cap, nd.stage, false));
+    UVO_TRY(grow(m, reinterpret_cast<void**>(&s.h_info), &s.h_info_cap, nd.subs * sizeof(uint32_t), true));
+    UVO_TRY(grow(m, reinterpret_cast<void**>(&s.d_sub), &s.d_sub_cap, jh_sub_bytes(nd.subs), false));
+    UVO_TRY(grow(m, reinterpret_cast<void**>(&s.d_coef), &s.coef_cap, nd.coef, false));
+    UVO_TRY(grow(m, reinterpret_cast<void**>(&s.d_planes), &s.planes_cap, nd.planes, false));
+    UVO_TRY(grow(m, reinterpret_cast<void**>(&s.d_out), &s.out_cap, nd.out, false));
+    UVO_TRY(grow(m, reinterpret_cast<void**>(&s.d_out2), &s.out2_cap, nd.out2, false));
+    return UVO_OK;
+}
+// Workspaces of the first nimg slots of every lane in `lanes`, as frames_plan does: made while nothing is in flight, refused otherwise
+static uvo_status jh_plan(Ctx* m, Ctx* const* lanes, size_t n_lanes, int nimg, const JhJob* jobs)
+{
+    bool fits = true;
+    for (size_t l = 0; l < n_lanes; l++) for (int i = 0; i < nimg; i++) fits = fits && jh_fits(jh_ws(lanes[l])->slot[i], jobs[i].need);
+    if (fits) return UVO_OK;
+    if (m->n_pending != 0) { m->err = "the lanes' JPEG workspaces must grow (a larger payload or picture) while entries are in flight: collect first"; return UVO_CAPACITY; }
+    for (size_t l = 0; l < n_lanes; l++) {
+        UVO_HIP_TRY(m, hipStreamSynchronize(lanes[l]->stream));
+        for (int i = 0; i < nimg; i++) UVO_TRY(jh_grow_slot(m, jh_ws(lanes[l])->slot[i], jobs[i].need));
+    }
+    return UVO_OK;
+}
+
+static void jpeg_pixel_args(const Jpeg& j, IdctArgs* ia, ColourArgs* ca)
+{
+    memset(ia, 0, sizeof(*ia)); memset(ca, 0, sizeof(*ca));
+    size_t poff = 0;
+    for (int k = 0; k < j.ncomp; k++) {
+        const Comp& q = j.comp[k];
+        ia->comp[k] = { q.coef_off, q.bw, q.bh, q.tq, poff };
+        ca->plane_off[k] = poff; ca->pw[k] = q.bw * 8;
+        ca->dw[k] = (j.w * q.h + j.hmax - 1) / j.hmax; ca->dh[k] = (j.h * q.v + j.vmax - 1) / j.vmax;
+        ca->hs[k] = j.hmax / q.h; ca->vs[k] = j.vmax / q.v;
+        poff += (size_t)q.bw * q.bh * 64;
+    }
+    for (int k = j.ncomp; k < 3; k++) ia->comp[k] = ia->comp[0];
+    ia->ncomp = j.ncomp; ia->total_blocks = j.total_blocks;
+    ca->ncomp = j.ncomp; ca->w = j.w; ca->h = j.h;
+}
+
+// Stages the job's scan on the calling thread (the payload is consumed here) and queues the decode on lane L's stream, into L's slot.
+// Nothing waits for the device.  pixels: also IDCT, colour and the Bayer step; *d_out is the image (B G R, or grey), on L's stream.
+static uvo_status jh_queue(Ctx* m, Ctx* L, int slot, const JhJob& job, bool pixels, bool stats, const uint8_t** d_out)
+{
+    JhSlot& sl = jh_ws(L)->slot[slot];
+    if (!jh_fits(sl, job.need)) { m->err = "JPEG: the lane's workspace was not planned"; return UVO_INVALID_ARG; }
+    hipStream_t st = L->stream;
+    jhuff::Scan s = job.s;
+    memcpy(sl.h_stage, job.tabs, kJhTabBytes);
+    memcpy(sl.h_stage + kJhTabBytes, job.j.quant, kJhQuantBytes);
+    jhuff::Staged sg;
+    if (!jhuff::stage_scan(job.scan, job.scan_n, s.sub_words, jhuff::expected_intervals(s), sl.h_stage + kJhHeadBytes, sl.h_stage_cap - kJhHeadBytes, sl.h_info, sl.h_info_cap / sizeof(uint32_t), &sg)) {
+        m->err = "JPEG: staging the scan exceeded its planned workspace"; return UVO_INVALID_ARG;
+    }
+    s.n_bytes = sg.n_bytes; s.n_sub = sg.n_sub; s.n_iv = sg.n_iv;
+    const uint32_t n_groups = (s.n_sub + kJhGroup - 1) / kJhGroup;
+    const size_t cap_subs = job.need.subs, cap_groups = (cap_subs + kJhGroup - 1) / kJhGroup;
+    if (s.n_sub > cap_subs) { m->err = "JPEG: staging the scan exceeded its planned workspace"; return UVO_INVALID_ARG; }
+    JhBufs b;
+    b.tabs = reinterpret_cast<const jhuff::Table*>(sl.d_stage); b.n_tabs = job.n_tabs;
+    b.scan = sl.d_stage + kJhHeadBytes;
+    b.entry = reinterpret_cast<jhuff::State*>(sl.d_sub); b.exit = b.entry + cap_subs; b.incoming = b.exit + cap_subs;
+    uint32_t* words = reinterpret_cast<uint32_t*>(b.incoming + cap_groups);
+    b.info = words; b.slots = words + cap_subs; b.first = b.slots + cap_subs;
+    b.stats = reinterpret_cast<int*>(b.first + cap_subs);
+    UVO_HIP_TRY(m, hipMemcpyAsync(sl.d_stage, sl.h_stage, kJhHeadBytes + (size_t)sg.n_bytes + jhuff::kPadBytes, hipMemcpyHostToDevice, st));
+    UVO_HIP_TRY(m, hipMemcpyAsync(words, sl.h_info, (size_t)s.n_sub * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    UVO_HIP_TRY(m, hipMemsetAsync(b.stats, 0, 4 * sizeof(int), st));
+    UVO_HIP_TRY(m, hipMemsetAsync(sl.d_coef, 0, job.need.coef, st));
+    hipLaunchKernelGGL(k_jh_pass1, dim3(n_groups), dim3(kJhGroup), 0, st, s, b);
+    hipLaunchKernelGGL(k_jh_cross, dim3(1), dim3(kJhWide), 0, st, s, b, n_groups);
+    hipLaunchKernelGGL(k_jh_emit, dim3(n_groups), dim3(kJhGroup), 0, st, s, b, sl.d_coef);
+    hipLaunchKernelGGL(k_jh_dc, dim3(job.j.ncomp), dim3(kJhWide), 0, st, s, sl.d_coef);
+    UVO_HIP_TRY(m, hipGetLastError());
+    sl.have_stats = false;
+    if (stats) {
+        UVO_HIP_TRY(m, hipMemcpyAsync(sl.h_stats, b.stats, 4 * sizeof(int), hipMemcpyDeviceToHost, st));
+        sl.n_sub = (int)s.n_sub; sl.n_groups = (int)n_groups; sl.scan_bytes = sg.consumed; sl.have_stats = true;
+    }
+    if (!pixels) return UVO_OK;
+    const Jpeg& j = job.j;
+    IdctArgs ia; ColourArgs ca;
+    jpeg_pixel_args(j, &ia, &ca);
+    hipLaunchKernelGGL(k_jpeg_idct, dim3((unsigned)((j.total_blocks + 31) / 32)), dim3(256), 0, st, ia, sl.d_coef, reinterpret_cast<const uint16_t*>(sl.d_stage + kJhTabBytes), sl.d_planes);
+    hipLaunchKernelGGL(k_jpeg_colour, dim3((j.w + 63) / 64, (j.h + 3) / 4), dim3(256), 0, st, ca, sl.d_planes, sl.d_out);
+    *d_out = sl.d_out;
+    if (job.bayer) {
+        hipLaunchKernelGGL(k_bayer_bggr, dim3((j.w + 63) / 64, (j.h + 3) / 4), dim3(256), 0, st, sl.d_out, j.w, j.h, j.w, sl.d_out2);
+        *d_out = sl.d_out2;
+    }
+    UVO_HIP_TRY(m, hipGetLastError());
+    return UVO_OK;
+}
+
+uvo_status codec_set_entropy(Ctx* c, int where)
+{
+    if (where != 0 && where != 1) { c->err = "uvo_ctx_set_jpeg_entropy: where is 0 (host) or 1 (device)"; return UVO_INVALID_ARG; }
+    jh_ws(c)->where = where;
+    return UVO_OK;
+}
+
+// uvo_decode_image's JPEG path with the device entropy decoder: lane 0, slot 0, synchronous
+static uvo_status jpeg_decode_device(Ctx* c, const uint8_t* data, size_t n, int bayer, const uint8_t** d_out, int* w, int* h, int* channels)
+{
+    JhWs* q = jh_ws(c);
+    UVO_HIP_TRY(c, hipStreamSynchronize(c->stream));                     // the pinned block of the previous call is free again
+    UVO_TRY(jh_prepare(c, data, n, bayer, 0, &q->job[0]));
+    Ctx* lane = c;
+    UVO_TRY(jh_plan(c, &lane, 1, 1, q->job));
+    UVO_TRY(jh_queue(c, c, 0, q->job[0], true, true, d_out));
+    UVO_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    *w = q->job[0].j.w; *h = q->job[0].j.h; *channels = bayer ? 3 : q->job[0].j.ncomp;
+    return UVO_OK;
+}
+
+// The compressed loop entries, in two steps.  codec_compressed_plan: every refusal by kind and the workspaces of all lanes, before
+// anything is queued.  codec_compressed_queue: stage + decode image i on lane L.  Both images' sizes come back from the plan.
+uvo_status codec_compressed_plan(Ctx* m, int nimg, const uint8_t* const* data, const size_t* n, const int* bayer, int* w, int* h)
+{
+    JhWs* q = jh_ws(m);
+    for (int i = 0; i < nimg; i++) {
+        if (!data[i] || n[i] == 0) { m->err = "compressed entry: empty payload"; return UVO_INVALID_ARG; }
+        if (png::is_png(data[i], n[i])) { m->err = "compressed entry: PNG payloads are not decoded on the device; use uvo_decode_image and the frames entries"; return UVO_INVALID_ARG; }
+        UVO_TRY(jh_prepare(m, data[i], n[i], bayer[i], 0, &q->job[i]));
+        if ((bayer[i] ? 3 : q->job[i].j.ncomp) != 3) { m->err = "compressed entry: the payload does not decode to three channels (a grey stream needs a bayer format)"; return UVO_INVALID_ARG; }
+        if (i == 1 && (q->job[1].j.w != q->job[0].j.w || q->job[1].j.h != q->job[0].j.h)) { m->err = "compressed entry: left and right pictures differ in size"; return UVO_INVALID_ARG; }
+    }
+    *w = q->job[0].j.w; *h = q->job[0].j.h;
+    return UVO_OK;
+}
+uvo_status codec_compressed_workspaces(Ctx* m, int nimg)
+{
+    return jh_plan(m, m->lanes.data(), m->lanes.size(), nimg, jh_ws(m)->job);
+}
+uvo_status codec_compressed_queue(Ctx* m, Ctx* L, int i, const uint8_t** d_rgb)
+{
+    return jh_queue(m, L, i, jh_ws(m)->job[i], true, false, d_rgb);
+}
+
+// test hooks: the coefficient buffer of either decoder, and the last device decode's figures (lane 0, slot 0)
+uvo_status codec_coefficients(Ctx* c, const uint8_t* data, size_t n, int where, int sub_words, int16_t* out, size_t cap, size_t* n_coefs)
+{
+    if (!c->codec_ws) c->codec_ws = new CodecWs();
+    CodecWs* ws = static_cast<CodecWs*>(c->codec_ws);
+    UVO_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (where == 0) {
+        Jpeg j;
+        memset(j.quant, 0, sizeof(j.quant));
+        UVO_TRY(jpeg_entropy_decode(c, nullptr, data, n, &j, true));       // the size first: a call with too little room decodes nothing
+        *n_coefs = j.total_blocks * 64;
+        if (*n_coefs > cap) { c->err = "uvo_jpeg_coefficients: output capacity too small"; return UVO_CAPACITY; }
+        j = Jpeg();
+        memset(j.quant, 0, sizeof(j.quant));
+        UVO_TRY(jpeg_entropy_decode(c, ws, data, n, &j));
+        memcpy(out, ws->h_coef, *n_coefs * sizeof(int16_t));
+        return UVO_OK;
+    }
+    JhWs* q = jh_ws(c);
+    UVO_TRY(jh_prepare(c, data, n, 0, sub_words, &q->job[0]));
+    *n_coefs = q->job[0].j.total_blocks * 64;
+    if (*n_coefs > cap) { c->err = "uvo_jpeg_coefficients: output capacity too small"; return UVO_CAPACITY; }
+    Ctx* lane = c;
+    UVO_TRY(jh_plan(c, &lane, 1, 1, q->job));
+    const uint8_t* unused = nullptr;
+    UVO_TRY(jh_queue(c, c, 0, q->job[0], false, true, &unused));
+    UVO_HIP_TRY(c, hipMemcpyAsync(out, q->slot[0].d_coef, *n_coefs * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream));
+    UVO_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return UVO_OK;
+}
+uvo_status codec_entropy_stats(Ctx* c, int* n_sub, int* n_groups, int* rounds_in_group, int* rounds_across, size_t* scan_bytes)
+{
+    const JhSlot& s = jh_ws(c)->slot[0];
+    if (!s.have_stats) { c->err = "uvo_jpeg_entropy_stats: no device decode has run on this context (uvo_decode_image after uvo_ctx_set_jpeg_entropy(c, 1), or uvo_jpeg_coefficients)"; return UVO_INVALID_ARG; }
+    UVO_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (n_sub) *n_sub = s.n_sub;
+    if (n_groups) *n_groups = s.n_groups;
+    if (rounds_in_group) *rounds_in_group = s.h_stats[0];
+    if (rounds_across) *rounds_across = s.h_stats[1];
+    if (scan_bytes) *scan_bytes = s.scan_bytes;
+    return UVO_OK;
+}
+
 // ------------------------------------------------------------------------------------------ orchestration
 // PNG samples -> what cv::imdecode(IMREAD_UNCHANGED) returns: grey (sub-byte depths scaled as png_set_expand_gray_1_2_4_to_8 does,
 // v * 255 / (2^d - 1)), palette -> B G R, RGB -> B G R, RGBA -> B G R A.  One thread per pixel.
@@ -451,6 +904,7 @@ uvo_status codec_decode(Ctx* c, const uint8_t* data, size_t n, int bayer, const 
         UVO_HIP_TRY(c, hipStreamSynchronize(c->stream));
         return UVO_OK;
     }
+    if (ws->jh && static_cast<JhWs*>(ws->jh)->where == 1) return jpeg_decode_device(c, data, n, bayer, d_out, w, h, channels);
     Jpeg j;
     memset(j.quant, 0, sizeof(j.quant));
     UVO_HIP_TRY(c, hipStreamSynchronize(c->stream));                     // the pinned coefficient buffer of the previous call is free again

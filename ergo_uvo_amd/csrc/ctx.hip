@@ -2417,6 +2417,94 @@ try {
     return mono_submit_body(c, L->d_img[0], dw, dh, dw, UVO_MEM_DEVICE, range, kFramesEntry);
 } UVO_ABI_CATCH(c)
 
+// ------------------------------------------------------------------------------------------ compressed frames into the loops
+// A compressed entry is its step's frames entry with the device JPEG decoder in front: the payloads are checked by kind and the
+// lanes' workspaces planned before anything is queued, then each payload is staged (consumed) on this thread and decoded on the lane
+// the body will pick, on its stage-A stream, into the lane's own decode buffers, which frames_queue reads as device frames.
+static uvo_status compressed_to_lane(uvo_ctx* c, bool loop_initialized, const uvo_compressed_image* a, const uvo_compressed_image* b, uvo_ctx** L, int* dw, int* dh)
+{
+    const uvo_compressed_image* im[2] = { a, b };
+    const int ncam = b ? 2 : 1;
+    const uint8_t* data[2] = { nullptr, nullptr }; size_t n[2] = { 0, 0 }; int bayer[2] = { 0, 0 };
+    for (int i = 0; i < ncam; i++) {
+        data[i] = im[i]->data; n[i] = im[i]->n;
+        bayer[i] = im[i]->format && std::string(im[i]->format).find("bayer") != std::string::npos ? 1 : 0;
+    }
+    int w = 0, h = 0;
+    UVO_TRY(codec_compressed_plan(c, ncam, data, n, bayer, &w, &h));
+    UVO_TRY(frames_plan(c, ncam, w, h, 3 * w, UVO_MEM_DEVICE, dw, dh));
+    UVO_TRY(codec_compressed_workspaces(c, ncam));
+    *L = loop_initialized ? static_cast<uvo_ctx*>(c->lanes[c->next_lane]) : c;
+    const uint8_t* rgb[2] = { nullptr, nullptr };
+    for (int i = 0; i < ncam; i++) UVO_TRY(codec_compressed_queue(c, *L, i, &rgb[i]));
+    const uvo_status st = frames_queue(c, *L, ncam, rgb, w, h, 3 * w, UVO_MEM_DEVICE, *dw, *dh);
+    if (st != UVO_OK && *L != c) c->err = (*L)->err;
+    return st;
+}
+static uvo_status stereo_compressed_to_lane(uvo_ctx* c, const char* who, const uvo_compressed_image* left, const uvo_compressed_image* right, uvo_ctx** L, int* dw, int* dh)
+{
+    if (!left || !right || !left->data || !right->data) { c->err = std::string(who) + ": NULL message / payload pointer"; return UVO_INVALID_ARG; }
+    UVO_TRY(stereo_submit_refusal(c, who));
+    (void)hipSetDevice(c->device);
+    return compressed_to_lane(c, c->vo_initialized, left, right, L, dw, dh);
+}
+extern "C" uvo_status uvo_stereo_submit_compressed(uvo_ctx* c, const uvo_compressed_image* left, const uvo_compressed_image* right)
+try {
+    if (!c) return UVO_INVALID_ARG;
+    uvo_ctx* L = nullptr; int dw = 0, dh = 0;
+    UVO_TRY(stereo_compressed_to_lane(c, "uvo_stereo_submit_compressed", left, right, &L, &dw, &dh));
+    return stereo_submit_body(c, L->d_img[0], L->d_img[1], dw, dh, dw, UVO_MEM_DEVICE, kFramesEntry);
+} UVO_ABI_CATCH(c)
+extern "C" uvo_status uvo_stereo_step_compressed(uvo_ctx* c, const uvo_compressed_image* left, const uvo_compressed_image* right, double dt, uvo_stereo_result* out)
+try {
+    if (!c) return UVO_INVALID_ARG;
+    if (!out) return fail(c, UVO_INVALID_ARG, "uvo_stereo_step_compressed: NULL result pointer");
+    if (c->n_pending != 0) return fail(c, UVO_INVALID_ARG, "uvo_stereo_step_compressed: pairs submitted with uvo_stereo_submit are still in flight");
+    uvo_ctx* L = nullptr; int dw = 0, dh = 0;
+    UVO_TRY(stereo_compressed_to_lane(c, "uvo_stereo_step_compressed", left, right, &L, &dw, &dh));
+    return stereo_step_body(c, L->d_img[0], L->d_img[1], dw, dh, dw, UVO_MEM_DEVICE, dt, out, kFramesEntry);
+} UVO_ABI_CATCH(c)
+extern "C" uvo_status uvo_mono_step_compressed(uvo_ctx* c, const uvo_compressed_image* img, double range, double dt, uvo_mono_result* out)
+try {
+    if (!c) return UVO_INVALID_ARG;
+    if (!img || !img->data || !out) return fail(c, UVO_INVALID_ARG, "uvo_mono_step_compressed: NULL message / payload / result pointer");
+    UVO_TRY(mono_step_refusal(c));
+    (void)hipSetDevice(c->device);
+    uvo_ctx* L = nullptr; int dw = 0, dh = 0;
+    UVO_TRY(compressed_to_lane(c, false, img, nullptr, &L, &dw, &dh));                       // the synchronous step runs on lane 0
+    return mono_step_body(c, L->d_img[0], dw, dh, dw, UVO_MEM_DEVICE, range, dt, out, kFramesEntry);
+} UVO_ABI_CATCH(c)
+extern "C" uvo_status uvo_mono_submit_compressed(uvo_ctx* c, const uvo_compressed_image* img, double range)
+try {
+    if (!c) return UVO_INVALID_ARG;
+    if (!img || !img->data) return fail(c, UVO_INVALID_ARG, "uvo_mono_submit_compressed: NULL message / payload pointer");
+    UVO_TRY(mono_submit_refusal(c, "uvo_mono_submit_compressed"));
+    (void)hipSetDevice(c->device);
+    uvo_ctx* L = nullptr; int dw = 0, dh = 0;
+    UVO_TRY(compressed_to_lane(c, c->mono_initialized, img, nullptr, &L, &dw, &dh));
+    return mono_submit_body(c, L->d_img[0], dw, dh, dw, UVO_MEM_DEVICE, range, kFramesEntry);
+} UVO_ABI_CATCH(c)
+extern "C" uvo_status uvo_ctx_set_jpeg_entropy(uvo_ctx* c, int where)
+try {
+    if (!c) return UVO_INVALID_ARG;
+    UVO_TRY(need_idle(c, "uvo_ctx_set_jpeg_entropy"));
+    return codec_set_entropy(c, where);
+} UVO_ABI_CATCH(c)
+extern "C" uvo_status uvo_jpeg_coefficients(uvo_ctx* c, const uint8_t* data, size_t n, int where, int sub_words, int16_t* out, size_t cap, size_t* n_coefs)
+try {
+    if (!c || !data || !out || !n_coefs || (where != 0 && where != 1) || sub_words < 0) return UVO_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    UVO_TRY(need_idle(c, "uvo_jpeg_coefficients"));
+    return codec_coefficients(c, data, n, where, sub_words, out, cap, n_coefs);
+} UVO_ABI_CATCH(c)
+extern "C" uvo_status uvo_jpeg_entropy_stats(uvo_ctx* c, int* n_sub, int* n_groups, int* rounds_in_group, int* rounds_across, size_t* scan_bytes)
+try {
+    if (!c) return UVO_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    UVO_TRY(need_idle(c, "uvo_jpeg_entropy_stats"));
+    return codec_entropy_stats(c, n_sub, n_groups, rounds_in_group, rounds_across, scan_bytes);
+} UVO_ABI_CATCH(c)
+
 // ------------------------------------------------------------------------------------------ pipeline trace
 // The UVO_TRACE machinery through the ABI: device timestamps (hipEvents on the lane's streams) and host timestamps (steady clock) of
 // every pipelined pair's phases, kept in a ring of 256 pairs per lane.

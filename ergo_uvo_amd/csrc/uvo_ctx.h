@@ -389,6 +389,12 @@ void codec_ws_free(Ctx* c);
 uvo_status codec_decode(Ctx* c, const uint8_t* data, size_t n, int bayer, const uint8_t** d_out, int* w, int* h, int* channels);
 uvo_status codec_peek(Ctx* c, const uint8_t* data, size_t n, int bayer, int* w, int* h, int* channels);
 uvo_status codec_bayer(Ctx* c, const uint8_t* bayer, int w, int h, int stride, int mem, const uint8_t** d_out);
+uvo_status codec_set_entropy(Ctx* c, int where);
+uvo_status codec_compressed_plan(Ctx* m, int nimg, const uint8_t* const* data, const size_t* n, const int* bayer, int* w, int* h);
+uvo_status codec_compressed_workspaces(Ctx* m, int nimg);
+uvo_status codec_compressed_queue(Ctx* m, Ctx* L, int i, const uint8_t** d_rgb);
+uvo_status codec_coefficients(Ctx* c, const uint8_t* data, size_t n, int where, int sub_words, int16_t* out, size_t cap, size_t* n_coefs);
+uvo_status codec_entropy_stats(Ctx* c, int* n_sub, int* n_groups, int* rounds_in_group, int* rounds_across, size_t* scan_bytes);
 // sift.hip
 void sift_ws_free(Ctx* c);
 // orb.hip

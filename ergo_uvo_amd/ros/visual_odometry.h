@@ -17,7 +17,12 @@
 //   loop            ros::Rate(NODE_FREQ): spinOnce, sleep, one loop body                  (visual_odometry.h:249-251, 528-530)
 // One parameter of this adapter's own: the private `~execution`, "operators" (default: the loop body operator by operator, as the
 // reference runs it) or "fused" (the same iteration as one call of the library's camera-frames loop entry; visual_odometry_hip.h).
-// Image decoding stays where the reference has it (cv_bridge::toCvCopy + COLOR_BayerBGGR2BGR for bayer formats,
+// And `~ingest`, "compressed" (default) or "decoded".  With "compressed" the callbacks hand the message itself on to the node class
+// (its payload and format string; the class keeps its own copy): Execution::fused gives it to the library's compressed loop entries,
+// which decode the JPEG on the device on the entry's pipeline lane, and falls back to decoding + the frames entry for a payload
+// those entries refuse by kind (PNG); Execution::operators decodes it to a host Mat as before.  "decoded" decodes in the callback
+// (a topic that always carries PNG would otherwise pay one refused call per frame).
+// With OpenCV present image decoding stays where the reference has it (cv_bridge::toCvCopy + COLOR_BayerBGGR2BGR for bayer formats,
 // uvo_libraries/src/math_utility.cpp:154-173) when OpenCV is present; without it the library's own decoder is used
 // (uvo_hip::decode_compressed_image, include/uvo_libraries_hip/image_codec.h).
 #pragma once
@@ -52,6 +57,7 @@ class visual_odometry_node
         std::string CAMERA_NAME;
         std::unique_ptr<uvo_hip::visual_odometry_core> core;          // the two loops and what they keep between iterations
         uvo_hip::Execution execution = uvo_hip::Execution::operators;  // ~execution
+        bool ingest_compressed = true;                                 // ~ingest
         ros::Publisher pub_estimated_linear_vel, pub_validity;
 
         // the parameter server's subtree -> ParamTree (same conversions afterwards as with the YAML loader)
@@ -96,6 +102,20 @@ class visual_odometry_node
         // the library's decoder with the image left in the GPU's memory, where the fused iteration reads it in place
         static uvo_hip::DeviceImage from_ros_to_device_image(const sensor_msgs::CompressedImage::ConstPtr& msg)
         { return uvo_hip::decode_compressed_image_device(msg->data.data(), msg->data.size(), msg->format); }
+        static uvo_hip::CompressedMessage from_ros_to_message(const sensor_msgs::CompressedImage::ConstPtr& msg)
+        {
+            uvo_hip::CompressedMessage m;
+            m.data.assign(msg->data.begin(), msg->data.end()); m.format = msg->format;
+            return m;
+        }
+        bool hand_on() const
+        {
+#ifdef UVO_HAVE_OPENCV
+            return false;                                                                              // decoding stays with cv_bridge
+#else
+            return ingest_compressed;
+#endif
+        }
         bool device_ingest() const
         {
 #ifdef UVO_HAVE_OPENCV
@@ -108,13 +128,15 @@ class visual_odometry_node
         // the subscribers' callbacks (visual_odometry.h:67-78, 88-95): the newest message replaces an unprocessed one
         void mono_imgs_callback(const sensor_msgs::CompressedImage::ConstPtr& msg)
         {
-            if (device_ingest()) core->mono_imgs_callback(from_ros_to_device_image(msg), msg->header.stamp.toSec());
+            if (hand_on()) core->mono_imgs_callback(from_ros_to_message(msg), msg->header.stamp.toSec());
+            else if (device_ingest()) core->mono_imgs_callback(from_ros_to_device_image(msg), msg->header.stamp.toSec());
             else core->mono_imgs_callback(from_ros_to_cv_image(msg), msg->header.stamp.toSec());
         }
         void range_callback(const sensor_msgs::Range::ConstPtr& msg) { core->range_callback(msg->range); }
         void stereo_imgs_callback(const sensor_msgs::CompressedImage::ConstPtr& left_image, const sensor_msgs::CompressedImage::ConstPtr& right_image)
         {
-            if (device_ingest()) core->stereo_imgs_callback(from_ros_to_device_image(left_image), from_ros_to_device_image(right_image), left_image->header.stamp.toSec());
+            if (hand_on()) core->stereo_imgs_callback(from_ros_to_message(left_image), from_ros_to_message(right_image), left_image->header.stamp.toSec());
+            else if (device_ingest()) core->stereo_imgs_callback(from_ros_to_device_image(left_image), from_ros_to_device_image(right_image), left_image->header.stamp.toSec());
             else core->stereo_imgs_callback(from_ros_to_cv_image(left_image), from_ros_to_cv_image(right_image), left_image->header.stamp.toSec());
         }
 
@@ -166,6 +188,13 @@ inline void visual_odometry_node::visual_odometry_workflow(std::string VO_NODE)
         return;
     }
     execution = exec_name == "fused" ? uvo_hip::Execution::fused : uvo_hip::Execution::operators;
+    std::string ingest_name = "compressed";
+    ros::param::get("~ingest", ingest_name);
+    if (ingest_name != "compressed" && ingest_name != "decoded") {
+        ROS_ERROR(" ################ WRONG SELECTION OF ~ingest - CHOOSE BETWEEN compressed AND decoded ################");
+        return;
+    }
+    ingest_compressed = ingest_name == "compressed";
     // get_VO_parameters + get_{stereo,mono}_camera_parameters (visual_odometry.h:757, 776, 787) run in the core's constructor
     core.reset(new uvo_hip::visual_odometry_core(VO_NODE, tree, CAMERA_NAME, execution));
     ros::Rate loop_rate(NODE_FREQ);                                                                    // visual_odometry.h:759

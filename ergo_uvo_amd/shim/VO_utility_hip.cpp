@@ -696,6 +696,26 @@ void mono_step_frames(const unsigned char* img, int w, int h, int stride, int me
 { SHIM_TRY(uvo_mono_step_frames(ctx_now(), img, w, h, stride, mem, range, dt, &out), "uvo_mono_step_frames"); }
 void mono_submit_frames(const unsigned char* img, int w, int h, int stride, int mem, double range)
 { SHIM_TRY(uvo_mono_submit_frames(ctx_now(), img, w, h, stride, mem, range), "uvo_mono_submit_frames"); }
+void loop_stereo_step_compressed(const unsigned char* left, size_t n_left, const unsigned char* right, size_t n_right, const std::string& format_left, const std::string& format_right, double dt, uvo_stereo_result& out)
+{
+    const uvo_compressed_image a = { left, n_left, format_left.c_str() }, b = { right, n_right, format_right.c_str() };
+    SHIM_TRY(uvo_stereo_step_compressed(ctx_now(), &a, &b, dt, &out), "uvo_stereo_step_compressed");
+}
+void loop_stereo_submit_compressed(const unsigned char* left, size_t n_left, const unsigned char* right, size_t n_right, const std::string& format_left, const std::string& format_right)
+{
+    const uvo_compressed_image a = { left, n_left, format_left.c_str() }, b = { right, n_right, format_right.c_str() };
+    SHIM_TRY(uvo_stereo_submit_compressed(ctx_now(), &a, &b), "uvo_stereo_submit_compressed");
+}
+void loop_mono_step_compressed(const unsigned char* img, size_t n, const std::string& format, double range, double dt, uvo_mono_result& out)
+{
+    const uvo_compressed_image a = { img, n, format.c_str() };
+    SHIM_TRY(uvo_mono_step_compressed(ctx_now(), &a, range, dt, &out), "uvo_mono_step_compressed");
+}
+void loop_mono_submit_compressed(const unsigned char* img, size_t n, const std::string& format, double range)
+{
+    const uvo_compressed_image a = { img, n, format.c_str() };
+    SHIM_TRY(uvo_mono_submit_compressed(ctx_now(), &a, range), "uvo_mono_submit_compressed");
+}
 void mono_collect(double dt, uvo_mono_result& out) { SHIM_TRY(uvo_mono_collect(ctx_now(), dt, &out), "uvo_mono_collect"); }
 int  stereo_get(const char* what, void* out, int cap_bytes) { return uvo_stereo_get(ctx_now(), what, out, cap_bytes); }
 int  mono_get(const char* what, void* out, int cap_bytes) { return uvo_mono_get(ctx_now(), what, out, cap_bytes); }

@@ -370,7 +370,7 @@ uvo_status uvo_mono_submit_frames(uvo_ctx* c, const uint8_t* rgb, int w, int h, 
  * cv_bridge::toCvCopy(sensor_msgs/CompressedImage) -> cv::imdecode, then cv::cvtColor(COLOR_BayerBGGR2BGR) when the message's
  * `format` contains "bayer".  data: the message payload, recognised by its signature as cv::imdecode does:
  *   JPEG  baseline / sequential Huffman, 8 bit, 1 or 3 components, sampling factors <= 2 (progressive and arithmetic-coded files are
- *         refused with UVO_INVALID_ARG).  Entropy decoding on the host; dequantisation + IDCT + chroma upsampling + colour
+ *         refused with UVO_INVALID_ARG).  Entropy decoding on the host (or on the device after uvo_ctx_set_jpeg_entropy(c, 1)); dequantisation + IDCT + chroma upsampling + colour
  *         conversion on the device, byte-identical to libjpeg's defaults (JDCT_ISLOW, fancy upsampling).
  *   PNG   non-interlaced; grey and palette at 1 / 2 / 4 / 8 bits, RGB and RGBA at 8 bits -> 1, 3, 3, 4 channels as
  *         imdecode(IMREAD_UNCHANGED) returns them (16-bit samples, grey + alpha, palettes with tRNS and Adam7 are refused).  zlib
@@ -381,6 +381,37 @@ uvo_status uvo_decode_image(uvo_ctx* c, const uint8_t* data, size_t n, const cha
                             int* w, int* h, int* channels);
 /* cv::cvtColor(src, dst, COLOR_BayerBGGR2BGR) of an 8-bit mosaic (bilinear; borders copy their neighbour) */
 uvo_status uvo_bayer_bggr2bgr(uvo_ctx* c, const uint8_t* bayer, int w, int h, int stride, int mem, uint8_t* out_bgr, int out_mem);
+
+/* ---- compressed frames into the loops: the payload of a sensor_msgs/CompressedImage as a loop entry, decoded on the device.
+ * The JPEG Huffman stream is decoded by the device entropy decoder (self-synchronising parallel decode: subsequences decoded in
+ * parallel, stitched to a fixed point, coefficients scattered by a slot scan; csrc/uvo_jhuff.h) on the entry's pipeline
+ * lane, in that lane's workspace, on that lane's stage-A stream in front of get_image: no stream and no event that the frames
+ * entries do not have, and no host wait.  Tables and launch arguments travel through the lane's pinned staging block.
+ * Defined result of a compressed entry, for a well-formed stream: what uvo_decode_image(..., UVO_MEM_DEVICE) of each payload (its
+ * Bayer step included when `format` contains "bayer") followed by the matching *_frames entry on that image (the stream's own w, h,
+ * stride 3 * w, UVO_MEM_DEVICE) gives: same collects, same uvo_stereo_get / uvo_mono_get keys; compressed, frames and grey entries
+ * may be mixed in one sequence.  The payload bytes are consumed before the call returns (staging copies them): unlike a frames
+ * entry's pixels, the message may be freed or overwritten at once.
+ * Accepted: exactly what uvo_decode_image's JPEG path accepts.  Refused with UVO_INVALID_ARG and a message naming the cause, before
+ * anything is queued and with uvo_ctx_pending unchanged: PNG payloads (use uvo_decode_image and the frames entries), progressive or
+ * arithmetic-coded files, a decode that does not give three channels, left and right of different size, a camera that is not set,
+ * and the step's own refusals.  Workspaces are planned for all lanes while nothing is in flight; a payload that would make them grow
+ * with entries in flight is refused with UVO_CAPACITY (collect first).
+ * A damaged entropy stream is not an error, as for uvo_decode_image: it decodes to some picture, with every index in range.  The
+ * device decoder need not give the host decoder's picture for such a stream.
+ * uvo_ctx_set_jpeg_entropy: where uvo_decode_image decodes Huffman streams: 0 host (default), 1 device (same pixels). */
+typedef struct { const uint8_t* data; size_t n; const char* format; } uvo_compressed_image;
+uvo_status uvo_ctx_set_jpeg_entropy(uvo_ctx* c, int where);
+uvo_status uvo_stereo_step_compressed(uvo_ctx* c, const uvo_compressed_image* left, const uvo_compressed_image* right, double dt, uvo_stereo_result* out);
+uvo_status uvo_stereo_submit_compressed(uvo_ctx* c, const uvo_compressed_image* left, const uvo_compressed_image* right);
+uvo_status uvo_mono_step_compressed(uvo_ctx* c, const uvo_compressed_image* img, double range, double dt, uvo_mono_result* out);
+uvo_status uvo_mono_submit_compressed(uvo_ctx* c, const uvo_compressed_image* img, double range);
+/* test hooks, idle contexts only.  uvo_jpeg_coefficients: the coefficient buffer the IDCT reads (component after component, the
+ * raster of each component's MCU-padded blocks, 64 int16 in natural order per block) from the host (where = 0) or the device
+ * (where = 1) entropy decoder; sub_words: 32-bit words per subsequence of the device decoder (0 = the default); cap in coefficients.
+ * uvo_jpeg_entropy_stats: figures of the last device decode on lane 0 through uvo_decode_image or uvo_jpeg_coefficients. */
+uvo_status uvo_jpeg_coefficients(uvo_ctx* c, const uint8_t* data, size_t n, int where, int sub_words, int16_t* out, size_t cap, size_t* n_coefs);
+uvo_status uvo_jpeg_entropy_stats(uvo_ctx* c, int* n_sub, int* n_groups, int* rounds_in_group, int* rounds_across, size_t* scan_bytes);
 
 /* ---- resize_camera_matrix (VO_utility.h:112 -> VO_utility.cpp:658-675), once per run, host arithmetic only (no context):
  * K (3x3 row-major, in/out) is divided by ratio = original_width / desired_width with the skew K[0][1] kept and K[2][2] = 1;

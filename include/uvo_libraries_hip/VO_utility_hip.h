@@ -134,6 +134,13 @@ void stereo_collect(double dt, uvo_stereo_result& out);
 void mono_step_frames(const unsigned char* img, int w, int h, int stride, int mem, double range, double dt, uvo_mono_result& out);
 void mono_submit_frames(const unsigned char* img, int w, int h, int stride, int mem, double range);
 void mono_collect(double dt, uvo_mono_result& out);
+// compressed frames (uvo_*_compressed): the payload of a sensor_msgs/CompressedImage and its format string, JPEG decoded on the device
+// on the entry's lane.  The payload is consumed before the call returns.  A payload the entries refuse by kind (PNG, grey without a
+// bayer format, progressive JPEG) throws Error(UVO_INVALID_ARG): decode_compressed_image_device + the frames entry serve those.
+void loop_stereo_step_compressed(const unsigned char* left, size_t n_left, const unsigned char* right, size_t n_right, const std::string& format_left, const std::string& format_right, double dt, uvo_stereo_result& out);
+void loop_stereo_submit_compressed(const unsigned char* left, size_t n_left, const unsigned char* right, size_t n_right, const std::string& format_left, const std::string& format_right);
+void loop_mono_step_compressed(const unsigned char* img, size_t n, const std::string& format, double range, double dt, uvo_mono_result& out);
+void loop_mono_submit_compressed(const unsigned char* img, size_t n, const std::string& format, double range);
 // uvo_stereo_get / uvo_mono_get of the last collected entry: the element count, or -(count) when cap_bytes is too small
 int  stereo_get(const char* what, void* out, int cap_bytes);
 int  mono_get(const char* what, void* out, int cap_bytes);

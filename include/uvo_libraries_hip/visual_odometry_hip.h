@@ -13,6 +13,12 @@
 // entry's result onto what it publishes.  The reference's quirks (appended init matches, state carried with empty sets after a failed
 // gate, the last t_prevCam_currCam published again) live in that entry and are not repeated here.  For recorded sequences the fused
 // mode also has a pipelined form: spin_submit() / spin_collect() keep up to set_depth() frames in flight.
+// The callbacks also take the compressed message itself (CompressedMessage: the payload and the format string of a
+// sensor_msgs/CompressedImage; the node keeps its own copy).  Execution::fused hands it to the compressed loop entries
+// (uvo_stereo_step_compressed / uvo_stereo_submit_compressed and the mono twins: the JPEG is decoded on the device, on the entry's lane),
+// and no image buffer is kept until the collect.  A payload those entries refuse by kind (PNG, for one) is decoded with
+// decode_compressed_image_device and goes through the frames entry instead; that decode works in lane 0's buffers, so with frames in
+// flight it is the library's refusal (spin_collect first).  Execution::operators decodes the message to a host Mat as before.
 //
 // Line references: VO = uvo/include/visual_odometry.h of the reference.
 #pragma once
@@ -21,6 +27,7 @@
 #include <string>
 #include <vector>
 #include "uvo_libraries_hip/uvo_config.h"
+#include "uvo_libraries_hip/image_codec.h"
 
 namespace uvo_hip {
 
@@ -33,6 +40,9 @@ struct Published {
 };
 
 enum class Execution { operators, fused };
+
+// a sensor_msgs/CompressedImage as the node keeps it: CompressedImage.data and CompressedImage.format
+struct CompressedMessage { std::vector<unsigned char> data; std::string format; };
 
 class visual_odometry_core {
 public:
@@ -54,22 +64,39 @@ public:
     visual_odometry_core& operator=(const visual_odometry_core&) = delete;
 
     // ---- the subscribers' callbacks (queue size 1: the newest message replaces an unprocessed one) ----
-    void mono_imgs_callback(const uvocv::Mat& img, double stamp) { camera_img_ = img; dev_img_ = DeviceImage(); stamp_ = stamp; first_img_ = true; new_img_available_ = true; }   // VO:67-73
+    void mono_imgs_callback(const uvocv::Mat& img, double stamp) { camera_img_ = img; dev_img_ = DeviceImage(); drop_messages(); stamp_ = stamp; first_img_ = true; new_img_available_ = true; }   // VO:67-73
     void range_callback(double range) { range_ = range; }                                                                                               // VO:75-78
     void stereo_imgs_callback(const uvocv::Mat& left, const uvocv::Mat& right, double stamp)                                                            // VO:88-95
-    { camera_left_ = left; camera_right_ = right; dev_left_ = dev_right_ = DeviceImage(); stamp_ = stamp; first_img_ = true; new_img_available_ = true; }
+    { camera_left_ = left; camera_right_ = right; dev_left_ = dev_right_ = DeviceImage(); drop_messages(); stamp_ = stamp; first_img_ = true; new_img_available_ = true; }
     // The same callbacks for images that are already in the GPU's memory (decode_compressed_image_device, image_codec.h): the fused
     // iterations read them in place; the operator loops take host Mats, so Execution::operators copies them down once, here.
     void mono_imgs_callback(const DeviceImage& img, double stamp)
     {
         if (exec_ == Execution::operators) { mono_imgs_callback(img.download(), stamp); return; }
-        dev_img_ = img; camera_img_ = Mat(); stamp_ = stamp; first_img_ = true; new_img_available_ = true;
+        dev_img_ = img; camera_img_ = Mat(); drop_messages(); stamp_ = stamp; first_img_ = true; new_img_available_ = true;
     }
     void stereo_imgs_callback(const DeviceImage& left, const DeviceImage& right, double stamp)
     {
         if (exec_ == Execution::operators) { stereo_imgs_callback(left.download(), right.download(), stamp); return; }
-        dev_left_ = left; dev_right_ = right; camera_left_ = Mat(); camera_right_ = Mat(); stamp_ = stamp; first_img_ = true; new_img_available_ = true;
+        dev_left_ = left; dev_right_ = right; camera_left_ = Mat(); camera_right_ = Mat(); drop_messages(); stamp_ = stamp; first_img_ = true; new_img_available_ = true;
     }
+    // The same callbacks for the compressed messages themselves: the fused iterations hand them to the compressed loop entries;
+    // Execution::operators decodes them to host Mats, here, as from_ros_to_cv_image does.
+    void mono_imgs_callback(const CompressedMessage& msg, double stamp)
+    {
+        if (exec_ == Execution::operators) { mono_imgs_callback(decode_compressed_image(msg.data.data(), msg.data.size(), msg.format), stamp); return; }
+        msg_[0] = msg; msg_[1] = CompressedMessage(); camera_img_ = Mat(); dev_img_ = DeviceImage(); stamp_ = stamp; first_img_ = true; new_img_available_ = true;
+    }
+    void stereo_imgs_callback(const CompressedMessage& left, const CompressedMessage& right, double stamp)
+    {
+        if (exec_ == Execution::operators) {
+            stereo_imgs_callback(decode_compressed_image(left.data.data(), left.data.size(), left.format), decode_compressed_image(right.data.data(), right.data.size(), right.format), stamp);
+            return;
+        }
+        msg_[0] = left; msg_[1] = right; camera_left_ = Mat(); camera_right_ = Mat(); dev_left_ = dev_right_ = DeviceImage(); stamp_ = stamp; first_img_ = true; new_img_available_ = true;
+    }
+    // compressed messages that went through decode_compressed_image_device and the frames entry because the compressed entry refused their kind
+    int compressed_fallbacks() const { return compressed_fallbacks_; }
 
     // ---- one iteration of the node's loop (after ros::spinOnce(); loop_rate.sleep()) ----
     Published spin_once()
@@ -101,11 +128,16 @@ public:
         if ((int)fifo_.size() >= depth_) throw Error(UVO_INVALID_ARG, "spin_submit: the pipeline is full (spin_collect first, or set_depth)");
         if (!depth_set_) set_depth(depth_);
         fifo_.push_back(take_frame());
-        const Frame& f = fifo_.back();
+        Frame& f = fifo_.back();
         try {
-            if (mode_ == "stereo") stereo_submit_frames(f.p[0], f.p[1], f.w, f.h, f.stride, f.mem);
-            else mono_submit_frames(f.p[0], f.w, f.h, f.stride, f.mem, (double)(float)f.range);
+            if (mode_ == "stereo")
+                enter(f, [&] { loop_stereo_submit_compressed(f.msg[0].data.data(), f.msg[0].data.size(), f.msg[1].data.data(), f.msg[1].data.size(), f.msg[0].format, f.msg[1].format); },
+                      [&] { stereo_submit_frames(f.p[0], f.p[1], f.w, f.h, f.stride, f.mem); });
+            else
+                enter(f, [&] { loop_mono_submit_compressed(f.msg[0].data.data(), f.msg[0].data.size(), f.msg[0].format, (double)(float)f.range); },
+                      [&] { mono_submit_frames(f.p[0], f.w, f.h, f.stride, f.mem, (double)(float)f.range); });
         } catch (...) { fifo_.pop_back(); throw; }
+        f.msg[0] = f.msg[1] = CompressedMessage();                       // the entry consumed the payloads: nothing of them is kept until the collect
         new_img_available_ = false;
         return true;
     }
@@ -141,11 +173,15 @@ private:
     // fused execution: the frame as the loop entry takes it, and the frames in flight in the order of their submission
     struct Frame {
         Mat host[2]; DeviceImage dev[2];                                 // keep the pixels alive until the collect
+        CompressedMessage msg[2];                                        // a compressed frame: the payloads, until its entry has consumed them
         const unsigned char* p[2] = {nullptr, nullptr};
         int w = 0, h = 0, stride = 0, mem = UVO_MEM_HOST;
         double stamp = 0, range = 0;
     };
     DeviceImage dev_img_, dev_left_, dev_right_;
+    CompressedMessage msg_[2];                                           // the compressed message(s) the callbacks last delivered (fused execution)
+    int compressed_fallbacks_ = 0;
+    void drop_messages() { msg_[0] = msg_[1] = CompressedMessage(); }
     std::deque<Frame> fifo_;
     int depth_ = 2; bool depth_set_ = false;
 
@@ -311,6 +347,13 @@ private:
         const bool stereo = mode_ == "stereo";
         const int ncam = stereo ? 2 : 1;
         f.stamp = stamp_; f.range = range_;
+        if (!msg_[0].data.empty()) {
+            for (int i = 0; i < ncam; i++) {
+                if (msg_[i].data.empty()) throw Error(UVO_INVALID_ARG, "fused iteration: an empty compressed message");
+                f.msg[i] = msg_[i];
+            }
+            return f;
+        }
         if (!(stereo ? dev_left_ : dev_img_).empty()) {
             f.dev[0] = stereo ? dev_left_ : dev_img_; if (stereo) f.dev[1] = dev_right_;
             for (int i = 0; i < ncam; i++) {
@@ -332,6 +375,36 @@ private:
         return f;
     }
 
+    // A frame into its loop entry: `frames` for pixels; for compressed messages `compressed`, and when that entry refuses the payload
+    // by kind (its "compressed entry:" refusals: a PNG, a decode that does not give three channels -- made before anything is queued),
+    // decode_compressed_image_device followed by `frames`
+    template <class Compressed, class Frames>
+    void enter(Frame& f, Compressed&& compressed, Frames&& frames)
+    {
+        if (f.msg[0].data.empty()) { frames(); return; }
+        try { compressed(); return; }
+        catch (const Error& e) { if (e.status != UVO_INVALID_ARG || std::string(e.what()).find("compressed entry:") == std::string::npos) throw; }
+        const int ncam = mode_ == "stereo" ? 2 : 1;
+        for (int i = 0; i < ncam; i++) {
+            f.dev[i] = decode_compressed_image_device(f.msg[i].data.data(), f.msg[i].data.size(), f.msg[i].format);
+            if (f.dev[i].empty() || f.dev[i].channels != 3 || f.dev[i].cols != f.dev[0].cols || f.dev[i].rows != f.dev[0].rows)
+                throw Error(UVO_INVALID_ARG, "fused iteration: 3-channel device images of one size expected");
+            f.p[i] = f.dev[i].data();
+        }
+        f.w = f.dev[0].cols; f.h = f.dev[0].rows; f.stride = f.w * 3; f.mem = UVO_MEM_DEVICE;
+        compressed_fallbacks_++;
+        frames();
+    }
+    // the size of a compressed message's picture, from its headers
+    static Mat size_of_message(const CompressedMessage& m)
+    {
+        int w = 0, h = 0, ch = 0;
+        uvo_ctx* c = context();
+        const uvo_status st = uvo_decode_image(c, m.data.data(), m.data.size(), m.format.c_str(), nullptr, 0, UVO_MEM_HOST, &w, &h, &ch);
+        if (st != UVO_OK) throw Error(st, std::string("uvo_decode_image: ") + uvo_last_error(c));
+        return Mat(h, w, uvocv::CV_8UC1);
+    }
+
     // once, on the first image (VO:188-189, 221-225 mono; VO:426-463 stereo): the cameras, the rig, the detector and the PnP method
     // (PNP_METHOD_FLAG reaches the context with the other parameter globals, in every shim call) go to the context
     void fused_setup()
@@ -340,19 +413,20 @@ private:
         const bool stereo = mode_ == "stereo";
         const DeviceImage& d0 = stereo ? dev_left_ : dev_img_;
         // resize_camera_matrix reads the size of the original image only
-        auto size_of = [](const Mat& m, const DeviceImage& d) { return d.empty() ? m : Mat(d.rows, d.cols, uvocv::CV_8UC1); };
+        const bool compressed = !msg_[0].data.empty();
+        auto size_of = [&](int cam, const Mat& m, const DeviceImage& d) { return compressed ? size_of_message(msg_[cam]) : (d.empty() ? m : Mat(d.rows, d.cols, uvocv::CV_8UC1)); };
         if (stereo) {
             K_left_ = mat33(fx_left, 0, ccx_left, 0, fy_left, ccy_left, 0, 0, 1); K_right_ = mat33(fx_right, 0, ccx_right, 0, fy_right, ccy_right, 0, 0, 1);
             dist_left_ = row4(k1_left, k2_left, p1_left, p2_left); dist_right_ = row4(k1_right, k2_right, p1_right, p2_right);
-            resize_camera_matrix(size_of(camera_left_, d0), K_left_, dist_left_, newK_left_);
-            resize_camera_matrix(size_of(camera_right_, dev_right_), K_right_, dist_right_, newK_right_);
+            resize_camera_matrix(size_of(0, camera_left_, d0), K_left_, dist_left_, newK_left_);
+            resize_camera_matrix(size_of(1, camera_right_, dev_right_), K_right_, dist_right_, newK_right_);
             loop_set_camera(0, K_left_, dist_left_, newK_left_);
             loop_set_camera(1, K_right_, dist_right_, newK_right_);
             loop_set_rig(newK_left_, newK_right_, R_right, t_right);
         } else {
             distortion_ = row4(k1, k2, p1, p2);
             camera_matrix_ = mat33(fx, 0, ccx, 0, fy, ccy, 0, 0, 1);
-            resize_camera_matrix(size_of(camera_img_, d0), camera_matrix_, distortion_, new_camera_matrix_);
+            resize_camera_matrix(size_of(0, camera_img_, d0), camera_matrix_, distortion_, new_camera_matrix_);
             loop_set_camera(0, camera_matrix_, distortion_, new_camera_matrix_);
             loop_set_mono_camera(new_camera_matrix_);
         }
@@ -369,16 +443,18 @@ private:
         if (!new_img_available_) return out;
         if (!fifo_.empty()) throw Error(UVO_INVALID_ARG, "spin_once: frames submitted with spin_submit are in flight (spin_collect first)");
         new_img_available_ = false;
-        const Frame f = take_frame();
+        Frame f = take_frame();
         const double dt = f.stamp - prev_time_;
         prev_time_ = f.stamp;
         if (mode_ == "stereo") {
             uvo_stereo_result r;
-            stereo_step_frames(f.p[0], f.p[1], f.w, f.h, f.stride, f.mem, dt, r);
+            enter(f, [&] { loop_stereo_step_compressed(f.msg[0].data.data(), f.msg[0].data.size(), f.msg[1].data.data(), f.msg[1].data.size(), f.msg[0].format, f.msg[1].format, dt, r); },
+                  [&] { stereo_step_frames(f.p[0], f.p[1], f.w, f.h, f.stride, f.mem, dt, r); });
             return published_of(r, f.stamp);
         }
         uvo_mono_result r;
-        mono_step_frames(f.p[0], f.w, f.h, f.stride, f.mem, (double)(float)f.range, dt, r);      // VO:366-368 (range narrows to float)
+        enter(f, [&] { loop_mono_step_compressed(f.msg[0].data.data(), f.msg[0].data.size(), f.msg[0].format, (double)(float)f.range, dt, r); },
+              [&] { mono_step_frames(f.p[0], f.w, f.h, f.stride, f.mem, (double)(float)f.range, dt, r); });      // VO:366-368 (range narrows to float)
         return published_of(r, f.stamp);
     }
     // the collect of the oldest submitted frame: deltaT is its stamp minus its predecessor's, as in the synchronous loop
