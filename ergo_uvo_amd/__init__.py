@@ -728,6 +728,29 @@ class Context:
             raise RuntimeError(f"five_point_models: the kernel counted {int(nm.min())}..{int(nm.max())} models for a subset, outside 0..10")
         return [models[i, :nm[i]].reshape(-1, 3, 3).copy() for i in range(len(sub))]
 
+    def solve_poly10(self, coeffs):
+        """Test hook (uvo_solve_poly10): the five-point kernel's cv::solvePoly on polynomials of eleven coefficients in increasing powers
+        (npoly x 11 float64), four per wave in the order given.  Returns (roots complex128 [npoly, 10], stats int32 [npoly, 5]); stats per
+        polynomial: degree used, sweeps run, sweeps with a zero root difference of its own, sweeps its wave redid with the
+        zero-difference test, 1 if its wave ran the runtime-degree code."""
+        c = _np(coeffs, np.float64)
+        if c.ndim != 2 or c.shape[1] != 11 or len(c) < 1:
+            raise ValueError("solve_poly10: coeffs npoly x 11")
+        re = np.full((len(c), 10), np.nan); im = np.full((len(c), 10), np.nan); stats = np.full((len(c), 5), -1, np.int32)
+        self._check(self._lib.uvo_solve_poly10(self._h, _p(c), len(c), _p(re), _p(im), _p(stats)))
+        roots = np.empty(re.shape, np.complex128); roots.real = re; roots.imag = im          # (re + 1j * im would turn an infinite part into NaN)
+        return roots, stats
+
+    def homography_models(self, src, dst, subsets):
+        """Test hook (uvo_homography_models): the four-point homography kernel on pixel points src, dst (n x 2 float32) and index subsets
+        (nsub x 4), with no subset check.  Returns (models float64 [nsub, 3, 3], nmodels int32 [nsub]); a row without a model stays NaN."""
+        src, dst, sub = _np(src, np.float32), _np(dst, np.float32), _np(subsets, np.int32)
+        if src.shape != dst.shape or src.ndim != 2 or src.shape[1] != 2 or sub.ndim != 2 or sub.shape[1] != 4:
+            raise ValueError("homography_models: src, dst n x 2 and subsets nsub x 4")
+        models = np.full((len(sub), 9), np.nan); nm = np.full(len(sub), -1, np.int32)
+        self._check(self._lib.uvo_homography_models(self._h, _p(src), _p(dst), len(src), _p(sub), len(sub), _p(models), _p(nm)))
+        return models.reshape(-1, 3, 3), nm
+
     def recoverPose(self, E, pts1, pts2, K, mask):
         E, p1, p2, K = _np(E, np.float64), _np(pts1, np.float32), _np(pts2, np.float32), _np(K, np.float64)
         m = _np(mask, np.uint8).copy(); R = np.empty((3, 3)); t = np.empty(3); good = C.c_int(0)

@@ -1871,6 +1871,23 @@ try {
     UVO_TRY(need_idle(c, "uvo_five_point_models"));
     return mono_five_point_models(c, q1, q2, n, subsets, nsub, models, nmodels);
 } UVO_ABI_CATCH(c)
+// test hook: cv::solvePoly as k_fivepoint_hyp runs it (solve_poly10, four polynomials per wave) on eleven-coefficient polynomials of the caller's
+extern "C" uvo_status uvo_solve_poly10(uvo_ctx* c, const double* coeffs, int npoly, double* roots_re, double* roots_im, int* stats)
+try {
+    if (!c || !coeffs || !roots_re || !roots_im || npoly < 1) return UVO_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    UVO_TRY(need_idle(c, "uvo_solve_poly10"));
+    return mono_solve_poly10(c, coeffs, npoly, roots_re, roots_im, stats);
+} UVO_ABI_CATCH(c)
+// test hook: k_h_hyp on the caller's pixel points and four-point subsets (no checkSubset: the caller decides what the kernel sees)
+extern "C" uvo_status uvo_homography_models(uvo_ctx* c, const float* src, const float* dst, int n, const int* subsets, int nsub, double* models, int* nmodels)
+try {
+    if (!c || !src || !dst || !subsets || !models || !nmodels || n < 1 || nsub < 1) return UVO_INVALID_ARG;
+    for (int i = 0; i < 4 * nsub; i++) if (subsets[i] < 0 || subsets[i] >= n) return fail(c, UVO_INVALID_ARG, "uvo_homography_models: a subset index is outside the points");
+    (void)hipSetDevice(c->device);
+    UVO_TRY(need_idle(c, "uvo_homography_models"));
+    return mono_homography_models(c, src, dst, n, subsets, nsub, models, nmodels);
+} UVO_ABI_CATCH(c)
 extern "C" uvo_status uvo_recover_pose(uvo_ctx* c, const double* E, const uvo_point2f* p1, const uvo_point2f* p2, int n, const double* K,
                                        double* R, double* t, uint8_t* mask, int* good)
 try {

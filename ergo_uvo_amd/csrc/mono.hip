@@ -9,6 +9,7 @@
 // (homography refit + Levenberg-Marquardt polish, decomposeHomographyMat) stay on the host as
 // SURVEY.md 2.3 (K5, K6) plans.
 //   k_fivepoint_hyp : four 5-point hypotheses per wave (Nister/Stewenius as in OpenCV's five-point.cpp)
+//   k_solve_poly10  : test hook -- k_fivepoint_hyp's cv::solvePoly alone, with per-row path counts
 //   k_e_score       : Sampson error of every (hypothesis, model) over all matches -> inlier count or median
 //   k_h_hyp         : normalised-DLT homographies, sixteen lanes per hypothesis (9x9 Jacobi eigen: pivot search, rotations and index rescans across the lanes)
 //   k_h_score       : reprojection error -> inlier count or median
@@ -150,14 +151,20 @@ __device__ __forceinline__ cplx dk_sweep(const cplx p, const double* cr, double 
 // makes the sequence periodic and the state after sweep 300 computable: with Brent's one-saved-state scheme two hypotheses in
 // three do recur, with periods from 2 to 126, but a third wander on without recurring inside 300 sweeps, and the launch lasts as long
 // as its slowest hypothesis: 912 us with the test against 879 without.  DESIGN.md section 9.)
-template <int NC>
-__device__ __forceinline__ cplx dk_sweeps(cplx z, const double* cr, double cn, int n, int l, int row)
+// STATS (the test hook k_solve_poly10 only; the hypothesis kernel's instantiation carries none of it): st[1] = the sweeps this row ran while
+// live, st[2] = those in which a lane of this row saw a zero difference, st[3] = those the wave redid CHECKED.
+template <int NC, bool STATS = false>
+__device__ __forceinline__ cplx dk_sweeps(cplx z, const double* cr, double cn, int n, int l, int row, int* st = nullptr)
 {
     bool live = true;
 #pragma unroll 1
     for (int iter = 0; iter < 300; iter++) {
         cplx q; bool sawzero;
         cplx zn = dk_sweep<NC, false>(z, cr, cn, n, l, q, sawzero);
+        if constexpr (STATS) {
+            const unsigned long long bz = __ballot(sawzero);
+            if (live) { st[1]++; st[2] += ((bz >> (16 * row)) & 0xffffull) != 0; st[3] += bz != 0; }
+        }
         if (__any(sawzero)) zn = dk_sweep<NC, true>(z, cr, cn, n, l, q, sawzero);
         bool moved = zn.re != z.re || zn.im != z.im;
         bool nonzero = q.re*q.re + q.im*q.im > 0;                   // sqrt(s) > 0  <=>  s > 0
@@ -170,7 +177,9 @@ __device__ __forceinline__ cplx dk_sweeps(cplx z, const double* cr, double cn, i
     return z;
 }
 // cv::solvePoly, real coefficients c[0..10] (increasing powers) in LDS at `cw`; roots to rre/rim.
-__device__ void solve_poly10(const double* cw, double* rre, double* rim, int l, int row)
+// STATS: st[0..4] (registers of the caller) = the degree used, dk_sweeps' three counts, 1 if the wave ran the NC = 0 instantiation.
+template <bool STATS = false>
+__device__ void solve_poly10(const double* cw, double* rre, double* rim, int l, int row, int* st = nullptr)
 {
     const int n0 = 10;
     int n = n0;
@@ -185,7 +194,11 @@ __device__ void solve_poly10(const double* cw, double* rre, double* rim, int l, 
 #pragma unroll 1
         for (int i = 0; i < n0; i++) { if (i == l && i < n) z = p; p = c_mul(p, r); }
     }
-    z = __all(n == n0) ? dk_sweeps<10>(z, cr, cn, n, l, row) : dk_sweeps<0>(z, cr, cn, n, l, row);
+    if constexpr (STATS) {
+        const bool full = __all(n == n0);
+        st[0] = n; st[1] = st[2] = st[3] = 0; st[4] = full ? 0 : 1;
+        z = full ? dk_sweeps<10, true>(z, cr, cn, n, l, row, st) : dk_sweeps<0, true>(z, cr, cn, n, l, row, st);
+    } else z = __all(n == n0) ? dk_sweeps<10>(z, cr, cn, n, l, row) : dk_sweeps<0>(z, cr, cn, n, l, row);
     if (l < n && fabs(z.im) < 1e-100) z.im = 0;
     int src = (l < n ? l : n - 1) + 16 * row;
     double ore = __shfl(z.re, src), oim = __shfl(z.im, src);
@@ -401,6 +414,30 @@ __global__ __launch_bounds__(64) void k_fivepoint_hyp(const double* q1, const do
         nmodels[hyp] = count;
     }
     FP_STAMP(6);
+}
+
+// test hook (uvo_solve_poly10): solve_poly10 alone on the caller's polynomials, four per wave, one per DPP row, their coefficients and
+// roots in LDS where k_fivepoint_hyp keeps them.  A ragged tail recomputes the last polynomial and writes nothing.
+__global__ __launch_bounds__(64) void k_solve_poly10(const double* coeffs /* npoly x 11 */, int npoly, double* roots_re, double* roots_im /* npoly x 10 */,
+                                                     int* stats /* npoly x 5 or null */)
+{
+    __shared__ double S2[kFpPerWg * FP_TOTAL];
+    const int row = threadIdx.x >> 4, l = threadIdx.x & 15;
+    const int poly_raw = blockIdx.x * kFpPerWg + row;
+    const bool real = poly_raw < npoly;
+    const int poly = real ? poly_raw : npoly - 1;
+    double* S = S2 + row * FP_TOTAL;
+    double* rre = S + FP_ROOTS; double* rim = rre + 10;
+    if (l < 11) S[FP_POLY + l] = coeffs[(size_t)poly * 11 + l];
+    __syncthreads();
+    int st[5];
+    solve_poly10<true>(S + FP_POLY, rre, rim, l, row, st);
+    __syncthreads();
+    if (real && l < 10) { roots_re[(size_t)poly * 10 + l] = rre[l]; roots_im[(size_t)poly * 10 + l] = rim[l]; }
+    if (real && stats && l == 0) {
+#pragma unroll
+        for (int k = 0; k < 5; k++) stats[(size_t)poly * 5 + k] = st[k];
+    }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1015,6 +1052,30 @@ uvo_status mono_five_point_models(Ctx* c, const double* q1, const double* q2, in
     return UVO_OK;
 }
 
+// test hook (uvo_solve_poly10): cv::solvePoly as the hypothesis kernel runs it, on polynomials of the caller's (k_solve_poly10)
+uvo_status mono_solve_poly10(Ctx* c, const double* coeffs, int npoly, double* roots_re, double* roots_im, int* stats)
+{
+    if (npoly > kMaxHyp) { c->err = "polynomial count exceeds the compiled hypothesis capacity (2048)"; return UVO_CAPACITY; }
+    MonoWs* w = mono_ws(c);
+    if (!w) { c->err = "mono workspace allocation failed"; return UVO_HIP_ERROR; }
+    hipStream_t st = c->stream;
+    // coefficients in the models buffer's first 11 doubles per polynomial, roots behind them (kMaxHyp x 90 has room for 11 + 20 each);
+    // the stats in `counts` (kMaxHyp x 10)
+    double* d_coeffs = w->models; double* d_re = w->models + (size_t)11 * kMaxHyp; double* d_im = d_re + (size_t)10 * kMaxHyp;
+    memcpy(w->h_models.data(), coeffs, sizeof(double) * 11 * npoly);
+    UVO_HIP_TRY(c, hipMemcpyAsync(d_coeffs, w->h_models.data(), sizeof(double) * 11 * npoly, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_solve_poly10, dim3((npoly + kFpPerWg - 1) / kFpPerWg), dim3(64), 0, st, d_coeffs, npoly, d_re, d_im, w->counts);
+    UVO_HIP_TRY(c, hipGetLastError());
+    UVO_HIP_TRY(c, hipMemcpyAsync(w->h_models.data(), d_re, sizeof(double) * 10 * npoly, hipMemcpyDeviceToHost, st));
+    UVO_HIP_TRY(c, hipMemcpyAsync(w->h_models.data() + (size_t)10 * kMaxHyp, d_im, sizeof(double) * 10 * npoly, hipMemcpyDeviceToHost, st));
+    UVO_HIP_TRY(c, hipMemcpyAsync(w->h_counts.data(), w->counts, sizeof(int) * 5 * npoly, hipMemcpyDeviceToHost, st));
+    UVO_HIP_TRY(c, host_sync(c, st));
+    memcpy(roots_re, w->h_models.data(), sizeof(double) * 10 * npoly);
+    memcpy(roots_im, w->h_models.data() + (size_t)10 * kMaxHyp, sizeof(double) * 10 * npoly);
+    if (stats) memcpy(stats, w->h_counts.data(), sizeof(int) * 5 * npoly);
+    return UVO_OK;
+}
+
 // decomposeEssentialMat (host; 3x3 Jacobi SVD)
 static void decompose_essential(const double* E, double* R1, double* R2, double* t)
 {
@@ -1318,6 +1379,29 @@ uvo_status mono_find_homography(Ctx* c, const uvo_point2f* p1, const uvo_point2f
     }
     if (!result) memset(mask, 0, n);
     *ok = result;
+    return UVO_OK;
+}
+
+// test hook (uvo_homography_models): the four-point hypothesis kernel alone on subsets of the caller's, launched as above; no checkSubset
+uvo_status mono_homography_models(Ctx* c, const float* src, const float* dst, int n, const int* subsets, int nsub, double* models, int* nmodels)
+{
+    if (n > c->cap) { c->err = "point count exceeds the context's max_kpts"; return UVO_CAPACITY; }
+    if (nsub > kMaxHyp) { c->err = "subset count exceeds the compiled hypothesis capacity (2048)"; return UVO_CAPACITY; }
+    MonoWs* w = mono_ws(c);
+    if (!w) { c->err = "mono workspace allocation failed"; return UVO_HIP_ERROR; }
+    hipStream_t st = c->stream;
+    memcpy(w->h_src.data(), src, sizeof(float) * 2 * n); memcpy(w->h_dst.data(), dst, sizeof(float) * 2 * n);
+    memcpy(w->h_subsets.data(), subsets, sizeof(int) * 4 * nsub);
+    UVO_HIP_TRY(c, hipMemcpyAsync(w->src, w->h_src.data(), sizeof(float) * 2 * n, hipMemcpyHostToDevice, st));
+    UVO_HIP_TRY(c, hipMemcpyAsync(w->dst, w->h_dst.data(), sizeof(float) * 2 * n, hipMemcpyHostToDevice, st));
+    UVO_HIP_TRY(c, hipMemcpyAsync(w->subsets, w->h_subsets.data(), sizeof(int) * 4 * nsub, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_h_hyp, dim3((nsub + kHPerWg - 1) / kHPerWg), dim3(64), 0, st, w->src, w->dst, w->subsets, nsub, w->models, w->nmodels);
+    UVO_HIP_TRY(c, hipGetLastError());
+    UVO_HIP_TRY(c, hipMemcpyAsync(w->h_nmodels.data(), w->nmodels, sizeof(int) * nsub, hipMemcpyDeviceToHost, st));
+    UVO_HIP_TRY(c, hipMemcpyAsync(w->h_models.data(), w->models, sizeof(double) * 9 * nsub, hipMemcpyDeviceToHost, st));
+    UVO_HIP_TRY(c, host_sync(c, st));
+    memcpy(nmodels, w->h_nmodels.data(), sizeof(int) * nsub);
+    for (int i = 0; i < nsub; i++) if (nmodels[i] == 1) memcpy(models + (size_t)9 * i, w->h_models.data() + (size_t)9 * i, sizeof(double) * 9);
     return UVO_OK;
 }
 

@@ -425,6 +425,8 @@ void mono_ws_free(Ctx* c);
 uvo_status mono_find_essential(Ctx* c, const uvo_point2f* p1, const uvo_point2f* p2, int n, const double* K, int method,
                                double prob, double threshold, int maxIters, double* E, uint8_t* mask, int* ok);
 uvo_status mono_five_point_models(Ctx* c, const double* q1, const double* q2, int n, const int* subsets, int nsub, double* models, int* nmodels);
+uvo_status mono_solve_poly10(Ctx* c, const double* coeffs, int npoly, double* roots_re, double* roots_im, int* stats);
+uvo_status mono_homography_models(Ctx* c, const float* src, const float* dst, int n, const int* subsets, int nsub, double* models, int* nmodels);
 uvo_status mono_recover_pose(Ctx* c, const double* E, const uvo_point2f* p1, const uvo_point2f* p2, int n, const double* K,
                              double* R, double* t, uint8_t* mask, int* good);
 uvo_status mono_find_homography(Ctx* c, const uvo_point2f* p1, const uvo_point2f* p2, int n, int method, double thr, int maxIters,

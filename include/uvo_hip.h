@@ -287,6 +287,16 @@ uvo_status uvo_find_essential_mat(uvo_ctx* c, const uvo_point2f* p1, const uvo_p
  * points (host), subsets: nsub x 5 indices into them (any indices in [0, n), repeats included), nsub <= 2048 (the compiled hypothesis
  * capacity, UVO_CAPACITY beyond).  models: nsub x 10 x 9 f64, nmodels: nsub (host); only the first nmodels[i] models of row i are written. */
 uvo_status uvo_five_point_models(uvo_ctx* c, const double* q1, const double* q2, int n, const int* subsets, int nsub, double* models, int* nmodels);
+/* test hook: cv::solvePoly as the five-point hypothesis kernel runs it -- the same device function, four polynomials per wave -- on
+ * polynomials of the caller's.  coeffs: npoly x 11 f64, increasing powers (host), npoly <= 2048 (UVO_CAPACITY beyond).  roots_re, roots_im:
+ * npoly x 10 f64 (host).  stats: npoly x 5 ints or NULL, per polynomial and counted only until its own iteration stopped: the degree used;
+ * the sweeps run (1..300); the sweeps in which the polynomial itself met a zero root difference; the sweeps its wave redid with the
+ * zero-difference test; 1 if its wave ran the runtime-degree code (some polynomial of the wave has a degree below 10). */
+uvo_status uvo_solve_poly10(uvo_ctx* c, const double* coeffs, int npoly, double* roots_re, double* roots_im, int* stats);
+/* test hook: the four-point homography hypothesis kernel on its own, launched as uvo_find_homography launches it, WITHOUT that call's
+ * subset check.  src, dst: n x 2 f32 pixel points (host), subsets: nsub x 4 indices into them (any indices in [0, n)), nsub <= 2048
+ * (UVO_CAPACITY beyond).  models: nsub x 9 f64, nmodels: nsub (host), 0 or 1; row i of models is written only when nmodels[i] is 1. */
+uvo_status uvo_homography_models(uvo_ctx* c, const float* src, const float* dst, int n, const int* subsets, int nsub, double* models, int* nmodels);
 /* cv::recoverPose(E, p1, p2, K, R, t, mask), distance threshold 50 (VO_utility.cpp:149); mask is in/out */
 uvo_status uvo_recover_pose(uvo_ctx* c, const double* E, const uvo_point2f* p1, const uvo_point2f* p2, int n, const double* K,
                             double* R, double* t, uint8_t* mask, int* good);

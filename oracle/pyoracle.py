@@ -346,7 +346,8 @@ def solve_poly(coeffs):
     c = _c(coeffs, np.float64); n = len(c) - 1
     re = np.empty(n); im = np.empty(n)
     lib().orc_solve_poly(_p(c), n, _p(re), _p(im))
-    return re + 1j * im
+    roots = np.empty(n, np.complex128); roots.real = re; roots.imag = im      # (re + 1j * im would turn an infinite part into NaN)
+    return roots
 
 
 def jacobi_eigen(A):
@@ -382,6 +383,14 @@ def find_homography(p1, p2, method=8, thr=0.1, max_iters=2000, conf=0.99):
     H = np.zeros((3, 3)); mask = np.zeros(max(len(p1), 1), np.uint8)
     ok = lib().orc_find_homography(_p(p1), _p(p2), len(p1), method, C.c_double(thr), max_iters, C.c_double(conf), _p(H), _p(mask))
     return bool(ok), H, mask[:len(p1)].copy()
+
+
+def homography_kernel(M, m):
+    """HomographyEstimatorCallback::runKernel on the points as given (no subset check): the model, or None where it returns none."""
+    M = _c(M, np.float32); m = _c(m, np.float32)
+    H = np.full(9, np.nan)
+    n = lib().orc_homography_kernel(_p(M), _p(m), len(M), _p(H))
+    return H.reshape(3, 3) if n > 0 else None
 
 
 def decompose_homography(H, K):

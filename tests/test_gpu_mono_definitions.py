@@ -37,8 +37,9 @@ def test_five_point_kernel_solutions(uctx, kind, nsub):
     and 7 in every case; at nsub = 129, 1 of 129 (0.8 %) in the coplanar case and 0 elsewhere.
     Pure sideways translation with R = I does NOT reach the reduced-degree (NC = 0) Durand-Kerner path: that path is taken when the
     leading coefficient is at most DBL_EPSILON in absolute value, and over these subsets it is never below 9.8e-5 (the solver's own SVD
-    null-space basis is not aligned with [t]_x).  NOT COVERED by any case here: the NC = 0 path, and the CHECKED re-sweep after a zero
-    root difference (nothing observable from outside says whether a subset took it).
+    null-space basis is not aligned with [t]_x).  The NC = 0 path and the CHECKED re-sweep after a zero root difference, which no choice
+    of image points reaches in a controlled way, are held bit for bit to a scalar statement of cv::solvePoly by
+    tests/test_gpu_solve_poly.py, through a hook on the polynomial itself that reports which path each row of a wave took.
     The `duplicate` case repeats one correspondence inside each subset: the 5 x 9 system has rank 4, no solution set is defined, and
     only finiteness, the count and the constraints are asserted.  Every loop of the kernel has a fixed bound -- the Jacobi SVD sweeps,
     the ten elimination steps, the 300 Durand-Kerner sweeps (an early exit can only shorten them), the 3 x 3 SVD per root -- so no

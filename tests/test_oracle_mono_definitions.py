@@ -9,6 +9,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import homography4_np as H4
 import mono_definitions_np as M
 
 
@@ -81,6 +82,52 @@ def test_recover_pose_of_an_estimated_essential_matrix(oracle):
     st = M.check_recover_pose(E, p1, p2, K, mask, g, R, t, mo, M.POSE_TOL_R, M.POSE_TOL_T)
     print(g, st)
     assert st["undecided_share"] <= 0.01 and st["decided"]
+
+
+# ------------------------------------------------------------------------------------------------------------------ four-point homography
+def test_homography_kernel_against_the_dlt_statement(oracle):
+    """oracle.homography_kernel (HomographyEstimatorCallback::runKernel, no subset check) against definitions_np.homography_dlt on the
+    four-point cases of tests/homography4_np.py, both scaled to H[2, 2] = 1, the difference relative to ||H||.  Largest difference
+    observed per family: generic 1.6e-10 (a noise-free subset with three points close to a line), exact 1.6e-13, near 8.2e-10,
+    scale 2.0e-13; the bound, here and for the HIP kernel (tests/test_gpu_homography_models.py), is twice that
+    (homography4_np.H4_OBSERVED / H4_BOUND).  Each model also maps its four src points onto its dst points within that bound carried
+    through the projective division (observed: below 1.1e-3 of the allowance)."""
+    worst = {}
+    for case in H4.LIVE:
+        H = oracle.homography_kernel(case.src, case.dst)
+        assert H is not None and np.isfinite(H).all(), case
+        d = H4.model_difference(H, H4.statement(case))
+        worst[case.family] = max(worst.get(case.family, 0.0), d)
+        assert d <= H4.H4_BOUND[case.family], (case, d)
+        assert H4.interpolation_excess(H, case, H4.H4_BOUND[case.family]) <= 1.0, case
+    print(worst)
+    assert sorted(worst) == sorted(H4.H4_BOUND) and all(H4.H4_BOUND[f] == 2 * H4.H4_OBSERVED[f] for f in worst)
+
+
+def test_homography_kernel_degenerate_subsets_give_no_model(oracle):
+    assert [c.name for c in H4.DEGENERATE] == ["degenerate-src-x", "degenerate-dst-y", "degenerate-one-point"]
+    for case in H4.DEGENERATE:
+        assert oracle.homography_kernel(case.src, case.dst) is None, case
+
+
+def test_homography_kernel_recovers_exact_maps(oracle):
+    """A translation, an axis scaling by 2 and a quarter turn about the image centre, each on a square and on a quadrilateral with
+    integer corners: the planted model comes back within the `exact` family's bound (observed 1.5e-13)."""
+    exact = [c for c in H4.LIVE if c.family == "exact"]
+    assert len(exact) == 6
+    for case in exact:
+        assert np.array_equal(H4.apply_h(case.planted, case.src), case.dst.astype(np.float64))        # the points are exact images
+        d = H4.model_difference(oracle.homography_kernel(case.src, case.dst), case.planted)
+        print(case, d)
+        assert d <= H4.H4_BOUND["exact"], (case, d)
+
+
+def test_mistake_homography_rows_swapped_is_rejected(oracle):
+    """The check tells a transposed model from the right one."""
+    case = H4.BY_NAME["generic-clean0"]
+    H = oracle.homography_kernel(case.src, case.dst)
+    assert H4.model_difference(H.T, H4.statement(case)) > H4.H4_BOUND["generic"]
+    assert H4.interpolation_excess(H.T, case, H4.H4_BOUND["generic"]) > 1.0
 
 
 # ------------------------------------------------------------------------------------------------------------------ seeded mistakes
