@@ -6,6 +6,7 @@
                      s = size * 1.2 / 9, centred on the keypoint and clamped to the image; area-averaged to 21 x 21 grey levels (8-bit,
                      round to nearest); 20 x 20 Haar differences weighted by a sigma = 3.3 Gaussian; 4 x 4 cells of 5 x 5 samples, each
                      (sum dx, sum dy, sum |dx|, sum |dy|); unit length.
+                     surf_patch / surf_tail are its two halves, shared with the oriented and the extended branch (tests/surf_oriented_np.py).
   * cv_rng_stream / ransac_subsets   cv::RNG's multiply-with-carry generator and RANSAC's subset draws (ptsetreg.cpp getSubset).
   * homography_dlt   the normalised 4-point (or n-point) direct linear transform.
   * pose_polish      maximum-likelihood polish of a PnP pose (scipy least_squares on the reprojection residuals)."""
@@ -50,12 +51,17 @@ def surf_window(img: np.ndarray, x: float, y: float, size: float):
     return img[np.ix_(ys, xs)].T.astype(np.float64), win            # [i: +x][j: -y]
 
 
-def surf64_upright(img: np.ndarray, x: float, y: float, size: float) -> np.ndarray:
-    win, n = surf_window(img, x, y, size)
-    if win is None:
-        return None
-    W = area_weights(n, 21)
-    patch = np.clip(round_half_even(W @ win @ W.T), 0, 255)          # 21 x 21 grey levels, 8-bit
+def surf_patch(win: np.ndarray) -> np.ndarray:
+    """The square window area-averaged to 21 x 21 grey levels (8-bit, round to nearest)."""
+    W = area_weights(win.shape[0], 21)
+    return np.clip(round_half_even(W @ win @ W.T), 0, 255)
+
+
+def surf_tail(patch: np.ndarray, extended=False, swap_halves=False) -> np.ndarray:
+    """21 x 21 grey levels -> the unit descriptor row: 20 x 20 Haar differences under the sigma = 3.3 Gaussian, 4 x 4 cells of 5 x 5
+    samples.  A cell holds (sum tx, sum ty, sum |tx|, sum |ty|); extended, it holds (sum tx, sum |tx|) over the samples with ty >= 0,
+    then over those with ty < 0, then (sum ty, sum |ty|) over tx >= 0, then over tx < 0.  (`swap_halves`: a seeded mistake, the two
+    halves of every split exchanged.)"""
     g = gaussian_kernel()
     dw = np.outer(g, g)
     p00, p01, p10, p11 = patch[:-1, :-1], patch[:-1, 1:], patch[1:, :-1], patch[1:, 1:]
@@ -65,9 +71,22 @@ def surf64_upright(img: np.ndarray, x: float, y: float, size: float) -> np.ndarr
     for ci in range(4):
         for cj in range(4):
             a, b = vx[ci * 5:ci * 5 + 5, cj * 5:cj * 5 + 5], vy[ci * 5:ci * 5 + 5, cj * 5:cj * 5 + 5]
-            out += [a.sum(), b.sum(), np.abs(a).sum(), np.abs(b).sum()]
+            if not extended:
+                out += [a.sum(), b.sum(), np.abs(a).sum(), np.abs(b).sum()]
+                continue
+            up, right = (b >= 0) != swap_halves, (a >= 0) != swap_halves
+            for t, first in ((a, up), (b, right)):
+                for half in (first, ~first):
+                    out += [t[half].sum(), np.abs(t[half]).sum()]
     out = np.array(out)
     return out / (np.sqrt((out * out).sum()) + np.finfo(np.float32).eps)
+
+
+def surf64_upright(img: np.ndarray, x: float, y: float, size: float) -> np.ndarray:
+    win, n = surf_window(img, x, y, size)
+    if win is None:
+        return None
+    return surf_tail(surf_patch(win))
 
 
 # ---------------------------------------------------------------------------------------------- cv::RNG, RANSAC subsets

@@ -19,7 +19,9 @@ Lowe's ratio test; DLT triangulation; VO_utility.cpp:188-237 for the 3-D filter;
   * solvePnPRansac recovers a planted pose, and its inliers reproject within the threshold under it.
 
 get_image, the preprocessing in front of the detectors, has its second statement in tests/preproc_definitions_np.py
-(tests/test_gpu_preproc_definitions.py holds the HIP kernels to it); AKAZE and SIFT in tests/detector_definitions_np.py."""
+(tests/test_gpu_preproc_definitions.py holds the HIP kernels to it); AKAZE and SIFT in tests/detector_definitions_np.py; the oriented and
+the extended SURF branch (surf_orientation, surf_window_rotated, surf_descriptor) in tests/surf_oriented_np.py, held by
+tests/test_gpu_surf_oriented_definitions.py."""
 import numpy as np
 import pytest
 

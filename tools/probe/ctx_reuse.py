@@ -2,9 +2,12 @@
 """Pipelined C3 rate of the 1st .. 5th context of ONE process, each destroyed before the next is created
 ("a context created after another one was destroyed runs ~10 % below its rate").
   UVO_STREAM_POOL=0 python tools/probe/ctx_reuse.py      # the runtime's own create / destroy
-  python tools/probe/ctx_reuse.py                         # streams parked in the library's pool"""
+  python tools/probe/ctx_reuse.py                         # streams parked in the library's pool
+The comparison is about which hardware queue a stream is bound to, so it needs a queue per stream of the six lanes: the probe runs
+with 16 whatever the caller's environment says (with an inherited 4 the lanes share queues, the loop runs at ~3300 pairs/s instead
+of ~5000 and the five rates scatter by 6-9 %, which says nothing about the binding).  UVO_PROBE_HW_QUEUES=n measures another count."""
 import os, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
+os.environ["GPU_MAX_HW_QUEUES"] = os.environ.get("UVO_PROBE_HW_QUEUES", "16")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
 import ergo_uvo_amd as uvo
