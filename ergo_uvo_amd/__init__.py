@@ -261,18 +261,22 @@ class Context:
             raise ValueError("orb_set_pattern: 256 x (x0, y0, x1, y1)")
         self._check(self._lib.uvo_orb_set_pattern(self._h, _p(pat)))
 
-    def orb_detect(self, img, cap=None, descriptors=True):
+    def orb_detect(self, img, cap=None, descriptors=True, width=None):
         """detect_features, FEATURE_DETECTOR == "ORB" (VO_utility.cpp:100-105): ORB::create(10000, 1.2, 8, 31, 0, 2, HARRIS_SCORE, 31, 10)
         ->detectAndCompute.  Returns (keypoints, n x 32 uint8 rBRIEF rows) -- rows for match_features_hamming; descriptors need
-        orb_set_pattern (descriptors=False: keypoints only)."""
-        h, w = img.shape[-2], img.shape[-1]
+        orb_set_pattern (descriptors=False: keypoints only).  `width`: the image is the first `width` columns of `img`, whose rows are
+        img.shape[-1] bytes apart (a pitched image)."""
+        h, pitch = img.shape[-2], img.shape[-1]
+        w = pitch if width is None else int(width)
+        if not 0 < w <= pitch:
+            raise ValueError("orb_detect: width must lie in 1 .. the row pitch")
         p, mem, keep = _ptr_mem(img, np.uint8)
         cap = int(cap if cap is not None else self.max_kpts)
         n = C.c_int(0)
         kps = np.empty(cap, KP_DTYPE)
         desc = np.empty((cap, 32), np.uint8) if descriptors else None
         self._order_after_producer(img)
-        self._check(self._lib.uvo_orb_detect(self._h, p, w, h, w, mem, _p(kps), _p(desc) if descriptors else None, cap, C.byref(n)))
+        self._check(self._lib.uvo_orb_detect(self._h, p, w, h, pitch, mem, _p(kps), _p(desc) if descriptors else None, cap, C.byref(n)))
         return kps[:n.value], (desc[:n.value] if descriptors else None)
 
     def orb_plane(self, level: int, what: int):
