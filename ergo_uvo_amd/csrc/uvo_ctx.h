@@ -237,6 +237,15 @@ struct Ctx {
     hipEvent_t evDet = nullptr, evPrevRead = nullptr; bool prev_read_pending = false;
     std::thread worker; std::mutex mu; std::condition_variable cv; bool quit = false;
     std::mutex b_mu; std::condition_variable b_cv; int b_running = 0, max_b = 3;   // master: PnP stages running / allowed at once
+    // The pipeline's HIP streams belong to the MASTER, by role (0 stage A, 1 PnP) and concurrency slot; a lane's `stream` / `pnp_stream`
+    // are handles assigned per entry (ctx.hip: "streams by role and slot"), never created or destroyed by the lane.
+    hipStream_t slot_streams[2][16] = {};        // master: [role][slot], created at first need (slot_stream)
+    bool shared_slots = false;                   // master: the stereo loop shares streams by slot (set_depth: fewer hardware queues than 2 x depth) -- else a pair per lane
+    int n_b = 1;                                 // master: PnP streams of the shared layout (max_b + 1)
+    long long b_seq = 0;                         // master: PnP stages started by the workers (under b_mu): stage k runs on PnP slot k mod n_b
+    long long a_launch = 0;                      // master: stage-A launch sets queued so far (a two-pair set counts once): set t runs on A slot t mod (a_overlap + 1)
+    long long plan_seq = 0;                      // master: pipelined entries planned so far (never reset) ..
+    long long assigned_seq = -1;                 // lane: .. and the entry this lane's handles were last assigned for
     int max_b_mono = 10;                         // ... and mono pose stages (env UVO_MAX_B_MONO): 2 ms of host-orchestrated, latency-bound kernels each (the
                                                  // five-point solver keeps one wave per SIMD busy for 0.9 ms), so many of them side by side cost little
 
