@@ -356,18 +356,31 @@ class Context:
         return out[:m.value].copy()
 
     def match_features_hamming(self, descriptors1, descriptors2, ratio=None, matches=None):
-        """The AKAZE / ORB branch of match_features (VO_utility.cpp:520-524): uint8 rows of up to 64 bytes, Hamming distance."""
+        """The AKAZE / ORB branch of match_features (VO_utility.cpp:520-524): uint8 rows of up to 64 bytes, Hamming distance.
+        Both sets as numpy arrays, or both as contiguous CUDA uint8 tensors."""
         ratio = float(self.params.LOWE_RATIO_THRESHOLD if ratio is None else ratio)
-        d1, d2 = _np(descriptors1, np.uint8), _np(descriptors2, np.uint8)
-        if d1.ndim != 2 or d2.ndim != 2 or d1.shape[1] != d2.shape[1]:
-            raise ValueError("binary descriptors: two uint8 matrices with the same number of columns")
+        p1, p2, n1, n2, nbytes, mem, _keep = self._binary_rows(descriptors1, descriptors2)
         prev = 0 if matches is None else len(matches)
-        out = np.zeros(prev + max(len(d1), 1), DM_DTYPE)
+        out = np.zeros(prev + max(n1, 1), DM_DTYPE)
         if prev:
             out[:prev] = matches
         m = C.c_int(prev)
-        self._check(self._lib.uvo_match_knn2_ratio_hamming(self._h, _p(d1), len(d1), _p(d2), len(d2), d1.shape[1], 0, C.c_float(ratio), _p(out), len(out), C.byref(m)))
+        self._check(self._lib.uvo_match_knn2_ratio_hamming(self._h, p1, n1, p2, n2, nbytes, mem, C.c_float(ratio), _p(out), len(out), C.byref(m)))
         return out[:m.value].copy()
+
+    @staticmethod
+    def _binary_rows(descriptors1, descriptors2):
+        """(pointer1, pointer2, n1, n2, bytes per row, mem, keepalive) of two sets of binary descriptors in one memory space"""
+        for d in (descriptors1, descriptors2):
+            if _is_device(d) and str(d.dtype) != "torch.uint8":
+                raise ValueError("binary descriptors on the device must be uint8 tensors")
+        p1, m1, k1 = _ptr_mem(descriptors1, np.uint8)
+        p2, m2, k2 = _ptr_mem(descriptors2, np.uint8)
+        if m1 != m2:
+            raise ValueError("descriptors1 and descriptors2 must live in the same memory space")
+        if k1.ndim != 2 or k2.ndim != 2 or k1.shape[1] != k2.shape[1]:
+            raise ValueError("binary descriptors: two uint8 matrices with the same number of columns")
+        return p1, p2, int(k1.shape[0]), int(k2.shape[0]), int(k1.shape[1]), m1, (k1, k2)
 
     def loop_knn_match_binary(self, descriptors1, descriptors2, metric="hamming"):
         """Test hook (uvo_match_loop_knn2): the fused steps' kNN-2 on uint8 rows -- metric "hamming" (stereo loop) or "l2" (mono loop's
@@ -381,10 +394,10 @@ class Context:
         return idx, dist
 
     def knn_match_hamming(self, descriptors1, descriptors2):
-        d1, d2 = _np(descriptors1, np.uint8), _np(descriptors2, np.uint8)
-        idx = np.empty((len(d1), 2), np.int32)
-        dist = np.empty((len(d1), 2), np.float32)
-        self._check(self._lib.uvo_match_knn2_hamming(self._h, _p(d1), len(d1), _p(d2), len(d2), d1.shape[1], 0, _p(idx), _p(dist)))
+        p1, p2, n1, n2, nbytes, mem, _keep = self._binary_rows(descriptors1, descriptors2)
+        idx = np.empty((n1, 2), np.int32)
+        dist = np.empty((n1, 2), np.float32)
+        self._check(self._lib.uvo_match_knn2_hamming(self._h, p1, n1, p2, n2, nbytes, mem, _p(idx), _p(dist)))
         return idx, dist
 
     def _check_desc_width(self, *descs, dim=None):

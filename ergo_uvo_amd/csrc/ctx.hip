@@ -919,6 +919,22 @@ static uvo_status stage_rows(uvo_ctx* c, int slot, const void* d, int n, size_t 
     *out = c->d_tmp_desc[slot];
     return UVO_OK;
 }
+// one side of a binary matcher call as match_knn2_bin reads it: rows padded to kBinRowWords words in the lower half of the side's staging
+// buffer (cap x 512 bytes).  Host rows go raw into the upper half first; device rows are padded straight from the caller's pointer.
+static uvo_status stage_pad_binary(uvo_ctx* c, int slot, const uint8_t* d, int n, int bytes, int mem, const uint8_t** out)
+{
+    if (n > c->cap) return fail(c, UVO_CAPACITY, "descriptor count exceeds the context's max_kpts");
+    uint8_t* rows = reinterpret_cast<uint8_t*>(c->d_tmp_desc[slot]);
+    const uint8_t* raw = d;
+    if (mem != UVO_MEM_DEVICE) {
+        uint8_t* staged = rows + (size_t)c->cap * 256;
+        if (n) UVO_HIP_TRY(c, hipMemcpyAsync(staged, d, (size_t)bytes * n, hipMemcpyHostToDevice, c->stream));
+        raw = staged;
+    }
+    UVO_TRY(pad_binary_rows(c, c->stream, raw, n, bytes, rows));
+    *out = rows;
+    return UVO_OK;
+}
 
 // Row width of the standalone matchers for the duration of one call.  The entries without a `dim` argument match THIS CONTEXT'S SURF
 // rows -- SURF::descriptorSize() = 64, or 128 with SURF_EXTENDED -- whatever detector the fused steps are switched to
@@ -931,7 +947,8 @@ static bool match_sets_ok(const uvo_ctx* c, const void* d1, int n1, const void* 
 // The prologue: lane 0 must be idle; an empty set is answered at once (*go stays false: "no neighbour" from the k-NN entries, which give
 // idx and dist, nothing appended by the ratio entries); else both sets are staged behind the producer and the 2-NN kernels queued, on
 // float rows of the open DimScope's width (bytes == 0: match_features' L2 arm) or binary rows of `bytes` bytes (VO_utility.cpp:520-524:
-// AKAZE / ORB, Hamming distance).  `who` is the entry that the messages name.
+// AKAZE / ORB, Hamming distance: padded once, then the fused steps' kernels with host counts, the grid sized from n1 / n2).  `who` is
+// the entry that the messages name.
 static uvo_status match_prologue(uvo_ctx* c, const char* who, const void* d1, int n1, const void* d2, int n2, int bytes, int mem, int* idx, float* dist, bool* go)
 {
     *go = false;
@@ -942,12 +959,18 @@ static uvo_status match_prologue(uvo_ctx* c, const char* who, const void* d1, in
         if (n2 == 0) { for (int i = 0; i < 2 * n1; i++) { idx[i] = -1; dist[i] = FLT_MAX; } return UVO_OK; }
     } else if (n1 == 0 || n2 == 0) return UVO_OK;          // knnMatch on an empty query/train set yields no matches
     UVO_TRY(wait_for_producer(c, c, mem));
-    const size_t row_bytes = bytes ? (size_t)bytes : sizeof(float) * c->desc_dim();
-    const void *q, *t;
-    UVO_TRY(stage_rows(c, 0, d1, n1, row_bytes, mem, &q));
-    UVO_TRY(stage_rows(c, 1, d2, n2, row_bytes, mem, &t));
-    UVO_TRY(bytes ? match_knn2_hamming(c, static_cast<const uint8_t*>(q), n1, static_cast<const uint8_t*>(t), n2, bytes)
-                  : match_knn2(c, static_cast<const float*>(q), nullptr, n1, static_cast<const float*>(t), nullptr, n2));
+    if (bytes) {
+        const uint8_t *q, *t;
+        UVO_TRY(stage_pad_binary(c, 0, static_cast<const uint8_t*>(d1), n1, bytes, mem, &q));
+        UVO_TRY(stage_pad_binary(c, 1, static_cast<const uint8_t*>(d2), n2, bytes, mem, &t));
+        UVO_TRY(match_knn2_bin(c, BIN_HAMMING, q, nullptr, n1, t, nullptr, n2));
+    } else {
+        const size_t row_bytes = sizeof(float) * c->desc_dim();
+        const void *q, *t;
+        UVO_TRY(stage_rows(c, 0, d1, n1, row_bytes, mem, &q));
+        UVO_TRY(stage_rows(c, 1, d2, n2, row_bytes, mem, &t));
+        UVO_TRY(match_knn2(c, static_cast<const float*>(q), nullptr, n1, static_cast<const float*>(t), nullptr, n2));
+    }
     *go = true;
     return UVO_OK;
 }
@@ -1026,14 +1049,9 @@ try {
     if (n1 > c->cap || n2 > c->cap) return fail(c, UVO_CAPACITY, "descriptor count exceeds the context's max_kpts");
     (void)hipSetDevice(c->device);
     UVO_TRY(need_idle(c, "uvo_match_loop_knn2"));
-    uint8_t* rows[2];
+    const uint8_t* rows[2];
     const uint8_t* src[2] = { d1, d2 }; const int n[2] = { n1, n2 };
-    for (int i = 0; i < 2; i++) {                      // raw rows in the upper half of the staging buffer (cap x 512 bytes), padded rows in the lower
-        rows[i] = reinterpret_cast<uint8_t*>(c->d_tmp_desc[i]);
-        uint8_t* raw = rows[i] + (size_t)c->cap * 256;
-        if (n[i]) UVO_HIP_TRY(c, hipMemcpyAsync(raw, src[i], (size_t)bytes * n[i], hipMemcpyHostToDevice, c->stream));
-        UVO_TRY(pad_binary_rows(c, c->stream, raw, n[i], bytes, rows[i]));
-    }
+    for (int i = 0; i < 2; i++) UVO_TRY(stage_pad_binary(c, i, src[i], n[i], bytes, UVO_MEM_HOST, &rows[i]));
     UVO_HIP_TRY(c, hipMemcpyAsync(c->d_tmp_idx, n, sizeof(n), hipMemcpyHostToDevice, c->stream));
     UVO_HIP_TRY(c, hipStreamSynchronize(c->stream));
     UVO_TRY(match_knn2_bin(c, metric, rows[0], c->d_tmp_idx, c->cap, rows[1], c->d_tmp_idx + 1, c->cap));

@@ -339,9 +339,10 @@ uvo_status surf_detect_lanes(Ctx* c, Ctx* c2, int nimg, int gate_min_features); 
 uvo_status surf_hessian_layer_debug(Ctx* c, int octave, int layer, float* det, float* trace);
 // match.hip
 uvo_status match_knn2(Ctx* c, const float* d_q, const int* d_nq, int nq_max, const float* d_t, const int* d_nt, int nt_max);
-uvo_status match_knn2_hamming(Ctx* c, const uint8_t* d_q, int nq, const uint8_t* d_t, int nt, int bytes);
-// kNN-2 on the fused steps' binary rows (kBinRowWords words each, zero-padded), counts on the device (d_n*: device pointer or null,
-// then n*_max): metric 0 Hamming (stereo loop: VOU:520-524), 1 exact L2 of the bytes (mono loop: BFMatcher(NORM_L2) on CV_8U, VOU:551-573).
+// kNN-2 on binary rows (kBinRowWords words each, zero-padded: the fused steps' rows as the detectors leave them, the standalone Hamming
+// entries' after pad_binary_rows), counts on the device (d_n*: device pointer or null, then n*_max is the count): metric 0 Hamming
+// (match_features' AKAZE / ORB branch and the stereo loop: VOU:520-524), 1 exact L2 of the bytes (mono loop: BFMatcher(NORM_L2) on CV_8U,
+// VOU:551-573).
 // Results in slot 0 (and 1) of the kNN buffers, as match_knn2 / match_knn2_two leave them.
 enum { BIN_HAMMING = 0, BIN_L2 = 1 };
 uvo_status match_knn2_bin(Ctx* c, int metric, const uint8_t* d_q, const int* d_nq, int nq_max, const uint8_t* d_t, const int* d_nt, int nt_max);

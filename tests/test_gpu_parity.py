@@ -899,6 +899,42 @@ def test_hamming_branch_of_match_features_bit_exact(ctx, oracle, bytes_):
             assert np.array_equal(m["distance"].view(np.uint32), om["distance"].view(np.uint32))
 
 
+@pytest.mark.parametrize("bytes_", [32, 61])
+@pytest.mark.parametrize("odd_base", [False, True])
+def test_hamming_branch_takes_device_rows_bit_exact(ctx, oracle, bytes_, odd_base):
+    """The same entries on rows that are already on the device (UVO_MEM_DEVICE): padded straight from the caller's pointer, which
+    need not be aligned -- a fresh allocation, and a view that starts one byte into a larger buffer (odd base address).  257 x 513:
+    two query workgroups, two train chunks, a duplicate row on either side of the chunk boundary."""
+    import torch
+    rng = np.random.default_rng(1000 + bytes_)
+    n1, n2 = 257, 513
+    a = rng.integers(0, 256, (n1, bytes_), dtype=np.uint8)
+    b = rng.integers(0, 256, (n2, bytes_), dtype=np.uint8)
+    b[512] = b[7]
+    a[:4] = b[7]                                        # distance 0 twice: indices 7 and 512 must come out in that order
+
+    def dev(x):
+        if not odd_base:
+            return torch.from_numpy(x).cuda()
+        buf = torch.zeros(x.size + 1, dtype=torch.uint8, device="cuda")
+        buf[1:] = torch.from_numpy(x.ravel()).cuda()
+        t = buf[1:].view(x.shape)
+        assert t.data_ptr() % 2 == 1 and t.is_contiguous()
+        return t
+
+    da, db = dev(a), dev(b)
+    torch.cuda.synchronize()                            # the library works on its own streams: device inputs must be complete
+    idx, dist = ctx.knn_match_hamming(da, db)
+    oidx, odist = oracle.knn2_hamming(a, b)
+    assert idx[:4].tolist() == [[7, 512]] * 4
+    assert np.array_equal(idx, oidx)
+    assert np.array_equal(dist.view(np.uint32), odist.view(np.uint32))
+    for ratio in (0.8, 0.97):
+        m, om = ctx.match_features_hamming(da, db, ratio), oracle.match_hamming(a, b, ratio)
+        assert np.array_equal(m["queryIdx"], om["queryIdx"]) and np.array_equal(m["trainIdx"], om["trainIdx"])
+        assert np.array_equal(m["distance"].view(np.uint32), om["distance"].view(np.uint32))
+
+
 def test_sift_arm_of_the_l2_branch_bit_exact(ctx, oracle):
     """VO_utility.cpp:525-529: "SIFT" descriptors go to the same BFMatcher(NORM_L2) as SURF's; they are 128 floats per row whatever
     SURF_EXTENDED says (this context's own rows are 64 wide).  SIFT rows are small non-negative integers stored as floats, so equal
