@@ -674,7 +674,7 @@ static uvo_status jh_plan(Ctx* m, Ctx* const* lanes, size_t n_lanes, int nimg, c
     bool fits = true;
     for (size_t l = 0; l < n_lanes; l++) for (int i = 0; i < nimg; i++) fits = fits && jh_fits(jh_ws(lanes[l])->slot[i], jobs[i].need);
     if (fits) return UVO_OK;
-    if (m->n_pending != 0) { m->err = "the lanes' JPEG workspaces must grow (a larger payload or picture) while entries are in flight: collect first"; return UVO_CAPACITY; }
+    if (m->sh->n_pending != 0) { m->err = "the lanes' JPEG workspaces must grow (a larger payload or picture) while entries are in flight: collect first"; return UVO_CAPACITY; }
     for (size_t l = 0; l < n_lanes; l++) {
         UVO_HIP_TRY(m, hipStreamSynchronize(lanes[l]->stream));
         for (int i = 0; i < nimg; i++) UVO_TRY(jh_grow_slot(m, jh_ws(lanes[l])->slot[i], jobs[i].need));
@@ -791,7 +791,7 @@ uvo_status codec_compressed_plan(Ctx* m, int nimg, const uint8_t* const* data, c
 }
 uvo_status codec_compressed_workspaces(Ctx* m, int nimg)
 {
-    return jh_plan(m, m->lanes.data(), m->lanes.size(), nimg, jh_ws(m)->job);
+    return jh_plan(m, m->sh->lanes.data(), m->sh->lanes.size(), nimg, jh_ws(m)->job);
 }
 uvo_status codec_compressed_queue(Ctx* m, Ctx* L, int i, const uint8_t** d_rgb)
 {

@@ -113,7 +113,7 @@ static hipError_t trace_alloc(Ctx* c)
 // every context of a process gets the first one's binding.  UVO_STREAM_POOL=0 restores create / destroy (measurement).
 namespace {
 std::mutex g_pool_mu;
-hipStream_t g_pool[64][2][uvo::Ctx::kMaxDepth];            // [device][role: 0 stage A, 1 PnP][slot]
+hipStream_t g_pool[64][2][uvo::Shared::kMaxDepth];            // [device][role: 0 stage A, 1 PnP][slot]
 bool pool_on() { static const bool on = !(getenv("UVO_STREAM_POOL") && atoi(getenv("UVO_STREAM_POOL")) == 0); return on; }
 // (Round 3 tried the highest stream priority for the PnP streams, so that their 1..8-workgroup kernels would be dispatched ahead of
 // queued detection tiles: no effect on a fresh context -- 3792 / 4309 pairs/s with, 3774 / 4308 without, 20- / 600-step forms --
@@ -127,7 +127,7 @@ hipError_t stream_acquire(int device, int role, int slot_i, hipStream_t* out)
         if (hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && greatest != least)
             return hipStreamCreateWithPriority(out, hipStreamNonBlocking, greatest);
     }
-    if (pool_on() && slot_i >= 0 && slot_i < uvo::Ctx::kMaxDepth) {
+    if (pool_on() && slot_i >= 0 && slot_i < uvo::Shared::kMaxDepth) {
         std::lock_guard<std::mutex> lk(g_pool_mu);
         hipStream_t& slot = g_pool[device & 63][role][slot_i];
         if (slot) { *out = slot; slot = nullptr; return hipSuccess; }
@@ -138,7 +138,7 @@ void stream_release(int device, int role, int slot_i, hipStream_t s)
 {
     if (!s) return;
     (void)hipStreamSynchronize(s);
-    if (pool_on() && !(role == 1 && pnp_priority()) && slot_i >= 0 && slot_i < uvo::Ctx::kMaxDepth) {
+    if (pool_on() && !(role == 1 && pnp_priority()) && slot_i >= 0 && slot_i < uvo::Shared::kMaxDepth) {
         std::lock_guard<std::mutex> lk(g_pool_mu);
         hipStream_t& slot = g_pool[device & 63][role][slot_i];
         if (!slot) { slot = s; return; }                    // (two live contexts of one process: the second one's streams are its own)
@@ -148,7 +148,7 @@ void stream_release(int device, int role, int slot_i, hipStream_t s)
 }  // namespace
 
 // ------------------------------------------------------------------------------------------ streams by role and slot
-// The master context owns the pipeline's streams, [role][slot]; a lane's `stream` / `pnp_stream` are handles, assigned when an entry
+// The context's Shared owns the pipeline's streams, [role][slot]; a lane's `stream` / `pnp_stream` are handles, assigned when an entry
 // is planned.  Two layouts (set_depth chooses; profiles/r09_stream_slots.json, DESIGN.md sections 4 and 5):
 //  * a stream pair per lane (slot = lane in both roles), when the process has a hardware queue for each of them: GPU_MAX_HW_QUEUES >=
 //    2 x depth.  This is the layout up to round 8 and the faster one where it fits (5000 pairs/s at 16 queues, depth 6).
@@ -178,10 +178,10 @@ void stream_release(int device, int role, int slot_i, hipStream_t s)
 // stage-A stream from the lane's worker, keeps a stream pair per lane in either layout.
 static hipStream_t slot_stream(uvo::Ctx* m, int role, int slot_i)
 {
-    slot_i = std::min(std::max(slot_i, 0), (int)uvo::Ctx::kMaxDepth - 1);
-    hipStream_t& s = m->slot_streams[role][slot_i];
+    slot_i = std::min(std::max(slot_i, 0), (int)uvo::Shared::kMaxDepth - 1);
+    hipStream_t& s = m->sh->slot_streams[role][slot_i];
     if (!s) {
-        if (stream_acquire(m->device, role, slot_i, &s) != hipSuccess) { s = nullptr; return m->slot_streams[role][0]; }   // (slot 0 exists from creation on)
+        if (stream_acquire(m->device, role, slot_i, &s) != hipSuccess) { s = nullptr; return m->sh->slot_streams[role][0]; }   // (slot 0 exists from creation on)
         // first use of a stream: its hardware queue and the queue's scratch are set up now, not inside a running pipeline (see prime_lanes)
         hipLaunchKernelGGL(k_prime, dim3(1), dim3(64), 0, s, m->d_countsB, 1);
         (void)hipStreamSynchronize(s);
@@ -190,38 +190,38 @@ static hipStream_t slot_stream(uvo::Ctx* m, int role, int slot_i)
 }
 static void sync_owned_streams(uvo::Ctx* m)
 {
-    for (int role = 0; role < 2; role++) for (hipStream_t s : m->slot_streams[role]) if (s) (void)hipStreamSynchronize(s);
+    for (int role = 0; role < 2; role++) for (hipStream_t s : m->sh->slot_streams[role]) if (s) (void)hipStreamSynchronize(s);
 }
 // hardware queues this process gets: what the operator (or this library's constructor) put in the environment, else ROCm's default
 static int hw_queues() { const char* q = getenv("GPU_MAX_HW_QUEUES"); const int n = q ? atoi(q) : 4; return n > 0 ? n : 4; }
 // Measurement switches: UVO_STREAM_SLOTS = 0 | 1 forces the per-lane / the shared layout, UVO_A_STREAMS / UVO_B_STREAMS set the shared layout's slot counts
 static bool shared_layout(int depth) { static const char* e = getenv("UVO_STREAM_SLOTS"); return e ? atoi(e) != 0 : hw_queues() < 2 * depth; }
-static bool a_per_lane(const uvo::Ctx* m, int depth) { return !m->shared_slots || m->a_overlap == 0 || depth <= m->a_overlap; }
-static int a_shared_streams(const uvo::Ctx* m) { static const int e = getenv("UVO_A_STREAMS") ? atoi(getenv("UVO_A_STREAMS")) : 0; return std::min(16, std::max(m->a_overlap, e > 0 ? e : m->a_overlap + 1)); }
+static bool a_per_lane(const uvo::Ctx* m, int depth) { return !m->sh->shared_slots || m->sh->a_overlap == 0 || depth <= m->sh->a_overlap; }
+static int a_shared_streams(const uvo::Ctx* m) { static const int e = getenv("UVO_A_STREAMS") ? atoi(getenv("UVO_A_STREAMS")) : 0; return std::min((int)Shared::kMaxDepth, std::max(m->sh->a_overlap, e > 0 ? e : m->sh->a_overlap + 1)); }
 static int stereo_a_streams(const uvo::Ctx* m, int depth) { return a_per_lane(m, depth) ? depth : a_shared_streams(m); }
 static int stereo_a_slot(const uvo::Ctx* m, int depth, int lane, long long launch) { return a_per_lane(m, depth) ? lane : (int)(launch % a_shared_streams(m)); }
 // a lane's handles for the entry about to be planned on it (idempotent per entry: the frames entries call it before their body does)
 static void assign_entry_streams(uvo::Ctx* m, uvo::Ctx* L, bool stereo, hipStream_t join = nullptr)
 {
-    if (L->assigned_seq == m->plan_seq) return;
-    L->assigned_seq = m->plan_seq;
-    const int depth = (int)m->lanes.size();
+    if (L->assigned_seq == m->sh->plan_seq) return;
+    L->assigned_seq = m->sh->plan_seq;
+    const int depth = (int)m->sh->lanes.size();
     if (!stereo) { L->stream = slot_stream(m, 0, L->lane_id); L->pnp_stream = slot_stream(m, 1, L->lane_id); return; }
-    L->stream = join ? join : slot_stream(m, 0, stereo_a_slot(m, depth, L->lane_id, m->a_launch++));
-    L->pnp_stream = slot_stream(m, 1, m->shared_slots ? (int)(m->plan_seq % m->n_b) : L->lane_id);
+    L->stream = join ? join : slot_stream(m, 0, stereo_a_slot(m, depth, L->lane_id, m->sh->a_launch++));
+    L->pnp_stream = slot_stream(m, 1, m->sh->shared_slots ? (int)(m->sh->plan_seq % m->sh->n_b) : L->lane_id);
 }
 // an idle pipeline's handles: lane i on the slots its first entries will use (set_depth; prime_lanes then touches every stream once)
 static void assign_idle_streams(uvo::Ctx* m)
 {
-    const int depth = (int)m->lanes.size();
-    m->shared_slots = shared_layout(depth);
-    m->n_b = std::min(16, m->max_b + 1);
-    if (const char* e = getenv("UVO_B_STREAMS")) m->n_b = std::min(16, std::max(1, atoi(e)));
-    m->a_launch = 0;
-    if (m->shared_slots) for (int i = 0; i < m->n_b; i++) (void)slot_stream(m, 1, i);      // (the workers only look streams up)
-    for (uvo::Ctx* l : m->lanes) {
+    const int depth = (int)m->sh->lanes.size();
+    m->sh->shared_slots = shared_layout(depth);
+    m->sh->n_b = std::min((int)Shared::kMaxDepth, m->sh->max_b + 1);
+    if (const char* e = getenv("UVO_B_STREAMS")) m->sh->n_b = std::min((int)Shared::kMaxDepth, std::max(1, atoi(e)));
+    m->sh->a_launch = 0;
+    if (m->sh->shared_slots) for (int i = 0; i < m->sh->n_b; i++) (void)slot_stream(m, 1, i);      // (the workers only look streams up)
+    for (uvo::Ctx* l : m->sh->lanes) {
         l->stream = slot_stream(m, 0, stereo_a_slot(m, depth, l->lane_id, l->lane_id));
-        l->pnp_stream = slot_stream(m, 1, m->shared_slots ? l->lane_id % m->n_b : l->lane_id);
+        l->pnp_stream = slot_stream(m, 1, m->sh->shared_slots ? l->lane_id % m->sh->n_b : l->lane_id);
         l->assigned_seq = -1;
     }
 }
@@ -240,7 +240,7 @@ static const char* unsupported_params(const uvo_params* p)
 // why the calling thread's last uvo_ctx_create refused its parameters: there is no context to hold the message, uvo_last_error(NULL) hands it out
 static thread_local const char* t_create_refusal = nullptr;
 
-static uvo_status create_one(const uvo_params* p, int device, int max_w, int max_h, int max_kpts, uvo_ctx** out, int lane = 0, uvo_ctx* master = nullptr)
+static uvo_status create_one(const uvo_params* p, int device, int max_w, int max_h, int max_kpts, uvo_ctx** out, int lane = 0, Shared* sh = nullptr)
 {
     if (!out) return UVO_INVALID_ARG;
     *out = nullptr;
@@ -251,7 +251,9 @@ static uvo_status create_one(const uvo_params* p, int device, int max_w, int max
     if (hipSetDevice(device) != hipSuccess) return UVO_HIP_ERROR;
     uvo_ctx* c = new (std::nothrow) uvo_ctx();
     if (!c) return UVO_HIP_ERROR;
-    c->p = *p; c->device = device; c->max_w = max_w; c->max_h = max_h; c->cap = max_kpts; c->lane_id = lane; c->master = master;
+    c->sh = sh ? sh : new (std::nothrow) Shared();        // lane 0 makes what every further lane points to
+    if (!c->sh) { delete c; return UVO_HIP_ERROR; }
+    c->p = *p; c->device = device; c->max_w = max_w; c->max_h = max_h; c->cap = max_kpts; c->lane_id = lane;
     const size_t cap = (size_t)max_kpts;
     const size_t npx = (size_t)max_w * max_h, nsum = (size_t)(max_w + 1) * (max_h + 1);
     const int nstrip = (max_h + 7) / 8;                          // integral image: strips of 8 rows (surf.hip)
@@ -259,9 +261,9 @@ static uvo_status create_one(const uvo_params* p, int device, int max_w, int max
     const size_t nchunks = (cap + 127) / 128;                   // matcher shortlist: (cap/128) x cap float4 (match.hip)
     hipError_t e = hipSuccess;
 #define A(expr) do { if (e == hipSuccess) e = (expr); } while (0)
-    // the master creates slot 0 of both roles; a further lane borrows them until set_depth hands out the pipeline's handles
-    if (master) { c->stream = master->slot_streams[0][0]; c->pnp_stream = master->slot_streams[1][0]; }
-    else { A(stream_acquire(device, 0, 0, &c->slot_streams[0][0])); c->stream = c->slot_streams[0][0]; }
+    // lane 0 creates slot 0 of both roles; a further lane borrows them until set_depth hands out the pipeline's handles
+    if (lane != 0) { c->stream = c->sh->slot_streams[0][0]; c->pnp_stream = c->sh->slot_streams[1][0]; }
+    else { A(stream_acquire(device, 0, 0, &c->sh->slot_streams[0][0])); c->stream = c->sh->slot_streams[0][0]; }
     A(hipEventCreate(&c->ev0)); A(hipEventCreate(&c->ev1));
     c->plane_pw = ((max_w + 1 + 3) / 4 + 1 + 1) & ~1;            // even: the integral kernel stores pairs of plane entries
     c->plane_stride = c->plane_pw * ((max_h + 1 + 3) / 4 + 1);
@@ -297,7 +299,7 @@ static uvo_status create_one(const uvo_params* p, int device, int max_w, int max
     A(hipEventCreateWithFlags(&c->evSync, hipEventDisableTiming));
     A(hipEventCreateWithFlags(&c->evProducer, hipEventDisableTiming));
     A(hipEventCreateWithFlags(&c->evDet, hipEventDisableTiming)); A(hipEventCreateWithFlags(&c->evPrevRead, hipEventDisableTiming));
-    if (!master) { A(stream_acquire(device, 1, 0, &c->slot_streams[1][0])); c->pnp_stream = c->slot_streams[1][0]; }
+    if (lane == 0) { A(stream_acquire(device, 1, 0, &c->sh->slot_streams[1][0])); c->pnp_stream = c->sh->slot_streams[1][0]; }
     A(dalloc(&c->d_countsB, (size_t)4)); A(hipHostMalloc(reinterpret_cast<void**>(&c->h_countsB), sizeof(int) * 4));
     A(dalloc(&c->d_counts, (size_t)CN_TOTAL));
     A(dalloc(&c->d_subsets, (size_t)kMaxHyp * 5)); A(dalloc(&c->d_models, (size_t)kMaxHyp * 6)); A(dalloc(&c->d_hcount, (size_t)kMaxHyp));
@@ -343,9 +345,9 @@ static void write_trace(uvo_ctx* c)
     struct Row { long long pair; int lane; float t[6]; };
     std::vector<Row> rows;
     hipEvent_t ref = nullptr; long long ref_pair = -1;
-    for (Ctx* l : c->lanes) for (auto& r : l->trace) if (r.pair >= 0 && (ref_pair < 0 || r.pair < ref_pair)) { ref = r.ev[0]; ref_pair = r.pair; }
+    for (Ctx* l : c->sh->lanes) for (auto& r : l->trace) if (r.pair >= 0 && (ref_pair < 0 || r.pair < ref_pair)) { ref = r.ev[0]; ref_pair = r.pair; }
     if (!ref) return;
-    for (Ctx* l : c->lanes) for (auto& r : l->trace) {
+    for (Ctx* l : c->sh->lanes) for (auto& r : l->trace) {
         if (r.pair < 0) continue;
         Row w; w.pair = r.pair; w.lane = l->lane_id;
         for (int k = 0; k < 6; k++) { w.t[k] = -1.f; if (k < 3 || r.b_used) (void)hipEventElapsedTime(&w.t[k], ref, r.ev[k]); }
@@ -382,51 +384,51 @@ static double host_cpu_budget()
     return b;
 }
 // The context's waiting policy for its current depth (uvo_ctx.h: worker_wait, stage_b_mode), stored where the lanes' own threads read
-// it: an atomic per lane -- never the master's lane list, which set_depth rewrites while earlier lanes' workers are running.
+// it: an atomic per lane -- never the context's lane list, which set_depth rewrites while earlier lanes' workers are running.
 static void apply_wait_policy(uvo_ctx* c)
 {
-    const int depth = (int)c->lanes.size();
-    c->cpu_budget = host_cpu_budget();
+    const int depth = (int)c->sh->lanes.size();
+    c->sh->cpu_budget = host_cpu_budget();
     int eff = c->worker_wait == 0 ? 0 : (c->worker_wait == 2 ? 2 : 1);
-    if (c->worker_wait == 1 && c->cpu_budget >= 2.0 * (depth + 2)) eff = 0;      // (logical CPUs: a core per thread -- two ranks of eight busy threads on eight CPUs each ran a 16-CPU container into its throttle: 343 pairs/s)
-    for (Ctx* l : c->lanes) l->wait_eff.store(eff, std::memory_order_release);
-    if (const char* e = getenv("UVO_STAGE_B")) c->stage_b_mode = !strcmp(e, "device") ? 1 : (!strcmp(e, "worker") ? 0 : -1);
+    if (c->worker_wait == 1 && c->sh->cpu_budget >= 2.0 * (depth + 2)) eff = 0;      // (logical CPUs: a core per thread -- two ranks of eight busy threads on eight CPUs each ran a 16-CPU container into its throttle: 343 pairs/s)
+    for (Ctx* l : c->sh->lanes) l->wait_eff.store(eff, std::memory_order_release);
+    if (const char* e = getenv("UVO_STAGE_B")) c->sh->stage_b_mode = !strcmp(e, "device") ? 1 : (!strcmp(e, "worker") ? 0 : -1);
 }
 // does a pipelined pair of this context take the device-driven PnP round (uvo_ctx.h: stage_b_mode)?
 static bool stage_b_on_device(const uvo_ctx* c)
 {
-    if (c->stage_b_mode >= 0) return c->stage_b_mode == 1;
-    return c->cpu_budget < (double)c->lanes.size() + 3.0;                          // no CPU for a worker per lane beside the submitter
+    if (c->sh->stage_b_mode >= 0) return c->sh->stage_b_mode == 1;
+    return c->sh->cpu_budget < (double)c->sh->lanes.size() + 3.0;                          // no CPU for a worker per lane beside the submitter
 }
 
 static uvo_status set_depth(uvo_ctx* c, int depth)
 {
-    if (depth < 1 || depth > Ctx::kMaxDepth) { c->err = "pipeline depth must be 1..16"; return UVO_INVALID_ARG; }
-    if (c->n_pending != 0) { c->err = "pipeline depth cannot change while pairs are in flight"; return UVO_INVALID_ARG; }
-    while ((int)c->lanes.size() > depth) { destroy_one(static_cast<uvo_ctx*>(c->lanes.back())); c->lanes.pop_back(); }
-    while ((int)c->lanes.size() < depth) {
+    if (depth < 1 || depth > Shared::kMaxDepth) { c->err = "pipeline depth must be 1..16"; return UVO_INVALID_ARG; }
+    if (c->sh->n_pending != 0) { c->err = "pipeline depth cannot change while pairs are in flight"; return UVO_INVALID_ARG; }
+    while ((int)c->sh->lanes.size() > depth) { destroy_one(static_cast<uvo_ctx*>(c->sh->lanes.back())); c->sh->lanes.pop_back(); }
+    while ((int)c->sh->lanes.size() < depth) {
         uvo_ctx* l = nullptr;
-        uvo_status st = create_one(&c->p, c->device, c->max_w, c->max_h, c->cap, &l, (int)c->lanes.size(), c);
+        uvo_status st = create_one(&c->p, c->device, c->max_w, c->max_h, c->cap, &l, (int)c->sh->lanes.size(), c->sh);
         if (st != UVO_OK) { c->err = "could not allocate a further pipeline lane"; return st; }
-        l->lane_id = (int)c->lanes.size(); l->timing = c->timing;
+        l->lane_id = (int)c->sh->lanes.size(); l->timing = c->timing;
         if (c->trace_on && !l->trace_on && trace_alloc(l) != hipSuccess) { destroy_one(l); c->err = "could not allocate a further pipeline lane"; return UVO_HIP_ERROR; }
-        c->lanes.push_back(l);
+        c->sh->lanes.push_back(l);
     }
     apply_wait_policy(c);
     assign_idle_streams(c);                     // the pipeline is idle (nothing in flight): every lane's handles are dealt afresh
-    c->warning.clear();
+    c->sh->warning.clear();
     {
         const int nq = hw_queues();
         if (depth > 2 && nq < 2 * depth)
-            c->warning = "GPU_MAX_HW_QUEUES = " + std::to_string(nq) + " with " + std::to_string(depth) + " pipeline lanes: no hardware queue per lane and role, so the "
-                         "stereo pipeline shares " + std::to_string(stereo_a_streams(c, depth)) + " stage-A + " + std::to_string(c->n_b) + " PnP streams among its lanes "
+            c->sh->warning = "GPU_MAX_HW_QUEUES = " + std::to_string(nq) + " with " + std::to_string(depth) + " pipeline lanes: no hardware queue per lane and role, so the "
+                         "stereo pipeline shares " + std::to_string(stereo_a_streams(c, depth)) + " stage-A + " + std::to_string(c->sh->n_b) + " PnP streams among its lanes "
                          "(measured at 4 queues and depth 6 only: 4000 pairs/s against 5000 with a queue per stream; other counts below " + std::to_string(2 * depth) +
                          " are unmeasured) and the mono pipeline's lanes share queues; set GPU_MAX_HW_QUEUES >= " +
                          std::to_string(2 * depth) + " before the HIP runtime starts for a stream pair and a queue per lane";
     }
     if (c->primed_w > 0) UVO_TRY(prime_lanes(c, c->primed_w, c->primed_h));                 // lanes added to a running sequence
     // the previous pair's "after stereo match" set may live in a lane that no longer exists: restart the sequence
-    if (c->prev_lane >= depth || c->next_lane >= depth) { c->vo_initialized = false; c->init_matches.clear(); c->prev_lane = 0; c->next_lane = 0; c->prev_sync = true; }
+    if (c->sh->prev_lane >= depth || c->sh->next_lane >= depth) { c->sh->vo_initialized = false; c->sh->init_matches.clear(); c->sh->prev_lane = 0; c->sh->next_lane = 0; c->sh->prev_sync = true; }
     return UVO_OK;
 }
 
@@ -437,7 +439,7 @@ static void precreate_streams(int device)
 {
     static const int order = getenv("UVO_STREAM_ORDER") ? atoi(getenv("UVO_STREAM_ORDER")) : 0;
     if (order < 1 || order > 2 || !pool_on()) return;
-    const int depth = getenv("UVO_PIPELINE_DEPTH") ? std::min((int)uvo::Ctx::kMaxDepth, std::max(1, atoi(getenv("UVO_PIPELINE_DEPTH")))) : 6;
+    const int depth = getenv("UVO_PIPELINE_DEPTH") ? std::min((int)uvo::Shared::kMaxDepth, std::max(1, atoi(getenv("UVO_PIPELINE_DEPTH")))) : 6;
     if (hipSetDevice(device) != hipSuccess) return;
     std::lock_guard<std::mutex> lk(g_pool_mu);
     int* sink = nullptr;
@@ -460,13 +462,13 @@ try {
     precreate_streams(device);
     uvo_status st = create_one(p, device, max_w, max_h, max_kpts, out);
     if (st != UVO_OK) return st;
-    (*out)->lanes.push_back(*out);
-    if (getenv("UVO_MAX_B")) (*out)->max_b = std::min(16, std::max(1, atoi(getenv("UVO_MAX_B"))));
-    if (getenv("UVO_A_OVERLAP")) (*out)->a_overlap = std::min(16, std::max(0, atoi(getenv("UVO_A_OVERLAP"))));
-    if (getenv("UVO_MAX_B_MONO")) (*out)->max_b_mono = std::min(16, std::max(1, atoi(getenv("UVO_MAX_B_MONO"))));
-    if (getenv("UVO_A_OVERLAP2")) (*out)->a_overlap2 = std::min(4, std::max(0, atoi(getenv("UVO_A_OVERLAP2"))));
-    if (getenv("UVO_BATCH")) (*out)->batch = atoi(getenv("UVO_BATCH")) == 2 ? 2 : 1;
-    if (getenv("UVO_A_OVERLAP_MONO")) (*out)->a_overlap_mono = std::min(8, std::max(0, atoi(getenv("UVO_A_OVERLAP_MONO"))));
+    (*out)->sh->lanes.push_back(*out);
+    if (getenv("UVO_MAX_B")) (*out)->sh->max_b = std::min((int)Shared::kMaxDepth, std::max(1, atoi(getenv("UVO_MAX_B"))));
+    if (getenv("UVO_A_OVERLAP")) (*out)->sh->a_overlap = std::min((int)Shared::kMaxDepth, std::max(0, atoi(getenv("UVO_A_OVERLAP"))));
+    if (getenv("UVO_MAX_B_MONO")) (*out)->sh->max_b_mono = std::min((int)Shared::kMaxDepth, std::max(1, atoi(getenv("UVO_MAX_B_MONO"))));
+    if (getenv("UVO_A_OVERLAP2")) (*out)->sh->a_overlap2 = std::min(4, std::max(0, atoi(getenv("UVO_A_OVERLAP2"))));
+    if (getenv("UVO_BATCH")) (*out)->sh->batch = atoi(getenv("UVO_BATCH")) == 2 ? 2 : 1;
+    if (getenv("UVO_A_OVERLAP_MONO")) (*out)->sh->a_overlap_mono = std::min(8, std::max(0, atoi(getenv("UVO_A_OVERLAP_MONO"))));
     st = set_depth(*out, 2);                      // two pairs in flight by default (uvo_stereo_set_depth changes it)
     if (st != UVO_OK) { uvo_ctx* made = *out; *out = nullptr; destroy_ctx(made); }
     return st;
@@ -476,8 +478,8 @@ extern "C" uvo_status uvo_stereo_set_batch(uvo_ctx* c, int pairs)
 try {
     if (!c) return UVO_INVALID_ARG;
     if (pairs != 1 && pairs != 2) { c->err = "uvo_stereo_set_batch: 1 or 2 pairs per launch set"; return UVO_INVALID_ARG; }
-    if (c->n_pending != 0) { c->err = "the launch mode cannot change while pairs are in flight"; return UVO_INVALID_ARG; }
-    c->batch = pairs;
+    if (c->sh->n_pending != 0) { c->err = "the launch mode cannot change while pairs are in flight"; return UVO_INVALID_ARG; }
+    c->sh->batch = pairs;
     return UVO_OK;
 } UVO_ABI_CATCH(c)
 
@@ -501,8 +503,8 @@ static void destroy_ctx(uvo_ctx* c)
                 uvo::g_bstat[8].load() / np, uvo::g_bstat[9].load() / np, uvo::g_bstat[10].load() / np, uvo::g_bstat[11].load() / np);
     }
     write_trace(c);
-    for (size_t i = c->lanes.size(); i > 1; i--) destroy_one(static_cast<uvo_ctx*>(c->lanes[i - 1]));
-    c->lanes.clear();
+    for (size_t i = c->sh->lanes.size(); i > 1; i--) destroy_one(static_cast<uvo_ctx*>(c->sh->lanes[i - 1]));
+    c->sh->lanes.clear();
     destroy_one(c);
 }
 extern "C" void uvo_ctx_destroy(uvo_ctx* c)
@@ -517,8 +519,8 @@ static void destroy_one(uvo_ctx* c)
         c->cv.notify_all();
         c->worker.join();
     }
-    // whatever this lane queued ran on streams of the master's: all of them are waited for before a buffer goes
-    sync_owned_streams(c->master ? c->master : c);
+    // whatever this lane queued ran on the context's streams: all of them are waited for before a buffer goes
+    sync_owned_streams(c);
     for (int i = 0; i < 2; i++) {
         (void)hipFree(c->d_img[i]); (void)hipFree(c->d_sum_base[i]); (void)hipFree(c->d_planes[i]); (void)hipFree(c->d_cand[i]); (void)hipFree(c->det[i].kps);
         (void)hipFree(c->det[i].desc); (void)hipFree(c->d_tmp_desc[i]); (void)hipFree(c->d_matches[i]);
@@ -551,8 +553,10 @@ static void destroy_one(uvo_ctx* c)
     if (c->evPrevRead) (void)hipEventDestroy(c->evPrevRead);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
-    if (!c->master)                                                     // the pipeline's streams go back to the pool, each to its role and slot
-        for (int role = 0; role < 2; role++) for (int i = 0; i < Ctx::kMaxDepth; i++) { stream_release(c->device, role, i, c->slot_streams[role][i]); c->slot_streams[role][i] = nullptr; }
+    if (c->lane_id == 0) {                                              // the pipeline's streams go back to the pool, each to its role and slot
+        for (int role = 0; role < 2; role++) for (int i = 0; i < Shared::kMaxDepth; i++) { stream_release(c->device, role, i, c->sh->slot_streams[role][i]); c->sh->slot_streams[role][i] = nullptr; }
+        delete c->sh;                                                   // last: every other lane is gone (destroy_ctx, set_depth)
+    }
     delete c;
 }
 
@@ -561,19 +565,19 @@ extern "C" void* uvo_ctx_stream(uvo_ctx* c) { return c ? (void*)c->stream : null
 extern "C" uvo_status uvo_ctx_set_params(uvo_ctx* c, const uvo_params* p)
 try {
     if (!c || !p) return UVO_INVALID_ARG;
-    if (c->n_pending != 0) { c->err = "parameters cannot change while pairs are in flight"; return UVO_INVALID_ARG; }
+    if (c->sh->n_pending != 0) { c->err = "parameters cannot change while pairs are in flight"; return UVO_INVALID_ARG; }
     if (const char* why = unsupported_params(p)) { c->err = why; return UVO_INVALID_ARG; }
-    if ((p->SURF_EXTENDED != 0) != (c->p.SURF_EXTENDED != 0) && (c->vo_initialized || c->mono_initialized)) {
+    if ((p->SURF_EXTENDED != 0) != (c->p.SURF_EXTENDED != 0) && (c->sh->vo_initialized || c->sh->mono_initialized)) {
         c->err = "SURF_EXTENDED changes the descriptor width: the previous frame's descriptors held by the running VO loop would not match (uvo_stereo_reset / uvo_mono_reset first)";
         return UVO_INVALID_ARG;
     }
-    for (Ctx* l : c->lanes) l->p = *p;
+    for (Ctx* l : c->sh->lanes) l->p = *p;
     return UVO_OK;
 } UVO_ABI_CATCH(c)
 extern "C" uvo_status uvo_ctx_set_producer_stream(uvo_ctx* c, void* hip_stream, int enabled)
 try {
     if (!c) return UVO_INVALID_ARG;
-    c->producer_stream = static_cast<hipStream_t>(hip_stream); c->has_producer = enabled != 0;
+    c->sh->producer_stream = static_cast<hipStream_t>(hip_stream); c->sh->has_producer = enabled != 0;
     return UVO_OK;
 } UVO_ABI_CATCH(c)
 // device memory of the context's GPU for callers built without the HIP headers (the C++ layer over this ABI is plain C++)
@@ -602,31 +606,31 @@ try {
     if (bytes) UVO_HIP_TRY(c, hipMemcpy(host_dst, device_src, bytes, hipMemcpyDeviceToHost));
     return UVO_OK;
 } UVO_ABI_CATCH(c)
-extern "C" const char* uvo_ctx_warning(const uvo_ctx* c) { return c ? c->warning.c_str() : ""; }
-extern "C" int uvo_ctx_pending(const uvo_ctx* c) { return c ? c->n_pending : 0; }
+extern "C" const char* uvo_ctx_warning(const uvo_ctx* c) { return c ? c->sh->warning.c_str() : ""; }
+extern "C" int uvo_ctx_pending(const uvo_ctx* c) { return c ? c->sh->n_pending : 0; }
 extern "C" const char* uvo_ctx_host_policy(uvo_ctx* c)
 try {
     if (!c) return "";
     static const char* const wn[3] = { "poll", "timed-sleep+poll", "interrupt" };
     char buf[160];
     snprintf(buf, sizeof(buf), "wait=%s stage_b=%s cpu_budget=%.2f depth=%d", wn[c->wait_eff.load() % 3], stage_b_on_device(c) ? "device" : "worker",
-             c->cpu_budget > 1e8 ? -1.0 : c->cpu_budget, (int)c->lanes.size());
-    c->policy_text = buf;
-    return c->policy_text.c_str();
+             c->sh->cpu_budget > 1e8 ? -1.0 : c->sh->cpu_budget, (int)c->sh->lanes.size());
+    c->sh->policy_text = buf;
+    return c->sh->policy_text.c_str();
 } UVO_ABI_CATCH_RET(c, "")
 
 // UVO_MEM_DEVICE inputs: order lane L's next reads after the work queued so far on the declared producer stream
 static uvo_status wait_for_producer(uvo_ctx* m, Ctx* L, int mem)
 {
-    if (mem != UVO_MEM_DEVICE || !m->has_producer) return UVO_OK;
-    UVO_HIP_TRY(m, hipEventRecord(L->evProducer, m->producer_stream));
+    if (mem != UVO_MEM_DEVICE || !m->sh->has_producer) return UVO_OK;
+    UVO_HIP_TRY(m, hipEventRecord(L->evProducer, m->sh->producer_stream));
     UVO_HIP_TRY(m, hipStreamWaitEvent(L->stream, L->evProducer, 0));
     return UVO_OK;
 }
 // the standalone operators work on lane 0's buffers and stream: not while pipelined pairs or frames are in flight
 static uvo_status need_idle(uvo_ctx* c, const char* who)
 {
-    if (c->n_pending == 0) return UVO_OK;
+    if (c->sh->n_pending == 0) return UVO_OK;
     c->err = std::string(who) + ": collect the pairs / frames in flight first (the operator uses lane 0's buffers)";
     return UVO_INVALID_ARG;
 }
@@ -708,7 +712,7 @@ static uvo_status detect_dispatch(Ctx* c, int nimg, int gate_min_features = -1)
 // the detector's per-lane workspaces at the sequence's image size (allocation synchronises the device: done when a sequence starts, not in it)
 static uvo_status prepare_lane_detectors(uvo_ctx* c, int w, int h, int nimg)
 {
-    for (Ctx* l : c->lanes) {
+    for (Ctx* l : c->sh->lanes) {
         uvo_status st = UVO_OK;
         if (c->use_sift()) st = sift_prepare_lane(l, w, h, nimg);
         else if (c->loop_detector() == 2) st = akaze_prepare_lane(l, w, h);
@@ -731,42 +735,42 @@ static const EntryOpts kFramesEntry = { true, true };
 // ... and ONE list of refusals per step, tested by both entries before anything is queued on a lane; `who` is the entry the message names
 static uvo_status stereo_submit_refusal(uvo_ctx* c, const char* who)
 {
-    if (!c->rig_set) return fail(c, UVO_INVALID_ARG, "uvo_stereo_set_rig has not been called");
+    if (!c->sh->rig_set) return fail(c, UVO_INVALID_ARG, "uvo_stereo_set_rig has not been called");
     UVO_TRY(need_loop_table(c));
-    if (c->n_pending >= (int)c->lanes.size()) { c->err = std::string(who) + ": the pipeline is full; collect a pair first (uvo_stereo_set_depth)"; return UVO_INVALID_ARG; }
-    if (c->timing && c->n_pending > 0) return fail(c, UVO_INVALID_ARG, "timing mode measures one pair at a time: collect before submitting");
+    if (c->sh->n_pending >= (int)c->sh->lanes.size()) { c->err = std::string(who) + ": the pipeline is full; collect a pair first (uvo_stereo_set_depth)"; return UVO_INVALID_ARG; }
+    if (c->timing && c->sh->n_pending > 0) return fail(c, UVO_INVALID_ARG, "timing mode measures one pair at a time: collect before submitting");
     return UVO_OK;
 }
 static uvo_status mono_step_refusal(uvo_ctx* c)
 {
-    if (!c->mono_cam_set) return fail(c, UVO_INVALID_ARG, "uvo_mono_set_camera has not been called");
-    if (c->mono_pipelined) return fail(c, UVO_INVALID_ARG, "uvo_mono_step after uvo_mono_submit: call uvo_mono_reset first (the previous frame is held by the pipeline)");
+    if (!c->sh->mono_cam_set) return fail(c, UVO_INVALID_ARG, "uvo_mono_set_camera has not been called");
+    if (c->sh->mono_pipelined) return fail(c, UVO_INVALID_ARG, "uvo_mono_step after uvo_mono_submit: call uvo_mono_reset first (the previous frame is held by the pipeline)");
     return need_loop_table(c);
 }
 static uvo_status mono_submit_refusal(uvo_ctx* c, const char* who)
 {
-    if (!c->mono_cam_set) return fail(c, UVO_INVALID_ARG, "uvo_mono_set_camera has not been called");
-    if (c->lanes.size() < 2) return fail(c, UVO_INVALID_ARG, "uvo_mono_submit needs at least two lanes (uvo_stereo_set_depth): a frame is matched against the previous lane's buffers");
+    if (!c->sh->mono_cam_set) return fail(c, UVO_INVALID_ARG, "uvo_mono_set_camera has not been called");
+    if (c->sh->lanes.size() < 2) return fail(c, UVO_INVALID_ARG, "uvo_mono_submit needs at least two lanes (uvo_stereo_set_depth): a frame is matched against the previous lane's buffers");
     UVO_TRY(need_loop_table(c));
-    if (c->n_pending >= (int)c->lanes.size()) { c->err = std::string(who) + ": the pipeline is full; collect a frame first (uvo_stereo_set_depth)"; return UVO_INVALID_ARG; }
+    if (c->sh->n_pending >= (int)c->sh->lanes.size()) { c->err = std::string(who) + ": the pipeline is full; collect a frame first (uvo_stereo_set_depth)"; return UVO_INVALID_ARG; }
     return UVO_OK;
 }
 static uvo_status set_loop_detector(uvo_ctx* c, int det)
 {
-    if (c->n_pending != 0) return fail(c, UVO_INVALID_ARG, "the feature detector cannot change while pairs are in flight");
-    if (det != c->detector && (c->vo_initialized || c->mono_initialized))
+    if (c->sh->n_pending != 0) return fail(c, UVO_INVALID_ARG, "the feature detector cannot change while pairs are in flight");
+    if (det != c->sh->detector && (c->sh->vo_initialized || c->sh->mono_initialized))
         return fail(c, UVO_INVALID_ARG, "the feature detector changes the descriptors: the previous frame's set held by the running VO loop would not match (uvo_stereo_reset / uvo_mono_reset first)");
-    if (det != c->detector) {                                           // the lanes' workspaces of the detector left behind go (SIFT: 0.5 GB per image slot)
+    if (det != c->sh->detector) {                                           // the lanes' workspaces of the detector left behind go (SIFT: 0.5 GB per image slot)
         (void)hipSetDevice(c->device);
         sync_owned_streams(c);
-        for (Ctx* l : c->lanes) {
-            if (c->detector == 1) sift_ws_free(l);
+        for (Ctx* l : c->sh->lanes) {
+            if (c->sh->detector == 1) sift_ws_free(l);
             // lane 0's AKAZE / ORB workspaces are also the operators' (uvo_akaze_detect / uvo_orb_detect): they, and the ORB table, stay
-            if (l != c && c->detector == 2) akaze_ws_free(l);
-            if (l != c && c->detector == 3) orb_ws_free(l);
+            if (l != c && c->sh->detector == 2) akaze_ws_free(l);
+            if (l != c && c->sh->detector == 3) orb_ws_free(l);
         }
     }
-    c->detector = det;
+    c->sh->detector = det;
     return UVO_OK;
 }
 
@@ -789,15 +793,15 @@ try {
 } UVO_ABI_CATCH(c)
 
 // cv::solvePnPRansac's `flags` (visual_odometry.h:647-648; the values of stereo_VO_parameters.yaml:32) for every PnP stage of the
-// context: the operator, the synchronous step and all pipeline lanes read it from the master context (Ctx::pnp_p3p).
+// context: the operator, the synchronous step and all pipeline lanes read it from the context's Shared (Ctx::pnp_p3p).
 extern "C" uvo_status uvo_ctx_set_pnp_method(uvo_ctx* c, int flag)
 try {
     if (!c) return UVO_INVALID_ARG;
-    if (c->n_pending != 0) return fail(c, UVO_INVALID_ARG, "uvo_ctx_set_pnp_method: the PnP method cannot change while pairs are in flight (collect them first)");
+    if (c->sh->n_pending != 0) return fail(c, UVO_INVALID_ARG, "uvo_ctx_set_pnp_method: the PnP method cannot change while pairs are in flight (collect them first)");
     if (flag < 1 || flag > 4)
         return fail(c, UVO_INVALID_ARG, "uvo_ctx_set_pnp_method: served are 1 (cv::SOLVEPNP_EPNP), 2 (SOLVEPNP_P3P), 3 (SOLVEPNP_DLS) and 4 (SOLVEPNP_UPNP; 3 and 4 run EPnP, as in OpenCV 4.5); "
                                          "0 (SOLVEPNP_ITERATIVE), 5 (SOLVEPNP_AP3P) and above are not implemented");
-    c->pnp_method = flag;
+    c->sh->pnp_method = flag;
     return UVO_OK;
 } UVO_ABI_CATCH(c)
 
@@ -1228,13 +1232,13 @@ __global__ void k_gather_desc_idx(const float* src, int nsrc, const int* idx, in
 // collect and drop every entry in flight, stereo pairs and mono frames alike (each collect dequeues its entry even when the pair failed)
 static void drain_in_flight(uvo_ctx* c)
 {
-    while (c->n_pending > 0) {
-        const int e = c->inflight[0];
-        const bool mono = e == Ctx::kInflightMonoInit || (e >= 0 && c->lanes[e]->job.kind == 1);
-        const int before = c->n_pending;
+    while (c->sh->n_pending > 0) {
+        const int e = c->sh->inflight[0];
+        const bool mono = e == Shared::kInflightMonoInit || (e >= 0 && c->sh->lanes[e]->job.kind == 1);
+        const int before = c->sh->n_pending;
         uvo_mono_result rm; uvo_stereo_result rs;
         try { (void)(mono ? mono_collect_body(c, 1.0, &rm) : stereo_collect_body(c, 1.0, &rs)); } catch (...) { (void)abi_caught(c); }   // a failure is dropped with the result
-        if (c->n_pending == before) break;                 // cannot happen; never spin
+        if (c->sh->n_pending == before) break;                 // cannot happen; never spin
     }
 }
 
@@ -1243,15 +1247,15 @@ static uvo_status stereo_reset_body(uvo_ctx* c)
     (void)hipSetDevice(c->device);
     drain_in_flight(c);                                    // results of whatever is still in flight are dropped
     sync_owned_streams(c);
-    for (Ctx* l : c->lanes) {
+    for (Ctx* l : c->sh->lanes) {
         UVO_HIP_TRY(c, hipMemsetAsync(l->d_counts, 0, sizeof(int) * CN_TOTAL, l->stream));
         UVO_HIP_TRY(c, hipStreamSynchronize(l->stream));
         l->as_w = 0; l->pending = Ctx::Pending();
     }
-    c->vo_initialized = false; c->init_matches.clear(); c->stereo_init_results.clear();
-    c->prev_lane = 0; c->prev_buf = 0; c->prev_sync = true; c->next_lane = 0;
-    c->n_pending = 0; c->n_submitted = c->n_collected = 0;
-    for (int i = 0; i < 3; i++) c->t_prev_curr[i] = c->rvec[i] = c->tvec[i] = 0;
+    c->sh->vo_initialized = false; c->sh->init_matches.clear(); c->sh->stereo_init_results.clear();
+    c->sh->prev_lane = 0; c->sh->prev_buf = 0; c->sh->prev_sync = true; c->sh->next_lane = 0;
+    c->sh->n_pending = 0; c->sh->n_submitted = c->sh->n_collected = 0;
+    for (int i = 0; i < 3; i++) c->sh->t_prev_curr[i] = c->sh->rvec[i] = c->sh->tvec[i] = 0;
     return UVO_OK;
 }
 extern "C" uvo_status uvo_stereo_reset(uvo_ctx* c)
@@ -1259,12 +1263,12 @@ try { return c ? stereo_reset_body(c) : UVO_INVALID_ARG; } UVO_ABI_CATCH(c)
 extern "C" uvo_status uvo_stereo_set_rig(uvo_ctx* c, const double* K_left, const double* K_right, const double* R_right, const double* t_right)
 try {
     if (!c || !K_left || !K_right || !R_right || !t_right) return UVO_INVALID_ARG;
-    memcpy(c->K_left, K_left, sizeof(double) * 9); memcpy(c->K_right, K_right, sizeof(double) * 9);
-    memcpy(c->R_right, R_right, sizeof(double) * 9); memcpy(c->t_right, t_right, sizeof(double) * 3);
+    memcpy(c->sh->K_left, K_left, sizeof(double) * 9); memcpy(c->sh->K_right, K_right, sizeof(double) * 9);
+    memcpy(c->sh->R_right, R_right, sizeof(double) * 9); memcpy(c->sh->t_right, t_right, sizeof(double) * 3);
     const double I[9] = {1,0,0,0,1,0,0,0,1}, z[3] = {0,0,0};
-    projection_matrix(I, z, K_left, c->P_eye_left);               // VO:460
-    projection_matrix(R_right, t_right, K_right, c->P_right);     // VO:462
-    c->rig_set = true;
+    projection_matrix(I, z, K_left, c->sh->P_eye_left);               // VO:460
+    projection_matrix(R_right, t_right, K_right, c->sh->P_right);     // VO:462
+    c->sh->rig_set = true;
     return stereo_reset_body(c);
 } UVO_ABI_CATCH(c)
 
@@ -1277,7 +1281,7 @@ static uvo_status stereo_init_step(uvo_ctx* c, uvo_stereo_result* out)
     const int nL = c->h_counts[CN_NL], nR = c->h_counts[CN_NR];
     out->n_left = nL; out->n_right = nR;
     c->last_nL = nL; c->last_nR = nR; c->last_M = c->last_T = c->last_G = c->last_ninl = 0;
-    c->kp_hint = nL > nR ? nL : nR;
+    c->sh->kp_hint = nL > nR ? nL : nR;
     if (nL >= p.MIN_NUM_FEATURES && nR >= p.MIN_NUM_FEATURES) {                         // VO:489
         if (c->use_binary()) UVO_TRY(match_knn2_bin(c, BIN_HAMMING, reinterpret_cast<const uint8_t*>(c->det[0].desc), nullptr, nL,
                                                     reinterpret_cast<const uint8_t*>(c->det[1].desc), nullptr, nR));                // VOU:520-524
@@ -1286,25 +1290,25 @@ static uvo_status stereo_init_step(uvo_ctx* c, uvo_stereo_result* out)
         UVO_TRY(read_counts(c));
         int m = c->h_counts[CN_M];
         if (m > c->cap) return fail(c, UVO_CAPACITY, "stereo matches exceed max_kpts");
-        size_t old = c->init_matches.size();
-        c->init_matches.resize(old + m);                                                  // VOU:538 appends
-        if (m) UVO_HIP_TRY(c, hipMemcpyAsync(c->init_matches.data() + old, c->d_matches[0], sizeof(uvo_dmatch) * m, hipMemcpyDeviceToHost, c->stream));
+        size_t old = c->sh->init_matches.size();
+        c->sh->init_matches.resize(old + m);                                                  // VOU:538 appends
+        if (m) UVO_HIP_TRY(c, hipMemcpyAsync(c->sh->init_matches.data() + old, c->d_matches[0], sizeof(uvo_dmatch) * m, hipMemcpyDeviceToHost, c->stream));
         UVO_HIP_TRY(c, hipStreamSynchronize(c->stream));
-        if ((int)c->init_matches.size() > p.MIN_NUM_FEATURES) c->vo_initialized = true;  // VO:500
+        if ((int)c->sh->init_matches.size() > p.MIN_NUM_FEATURES) c->sh->vo_initialized = true;  // VO:500
     }
-    const int total = (int)c->init_matches.size();
+    const int total = (int)c->sh->init_matches.size();
     out->n_stereo_matches = total; c->last_M = total;
-    if (c->vo_initialized) {
+    if (c->sh->vo_initialized) {
         if (total > c->cap) return fail(c, UVO_CAPACITY, "accumulated init matches exceed max_kpts");
         // VO:508-520 with the reference's bounds checks (stale indices from failed attempts)
         std::vector<int> iL(total), iR(total), vL, vR;
-        for (int i = 0; i < total; i++) { iL[i] = c->init_matches[i].queryIdx; iR[i] = c->init_matches[i].trainIdx; }
+        for (int i = 0; i < total; i++) { iL[i] = c->sh->init_matches[i].queryIdx; iR[i] = c->sh->init_matches[i].trainIdx; }
         for (int i = 0; i < total; i++) { if (iL[i] >= 0 && iL[i] < nL) vL.push_back(iL[i]); if (iR[i] >= 0 && iR[i] < nR) vR.push_back(iR[i]); }
         if ((int)vL.size() != total || (int)vR.size() != total)
             return fail(c, UVO_INVALID_ARG, "stale stereo-init matches index past the current keypoints; the reference's "
                                             "keypoint/descriptor sets would go out of step (OpenCV asserts downstream)");
         const int b = c->as_w;         // lane 0 writes the first "after stereo match" set, synchronously
-        c->as_w ^= 1; c->prev_lane = 0; c->prev_buf = b; c->prev_sync = true;
+        c->as_w ^= 1; c->sh->prev_lane = 0; c->sh->prev_buf = b; c->sh->prev_sync = true;
         int* d_idx = c->d_tmp_idx;     // scratch
         UVO_HIP_TRY(c, hipMemcpyAsync(d_idx, iL.data(), sizeof(int) * total, hipMemcpyHostToDevice, c->stream));
         hipLaunchKernelGGL(k_gather_desc_idx, dim3((total + 15) / 16), dim3(256), 0, c->stream, c->det[0].desc, nL, d_idx, total, c->d_as_descL[b], c->loop_words());
@@ -1313,10 +1317,10 @@ static uvo_status stereo_init_step(uvo_ctx* c, uvo_stereo_result* out)
         UVO_HIP_TRY(c, hipMemcpyAsync(d_idx, iR.data(), sizeof(int) * total, hipMemcpyHostToDevice, c->stream));
         hipLaunchKernelGGL(k_gather_kps_idx, dim3((total + 255) / 256), dim3(256), 0, c->stream, c->det[1].kps, d_idx, total, c->d_as_kpsR[b]);
         UVO_HIP_TRY(c, hipMemcpyAsync(c->d_as_n + b, &total, sizeof(int), hipMemcpyHostToDevice, c->stream));
-        UVO_HIP_TRY(c, hipMemcpyAsync(c->d_matches[0], c->init_matches.data(), sizeof(uvo_dmatch) * total, hipMemcpyHostToDevice, c->stream));
+        UVO_HIP_TRY(c, hipMemcpyAsync(c->d_matches[0], c->sh->init_matches.data(), sizeof(uvo_dmatch) * total, hipMemcpyHostToDevice, c->stream));
         {   // the set's rows, triangulated for the pair that follows (every later pair does this in the tail of its stage A)
             const double I[9] = {1,0,0,0,1,0,0,0,1}, z[3] = {0,0,0};
-            UVO_TRY(pose_as_triangulate(c, c->stream, b, nullptr, total, c->P_eye_left, c->P_right, I, z, c->R_right, c->t_right, c->K_left, c->K_right));
+            UVO_TRY(pose_as_triangulate(c, c->stream, b, nullptr, total, c->sh->P_eye_left, c->sh->P_right, I, z, c->sh->R_right, c->sh->t_right, c->sh->K_left, c->sh->K_right));
         }
         UVO_HIP_TRY(c, hipStreamSynchronize(c->stream));
         UVO_HIP_TRY(c, hipGetLastError());
@@ -1342,14 +1346,14 @@ static void lane_await_done(uvo_ctx* L, double spin_us)
     L->job.state = 0; L->job_state_a.store(0, std::memory_order_release);
 }
 // The oldest entry in flight leaves the queue and is the one collected last: a lane's index (the lane holds no pending entry any more), or
-// Ctx::kInflightStereoInit / kInflightMonoInit (a synchronous init entry, which ran on lane 0)
+// Shared::kInflightStereoInit / kInflightMonoInit (a synchronous init entry, which ran on lane 0)
 static int pop_oldest_inflight(uvo_ctx* c)
 {
-    const int e = c->inflight[0];
-    for (int i = 1; i < c->n_pending; i++) c->inflight[i - 1] = c->inflight[i];
-    c->n_pending--; c->n_collected++;
-    c->last_lane = e < 0 ? 0 : e;
-    if (e >= 0) c->lanes[e]->pending.used = false;
+    const int e = c->sh->inflight[0];
+    for (int i = 1; i < c->sh->n_pending; i++) c->sh->inflight[i - 1] = c->sh->inflight[i];
+    c->sh->n_pending--; c->sh->n_collected++;
+    c->sh->last_lane = e < 0 ? 0 : e;
+    if (e >= 0) c->sh->lanes[e]->pending.used = false;
     return e;
 }
 // First use of a pipeline lane costs what every first use costs -- the hardware queues behind its two HIP streams are created at
@@ -1370,7 +1374,7 @@ __global__ void k_prime(int* sink, int n)
 }
 static uvo_status prime_lanes(uvo_ctx* c, int w, int h)
 {
-    for (Ctx* l : c->lanes) {
+    for (Ctx* l : c->sh->lanes) {
         if (l->primed_w == w && l->primed_h == h) continue;
         uvo_status st = surf_prepare(l, w, h);
         if (st != UVO_OK) { if (l != c) c->err = l->err; return st; }
@@ -1392,9 +1396,9 @@ static uvo_status prime_lanes(uvo_ctx* c, int w, int h)
 // lane's pinned mirror, an event marks completion and the lane's worker thread takes over for stage B.
 static uvo_status stereo_submit_body(uvo_ctx* c, const uint8_t* left, const uint8_t* right, int w, int h, int stride, int mem, EntryOpts o)
 {
-    const int depth = (int)c->lanes.size();
+    const int depth = (int)c->sh->lanes.size();
     const uvo_params& p = c->p;
-    if (!c->vo_initialized) {                                                               // VO:474-520, on lane 0, synchronous
+    if (!c->sh->vo_initialized) {                                                               // VO:474-520, on lane 0, synchronous
         // (earlier init pairs may still await their collect: they are complete, only their results are queued)
         uvo_stereo_result res;
         memset(&res, 0, sizeof(res));
@@ -1405,32 +1409,32 @@ static uvo_status stereo_submit_body(uvo_ctx* c, const uint8_t* left, const uint
         UVO_TRY(stereo_init_step(c, &res));
         UVO_TRY(prime_lanes(c, w, h));
         UVO_TRY(prepare_lane_detectors(c, w, h, 2));
-        c->stereo_init_results.push_back(res);
-        c->inflight[c->n_pending++] = Ctx::kInflightStereoInit; c->n_submitted++;
-        c->next_lane = 0;
+        c->sh->stereo_init_results.push_back(res);
+        c->sh->inflight[c->sh->n_pending++] = Shared::kInflightStereoInit; c->sh->n_submitted++;
+        c->sh->next_lane = 0;
         return UVO_OK;
     }
     // ---- plan: lane, buffers, what the pair reads from its predecessor; the sequential state moves on here, in submit order ----
-    const int li = c->next_lane;
+    const int li = c->sh->next_lane;
     Range r_submit("uvo:stereo_submit");
-    uvo_ctx* L = static_cast<uvo_ctx*>(c->lanes[li]);
+    uvo_ctx* L = static_cast<uvo_ctx*>(c->sh->lanes[li]);
     L->pending = Ctx::Pending();
     L->pending.used = true;
     Ctx::StagePlan& pl = L->plan;
-    pl.lane = li; pl.prev_lane = c->prev_lane; pl.prev_buf = c->prev_buf; pl.prev_sync = c->prev_sync; pl.curr = L->as_w;
-    pl.pending_before = c->n_pending; pl.trace_slot = -1;
+    pl.lane = li; pl.prev_lane = c->sh->prev_lane; pl.prev_buf = c->sh->prev_buf; pl.prev_sync = c->sh->prev_sync; pl.curr = L->as_w;
+    pl.pending_before = c->sh->n_pending; pl.trace_slot = -1;
     if (L->trace_on) {
         L->trace_cur = (int)(L->trace_count++ % Ctx::kTraceRing);
         pl.trace_slot = L->trace_cur;
         Ctx::TraceRec* tr = &L->trace[L->trace_cur];
-        tr->pair = c->n_submitted; tr->b_used = false; tr->det_marked = false;
+        tr->pair = c->sh->n_submitted; tr->b_used = false; tr->det_marked = false;
         for (double& v : tr->host_us) v = 0;
         tr->host_us[0] = uvo::now_us();
     }
     // a pair joins a two-pair launch when the mode is on and the pair can take that path: upright SURF, not the synchronous step,
     // no per-stage timing, two lanes at least, not an entry that goes alone
-    const bool may_batch = c->batch == 2 && !o.alone && depth >= 2 && !c->in_sync_step && !c->timing && c->loop_detector() == 0 && p.SURF_UPRIGHT && p.SURF_OCTAVES_NUMBER == 4;
-    uvo_ctx* S = c->stashed_lane >= 0 ? static_cast<uvo_ctx*>(c->lanes[c->stashed_lane]) : nullptr;      // the pair before, waiting for this one
+    const bool may_batch = c->sh->batch == 2 && !o.alone && depth >= 2 && !c->sh->in_sync_step && !c->timing && c->loop_detector() == 0 && p.SURF_UPRIGHT && p.SURF_OCTAVES_NUMBER == 4;
+    uvo_ctx* S = c->sh->stashed_lane >= 0 ? static_cast<uvo_ctx*>(c->sh->lanes[c->sh->stashed_lane]) : nullptr;      // the pair before, waiting for this one
     // The pair's streams ("streams by role and slot"): the stage-A slot of its launch set -- the second pair of a two-pair set rides on
     // the first one's stream, which runs the set's kernels -- and the PnP slot of a device-driven round.  (A frames entry has its handles
     // already: its get_image kernels are queued on them.)
@@ -1440,17 +1444,17 @@ static uvo_status stereo_submit_body(uvo_ctx* c, const uint8_t* left, const uint
     if (up == UVO_OK) up = surf_upload(L, 0, left, w, h, stride, mem);
     if (up == UVO_OK) up = surf_upload(L, 1, right, w, h, stride, mem);
     if (up != UVO_OK) { if (L != c) c->err = L->err; L->pending.used = false; return up; }
-    c->plan_seq++;                                             // the entry is planned: the next one gets handles of its own
+    c->sh->plan_seq++;                                             // the entry is planned: the next one gets handles of its own
     // state carry VO:727-733: this pair's set is the next pair's "prev"
     L->as_w = pl.curr ^ 1;
-    c->prev_lane = li; c->prev_buf = pl.curr; c->prev_sync = false;
-    c->next_lane = (li + 1) % depth;
-    c->inflight[c->n_pending++] = li; c->n_submitted++;
-    L->inline_b = c->in_sync_step;
+    c->sh->prev_lane = li; c->sh->prev_buf = pl.curr; c->sh->prev_sync = false;
+    c->sh->next_lane = (li + 1) % depth;
+    c->sh->inflight[c->sh->n_pending++] = li; c->sh->n_submitted++;
+    L->inline_b = c->sh->in_sync_step;
     L->job.kind = 0;                                           // a stereo pair (the lane is free: its worker holds no job)
     if (S && (!may_batch || S->img_w != L->img_w || S->img_h != L->img_h)) { UVO_TRY(queue_stage_a(c, S, nullptr)); S = nullptr; }   // cannot pair up: the waiting pair goes alone
     if (S) return queue_stage_a(c, S, L);
-    if (may_batch) { c->stashed_lane = li; return UVO_OK; }           // waits for its partner (or for the collect that needs it)
+    if (may_batch) { c->sh->stashed_lane = li; return UVO_OK; }           // waits for its partner (or for the collect that needs it)
     return queue_stage_a(c, L, nullptr);
 }
 extern "C" uvo_status uvo_stereo_submit(uvo_ctx* c, const uint8_t* left, const uint8_t* right, int w, int h, int stride, int mem)
@@ -1467,11 +1471,11 @@ try {
 static uvo_status queue_stage_a(uvo_ctx* c, uvo_ctx* A, uvo_ctx* B)
 {
     const uvo_params& p = c->p;
-    const int depth = (int)c->lanes.size();
+    const int depth = (int)c->sh->lanes.size();
     const double t_sub = uvo::g_bdbg ? uvo::now_us() : 0;
-    if (c->stashed_lane == A->plan.lane) c->stashed_lane = -1;
+    if (c->sh->stashed_lane == A->plan.lane) c->sh->stashed_lane = -1;
     const Ctx::StagePlan& pa = A->plan;
-    Ctx* P = c->lanes[pa.prev_lane];
+    Ctx* P = c->sh->lanes[pa.prev_lane];
     hipStream_t st = A->stream;
     Ctx::TraceRec* trA = pa.trace_slot >= 0 ? &A->trace[pa.trace_slot] : nullptr;
     Ctx::TraceRec* trB = (B && B->plan.trace_slot >= 0) ? &B->trace[B->plan.trace_slot] : nullptr;
@@ -1494,9 +1498,9 @@ static uvo_status queue_stage_a(uvo_ctx* c, uvo_ctx* A, uvo_ctx* B)
     // (Queueing the light integral kernels ahead of the wait was tried: no gain.)  A two-pair launch set counts as one stage A and
     // waits for the set a_overlap2 sets before it.
     {
-        const int back = B ? 2 * c->a_overlap2 : c->a_overlap;
+        const int back = B ? 2 * c->sh->a_overlap2 : c->sh->a_overlap;
         if (back > 0 && depth > back && pa.pending_before >= back) {
-            Ctx* H = c->lanes[(pa.lane + depth - back) % depth];
+            Ctx* H = c->sh->lanes[(pa.lane + depth - back) % depth];
             (void)uvo::poll_event(H->evA[1]);
         }
     }
@@ -1553,16 +1557,16 @@ static uvo_status queue_stage_a(uvo_ctx* c, uvo_ctx* A, uvo_ctx* B)
         // triangulation + extract_3Dpoints (VO:631-632) of both pairs on the point pairs just gathered; the rows of the second pair's set
         // for a pair that follows alone (the first pair's set is read by the second only)
         Range r_tri("uvo:triangulatePoints + extract_3Dpoints");
-        LANE_TRY(pose_triangulate_extract3d(A, 0, c->P_eye_left, c->P_right, I, z, c->R_right, c->t_right, c->K_left, c->K_right, cn + CN_T, cap,
+        LANE_TRY(pose_triangulate_extract3d(A, 0, c->sh->P_eye_left, c->sh->P_right, I, z, c->sh->R_right, c->sh->t_right, c->sh->K_left, c->sh->K_right, cn + CN_T, cap,
                                             A->h_countsA[0], B, B->h_countsA[0]));              // the counters land in pinned memory, no copy queued
-        LANE_TRY(pose_as_triangulate(B, st, B->plan.curr, B->d_as_n + B->plan.curr, cap, c->P_eye_left, c->P_right, I, z, c->R_right, c->t_right, c->K_left, c->K_right));
+        LANE_TRY(pose_as_triangulate(B, st, B->plan.curr, B->d_as_n + B->plan.curr, cap, c->sh->P_eye_left, c->sh->P_right, I, z, c->sh->R_right, c->sh->t_right, c->sh->K_left, c->sh->K_right));
         UVO_HIP_TRY(c, hipEventRecord(A->evAS, st));
         UVO_HIP_TRY(c, hipEventRecord(B->evAS, st));
     } else {
         // one launch: this pair's set (VO:569-579) and its rows triangulated for the next pair; extract_3Dpoints (VO:632) on the rows of
         // the previous pair's set that the triangular matches select (VO:631's points, triangulated in that pair's tail)
         Range r_tri("uvo:select + triangulatePoints + extract_3Dpoints");
-        LANE_TRY(pose_stereo_tail(A, P, prev, curr, 0, c->P_eye_left, c->P_right, I, z, c->R_right, c->t_right, c->K_left, c->K_right, A->h_countsA[0]));
+        LANE_TRY(pose_stereo_tail(A, P, prev, curr, 0, c->sh->P_eye_left, c->sh->P_right, I, z, c->sh->R_right, c->sh->t_right, c->sh->K_left, c->sh->K_right, A->h_countsA[0]));
         UVO_HIP_TRY(c, hipEventRecord(A->evAS, st));
     }
     }
@@ -1586,7 +1590,7 @@ static uvo_status queue_stage_a(uvo_ctx* c, uvo_ctx* A, uvo_ctx* B)
     if (B) B->spec_queued = false;
     hipStream_t sb = st;
     if (dev_b) { sb = A->pnp_stream; UVO_HIP_TRY(c, hipStreamWaitEvent(sb, A->evA[1], 0)); }
-    if (A->spec_queued) LANE_TRY(pose_pnp_spec_launch(A, sb, c->K_left, p.ITERATIONS_COUNT, (float)p.REPROJECTION_ERROR_THRESHOLD, p.CONFIDENCE, p.MIN_NUM_3DPOINTS));
+    if (A->spec_queued) LANE_TRY(pose_pnp_spec_launch(A, sb, c->sh->K_left, p.ITERATIONS_COUNT, (float)p.REPROJECTION_ERROR_THRESHOLD, p.CONFIDENCE, p.MIN_NUM_3DPOINTS));
     if (dev_b) UVO_HIP_TRY(c, hipEventRecord(A->evB, sb));                                  // what uvo_stereo_collect waits for
     else {
         UVO_HIP_TRY(c, hipEventRecord(A->evA[0], sb));                                      // what the lane's worker waits for
@@ -1619,7 +1623,6 @@ static uvo_status queue_stage_a(uvo_ctx* c, uvo_ctx* A, uvo_ctx* B)
 static void run_stage_b(uvo_ctx* L, bool stage_a_ok)
 {
     Ctx::BJob& j = L->job;
-    const Ctx* m = L->master ? L->master : L;
     j.st = UVO_OK; j.err.clear(); j.ran = j.ninl = j.ok = j.wrote = 0;
     if (!stage_a_ok) { j.st = UVO_HIP_ERROR; j.err = "stage A of the pair failed"; return; }
     const int* hc = L->h_countsA[0];
@@ -1634,7 +1637,7 @@ static void run_stage_b(uvo_ctx* L, bool stage_a_ok)
         Ctx* one[1] = { L };
         if (L->spec_queued && pose_pnp_spec_accept(L, G, p.ITERATIONS_COUNT, p.CONFIDENCE, &r)) j.st = UVO_OK;      // the device's round, confirmed by the host's scan
         else
-        j.st = pose_pnp_ransac_batch(L, 1, one, &G, m->K_left, p.ITERATIONS_COUNT, (float)p.REPROJECTION_ERROR_THRESHOLD, p.CONFIDENCE, &r);   // VO:647-648
+        j.st = pose_pnp_ransac_batch(L, 1, one, &G, L->sh->K_left, p.ITERATIONS_COUNT, (float)p.REPROJECTION_ERROR_THRESHOLD, p.CONFIDENCE, &r);   // VO:647-648
         if (j.st == UVO_OK) j.st = r.st;
         if (j.st != UVO_OK) j.err = L->err;
         else { j.wrote = r.wrote; j.ok = r.ok; j.ninl = r.ninl; memcpy(j.rvec, r.rvec, sizeof(j.rvec)); memcpy(j.tvec, r.tvec, sizeof(j.tvec)); }
@@ -1693,7 +1696,7 @@ static void lane_worker(uvo_ctx* L)
         Ctx::TraceRec* wtr = (L->trace_on && L->trace_cur >= 0 && L->job.kind == 0) ? &L->trace[L->trace_cur] : nullptr;
         if (wtr) wtr->host_us[3] = now_us();
         {   // at most max_b PnP stages at a time over all lanes: their thin, latency-bound kernels slow down and are slowed by stage A's
-            Ctx* m = L->master ? L->master : L;
+            Shared* m = L->sh;
             std::unique_lock<std::mutex> g(m->b_mu);
             const double tw = g_bdbg ? now_us() : 0;
             const int limit = L->job.kind == 1 ? m->max_b_mono : m->max_b;                  // the mono pose stage is far longer and thinner (see uvo_ctx.h)
@@ -1728,20 +1731,20 @@ static void lane_worker(uvo_ctx* L)
 // Result of the oldest submitted pair: gates, pose inversion and output (VO:634-717, VO:148-159), in order.
 static uvo_status stereo_collect_body(uvo_ctx* c, double dt, uvo_stereo_result* out)
 {
-    if (c->n_pending <= 0) return fail(c, UVO_INVALID_ARG, "uvo_stereo_collect: nothing submitted");
-    if (c->inflight[0] == Ctx::kInflightMonoInit || (c->inflight[0] >= 0 && c->lanes[c->inflight[0]]->job.kind != 0))
+    if (c->sh->n_pending <= 0) return fail(c, UVO_INVALID_ARG, "uvo_stereo_collect: nothing submitted");
+    if (c->sh->inflight[0] == Shared::kInflightMonoInit || (c->sh->inflight[0] >= 0 && c->sh->lanes[c->sh->inflight[0]]->job.kind != 0))
         return fail(c, UVO_INVALID_ARG, "uvo_stereo_collect: the oldest entry in flight is a mono frame (uvo_mono_collect)");
     (void)hipSetDevice(c->device);
     Range r_collect("uvo:stereo_collect");
     const uvo_params& p = c->p;
     const int li = pop_oldest_inflight(c);
-    if (li == Ctx::kInflightStereoInit) {                       // a synchronous init pair (its state is already applied)
-        *out = c->stereo_init_results.front();
-        c->stereo_init_results.pop_front();
+    if (li == Shared::kInflightStereoInit) {                       // a synchronous init pair (its state is already applied)
+        *out = c->sh->stereo_init_results.front();
+        c->sh->stereo_init_results.pop_front();
         return UVO_OK;
     }
-    uvo_ctx* L = static_cast<uvo_ctx*>(c->lanes[li]);
-    if (c->stashed_lane == li) {                               // the pair was waiting for a partner that has not come: it goes alone, now
+    uvo_ctx* L = static_cast<uvo_ctx*>(c->sh->lanes[li]);
+    if (c->sh->stashed_lane == li) {                               // the pair was waiting for a partner that has not come: it goes alone, now
         const uvo_status qs = queue_stage_a(c, L, nullptr);
         if (qs != UVO_OK) return qs;
     }
@@ -1771,36 +1774,36 @@ static uvo_status stereo_collect_body(uvo_ctx* c, double dt, uvo_stereo_result* 
     const int nL = hc[CN_NL], nR = hc[CN_NR], M = hc[CN_M], T = hc[CN_TRAW], G = hc[CN_G];
     out->n_left = nL; out->n_right = nR; out->n_stereo_matches = M; out->n_tri_matches = T; out->n_good3d = G;
     L->last_nL = nL; L->last_nR = nR; L->last_M = M; L->last_T = hc[CN_T]; L->last_G = G; L->last_ninl = 0;
-    c->kp_hint = nL > nR ? nL : nR;
+    c->sh->kp_hint = nL > nR ? nL : nR;
     int valid = 0;
     if (j.ran) {                                                                           // VO:634
         if (j.st != UVO_OK) return fail(c, j.st, j.err.c_str());
-        if (j.wrote) { memcpy(c->rvec, j.rvec, sizeof(c->rvec)); memcpy(c->tvec, j.tvec, sizeof(c->tvec)); }     // also the last hypothesis of a failed RANSAC, as OpenCV
+        if (j.wrote) { memcpy(c->sh->rvec, j.rvec, sizeof(c->sh->rvec)); memcpy(c->sh->tvec, j.tvec, sizeof(c->sh->tvec)); }     // also the last hypothesis of a failed RANSAC, as OpenCV
         L->last_ninl = j.ninl; out->n_inliers = j.ninl;
         if (j.ninl >= p.MIN_NUM_INLIERS) {                                                 // VO:665
             double R[9];
-            rodrigues_vec2mat(c->rvec, R);                                                 // VO:673
+            rodrigues_vec2mat(c->sh->rvec, R);                                                 // VO:673
             for (int i = 0; i < 3; i++) {                                                  // VO:675: -R^T t
                 double acc = 0;
-                for (int k = 0; k < 3; k++) acc += R[k*3 + i] * c->tvec[k];
-                c->t_prev_curr[i] = acc * -1.0;
+                for (int k = 0; k < 3; k++) acc += R[k*3 + i] * c->sh->tvec[k];
+                c->sh->t_prev_curr[i] = acc * -1.0;
             }
             valid = 1;
         }
     }
     out->valid = valid;
     for (int i = 0; i < 3; i++) {
-        out->rvec[i] = c->rvec[i]; out->tvec[i] = c->tvec[i]; out->t_prev_curr[i] = c->t_prev_curr[i];
-        out->velocity[i] = c->t_prev_curr[i] / dt;                                         // VO:152
+        out->rvec[i] = c->sh->rvec[i]; out->tvec[i] = c->sh->tvec[i]; out->t_prev_curr[i] = c->sh->t_prev_curr[i];
+        out->velocity[i] = c->sh->t_prev_curr[i] / dt;                                         // VO:152
     }
     return UVO_OK;
 }
 extern "C" uvo_status uvo_stereo_collect(uvo_ctx* c, double dt, uvo_stereo_result* out)
 try { return c && out ? stereo_collect_body(c, dt, out) : UVO_INVALID_ARG; } UVO_ABI_CATCH(c)
 
-// The synchronous step: one pair submitted and collected by the calling thread, which finishes stage B itself.  Ctx::in_sync_step, read
+// The synchronous step: one pair submitted and collected by the calling thread, which finishes stage B itself.  Shared::in_sync_step, read
 // by the submit and by the SIFT detector, is false again however the submit ends.
-namespace { struct SyncStepScope { uvo_ctx* c; explicit SyncStepScope(uvo_ctx* c_) : c(c_) { c->in_sync_step = true; } ~SyncStepScope() { c->in_sync_step = false; } }; }
+namespace { struct SyncStepScope { uvo_ctx* c; explicit SyncStepScope(uvo_ctx* c_) : c(c_) { c->sh->in_sync_step = true; } ~SyncStepScope() { c->sh->in_sync_step = false; } }; }
 static uvo_status stereo_step_body(uvo_ctx* c, const uint8_t* left, const uint8_t* right, int w, int h, int stride, int mem, double dt, uvo_stereo_result* out, EntryOpts o)
 {
     { SyncStepScope sync(c); UVO_TRY(stereo_submit_body(c, left, right, w, h, stride, mem, o)); }
@@ -1809,7 +1812,7 @@ static uvo_status stereo_step_body(uvo_ctx* c, const uint8_t* left, const uint8_
 extern "C" uvo_status uvo_stereo_step(uvo_ctx* c, const uint8_t* left, const uint8_t* right, int w, int h, int stride, int mem, double dt, uvo_stereo_result* out)
 try {
     if (!c || !out) return UVO_INVALID_ARG;
-    if (c->n_pending != 0) return fail(c, UVO_INVALID_ARG, "uvo_stereo_step: pairs submitted with uvo_stereo_submit are still in flight");
+    if (c->sh->n_pending != 0) return fail(c, UVO_INVALID_ARG, "uvo_stereo_step: pairs submitted with uvo_stereo_submit are still in flight");
     if (!left || !right) return UVO_INVALID_ARG;
     UVO_TRY(stereo_submit_refusal(c, "uvo_stereo_submit"));
     (void)hipSetDevice(c->device);
@@ -1820,7 +1823,7 @@ extern "C" int uvo_stereo_get(uvo_ctx* m, const char* what, void* out, int cap_b
 try {
     if (!m || !what || !out) return 0;
     (void)hipSetDevice(m->device);
-    const Ctx* c = m->lanes.empty() ? m : m->lanes[m->last_lane];    // the lane of the last collected pair
+    const Ctx* c = m->sh->lanes.empty() ? m : m->sh->lanes[m->sh->last_lane];    // the lane of the last collected pair
     const void* src = nullptr; int count = 0; size_t esz = 0;
     std::string w(what);
     if (c->use_binary() && (w == "desc_left" || w == "desc_right")) {        // AKAZE / ORB: the rows' bytes, without the padding
@@ -2116,22 +2119,22 @@ try {
 static uvo_status mono_reset_body(uvo_ctx* c)
 {
     drain_in_flight(c);                                    // results of whatever is still in flight are dropped
-    c->mono_init_results.clear();
+    c->sh->mono_init_results.clear();
     sync_owned_streams(c);
-    for (Ctx* l : c->lanes) { l->prev_read_pending = false; l->pending = Ctx::Pending(); }
-    if (c->n_pending == 0) { c->prev_lane = 0; c->next_lane = 0; }
-    c->mono_pipelined = false;
-    c->mono_initialized = false; c->mono_use_essential = 1; c->mono_SF = 1.0; c->mono_n_prev = 0;
+    for (Ctx* l : c->sh->lanes) { l->prev_read_pending = false; l->pending = Ctx::Pending(); }
+    if (c->sh->n_pending == 0) { c->sh->prev_lane = 0; c->sh->next_lane = 0; }
+    c->sh->mono_pipelined = false;
+    c->sh->mono_initialized = false; c->sh->mono_use_essential = 1; c->sh->mono_SF = 1.0; c->mono_n_prev = 0;
     const double I[9] = {1,0,0,0,1,0,0,0,1};
-    memcpy(c->mono_R, I, sizeof(I)); c->mono_t[0] = c->mono_t[1] = c->mono_t[2] = 0;
+    memcpy(c->sh->mono_R, I, sizeof(I)); c->sh->mono_t[0] = c->sh->mono_t[1] = c->sh->mono_t[2] = 0;
     c->mono_mask.clear(); c->mono_good_pts.clear(); c->mono_dev_n = c->mono_dev_M = c->mono_dev_G = 0; c->mono_good_on_host = true; c->mono_matched = false;
     return UVO_OK;
 }
 extern "C" uvo_status uvo_mono_set_camera(uvo_ctx* c, const double* K)
 try {
     if (!c || !K) return UVO_INVALID_ARG;
-    memcpy(c->mono_K, K, sizeof(c->mono_K));
-    c->mono_cam_set = true;
+    memcpy(c->sh->mono_K, K, sizeof(c->sh->mono_K));
+    c->sh->mono_cam_set = true;
     return mono_reset_body(c);
 } UVO_ABI_CATCH(c)
 extern "C" uvo_status uvo_mono_reset(uvo_ctx* c)
@@ -2165,7 +2168,7 @@ __global__ __launch_bounds__(256) void k_gather_mono_pairs(const uvo_dmatch* __r
 static void run_mono_stage_b(uvo_ctx* L, bool stage_a_ok)
 {
     Ctx::BJob& j = L->job;
-    const Ctx* m = L->master ? L->master : L;
+    const double* K = L->sh->mono_K;
     const uvo_params& p = L->p;
     j.st = UVO_OK; j.err.clear(); j.pose_written = j.sf_written = false;
     memset(&j.mres, 0, sizeof(j.mres));
@@ -2203,7 +2206,7 @@ static void run_mono_stage_b(uvo_ctx* L, bool stage_a_ok)
     for (int attempt = 0; attempt < 2 && !success; attempt++) {                            // estimate_relative_pose (VOU:134-180)
         int valid_inliers = 0;
         if (use_essential && attempt == 0) {
-            j.st = mono_essential_resident(L, M, m->mono_K, p.ESSENTIAL_OUTLIER_METHOD, p.ESSENTIAL_CONFIDENCE, p.ESSENTIAL_THRESHOLD, (int)p.ESSENTIAL_MAX_ITERS, &mr);
+            j.st = mono_essential_resident(L, M, K, p.ESSENTIAL_OUTLIER_METHOD, p.ESSENTIAL_CONFIDENCE, p.ESSENTIAL_THRESHOLD, (int)p.ESSENTIAL_MAX_ITERS, &mr);
             if (j.st != UVO_OK) { j.err = L->err; return; }
             n_in = mr.n_in;
             if (mr.ok) { memcpy(R, mr.R, sizeof(R)); memcpy(t, mr.t, sizeof(t)); memcpy(L->mono_mask.data(), mr.mask, (size_t)M); valid_inliers = mr.valid_inliers; }
@@ -2211,7 +2214,7 @@ static void run_mono_stage_b(uvo_ctx* L, bool stage_a_ok)
             resident = true;
         } else {
             in1.resize(M); in2.resize(M);
-            j.st = estimate_once(L, k1, k2, M, m->mono_K, use_essential, R, t, in1.data(), in2.data(), &n_in, L->mono_mask.data(), &valid_inliers);
+            j.st = estimate_once(L, k1, k2, M, K, use_essential, R, t, in1.data(), in2.data(), &n_in, L->mono_mask.data(), &valid_inliers);
             if (j.st != UVO_OK) { j.err = L->err; return; }
             resident = false;
         }
@@ -2233,13 +2236,13 @@ static void run_mono_stage_b(uvo_ctx* L, bool stage_a_ok)
         } else {
             const double I[9] = {1,0,0,0,1,0,0,0,1}, z[3] = {0,0,0};
             double P_prev[12], P_curr[12];
-            projection_matrix(I, z, m->mono_K, P_prev);
-            projection_matrix(R, t, m->mono_K, P_curr);
+            projection_matrix(I, z, K, P_prev);
+            projection_matrix(R, t, K, P_curr);
             if (n_in > 0) {
                 if (!hip_ok(hipMemcpyAsync(L->d_x1, in1.data(), sizeof(uvo_point2f) * n_in, hipMemcpyHostToDevice, st))) return;
                 if (!hip_ok(hipMemcpyAsync(L->d_x2, in2.data(), sizeof(uvo_point2f) * n_in, hipMemcpyHostToDevice, st))) return;
                 if (!hip_ok(hipMemcpyAsync(L->d_xc, in2.data(), sizeof(uvo_point2f) * n_in, hipMemcpyHostToDevice, st))) return;
-                if ((j.st = pose_triangulate_extract3d(L, 0, P_prev, P_curr, I, z, R, t, m->mono_K, m->mono_K, nullptr, n_in)) != UVO_OK) { j.err = L->err; return; }   // VO:355-356
+                if ((j.st = pose_triangulate_extract3d(L, 0, P_prev, P_curr, I, z, R, t, K, K, nullptr, n_in)) != UVO_OK) { j.err = L->err; return; }   // VO:355-356
                 if ((j.st = read_counts(L)) != UVO_OK) { j.err = L->err; return; }
                 G = L->h_counts[CN_G];
                 L->mono_good_pts.resize((size_t)3 * G);
@@ -2269,20 +2272,20 @@ static void run_mono_stage_b(uvo_ctx* L, bool stage_a_ok)
 static void apply_mono_result(uvo_ctx* c, const Ctx::BJob& j, double dt, uvo_mono_result* out)
 {
     *out = j.mres;
-    if (j.mres.n_kps > 0) c->kp_hint = j.mres.n_kps;          // sizes the descriptor launch's small-window grid of the frames to come
-    if (j.pose_written) { memcpy(c->mono_R, j.R, sizeof(c->mono_R)); memcpy(c->mono_t, j.t, sizeof(c->mono_t)); }
-    if (j.sf_written) c->mono_SF = j.SF;
-    c->mono_use_essential = j.mres.published ? j.mres.used_essential : c->mono_use_essential;
+    if (j.mres.n_kps > 0) c->sh->kp_hint = j.mres.n_kps;          // sizes the descriptor launch's small-window grid of the frames to come
+    if (j.pose_written) { memcpy(c->sh->mono_R, j.R, sizeof(c->sh->mono_R)); memcpy(c->sh->mono_t, j.t, sizeof(c->sh->mono_t)); }
+    if (j.sf_written) c->sh->mono_SF = j.SF;
+    c->sh->mono_use_essential = j.mres.published ? j.mres.used_essential : c->sh->mono_use_essential;
     if (j.mres.published) {
         // -SF * R^T * t / dt as one gemm with alpha = (-SF) * (1/dt)
-        double alpha = (-c->mono_SF) * (1.0 / dt);
+        double alpha = (-c->sh->mono_SF) * (1.0 / dt);
         for (int i = 0; i < 3; i++) {
             double acc = 0;
-            for (int k = 0; k < 3; k++) acc += c->mono_R[k*3 + i] * c->mono_t[k];
+            for (int k = 0; k < 3; k++) acc += c->sh->mono_R[k*3 + i] * c->sh->mono_t[k];
             out->velocity[i] = acc * alpha;
         }
-        out->SF = c->mono_SF;
-        memcpy(out->R, c->mono_R, sizeof(out->R)); memcpy(out->t, c->mono_t, sizeof(out->t));
+        out->SF = c->sh->mono_SF;
+        memcpy(out->R, c->sh->mono_R, sizeof(out->R)); memcpy(out->t, c->sh->mono_t, sizeof(out->t));
     }
 }
 
@@ -2300,7 +2303,7 @@ static uvo_status queue_mono_match(uvo_ctx* c, uvo_ctx* L, const float* prev_des
     hipLaunchKernelGGL(k_gather_mono_pairs, dim3((cap + 255) / 256), dim3(256), 0, L->stream, L->d_matches[0], L->d_counts + CN_M, cap,
                        prev_kps, L->det[0].kps, L->d_x1, L->d_x2);
     UVO_HIP_TRY(c, hipGetLastError());
-    LANE_TRY(mono_prep_launch(L, L->stream, c->mono_K, p.DISTANCE));
+    LANE_TRY(mono_prep_launch(L, L->stream, c->sh->mono_K, p.DISTANCE));
     return UVO_OK;
 }
 // mono loop body, visual_odometry_node::mono_VO (visual_odometry.h:227-245 init, 247-397 main loop, 126-140 output), one frame at a
@@ -2318,7 +2321,7 @@ static uvo_status mono_step_body(uvo_ctx* c, const uint8_t* img, int w, int h, i
     UVO_TRY(surf_upload(c, 0, img, w, h, stride, mem));
     UVO_TRY(detect_dispatch(c, 1));                                                        // VO:238 / VO:274
     // the match against the rolled previous frame -- whether the gates let the frame use it is decided below, from the counts
-    c->mono_matched = c->mono_initialized && c->mono_n_prev > 0;
+    c->mono_matched = c->sh->mono_initialized && c->mono_n_prev > 0;
     if (c->mono_matched) UVO_TRY(queue_mono_match(c, c, c->d_as_descL[0], c->d_as_kpsL[0], nullptr, c->mono_n_prev));
     UVO_HIP_TRY(c, hipMemcpyAsync(c->h_countsA[0], c->d_counts, sizeof(int) * CN_TOTAL, hipMemcpyDeviceToHost, c->stream));
     UVO_HIP_TRY(c, host_sync(c, c->stream));
@@ -2326,7 +2329,7 @@ static uvo_status mono_step_body(uvo_ctx* c, const uint8_t* img, int w, int h, i
     UVO_TRY(check_cand_overflow(c, 1));
     const int n = c->h_counts[CN_NL];
     out->n_kps = n;
-    c->kp_hint = n;
+    c->sh->kp_hint = n;
     c->mono_dev_n = n;
     auto roll_state = [&]() -> uvo_status {                                                // VO:279-282 / VO:392-395 (stream-ordered: the next frame's kernels follow)
         if (n) {
@@ -2336,9 +2339,9 @@ static uvo_status mono_step_body(uvo_ctx* c, const uint8_t* img, int w, int h, i
         c->mono_n_prev = n;
         return UVO_OK;
     };
-    if (!c->mono_initialized) {                                                            // VO:227-245
+    if (!c->sh->mono_initialized) {                                                            // VO:227-245
         UVO_TRY(roll_state());
-        if (n >= p.MIN_NUM_FEATURES) c->mono_initialized = true;
+        if (n >= p.MIN_NUM_FEATURES) c->sh->mono_initialized = true;
         return UVO_OK;
     }
     c->job.kind = 1; c->job.range = range;
@@ -2357,37 +2360,37 @@ try {
 
 static uvo_status mono_submit_body(uvo_ctx* c, const uint8_t* img, int w, int h, int stride, int mem, double range, EntryOpts o)
 {
-    const int depth = (int)c->lanes.size();
+    const int depth = (int)c->sh->lanes.size();
     Range r_submit("uvo:mono_submit");
-    if (!c->mono_initialized) {                                                            // VO:227-245 on lane 0, synchronous
+    if (!c->sh->mono_initialized) {                                                            // VO:227-245 on lane 0, synchronous
         // (earlier init frames may still await their collect: they are complete, only their result is queued)
         uvo_mono_result r;
         memset(&r, 0, sizeof(r));
         UVO_TRY(mono_step_body(c, img, w, h, stride, mem, range, 1.0, &r, o));             // nothing is published before initialisation
-        c->mono_init_results.push_back(r);
-        c->inflight[c->n_pending++] = Ctx::kInflightMonoInit; c->n_submitted++;                // a synchronous init frame
-        c->prev_lane = 0; c->next_lane = 1 % depth;
+        c->sh->mono_init_results.push_back(r);
+        c->sh->inflight[c->sh->n_pending++] = Shared::kInflightMonoInit; c->sh->n_submitted++;                // a synchronous init frame
+        c->sh->prev_lane = 0; c->sh->next_lane = 1 % depth;
         UVO_HIP_TRY(c, hipEventRecord(c->evDet, c->stream));                               // lane 0 holds the frame the next one matches against
         // the mono loop's stream pair per lane, created (and first used) here rather than inside the running pipeline
-        for (Ctx* l : c->lanes) if (!l->pending.used) { l->stream = slot_stream(c, 0, l->lane_id); l->pnp_stream = slot_stream(c, 1, l->lane_id); }
+        for (Ctx* l : c->sh->lanes) if (!l->pending.used) { l->stream = slot_stream(c, 0, l->lane_id); l->pnp_stream = slot_stream(c, 1, l->lane_id); }
         UVO_TRY(prime_lanes(c, w, h));
         UVO_TRY(prepare_lane_detectors(c, w, h, 1));
         return UVO_OK;
     }
-    const int li = c->next_lane;
-    uvo_ctx* L = static_cast<uvo_ctx*>(c->lanes[li]);
-    Ctx* P = c->lanes[c->prev_lane];
-    c->mono_pipelined = true;                  // the previous frame now lives in a lane's buffers, not in uvo_mono_step's rolled state
+    const int li = c->sh->next_lane;
+    uvo_ctx* L = static_cast<uvo_ctx*>(c->sh->lanes[li]);
+    Ctx* P = c->sh->lanes[c->sh->prev_lane];
+    c->sh->mono_pipelined = true;                  // the previous frame now lives in a lane's buffers, not in uvo_mono_step's rolled state
     assign_entry_streams(c, L, false);         // the mono loop keeps a stream pair per lane: its pose stage runs on the lane's stage-A stream
-    c->plan_seq++;
+    c->sh->plan_seq++;
     hipStream_t st = L->stream;
     L->pending = Ctx::Pending(); L->pending.used = true;
     if (L->prev_read_pending) { UVO_HIP_TRY(c, hipStreamWaitEvent(st, L->evPrevRead, 0)); L->prev_read_pending = false; }   // the frame after this lane's last one has read its buffers
     if (!o.producer_waited) UVO_TRY(wait_for_producer(c, L, mem));
     LANE_TRY(surf_upload(L, 0, img, w, h, stride, mem));
-    if (c->a_overlap_mono > 0 && depth > c->a_overlap_mono) {                              // as uvo_stereo_submit: paced by this thread; one image per frame, so more stage As side by side
-        Ctx* H = c->lanes[(li + depth - c->a_overlap_mono) % depth];
-        if (c->n_pending >= c->a_overlap_mono) (void)uvo::poll_event(H->evA[1]);
+    if (c->sh->a_overlap_mono > 0 && depth > c->sh->a_overlap_mono) {                              // as uvo_stereo_submit: paced by this thread; one image per frame, so more stage As side by side
+        Ctx* H = c->sh->lanes[(li + depth - c->sh->a_overlap_mono) % depth];
+        if (c->sh->n_pending >= c->sh->a_overlap_mono) (void)uvo::poll_event(H->evA[1]);
     }
     LANE_TRY(detect_dispatch(L, 1));                                                       // VO:274
     UVO_HIP_TRY(c, hipEventRecord(L->evDet, st));
@@ -2398,8 +2401,8 @@ static uvo_status mono_submit_body(uvo_ctx* c, const uint8_t* img, int w, int h,
     UVO_HIP_TRY(c, hipMemcpyAsync(L->h_countsA[0], L->d_counts, sizeof(int) * CN_TOTAL, hipMemcpyDeviceToHost, st));
     UVO_HIP_TRY(c, hipEventRecord(L->evA[0], st));
     UVO_HIP_TRY(c, hipEventRecord(L->evA[1], st));                                          // the same point for other streams (see uvo_ctx.h)
-    c->prev_lane = li; c->next_lane = (li + 1) % depth;
-    c->inflight[c->n_pending++] = li; c->n_submitted++;
+    c->sh->prev_lane = li; c->sh->next_lane = (li + 1) % depth;
+    c->sh->inflight[c->sh->n_pending++] = li; c->sh->n_submitted++;
     L->t_handover_us = uvo::now_us();
     lane_hand_over(L, 1, range);
     return UVO_OK;
@@ -2415,21 +2418,21 @@ try {
 
 static uvo_status mono_collect_body(uvo_ctx* c, double dt, uvo_mono_result* out)
 {
-    if (c->n_pending <= 0) return fail(c, UVO_INVALID_ARG, "uvo_mono_collect: nothing submitted");
-    if (c->inflight[0] == Ctx::kInflightStereoInit || (c->inflight[0] >= 0 && c->lanes[c->inflight[0]]->job.kind != 1))
+    if (c->sh->n_pending <= 0) return fail(c, UVO_INVALID_ARG, "uvo_mono_collect: nothing submitted");
+    if (c->sh->inflight[0] == Shared::kInflightStereoInit || (c->sh->inflight[0] >= 0 && c->sh->lanes[c->sh->inflight[0]]->job.kind != 1))
         return fail(c, UVO_INVALID_ARG, "uvo_mono_collect: the oldest entry in flight is a stereo pair (uvo_stereo_collect)");
     (void)hipSetDevice(c->device);
     const int li = pop_oldest_inflight(c);
     if (li < 0) {                                          // a synchronous init frame (its state is already applied)
-        *out = c->mono_init_results.front();
-        c->mono_init_results.pop_front();
+        *out = c->sh->mono_init_results.front();
+        c->sh->mono_init_results.pop_front();
         return UVO_OK;
     }
-    uvo_ctx* L = static_cast<uvo_ctx*>(c->lanes[li]);
+    uvo_ctx* L = static_cast<uvo_ctx*>(c->sh->lanes[li]);
     lane_await_done(L, 5000.0);
     const Ctx::BJob& j = L->job;
     if (j.st != UVO_OK) return fail(c, j.st, j.err.c_str());
-    // (uvo_mono_get reads the frame's intermediates from this lane, c->last_lane, until the lane is submitted to again)
+    // (uvo_mono_get reads the frame's intermediates from this lane, c->sh->last_lane, until the lane is submitted to again)
     apply_mono_result(c, j, dt, out);
     return UVO_OK;
 }
@@ -2444,7 +2447,7 @@ try {
     (void)hipSetDevice(c->device);
     const void* src = nullptr; size_t nb = 0; int count = 0; bool on_device = false;
     std::string w(what);
-    const Ctx* f = c->mono_pipelined ? c->lanes[c->last_lane] : c;       // the lane of the last collected frame
+    const Ctx* f = c->sh->mono_pipelined ? c->sh->lanes[c->sh->last_lane] : c;       // the lane of the last collected frame
     if (w == "kps") { src = f->det[0].kps; count = f->mono_dev_n; nb = (size_t)count * sizeof(uvo_keypoint); on_device = true; }
     else if (w == "matches") { src = f->d_matches[0]; count = f->mono_dev_M; nb = (size_t)count * sizeof(uvo_dmatch); on_device = true; }
     else if (w == "mask") { src = f->mono_mask.data(); count = (int)f->mono_mask.size(); nb = (size_t)count; }
@@ -2480,7 +2483,7 @@ try {
     if (!K || !dist4 || !newK) return fail(c, UVO_INVALID_ARG, "uvo_ctx_set_camera: NULL camera matrix / distortion pointer");
     if (cam < 0 || cam > 1) return fail(c, UVO_INVALID_ARG, "uvo_ctx_set_camera: cam is 0 (left or mono) or 1 (right)");
     if (desired_width <= 0) return fail(c, UVO_INVALID_ARG, "uvo_ctx_set_camera: desired_width must be positive");
-    if (c->n_pending != 0) return fail(c, UVO_INVALID_ARG, "uvo_ctx_set_camera: a camera cannot change while pairs / frames are in flight (collect first)");
+    if (c->sh->n_pending != 0) return fail(c, UVO_INVALID_ARG, "uvo_ctx_set_camera: a camera cannot change while pairs / frames are in flight (collect first)");
     return frames_set_camera(c, cam, K, dist4, newK, desired_width, clahe, clip_limit);
 } UVO_ABI_CATCH(c)
 
@@ -2490,7 +2493,7 @@ static uvo_status frames_to_lane(uvo_ctx* c, bool loop_initialized, const uint8_
     const uint8_t* rgb[2] = { rgb0, rgb1 };
     const int ncam = rgb1 ? 2 : 1;
     UVO_TRY(frames_plan(c, ncam, w, h, stride, mem, dw, dh));
-    *L = loop_initialized ? static_cast<uvo_ctx*>(c->lanes[c->next_lane]) : c;
+    *L = loop_initialized ? static_cast<uvo_ctx*>(c->sh->lanes[c->sh->next_lane]) : c;
     if (loop_initialized) assign_entry_streams(c, *L, ncam == 2);       // the entry's handles now: get_image and the body's stage A share a stream
     UVO_TRY(wait_for_producer(c, *L, mem));
     const uvo_status st = frames_queue(c, *L, ncam, rgb, w, h, stride, mem, *dw, *dh);
@@ -2503,7 +2506,7 @@ static uvo_status stereo_frames_to_lane(uvo_ctx* c, const uint8_t* left_rgb, con
     if (!left_rgb || !right_rgb) return fail(c, UVO_INVALID_ARG, "uvo_stereo_submit_frames: NULL frame pointer");
     UVO_TRY(stereo_submit_refusal(c, "uvo_stereo_submit_frames"));
     (void)hipSetDevice(c->device);
-    return frames_to_lane(c, c->vo_initialized, left_rgb, right_rgb, w, h, stride, mem, L, dw, dh);
+    return frames_to_lane(c, c->sh->vo_initialized, left_rgb, right_rgb, w, h, stride, mem, L, dw, dh);
 }
 extern "C" uvo_status uvo_stereo_submit_frames(uvo_ctx* c, const uint8_t* left_rgb, const uint8_t* right_rgb, int w, int h, int stride, int mem)
 try {
@@ -2517,7 +2520,7 @@ extern "C" uvo_status uvo_stereo_step_frames(uvo_ctx* c, const uint8_t* left_rgb
 try {
     if (!c) return UVO_INVALID_ARG;
     if (!out) return fail(c, UVO_INVALID_ARG, "uvo_stereo_step_frames: NULL result pointer");
-    if (c->n_pending != 0) return fail(c, UVO_INVALID_ARG, "uvo_stereo_step_frames: pairs submitted with uvo_stereo_submit are still in flight");
+    if (c->sh->n_pending != 0) return fail(c, UVO_INVALID_ARG, "uvo_stereo_step_frames: pairs submitted with uvo_stereo_submit are still in flight");
     uvo_ctx* L = nullptr; int dw = 0, dh = 0;
     UVO_TRY(stereo_frames_to_lane(c, left_rgb, right_rgb, w, h, stride, mem, &L, &dw, &dh));
     return stereo_step_body(c, L->d_img[0], L->d_img[1], dw, dh, dw, UVO_MEM_DEVICE, dt, out, kFramesEntry);
@@ -2539,7 +2542,7 @@ try {
     UVO_TRY(mono_submit_refusal(c, "uvo_mono_submit_frames"));
     (void)hipSetDevice(c->device);
     uvo_ctx* L = nullptr; int dw = 0, dh = 0;
-    UVO_TRY(frames_to_lane(c, c->mono_initialized, rgb, nullptr, w, h, stride, mem, &L, &dw, &dh));
+    UVO_TRY(frames_to_lane(c, c->sh->mono_initialized, rgb, nullptr, w, h, stride, mem, &L, &dw, &dh));
     return mono_submit_body(c, L->d_img[0], dw, dh, dw, UVO_MEM_DEVICE, range, kFramesEntry);
 } UVO_ABI_CATCH(c)
 
@@ -2560,7 +2563,7 @@ static uvo_status compressed_to_lane(uvo_ctx* c, bool loop_initialized, const uv
     UVO_TRY(codec_compressed_plan(c, ncam, data, n, bayer, &w, &h));
     UVO_TRY(frames_plan(c, ncam, w, h, 3 * w, UVO_MEM_DEVICE, dw, dh));
     UVO_TRY(codec_compressed_workspaces(c, ncam));
-    *L = loop_initialized ? static_cast<uvo_ctx*>(c->lanes[c->next_lane]) : c;
+    *L = loop_initialized ? static_cast<uvo_ctx*>(c->sh->lanes[c->sh->next_lane]) : c;
     if (loop_initialized) assign_entry_streams(c, *L, ncam == 2);       // (as frames_to_lane)
     const uint8_t* rgb[2] = { nullptr, nullptr };
     for (int i = 0; i < ncam; i++) UVO_TRY(codec_compressed_queue(c, *L, i, &rgb[i]));
@@ -2573,7 +2576,7 @@ static uvo_status stereo_compressed_to_lane(uvo_ctx* c, const char* who, const u
     if (!left || !right || !left->data || !right->data) { c->err = std::string(who) + ": NULL message / payload pointer"; return UVO_INVALID_ARG; }
     UVO_TRY(stereo_submit_refusal(c, who));
     (void)hipSetDevice(c->device);
-    return compressed_to_lane(c, c->vo_initialized, left, right, L, dw, dh);
+    return compressed_to_lane(c, c->sh->vo_initialized, left, right, L, dw, dh);
 }
 extern "C" uvo_status uvo_stereo_submit_compressed(uvo_ctx* c, const uvo_compressed_image* left, const uvo_compressed_image* right)
 try {
@@ -2586,7 +2589,7 @@ extern "C" uvo_status uvo_stereo_step_compressed(uvo_ctx* c, const uvo_compresse
 try {
     if (!c) return UVO_INVALID_ARG;
     if (!out) return fail(c, UVO_INVALID_ARG, "uvo_stereo_step_compressed: NULL result pointer");
-    if (c->n_pending != 0) return fail(c, UVO_INVALID_ARG, "uvo_stereo_step_compressed: pairs submitted with uvo_stereo_submit are still in flight");
+    if (c->sh->n_pending != 0) return fail(c, UVO_INVALID_ARG, "uvo_stereo_step_compressed: pairs submitted with uvo_stereo_submit are still in flight");
     uvo_ctx* L = nullptr; int dw = 0, dh = 0;
     UVO_TRY(stereo_compressed_to_lane(c, "uvo_stereo_step_compressed", left, right, &L, &dw, &dh));
     return stereo_step_body(c, L->d_img[0], L->d_img[1], dw, dh, dw, UVO_MEM_DEVICE, dt, out, kFramesEntry);
@@ -2608,7 +2611,7 @@ try {
     UVO_TRY(mono_submit_refusal(c, "uvo_mono_submit_compressed"));
     (void)hipSetDevice(c->device);
     uvo_ctx* L = nullptr; int dw = 0, dh = 0;
-    UVO_TRY(compressed_to_lane(c, c->mono_initialized, img, nullptr, &L, &dw, &dh));
+    UVO_TRY(compressed_to_lane(c, c->sh->mono_initialized, img, nullptr, &L, &dw, &dh));
     return mono_submit_body(c, L->d_img[0], dw, dh, dw, UVO_MEM_DEVICE, range, kFramesEntry);
 } UVO_ABI_CATCH(c)
 extern "C" uvo_status uvo_ctx_set_jpeg_entropy(uvo_ctx* c, int where)
@@ -2638,9 +2641,9 @@ try {
 extern "C" uvo_status uvo_trace_enable(uvo_ctx* c, int on)
 try {
     if (!c) return UVO_INVALID_ARG;
-    if (c->n_pending != 0) { c->err = "the pipeline trace cannot change while pairs are in flight"; return UVO_INVALID_ARG; }
+    if (c->sh->n_pending != 0) { c->err = "the pipeline trace cannot change while pairs are in flight"; return UVO_INVALID_ARG; }
     (void)hipSetDevice(c->device);
-    for (Ctx* l : c->lanes) {
+    for (Ctx* l : c->sh->lanes) {
         if (on) { UVO_HIP_TRY(c, trace_alloc(l)); for (auto& r : l->trace) r.pair = -1; l->trace_count = 0; l->trace_cur = -1; }
         else l->trace_on = false;
     }
@@ -2648,14 +2651,14 @@ try {
 } UVO_ABI_CATCH(c)
 extern "C" int uvo_trace_read(uvo_ctx* c, uvo_trace_row* rows, int cap)
 try {
-    if (!c || (cap > 0 && !rows) || c->n_pending != 0) return -1;
+    if (!c || (cap > 0 && !rows) || c->sh->n_pending != 0) return -1;
     (void)hipSetDevice(c->device);
     sync_owned_streams(c);
     hipEvent_t ref = nullptr; long long ref_pair = -1; double ref_host = 0;
-    for (Ctx* l : c->lanes) for (auto& r : l->trace) if (r.pair >= 0 && (ref_pair < 0 || r.pair < ref_pair)) { ref = r.ev[0]; ref_pair = r.pair; ref_host = r.host_us[0]; }
+    for (Ctx* l : c->sh->lanes) for (auto& r : l->trace) if (r.pair >= 0 && (ref_pair < 0 || r.pair < ref_pair)) { ref = r.ev[0]; ref_pair = r.pair; ref_host = r.host_us[0]; }
     if (!ref) return 0;
     int n = 0;
-    for (Ctx* l : c->lanes) for (auto& r : l->trace) {
+    for (Ctx* l : c->sh->lanes) for (auto& r : l->trace) {
         if (r.pair < 0) continue;
         if (n < cap) {
             uvo_trace_row& w = rows[n];
@@ -2677,8 +2680,8 @@ try {
 extern "C" uvo_status uvo_timing_enable(uvo_ctx* c, int on)
 try {
     if (!c) return UVO_INVALID_ARG;
-    if (c->n_pending != 0) { c->err = "timing mode cannot change while pairs are in flight"; return UVO_INVALID_ARG; }
-    for (Ctx* l : c->lanes) l->timing = on != 0;
+    if (c->sh->n_pending != 0) { c->err = "timing mode cannot change while pairs are in flight"; return UVO_INVALID_ARG; }
+    for (Ctx* l : c->sh->lanes) l->timing = on != 0;
     return UVO_OK;
 } UVO_ABI_CATCH(c)
 extern "C" int uvo_timing_count(uvo_ctx*) { return ST_COUNT; }
@@ -2687,7 +2690,7 @@ extern "C" uvo_status uvo_timing_get(uvo_ctx* c, int i, double* ms, long long* l
 try {
     if (!c || i < 0 || i >= ST_COUNT) return UVO_INVALID_ARG;
     double t = 0; long long n = 0;
-    for (Ctx* l : c->lanes) { t += l->stage_ms[i]; n += l->stage_n[i]; }
+    for (Ctx* l : c->sh->lanes) { t += l->stage_ms[i]; n += l->stage_n[i]; }
     if (ms) *ms = t;
     if (launches) *launches = n;
     return UVO_OK;
@@ -2695,6 +2698,6 @@ try {
 extern "C" uvo_status uvo_timing_reset(uvo_ctx* c)
 try {
     if (!c) return UVO_INVALID_ARG;
-    for (Ctx* l : c->lanes) for (int i = 0; i < ST_COUNT; i++) { l->stage_ms[i] = 0; l->stage_n[i] = 0; }
+    for (Ctx* l : c->sh->lanes) for (int i = 0; i < ST_COUNT; i++) { l->stage_ms[i] = 0; l->stage_n[i] = 0; }
     return UVO_OK;
 } UVO_ABI_CATCH(c)

@@ -533,21 +533,19 @@ uvo_status orb_detect(Ctx* c, const uint8_t* gray, int w, int h, int stride, int
     return UVO_OK;
 }
 
-// ---- detect_features' ORB branch inside the fused steps.  The parameters and the sampling table are the master context's (uvo_orb_configure /
+// ---- detect_features' ORB branch inside the fused steps.  The parameters and the sampling table are lane 0's (uvo_orb_configure /
 // uvo_orb_set_pattern); each lane keeps its own level buffers, made when a sequence starts.  Both images of a pair go through them in turn:
 // the two retainBest rankings between the launches wait for the device.
 bool orb_has_pattern(Ctx* c)
 {
-    Ctx* m = c->master ? c->master : c;
-    const OrbWs* s = static_cast<const OrbWs*>(m->orb_ws);
+    const OrbWs* s = static_cast<const OrbWs*>(c->sh->lanes[0]->orb_ws);
     return s && s->has_pattern;
 }
 uvo_status orb_prepare_lane(Ctx* c, int w, int h)
 {
-    Ctx* m = c->master ? c->master : c;
-    const OrbWs* ms = orb_state(m);
+    const OrbWs* ms = orb_state(c->sh->lanes[0]);
     OrbWs* s = orb_state(c);
-    if (s != ms && memcmp(&s->p, &ms->p, sizeof(OrbParams)) != 0) { s->p = ms->p; orb_free_sized(s); }     // the master's configuration
+    if (s != ms && memcmp(&s->p, &ms->p, sizeof(OrbParams)) != 0) { s->p = ms->p; orb_free_sized(s); }     // lane 0's configuration
     return orb_plan(c, s, w, h);
 }
 uvo_status orb_detect_lane(Ctx* c, int slot, int* n)
@@ -558,7 +556,7 @@ uvo_status orb_detect_lane(Ctx* c, int slot, int* n)
     if (!orb_has_pattern(c)) { c->err = kOrbLoopNoTable; return UVO_INVALID_ARG; }
     UVO_TRY(orb_prepare_lane(c, w, h));                                       // (a no-op once the lane is primed)
     OrbWs* s = static_cast<OrbWs*>(c->orb_ws);
-    const OrbWs* ms = static_cast<const OrbWs*>((c->master ? c->master : c)->orb_ws);
+    const OrbWs* ms = static_cast<const OrbWs*>(c->sh->lanes[0]->orb_ws);
     UVO_TRY(orb_run(c, s, c->stream, c->img[slot], w, h, w, UVO_MEM_DEVICE, ms->d_pattern, n));
     if (*n > c->cap || *n == 0) return UVO_OK;
     UVO_HIP_TRY(c, hipMemcpyAsync(c->det[slot].kps, s->d_kps, sizeof(uvo_keypoint) * (size_t)*n, hipMemcpyDeviceToDevice, c->stream));

@@ -1026,8 +1026,8 @@ uvo_status pose_stereo_tail(Ctx* a, Ctx* p, int prev, int curr, int slot, const 
     ta.okL = a->d_as_kpsL[curr]; ta.okR = a->d_as_kpsR[curr]; ta.odL = a->d_as_descL[curr]; ta.dim = a->loop_words();
     ta.as_pts4 = a->d_as_pts4[curr]; ta.as_cam1 = a->d_as_cam1[curr]; ta.as_flag = a->d_as_flag[curr];
     // rows to expect: the keypoints of the last pair whose counts reached the host, plus a quarter (max_kpts before that)
-    const Ctx* hm = a->master ? a->master : a;
-    int rows = hm->kp_hint > 0 ? hm->kp_hint + hm->kp_hint / 4 : cap;
+    const int hint = a->sh->kp_hint;
+    int rows = hint > 0 ? hint + hint / 4 : cap;
     rows = rows < 256 ? 256 : (rows > cap ? cap : rows);
     ta.tri_blocks = (rows + kTailTri - 1) / kTailTri;
     ta.gather_blocks = (rows + kTailThreads / 16 - 1) / (kTailThreads / 16);

@@ -321,8 +321,8 @@ uvo_status pre_get_image(Ctx* c, const uint8_t* rgb, int w, int h, int stride, i
 //   k_fr_remap       : k_remap_bilinear, maps of the image's camera
 //   k_fr_clahe_lut   : k_clahe_lut, 64 workgroups per image
 //   k_fr_clahe_apply : k_clahe_apply
-// The undistortion maps live in the master context, one slot per camera (uvo_ctx_set_camera): built by k_undistort_map on the
-// master's stream once per (camera parameters, output size) and complete (host sync) before a lane's kernels are queued.
+// The undistortion maps live in lane 0's workspace, one slot per camera (uvo_ctx_set_camera): built by k_undistort_map on
+// lane 0's stream once per (camera parameters, output size) and complete (host sync) before a lane's kernels are queued.
 struct FrImg {
     const uint8_t* src; uint8_t* gray;            // the colour frame (device), its grey image at the output size
     const int16_t* map1; const uint16_t* map2;
@@ -338,7 +338,7 @@ struct FrCam {
     int16_t* map1 = nullptr; uint16_t* map2 = nullptr; size_t map_cap = 0; int map_w = 0, map_h = 0; bool map_valid = false;
 };
 struct FramesWs {
-    FrCam cam[2];                                 // master only
+    FrCam cam[2];                                 // used in lane 0's workspace only
     uint8_t *rgb[2] = {nullptr, nullptr}, *gray[2] = {nullptr, nullptr}, *und[2] = {nullptr, nullptr}, *lut = nullptr;   // per lane
     size_t cap_in = 0, cap_out = 0;
 };
@@ -559,9 +559,9 @@ uvo_status frames_plan(Ctx* m, int ncam, int w, int h, int stride, int mem, int*
     const size_t n_out = (size_t)dw * dh, n_in = mem == UVO_MEM_DEVICE ? 0 : (size_t)h * stride;
     bool stale = false, grow = false;
     for (int i = 0; i < ncam; i++) stale = stale || !f->cam[i].map_valid || f->cam[i].map_w != dw || f->cam[i].map_h != dh;
-    for (Ctx* l : m->lanes) { const FramesWs* lf = static_cast<const FramesWs*>(l->frames_ws); grow = grow || !lf || lf->cap_out < n_out || lf->cap_in < n_in; }
+    for (Ctx* l : m->sh->lanes) { const FramesWs* lf = static_cast<const FramesWs*>(l->frames_ws); grow = grow || !lf || lf->cap_out < n_out || lf->cap_in < n_in; }
     if (!stale && !grow) { *out_w = dw; *out_h = dh; return UVO_OK; }
-    if (m->n_pending != 0) {
+    if (m->sh->n_pending != 0) {
         m->err = stale ? "the frame size or a camera changed while entries are in flight: collect first (the lanes read the cameras' maps)"
                        : "the lanes' frame workspaces must grow (first frames from host memory, or a larger frame / stride) while entries are in flight: collect first";
         return UVO_INVALID_ARG;
@@ -585,7 +585,7 @@ uvo_status frames_plan(Ctx* m, int ncam, int w, int h, int stride, int mem, int*
         fc.map_w = dw; fc.map_h = dh; fc.map_valid = true;
     }
     UVO_HIP_TRY(m, hipStreamSynchronize(m->stream));
-    for (Ctx* l : m->lanes) {
+    for (Ctx* l : m->sh->lanes) {
         FramesWs* lf = frames_ws(l);
         if (lf->cap_in < n_in) {
             for (int i = 0; i < 2; i++) { (void)hipFree(lf->rgb[i]); lf->rgb[i] = nullptr; }

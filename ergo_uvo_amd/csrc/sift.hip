@@ -1116,8 +1116,7 @@ uvo_status sift_detect_lane(Ctx* c, int nimg, int gate_min_features)
     // latency-bound stretches of one under the chip-filling ones of the other (two events: fork after the uploads, join before the
     // counters are published).  With several pairs in flight the lanes overlap each other and a queue parked on an event wait costs
     // the others, so everything stays on the lane's stream.
-    const Ctx* m = c->master ? c->master : c;
-    const bool fork = nimg == 2 && m->in_sync_step && c->pnp_stream != nullptr && !c->timing;
+    const bool fork = nimg == 2 && c->sh->in_sync_step && c->pnp_stream != nullptr && !c->timing;
     hipStream_t streams[2] = { c->stream, fork ? c->pnp_stream : c->stream };
     if (fork) {
         SiftWs* f = ws[1];

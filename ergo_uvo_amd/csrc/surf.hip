@@ -2345,7 +2345,7 @@ uvo_status surf_detect_lanes(Ctx* c, Ctx* c2, int nimg, int gate_min_features)
             if (lds_pad > lds) { static bool once = false; if (!once) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_launch); once = true; } }
             static const char* stamps_path = UVO_STAMPS ? getenv("UVO_HESS_STAMPS") : nullptr;
             static long long* d_stamps = nullptr; static size_t stamps_n = 0;
-            if (stamps_path && c->lane_id == 0 && !c->master) {
+            if (stamps_path && c->lane_id == 0) {
                 if (!d_stamps) { stamps_n = (size_t)total * 4 * 8; (void)hipMalloc(reinterpret_cast<void**>(&d_stamps), sizeof(long long) * stamps_n); (void)hipMemcpyToSymbol(HIP_SYMBOL(g_hess_stamps), &d_stamps, sizeof(d_stamps)); }
                 (void)hipMemsetAsync(d_stamps, 0, sizeof(long long) * stamps_n, c->stream);
             }
@@ -2360,7 +2360,7 @@ uvo_status surf_detect_lanes(Ctx* c, Ctx* c2, int nimg, int gate_min_features)
             if (trh) (void)hipEventRecord(trh->ev[6], c->stream);
             hipLaunchKernelGGL(kern, dim3(total, nim), dim3(kP23Threads), lds_launch, c->stream, lp, w, h, hd, thr, c->d_hess_order);
             if (trh) { (void)hipEventRecord(trh->ev[7], c->stream); trh->det_marked = true; }
-            if (stamps_path && d_stamps && c->lane_id == 0 && !c->master) {        // (measurement: synchronous, every launch rewrites the file)
+            if (stamps_path && d_stamps && c->lane_id == 0) {        // (measurement: synchronous, every launch rewrites the file)
                 std::vector<long long> hs(stamps_n);
                 (void)hipStreamSynchronize(c->stream);
                 (void)hipMemcpy(hs.data(), d_stamps, sizeof(long long) * stamps_n, hipMemcpyDeviceToHost);
@@ -2417,16 +2417,16 @@ uvo_status surf_detect_lanes(Ctx* c, Ctx* c2, int nimg, int gate_min_features)
             static const int desc_part = getenv("UVO_DESC_PART") ? atoi(getenv("UVO_DESC_PART")) : 0;      // measurement only
             static const char* dstamps_path = UVO_STAMPS ? getenv("UVO_DESC_STAMPS") : nullptr;
             static long long* d_dstamps = nullptr; const size_t dstamps_n = (size_t)4 * 16384 * 8;
-            const bool dstamp = dstamps_path && c->lane_id == 0 && !c->master && nim == 2;
+            const bool dstamp = dstamps_path && c->lane_id == 0 && nim == 2;
             if (dstamp) {
                 if (!d_dstamps) { (void)hipMalloc(reinterpret_cast<void**>(&d_dstamps), sizeof(long long) * dstamps_n); (void)hipMemcpyToSymbol(HIP_SYMBOL(g_desc_stamps), &d_dstamps, sizeof(d_dstamps)); }
                 (void)hipMemsetAsync(d_dstamps, 0, sizeof(long long) * dstamps_n, c->stream);
             }
             // small-window part: a workgroup per keypoint -- as many as the last pair whose counts reached the host had, plus a quarter
             // (the workgroups walk the list when there are more: any grid gives the same descriptors); max_kpts of them before that
-            const Ctx* hm = c->master ? c->master : c;
             static const int fixed_grid = getenv("UVO_DESC_GRID") ? atoi(getenv("UVO_DESC_GRID")) : 0;              // measurement: 0 = by the hint, -1 = max_kpts, n = n
-            int nsmall = hm->kp_hint > 0 ? ((hm->kp_hint + hm->kp_hint / 4 + 255) & ~255) : c->cap;
+            const int hint = c->sh->kp_hint;
+            int nsmall = hint > 0 ? ((hint + hint / 4 + 255) & ~255) : c->cap;
             if (fixed_grid != 0) nsmall = fixed_grid < 0 ? c->cap : fixed_grid;
             nsmall = nsmall < 512 ? 512 : (nsmall > c->cap ? c->cap : nsmall);
             // order 2 + the hint-sized grid: 57.2 us; image by image on max_kpts workgroups (rounds 2-4): 60.5; large-window waves first,

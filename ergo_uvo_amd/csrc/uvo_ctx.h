@@ -58,12 +58,92 @@ struct DetectSet {                    // one image's detector outputs (device)
     int* n;                           // device count (clamped to cap)
 };
 
+// What exists once per caller-held context: the sequence state of both loops, the rig, the pipeline's plan and FIFO, its streams and
+// knobs.  Every lane of the context points to the same object (Ctx::sh); lane 0 creates it and deletes it last.  Written by the thread
+// that calls the ABI, but for the PnP semaphore at the end, which the lanes' workers write.
+struct Ctx;
+struct Shared {
+    static const int kMaxDepth = 16;
+    static const int kInflightMonoInit = -1, kInflightStereoInit = -2;      // inflight[] entries of the synchronous init frames / pairs (else: the lane)
+    std::vector<Ctx*> lanes;                     // lanes[0] is the context the caller holds.  EMPTY while lane 0 is created (create_one) and while it is
+                                                 // destroyed (destroy_ctx clears it first): nothing reached from there, a *_ws_free included, may read lanes[0]
+    // ---- planning and FIFO (the submitting / collecting thread) ----
+    int next_lane = 0;                           // lane of the next submitted pair
+    int prev_lane = 0, prev_buf = 0;             // where the previous pair's as-set lives
+    bool prev_sync = true;                       // that set was written synchronously (init step), no event to wait for
+    int stashed_lane = -1;                       // lane of the pair that waits for its partner (-1: none)
+    int inflight[kMaxDepth]; int n_pending = 0;  // lanes of the submitted, not yet collected pairs (FIFO)
+    long long n_submitted = 0, n_collected = 0;
+    int last_lane = 0;
+    long long plan_seq = 0;                      // pipelined entries planned so far (never reset); Ctx::assigned_seq is the lane's side
+    long long a_launch = 0;                      // stage-A launch sets queued so far (a two-pair set counts once): set t runs on A slot t mod (a_overlap + 1)
+    bool in_sync_step = false;                   // the submit in progress is uvo_stereo_step's (one pair in flight)
+    // keypoints per image of the last pair / frame whose counts reached the host (0: none yet): sizes the descriptor launch's
+    // small-window part -- a grid of max_kpts workgroups spends a sixth of the launch's wave-time on workgroups that find no keypoint
+    int kp_hint = 0;
+    // ---- stereo sequence ----
+    bool vo_initialized = false;
+    std::vector<uvo_dmatch> init_matches;        // results_match_prev (VO:468): survives failed init attempts
+    bool rig_set = false;
+    double t_prev_curr[3] = {0, 0, 0}, rvec[3] = {0, 0, 0}, tvec[3] = {0, 0, 0};
+    std::deque<uvo_stereo_result> stereo_init_results;   // uvo_stereo_submit: results of the synchronous init pairs (VO:474-520) awaiting their collect
+    // ---- mono sequence ----
+    bool mono_cam_set = false, mono_initialized = false, mono_pipelined = false;
+    int mono_use_essential = 1;                  // the reference's global `use_essential` (VOH:89)
+    double mono_R[9] = {1,0,0,0,1,0,0,0,1}, mono_t[3] = {0,0,0}, mono_SF = 1.0;
+    std::deque<uvo_mono_result> mono_init_results;   // uvo_mono_submit: the same for the mono init frames
+    // ---- producer (uvo_ctx_set_producer_stream) ----
+    hipStream_t producer_stream = nullptr; bool has_producer = false;
+    std::string warning, policy_text;
+    // ---- what the lanes' workers read for every pair, written only between sequences: kept apart from the plan and FIFO above ----
+    double K_left[9], K_right[9], R_right[9], t_right[3], P_eye_left[12], P_right[12];
+    double mono_K[9];
+    // ---- policy and knobs ----
+    // Who drives the PnP stage of a PIPELINED pair (env UVO_STAGE_B = worker | device; default auto):
+    //   0 worker -- the lane's worker thread wakes at the end of stage A, draws the subsets, launches hypotheses + scoring, waits, replays
+    //               the scan, launches mask + refit, waits (two host round trips; `depth` workers + the submitter = 7-9 busy host
+    //               threads per GPU at depth 6 when they poll)
+    //   1 device -- the first RANSAC round (k_pnp_*_spec, pose.hip) is queued on the lane's PnP stream behind stage A's event at submit
+    //               time; nobody is handed the pair.  uvo_stereo_collect waits for the round's event, replays the scan over the counts
+    //               in pinned memory with the host's libm (pose_pnp_spec_accept) and takes the device's pose when it arrives at the
+    //               same winner; otherwise -- the scan needs more than the round's 64 hypotheses, too few inliers for the parallel
+    //               refit, exactly five points -- the COLLECTING thread runs the host-driven stage.  Results are those of the worker
+    //               path by construction; a rank then keeps ONE host thread busy (submit / collect), whatever the depth.
+    //   auto     -- device when the CPU budget cannot carry a polling thread per lane, else worker
+    int stage_b_mode = -1;                       // -1 auto, 0 worker, 1 device
+    double cpu_budget = 0;                       // logical CPUs this process may keep busy (host_cpu_budget(), ctx.hip)
+    int a_overlap = 2;                           // stage As (detect .. extract_3Dpoints) allowed side by side (env UVO_A_OVERLAP, 0 = no limit)
+    int a_overlap_mono = 4;                      // the same for mono frames (one image each; env UVO_A_OVERLAP_MONO)
+    // Two-pair launches (uvo_stereo_set_batch(c, 2); env UVO_BATCH): uvo_stereo_submit holds every first pair of two back until the
+    // next one arrives and queues the stage As of both -- lanes i and i + 1 -- as ONE set of launches on lane i's stream.  A pair
+    // waiting alone is queued by the first collect that needs it.  Results are those of single launches, pair for pair.
+    int batch = 1;                               // pairs per launch set (1 or 2)
+    int a_overlap2 = 2;                          // two-pair launch sets allowed side by side (env UVO_A_OVERLAP2)
+    int max_b = 3;                               // PnP stages allowed at once (env UVO_MAX_B) ..
+    int max_b_mono = 10;                         // ... and mono pose stages (env UVO_MAX_B_MONO): 2 ms of host-orchestrated, latency-bound kernels each (the
+                                                 // five-point solver keeps one wave per SIMD busy for 0.9 ms), so many of them side by side cost little
+    int detector = 0;                            // the reference's global FEATURE_DETECTOR for the fused steps: 0 SURF, 1 SIFT, 2 AKAZE, 3 ORB
+                                                 // (uvo_ctx_set_loop_detector / uvo_ctx_set_feature_detector)
+    // cv::solvePnPRansac's `flags` (uvo_ctx_set_pnp_method): 1 EPnP; 3 DLS and 4 UPNP run EPnP in OpenCV 4.5; 2 P3P: a four-point RANSAC
+    // kernel (k_pnp_hyp_p3p), the final refit stays EPnP.  uvo_ctx_set_params leaves it alone.
+    int pnp_method = 1;
+    // ---- streams ----
+    // The pipeline's HIP streams belong to the context, by role (0 stage A, 1 PnP) and concurrency slot; a lane's `stream` / `pnp_stream`
+    // are handles assigned per entry (ctx.hip: "streams by role and slot"), never created or destroyed by the lane.
+    bool shared_slots = false;                   // the stereo loop shares streams by slot (set_depth: fewer hardware queues than 2 x depth) -- else a pair per lane
+    int n_b = 1;                                 // PnP streams of the shared layout (max_b + 1)
+    hipStream_t slot_streams[2][kMaxDepth] = {};        // [role][slot], created at first need (slot_stream)
+    // ---- PnP semaphore (the lanes' workers, under b_mu): kept last, away from what the submitting thread writes ----
+    std::mutex b_mu; std::condition_variable b_cv;
+    int b_running = 0;                           // PnP stages running
+    long long b_seq = 0;                         // PnP stages started by the workers: stage k runs on PnP slot k mod n_b
+};
+
 struct Ctx {
     uvo_params p;
     int device = 0, max_w = 0, max_h = 0, cap = 0;
     hipStream_t stream = nullptr;
-    std::string err, warning, policy_text;
-    hipStream_t producer_stream = nullptr; bool has_producer = false;   // master: uvo_ctx_set_producer_stream
+    std::string err;
     hipEvent_t evProducer = nullptr;             // this lane's marker on the producer stream
 
     // ---- SURF ----
@@ -111,11 +191,6 @@ struct Ctx {
     // the rows of a set, triangulated (triangulatePoints + the per-point half of extract_3Dpoints are functions of a row's two keypoints
     // and the rig): filled by the pair that builds the set, read by the next pair through its triangular matches (pose.hip: k_stereo_tail)
     float4* d_as_pts4[2] = {nullptr, nullptr};  double* d_as_cam1[2] = {nullptr, nullptr};  int* d_as_flag[2] = {nullptr, nullptr};
-    bool vo_initialized = false;
-    std::vector<uvo_dmatch> init_matches;        // results_match_prev (VO:468): survives failed init attempts
-    double K_left[9], K_right[9], R_right[9], t_right[3], P_eye_left[12], P_right[12];
-    bool rig_set = false;
-    double t_prev_curr[3] = {0, 0, 0}, rvec[3] = {0, 0, 0}, tvec[3] = {0, 0, 0};
 
     // ---- triangulation / extract_3Dpoints ----
     uvo_point2f *d_x1 = nullptr, *d_x2 = nullptr, *d_xc = nullptr;   // prevL, prevR, currL points of the T matches
@@ -142,13 +217,13 @@ struct Ctx {
     void* d_spec = nullptr; void* h_spec = nullptr;                  // PnpSpecState of the lane's pair, device / pinned
     bool spec_queued = false;                    // this lane's pair has a speculative PnP round queued on `stream`
     hipEvent_t evSync = nullptr; bool inline_b = false;              // synchronous step: end of the pair's device work, polled by the calling thread, which runs stage B itself
-    bool in_sync_step = false;                   // master: the submit in progress is uvo_stereo_step's (one pair in flight)
 
     // ---- pipeline: stage A (detect .. extract_3Dpoints) on `stream`, stage B (PnP) on `pnp_stream` ----
-    // A context is also one LANE of the stereo pipeline.  Lane 0 is the context the caller holds; uvo_stereo_set_depth
-    // adds child contexts (own buffers, streams and stage-B worker thread) so that `depth` consecutive pairs are in
-    // flight at once: pair k runs on lane k mod depth.  The only data one pair takes from the previous one is its
-    // "after stereo match" set, read from the previous lane's buffers behind an event.
+    // A Ctx is one LANE of the pipeline.  Lane 0 is the context the caller holds; uvo_stereo_set_depth adds further
+    // lanes (own buffers, stream handles and stage-B worker thread) so that `depth` consecutive pairs are in
+    // flight at once: pair k runs on lane k mod depth.  What exists once per caller-held context is in Shared
+    // (sh).  The only data one pair takes from the previous one is its "after stereo match" set, read from the
+    // previous lane's buffers behind an event.
     hipStream_t pnp_stream = nullptr;
     int* d_countsB = nullptr;  int* h_countsB = nullptr;             // [0] = n_inliers
     hipEvent_t evA[2] = {nullptr, nullptr};      // stage A of this lane's pair finished (counts in h_countsA[0]): [0] is the one the lane's worker
@@ -166,61 +241,28 @@ struct Ctx {
     //                  evBlock): for hosts with fewer cores than threads.  Until round 4 the stage-A wait did this by default, and about
     //                  one such wait in a hundred woke 3-4 ms late -- the stall behind round 3's 1990 pairs/s driver record
     // Inside the PnP stage the two short syncs (host_sync) poll in every mode but block-all.
-    // Which thread runs the PnP stage of a pipelined pair is a separate choice: stage_b_mode below.
+    // Which thread runs the PnP stage of a pipelined pair is a separate choice: Shared::stage_b_mode.
     int worker_wait = 1;
-    // What the lane's threads read instead of walking the master's lane list (which set_depth rewrites while workers run): how this
+    // What the lane's threads read instead of walking the context's lane list (which set_depth rewrites while workers run): how this
     // lane's waits behave -- 0 poll, 1 timed sleep + poll, 2 sleep on the interrupt.  Stored by create_one / set_depth.
     std::atomic<int> wait_eff{1};
-    // Who drives the PnP stage of a PIPELINED pair (env UVO_STAGE_B = worker | device; default auto):
-    //   0 worker -- the lane's worker thread wakes at the end of stage A, draws the subsets, launches hypotheses + scoring, waits, replays
-    //               the scan, launches mask + refit, waits (two host round trips; `depth` workers + the submitter = 7-9 busy host
-    //               threads per GPU at depth 6 when they poll)
-    //   1 device -- the first RANSAC round (k_pnp_*_spec, pose.hip) is queued on the lane's PnP stream behind stage A's event at submit
-    //               time; nobody is handed the pair.  uvo_stereo_collect waits for the round's event, replays the scan over the counts
-    //               in pinned memory with the host's libm (pose_pnp_spec_accept) and takes the device's pose when it arrives at the
-    //               same winner; otherwise -- the scan needs more than the round's 64 hypotheses, too few inliers for the parallel
-    //               refit, exactly five points -- the COLLECTING thread runs the host-driven stage.  Results are those of the worker
-    //               path by construction; a rank then keeps ONE host thread busy (submit / collect), whatever the depth.
-    //   auto     -- device when the CPU budget cannot carry a polling thread per lane, else worker
-    int stage_b_mode = -1;                       // master: -1 auto, 0 worker, 1 device
-    bool dev_b = false;                          // lane: this lane's pair was queued device-driven (uvo_stereo_collect finishes it)
-    hipEvent_t evB = nullptr;                    // lane: the device-driven round of this lane's pair has finished (on pnp_stream)
-    double cpu_budget = 0;                       // master: logical CPUs this process may keep busy (host_cpu_budget(), ctx.hip)
-    double stage_a_mean_us = 0;                  // lane (its worker's own): hand-over -> end of stage A, running mean (the timed sleep)
-    double t_handover_us = 0;                    // lane: when the pair's stage A was handed to the worker
-    std::atomic<int> job_state_a{0};             // lane: job.state again, for the threads that poll for it before they sleep on cv (ctx.hip: wait_job_state)
+    bool dev_b = false;                          // this lane's pair was queued device-driven (uvo_stereo_collect finishes it)
+    hipEvent_t evB = nullptr;                    // the device-driven round of this lane's pair has finished (on pnp_stream)
+    double stage_a_mean_us = 0;                  // the lane worker's own: hand-over -> end of stage A, running mean (the timed sleep)
+    double t_handover_us = 0;                    // when the pair's stage A was handed to the worker
+    std::atomic<int> job_state_a{0};             // job.state again, for the threads that poll for it before they sleep on cv (ctx.hip: wait_job_state)
     hipEvent_t evBlock = nullptr;                // hipEventBlockingSync marker for host_sync()
     hipEvent_t evPoll = nullptr;                 // host_sync()'s marker when it polls
     int* h_countsA[2] = {nullptr, nullptr};      // pinned copy of d_counts
     hipEvent_t evAS = nullptr;                   // this lane's "after stereo match" set is written
-    int a_overlap = 2;                           // master: stage As (detect .. extract_3Dpoints) allowed side by side (env UVO_A_OVERLAP, 0 = no limit)
-    int a_overlap_mono = 4;                      // the same for mono frames (one image each; env UVO_A_OVERLAP_MONO)
-    // Two-pair launches (uvo_stereo_set_batch(c, 2); env UVO_BATCH): uvo_stereo_submit holds every first pair of two back until the
-    // next one arrives and queues the stage As of both -- lanes i and i + 1 -- as ONE set of launches on lane i's stream.  A pair
-    // waiting alone is queued by the first collect that needs it.  Results are those of single launches, pair for pair.
-    int batch = 1;                               // master: pairs per launch set (1 or 2)
-    int a_overlap2 = 2;                          // master: two-pair launch sets allowed side by side (env UVO_A_OVERLAP2)
     struct StagePlan { int lane = -1, prev_lane = 0, prev_buf = 0, curr = 0, pending_before = 0; bool prev_sync = true; int trace_slot = -1; };
-    StagePlan plan;                              // lane: this lane's pair as uvo_stereo_submit planned it
-    int stashed_lane = -1;                       // master: lane of the pair that waits for its partner (-1: none)
-    std::vector<Ctx*> lanes;                     // master only: lanes[0] == this
-    // keypoints per image of the last pair / frame whose counts reached the host (master; 0: none yet): sizes the descriptor launch's
-    // small-window part -- a grid of max_kpts workgroups spends a sixth of the launch's wave-time on workgroups that find no keypoint
-    int kp_hint = 0;
-    Ctx* master = nullptr;                       // children only
+    StagePlan plan;                              // this lane's pair as uvo_stereo_submit planned it
+    Shared* sh = nullptr;                        // the same object for every lane of a context; lane 0 creates and deletes it
     int lane_id = 0;
     int primed_w = 0, primed_h = 0;              // image size this lane's streams and detector tables are ready for (prime_lanes)
     int as_w = 0;                                // the as-buffer this lane writes next
-    int prev_lane = 0, prev_buf = 0;             // master: where the previous pair's as-set lives
-    bool prev_sync = true;                       // master: that set was written synchronously (init step), no event to wait for
-    int next_lane = 0;                           // master: lane of the next submitted pair
     struct Pending { bool used = false; };
-    static const int kInflightMonoInit = -1, kInflightStereoInit = -2;      // inflight[] entries of the synchronous init frames / pairs (else: the lane)
     Pending pending;                             // this lane's pair
-    static const int kMaxDepth = 16;
-    int inflight[kMaxDepth]; int n_pending = 0;          // master: lanes of the submitted, not yet collected pairs (FIFO)
-    long long n_submitted = 0, n_collected = 0;
-    int last_lane = 0;
     // stage-B worker of this lane
     struct BJob {
         int state = 0;                           // 0 idle, 1 queued, 2 done
@@ -236,18 +278,7 @@ struct Ctx {
     // mono pipeline: this lane's keypoints/descriptors are ready (evDet); the following frame has finished reading them (evPrevRead)
     hipEvent_t evDet = nullptr, evPrevRead = nullptr; bool prev_read_pending = false;
     std::thread worker; std::mutex mu; std::condition_variable cv; bool quit = false;
-    std::mutex b_mu; std::condition_variable b_cv; int b_running = 0, max_b = 3;   // master: PnP stages running / allowed at once
-    // The pipeline's HIP streams belong to the MASTER, by role (0 stage A, 1 PnP) and concurrency slot; a lane's `stream` / `pnp_stream`
-    // are handles assigned per entry (ctx.hip: "streams by role and slot"), never created or destroyed by the lane.
-    hipStream_t slot_streams[2][16] = {};        // master: [role][slot], created at first need (slot_stream)
-    bool shared_slots = false;                   // master: the stereo loop shares streams by slot (set_depth: fewer hardware queues than 2 x depth) -- else a pair per lane
-    int n_b = 1;                                 // master: PnP streams of the shared layout (max_b + 1)
-    long long b_seq = 0;                         // master: PnP stages started by the workers (under b_mu): stage k runs on PnP slot k mod n_b
-    long long a_launch = 0;                      // master: stage-A launch sets queued so far (a two-pair set counts once): set t runs on A slot t mod (a_overlap + 1)
-    long long plan_seq = 0;                      // master: pipelined entries planned so far (never reset) ..
-    long long assigned_seq = -1;                 // lane: .. and the entry this lane's handles were last assigned for
-    int max_b_mono = 10;                         // ... and mono pose stages (env UVO_MAX_B_MONO): 2 ms of host-orchestrated, latency-bound kernels each (the
-                                                 // five-point solver keeps one wave per SIMD busy for 0.9 ms), so many of them side by side cost little
+    long long assigned_seq = -1;                 // the entry (Shared::plan_seq) this lane's handles were last assigned for
 
     // last-step bookkeeping for uvo_stereo_get
     int last_nL = 0, last_nR = 0, last_M = 0, last_T = 0, last_G = 0, last_ninl = 0;
@@ -255,23 +286,16 @@ struct Ctx {
     // ---- mono stage (mono.hip) ----
     void* mono_ws = nullptr;                     // MonoWs*, allocated on first use
     void* pre_ws = nullptr;                      // PreWs* (get_image), allocated on first use
-    void* frames_ws = nullptr;                   // FramesWs* (the *_frames loop entries): the lane's get_image buffers; master: the cameras and their maps
+    void* frames_ws = nullptr;                   // FramesWs* (the *_frames loop entries): the lane's get_image buffers; lane 0's also holds the cameras and their maps
     void* codec_ws = nullptr;                    // CodecWs* (uvo_decode_image), allocated on first use
     void* orb_ws = nullptr;                      // OrbWs* (uvo_orb_detect): parameters, sampling table, buffers of the last image size
     void* akaze_ws = nullptr;                    // AkazeWs* (uvo_akaze_detect), allocated on first use per image size
     void* sift_ws[2] = {nullptr, nullptr};       // SiftWs* per image slot (uvo_sift_detect uses slot 0), allocated on first use
-    int detector = 0;                            // the reference's global FEATURE_DETECTOR for the fused steps: 0 SURF, 1 SIFT, 2 AKAZE, 3 ORB
-                                                 // (uvo_ctx_set_loop_detector / uvo_ctx_set_feature_detector); read from the master context
-    double mono_K[9]; bool mono_cam_set = false, mono_initialized = false, mono_pipelined = false;
-    int mono_use_essential = 1;                  // the reference's global `use_essential` (VOH:89)
-    double mono_R[9] = {1,0,0,0,1,0,0,0,1}, mono_t[3] = {0,0,0}, mono_SF = 1.0;
     // the last frame's intermediates for uvo_mono_get: keypoints (det[0].kps), matches (d_matches[0]) and, after the device-resident pose
     // chain, the good points (d_good_pts[0]) stay in the lane's device buffers -- counts here -- until someone asks
     int mono_dev_n = 0, mono_dev_M = 0, mono_dev_G = 0; bool mono_good_on_host = true;
     bool mono_matched = false;                   // this lane's frame was matched against a previous one (CN_M is this frame's)
     int mono_n_prev = 0;                         // rows of the prev descriptors kept in d_as_descL[0]
-    std::deque<uvo_mono_result> mono_init_results;   // uvo_mono_submit: results of the synchronous init frames awaiting their collect
-    std::deque<uvo_stereo_result> stereo_init_results;   // uvo_stereo_submit: the same for the stereo init pairs (VO:474-520)
     std::vector<uint8_t> mono_mask; std::vector<double> mono_good_pts;
 
     // ---- UVO_TRACE=<file>: device timestamps of every pipelined pair's phases (hipEvents with timing), written as CSV by
@@ -284,11 +308,8 @@ struct Ctx {
     bool trace_on = false;                       // UVO_TRACE=<file> at creation, or uvo_trace_enable (the events are created at first use)
 
     int match_dim = 0;                           // uvo_match_knn2*_dim: row width of the standalone matcher for the duration of one call (0 = SURF's)
-    int loop_detector() const { return (master ? master : this)->detector; }
-    // cv::solvePnPRansac's `flags` (uvo_ctx_set_pnp_method): 1 EPnP; 3 DLS and 4 UPNP run EPnP in OpenCV 4.5; 2 P3P: a four-point RANSAC
-    // kernel (k_pnp_hyp_p3p), the final refit stays EPnP.  Read from the master context; uvo_ctx_set_params leaves it alone.
-    int pnp_method = 1;
-    bool pnp_p3p() const { return (master ? master : this)->pnp_method == 2; }
+    int loop_detector() const { return sh->detector; }
+    bool pnp_p3p() const { return sh->pnp_method == 2; }
     bool use_sift() const { return loop_detector() == 1; }
     bool use_binary() const { return loop_detector() >= 2; }      // AKAZE / ORB: CV_8U rows, kept as 64-byte zero-padded rows in det[].desc
     int desc_bytes() const { return loop_detector() == 2 ? 61 : 32; }     // bytes of a binary row: AKAZE's M-LDB 61, ORB's rBRIEF 32
@@ -389,7 +410,7 @@ int ransac_update_num_iters(double p, double ep, int modelPoints, int maxIters);
 void pre_ws_free(Ctx* c);
 uvo_status pre_get_image(Ctx* c, const uint8_t* rgb, int w, int h, int stride, int mem, const double* K, const double* dist4, const double* newK,
                          int desired_width, int clahe_on, int clip_limit, const uint8_t** d_out, int* out_w, int* out_h);
-// camera frames into the loops' lanes (preproc.hip, "camera frames"): the master keeps the cameras, every lane its buffers
+// camera frames into the loops' lanes (preproc.hip, "camera frames"): lane 0 (m) keeps the cameras, every lane its buffers
 void frames_ws_free(Ctx* c);
 uvo_status frames_set_camera(Ctx* m, int cam, const double* K, const double* dist4, const double* newK, int desired_width, int clahe, int clip_limit);
 uvo_status frames_plan(Ctx* m, int ncam, int w, int h, int stride, int mem, int* out_w, int* out_h);
