@@ -675,8 +675,10 @@ class Context:
         self._drained()
 
     def stereo_set_batch(self, pairs: int):
-        """uvo_stereo_set_batch: 2 = consecutive pairs are queued two at a time, one launch per kernel for both (batch consumers)."""
-        self._check(self._lib.uvo_stereo_set_batch(self._h, int(pairs)))
+        """Pairs per stage-A launch set.  Only 1 exists: the two-pair path (round 4) measured slower and was removed; no library call."""
+        if int(pairs) != 1:
+            raise UvoError(1, "stereo_set_batch: the two-pair launch path was removed (measured 22-38 % slower than single launches: "
+                              "docs/DESIGN_round_4.md); only 1 pair per launch set exists")
 
     def stereo_submit(self, left, right):
         """Enqueue detect..extract_3Dpoints of a pair (no host sync); at most two pairs in flight."""

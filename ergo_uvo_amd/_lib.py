@@ -29,10 +29,6 @@ EXPORTS = [
 ]
 
 
-# exported, but not part of the drop-in ABI (ergo_uvo_amd/csrc/uvo_experimental.h): measurement hooks
-EXPERIMENTAL = ["uvo_stereo_set_batch"]
-
-
 def build(force: bool = False) -> str:
     """Compile csrc/*.hip for gfx950 into lib/libuvo_hip.so (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))]
@@ -92,6 +88,6 @@ def lib() -> C.CDLL:
         _lib.uvo_trace_read.restype = C.c_int
         _lib.uvo_trace_read.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         _lib.uvo_trace_enable.argtypes = [C.c_void_p, C.c_int]
-        for name in EXPORTS + EXPERIMENTAL:
+        for name in EXPORTS:
             getattr(_lib, name)  # fail loudly if the ABI and the header drift apart
     return _lib

@@ -92,7 +92,7 @@ static uvo_status mono_collect_body(uvo_ctx* c, double dt, uvo_mono_result* out)
 static void run_mono_stage_b(uvo_ctx* L, bool stage_a_ok);
 static void destroy_one(uvo_ctx* c);
 static void destroy_ctx(uvo_ctx* c);
-static uvo_status queue_stage_a(uvo_ctx* c, uvo_ctx* A, uvo_ctx* B);
+static uvo_status queue_stage_a(uvo_ctx* c, uvo_ctx* A);
 // the ring of timing events behind UVO_TRACE / uvo_trace_enable (a lane's, created once)
 static hipError_t trace_alloc(Ctx* c)
 {
@@ -158,8 +158,7 @@ void stream_release(int device, int role, int slot_i, hipStream_t s)
 //      - stage A: the submitting thread queues launch set t only after set t - a_overlap has finished on the device (queue_stage_a
 //        polls its evA[1]; with fewer entries in flight that set has been collected).  Set t runs on A slot t mod n_a, n_a = a_overlap
 //        + 1: the stream is empty of the earlier sets' work when the kernels are queued, so sharing it orders nothing that the pacing
-//        has not ordered already.  t counts launch sets, not lanes, so an odd depth keeps the rule, and a two-pair set counts once (its
-//        second pair rides on the first one's stream).  Without pacing (a_overlap 0, or depth <= a_overlap) slot = lane.
+//        has not ordered already.  t counts launch sets, not lanes, so an odd depth keeps the rule.  Without pacing (a_overlap 0, or depth <= a_overlap) slot = lane.
 //      - PnP: at most max_b stages run at a time.  The k-th stage a worker starts runs on B slot k mod n_b, n_b = max_b + 1; the
 //        device-driven round of the entry planned p-th on B slot p mod n_b behind the pair's evA[1].  Two stages that meet on a stream
 //        (one outlived n_b later ones) each wait on the host for their own kernels; the stream only orders their launches.
@@ -201,13 +200,13 @@ static int a_shared_streams(const uvo::Ctx* m) { static const int e = getenv("UV
 static int stereo_a_streams(const uvo::Ctx* m, int depth) { return a_per_lane(m, depth) ? depth : a_shared_streams(m); }
 static int stereo_a_slot(const uvo::Ctx* m, int depth, int lane, long long launch) { return a_per_lane(m, depth) ? lane : (int)(launch % a_shared_streams(m)); }
 // a lane's handles for the entry about to be planned on it (idempotent per entry: the frames entries call it before their body does)
-static void assign_entry_streams(uvo::Ctx* m, uvo::Ctx* L, bool stereo, hipStream_t join = nullptr)
+static void assign_entry_streams(uvo::Ctx* m, uvo::Ctx* L, bool stereo)
 {
     if (L->assigned_seq == m->sh->plan_seq) return;
     L->assigned_seq = m->sh->plan_seq;
     const int depth = (int)m->sh->lanes.size();
     if (!stereo) { L->stream = slot_stream(m, 0, L->lane_id); L->pnp_stream = slot_stream(m, 1, L->lane_id); return; }
-    L->stream = join ? join : slot_stream(m, 0, stereo_a_slot(m, depth, L->lane_id, m->sh->a_launch++));
+    L->stream = slot_stream(m, 0, stereo_a_slot(m, depth, L->lane_id, m->sh->a_launch++));
     L->pnp_stream = slot_stream(m, 1, m->sh->shared_slots ? (int)(m->sh->plan_seq % m->sh->n_b) : L->lane_id);
 }
 // an idle pipeline's handles: lane i on the slots its first entries will use (set_depth; prime_lanes then touches every stream once)
@@ -466,22 +465,11 @@ try {
     if (getenv("UVO_MAX_B")) (*out)->sh->max_b = std::min((int)Shared::kMaxDepth, std::max(1, atoi(getenv("UVO_MAX_B"))));
     if (getenv("UVO_A_OVERLAP")) (*out)->sh->a_overlap = std::min((int)Shared::kMaxDepth, std::max(0, atoi(getenv("UVO_A_OVERLAP"))));
     if (getenv("UVO_MAX_B_MONO")) (*out)->sh->max_b_mono = std::min((int)Shared::kMaxDepth, std::max(1, atoi(getenv("UVO_MAX_B_MONO"))));
-    if (getenv("UVO_A_OVERLAP2")) (*out)->sh->a_overlap2 = std::min(4, std::max(0, atoi(getenv("UVO_A_OVERLAP2"))));
-    if (getenv("UVO_BATCH")) (*out)->sh->batch = atoi(getenv("UVO_BATCH")) == 2 ? 2 : 1;
     if (getenv("UVO_A_OVERLAP_MONO")) (*out)->sh->a_overlap_mono = std::min(8, std::max(0, atoi(getenv("UVO_A_OVERLAP_MONO"))));
     st = set_depth(*out, 2);                      // two pairs in flight by default (uvo_stereo_set_depth changes it)
     if (st != UVO_OK) { uvo_ctx* made = *out; *out = nullptr; destroy_ctx(made); }
     return st;
 } UVO_ABI_CATCH(nullptr)
-
-extern "C" uvo_status uvo_stereo_set_batch(uvo_ctx* c, int pairs)
-try {
-    if (!c) return UVO_INVALID_ARG;
-    if (pairs != 1 && pairs != 2) { c->err = "uvo_stereo_set_batch: 1 or 2 pairs per launch set"; return UVO_INVALID_ARG; }
-    if (c->sh->n_pending != 0) { c->err = "the launch mode cannot change while pairs are in flight"; return UVO_INVALID_ARG; }
-    c->sh->batch = pairs;
-    return UVO_OK;
-} UVO_ABI_CATCH(c)
 
 extern "C" uvo_status uvo_stereo_set_depth(uvo_ctx* c, int depth)
 try {
@@ -729,9 +717,9 @@ static uvo_status need_loop_table(uvo_ctx* c)
 }
 
 // Each loop step has a grey-image entry and a camera-frames entry (uvo_*_frames) over ONE body.  What differs between them is an argument of the call, never
-// context state: the pair joins no two-pair launch (the set's kernels run on the other lane's stream); the producer wait is queued already, before the preprocessing
-struct EntryOpts { bool alone = false, producer_waited = false; };
-static const EntryOpts kFramesEntry = { true, true };
+// context state: the producer wait is queued already, before the preprocessing
+struct EntryOpts { bool producer_waited = false; };
+static const EntryOpts kFramesEntry = { true };
 // ... and ONE list of refusals per step, tested by both entries before anything is queued on a lane; `who` is the entry the message names
 static uvo_status stereo_submit_refusal(uvo_ctx* c, const char* who)
 {
@@ -1173,44 +1161,6 @@ try {
 } UVO_ABI_CATCH(nullptr)
 
 // ------------------------------------------------------------------------------------------ stereo step
-// VO:569-579: curr_{left,right}_{descr,keypoints}_after_stereo_match by the stereo matches' indices
-__device__ __forceinline__ void gather_after_stereo(int bx, const uvo_dmatch* m, const int* cn, const uvo_keypoint* kL, const uvo_keypoint* kR,
-                                                    const float* dL, uvo_keypoint* okL, uvo_keypoint* okR, float* odL, int dim)
-{
-    const int meff = cn[CN_MEFF];
-    const int row = bx * 16 + (threadIdx.x >> 4), sub = threadIdx.x & 15;
-    if (row >= meff) return;
-    const int q = m[row].queryIdx, t = m[row].trainIdx;
-    for (int v = sub; v < dim / 4; v += 16) reinterpret_cast<uint4*>(odL + (size_t)row * dim)[v] = reinterpret_cast<const uint4*>(dL + (size_t)q * dim)[v];   // rows as words
-    if (sub == 0) { okL[row] = kL[q]; okR[row] = kR[t]; }
-}
-// VO:601-617, 637-640: points of the triangular matches (prev left / prev right by queryIdx, curr left by trainIdx).  pmap (two-pair
-// launch): the previous pair's set is not gathered yet -- its row q is keypoint pmap[q].queryIdx of that pair's left list and
-// pmap[q].trainIdx of its right list (pL, pR are then those lists)
-__device__ __forceinline__ void gather_triangular(int bx, const uvo_dmatch* m, const int* cn, const uvo_keypoint* pL, const uvo_keypoint* pR,
-                                                  const uvo_keypoint* cL, uvo_point2f* x1, uvo_point2f* x2, uvo_point2f* xc, const uvo_dmatch* pmap)
-{
-    const int T = cn[CN_T];
-    const int i = bx * 256 + threadIdx.x;
-    if (i >= T) return;
-    const int q = m[i].queryIdx, t = m[i].trainIdx;
-    const int ql = pmap ? pmap[q].queryIdx : q, qr = pmap ? pmap[q].trainIdx : q;
-    x1[i] = uvo_point2f{pL[ql].x, pL[ql].y};
-    x2[i] = uvo_point2f{pR[qr].x, pR[qr].y};
-    xc[i] = uvo_point2f{cL[t].x, cL[t].y};
-}
-// both gathers of a stereo step in one launch: blocks [0, n_as) build this pair's "after stereo match" set, the rest the point
-// pairs of the triangular matches; blockIdx.y: the pair of a two-pair launch
-struct GatherArgs { const uvo_dmatch* m_s; const uvo_dmatch* m_t; const int* cn; const uvo_keypoint* kL; const uvo_keypoint* kR; const float* dL;
-                    uvo_keypoint* okL; uvo_keypoint* okR; float* odL; int dim; const uvo_keypoint* pL; const uvo_keypoint* pR;
-                    uvo_point2f* x1; uvo_point2f* x2; uvo_point2f* xc; int n_as; const uvo_dmatch* pmap; };
-struct GatherPair { GatherArgs g[2]; };
-__global__ __launch_bounds__(256) void k_gather_stereo_step(GatherPair gp)
-{
-    const GatherArgs& a = gp.g[blockIdx.y];
-    if ((int)blockIdx.x < a.n_as) gather_after_stereo(blockIdx.x, a.m_s, a.cn, a.kL, a.kR, a.dL, a.okL, a.okR, a.odL, a.dim);
-    else gather_triangular(blockIdx.x - a.n_as, a.m_t, a.cn, a.pL, a.pR, a.kL, a.x1, a.x2, a.xc, a.pmap);
-}
 __global__ void k_gather_kps_idx(const uvo_keypoint* src, const int* idx, int n, uvo_keypoint* dst)
 {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1397,7 +1347,6 @@ static uvo_status prime_lanes(uvo_ctx* c, int w, int h)
 static uvo_status stereo_submit_body(uvo_ctx* c, const uint8_t* left, const uint8_t* right, int w, int h, int stride, int mem, EntryOpts o)
 {
     const int depth = (int)c->sh->lanes.size();
-    const uvo_params& p = c->p;
     if (!c->sh->vo_initialized) {                                                               // VO:474-520, on lane 0, synchronous
         // (earlier init pairs may still await their collect: they are complete, only their results are queued)
         uvo_stereo_result res;
@@ -1431,15 +1380,10 @@ static uvo_status stereo_submit_body(uvo_ctx* c, const uint8_t* left, const uint
         for (double& v : tr->host_us) v = 0;
         tr->host_us[0] = uvo::now_us();
     }
-    // a pair joins a two-pair launch when the mode is on and the pair can take that path: upright SURF, not the synchronous step,
-    // no per-stage timing, two lanes at least, not an entry that goes alone
-    const bool may_batch = c->sh->batch == 2 && !o.alone && depth >= 2 && !c->sh->in_sync_step && !c->timing && c->loop_detector() == 0 && p.SURF_UPRIGHT && p.SURF_OCTAVES_NUMBER == 4;
-    uvo_ctx* S = c->sh->stashed_lane >= 0 ? static_cast<uvo_ctx*>(c->sh->lanes[c->sh->stashed_lane]) : nullptr;      // the pair before, waiting for this one
-    // The pair's streams ("streams by role and slot"): the stage-A slot of its launch set -- the second pair of a two-pair set rides on
-    // the first one's stream, which runs the set's kernels -- and the PnP slot of a device-driven round.  (A frames entry has its handles
-    // already: its get_image kernels are queued on them.)
+    // The pair's streams ("streams by role and slot"): the stage-A slot of its launch set and the PnP slot of a device-driven round.
+    // (A frames entry has its handles already: its get_image kernels are queued on them.)
     // uploads: a pair's images go to its own lane's buffers (or are read in place), on the stream that will run the kernels
-    assign_entry_streams(c, L, true, (S && may_batch) ? S->stream : nullptr);
+    assign_entry_streams(c, L, true);
     uvo_status up = o.producer_waited ? UVO_OK : wait_for_producer(c, L, mem);
     if (up == UVO_OK) up = surf_upload(L, 0, left, w, h, stride, mem);
     if (up == UVO_OK) up = surf_upload(L, 1, right, w, h, stride, mem);
@@ -1452,10 +1396,7 @@ static uvo_status stereo_submit_body(uvo_ctx* c, const uint8_t* left, const uint
     c->sh->inflight[c->sh->n_pending++] = li; c->sh->n_submitted++;
     L->inline_b = c->sh->in_sync_step;
     L->job.kind = 0;                                           // a stereo pair (the lane is free: its worker holds no job)
-    if (S && (!may_batch || S->img_w != L->img_w || S->img_h != L->img_h)) { UVO_TRY(queue_stage_a(c, S, nullptr)); S = nullptr; }   // cannot pair up: the waiting pair goes alone
-    if (S) return queue_stage_a(c, S, L);
-    if (may_batch) { c->sh->stashed_lane = li; return UVO_OK; }           // waits for its partner (or for the collect that needs it)
-    return queue_stage_a(c, L, nullptr);
+    return queue_stage_a(c, L);
 }
 extern "C" uvo_status uvo_stereo_submit(uvo_ctx* c, const uint8_t* left, const uint8_t* right, int w, int h, int stride, int mem)
 try {
@@ -1465,23 +1406,20 @@ try {
     return stereo_submit_body(c, left, right, w, h, stride, mem, EntryOpts());
 } UVO_ABI_CATCH(c)
 
-// Stage A of one pair (VO:548-632) -- or of two consecutive pairs, lanes A and B, in one set of launches on A's stream: detect,
-// stereo match, triangular match, gathers, triangulation, extract_3Dpoints -- queued without a host sync; the counters land in each
-// lane's pinned mirror, events mark completion and each lane's worker thread takes over for stage B.
-static uvo_status queue_stage_a(uvo_ctx* c, uvo_ctx* A, uvo_ctx* B)
+// Stage A of one pair, lane A (VO:548-632): detect, stereo match, triangular match, gathers, triangulation, extract_3Dpoints -- queued
+// without a host sync; the counters land in the lane's pinned mirror, events mark completion and the lane's worker thread takes over
+// for stage B.
+static uvo_status queue_stage_a(uvo_ctx* c, uvo_ctx* A)
 {
     const uvo_params& p = c->p;
     const int depth = (int)c->sh->lanes.size();
     const double t_sub = uvo::g_bdbg ? uvo::now_us() : 0;
-    if (c->sh->stashed_lane == A->plan.lane) c->sh->stashed_lane = -1;
     const Ctx::StagePlan& pa = A->plan;
     Ctx* P = c->sh->lanes[pa.prev_lane];
     hipStream_t st = A->stream;
     Ctx::TraceRec* trA = pa.trace_slot >= 0 ? &A->trace[pa.trace_slot] : nullptr;
-    Ctx::TraceRec* trB = (B && B->plan.trace_slot >= 0) ? &B->trace[B->plan.trace_slot] : nullptr;
 #define LANE_TRY(expr) do { uvo_status st_ = (expr); if (st_ != UVO_OK) { if (A != c) c->err = A->err; return st_; } } while (0)
     if (trA) UVO_HIP_TRY(c, hipEventRecord(trA->ev[0], st));
-    if (trB) UVO_HIP_TRY(c, hipEventRecord(trB->ev[0], st));
     // Stage A is a run of chip-filling detection kernels followed by thin ones.  Two stage As side by side fill each other's
     // gaps; three or more interleave at kernel granularity, evict each other's LDS-sized workgroups and every one of them
     // slows down (measured with UVO_TRACE: detection 390 us with two, 1050 us with five lanes in stage A).
@@ -1495,10 +1433,9 @@ static uvo_status queue_stage_a(uvo_ctx* c, uvo_ctx* A, uvo_ctx* B)
     // an event that is still pending, so that the kernels sit behind a barrier packet in their hardware queue) was measured at 1200-2200
     // pairs/s against 3800: a queue parked on a barrier slows the other queues down.  evA[1] is the twin of the event the lane's worker
     // blocks on -- the runtime holds an event's lock while a thread waits on it.
-    // (Queueing the light integral kernels ahead of the wait was tried: no gain.)  A two-pair launch set counts as one stage A and
-    // waits for the set a_overlap2 sets before it.
+    // (Queueing the light integral kernels ahead of the wait was tried: no gain.)
     {
-        const int back = B ? 2 * c->sh->a_overlap2 : c->sh->a_overlap;
+        const int back = c->sh->a_overlap;
         if (back > 0 && depth > back && pa.pending_before >= back) {
             Ctx* H = c->sh->lanes[(pa.lane + depth - back) % depth];
             (void)uvo::poll_event(H->evA[1]);
@@ -1506,74 +1443,39 @@ static uvo_status queue_stage_a(uvo_ctx* c, uvo_ctx* A, uvo_ctx* B)
     }
     seg(9);                                                                                // the pacing wait
     if (trA) trA->host_us[1] = uvo::now_us();
-    if (trB) trB->host_us[1] = uvo::now_us();
     { Range r("uvo:detect_features x2");                                                   // VO:548-549, and the VO:556 gate
-      if (B) LANE_TRY(surf_detect_lanes(A, B, 2, p.MIN_NUM_FEATURES)); else LANE_TRY(detect_dispatch(A, 2, p.MIN_NUM_FEATURES)); }
+      LANE_TRY(detect_dispatch(A, 2, p.MIN_NUM_FEATURES)); }
     seg(10);                                                                               // detector launches
     if (trA) UVO_HIP_TRY(c, hipEventRecord(trA->ev[1], st));
-    if (trB) UVO_HIP_TRY(c, hipEventRecord(trB->ev[1], st));
     const int cap = c->cap, curr = pa.curr, prev = pa.prev_buf;
     int* cn = A->d_counts;
     const float ratio = (float)p.LOWE_RATIO_THRESHOLD;
     // Stereo matching L -> R (VO:558, gated on the device by VO:556) and triangular matching prev-left-after-stereo -> curr-left
     // (VO:592) share their launches: both only need this pair's descriptors and the previous pair's "after stereo match" set
     // (another lane's buffers, behind its event).  The triangular match is computed for every row of that set; whether it is used
-    // is VO:567's decision, taken by the first compaction's gate and read by the second's (cn[CN_NQB]).  In a two-pair launch the
-    // second pair's previous set is the first pair's, which does not exist yet: match_two_pairs goes through the first pair's stereo matches.
+    // is VO:567's decision, taken by the first compaction's gate and read by the second's (cn[CN_NQB]).
     { Range r_ms("uvo:match_features stereo + triangular, select");
     if (!pa.prev_sync && P != A) UVO_HIP_TRY(c, hipStreamWaitEvent(st, P->evAS, 0));
-    GatherPair gp;
-    gp.g[0] = GatherArgs{ A->d_matches[0], A->d_matches[1], cn, A->det[0].kps, A->det[1].kps, A->det[0].desc,
-                          A->d_as_kpsL[curr], A->d_as_kpsR[curr], A->d_as_descL[curr], A->loop_words(), P->d_as_kpsL[prev], P->d_as_kpsR[prev],
-                          A->d_x1, A->d_x2, A->d_xc, (cap + 15) / 16, nullptr };
-    if (!B) {
-        if (A->use_binary()) {                                                             // VOU:520-524: Hamming on the padded rows
-            auto u8 = [](const float* d) { return reinterpret_cast<const uint8_t*>(d); };
-            LANE_TRY(match_knn2_bin_two(A, BIN_HAMMING, u8(A->det[0].desc), cn + CN_NQA, u8(A->det[1].desc), cn + CN_NR,
-                                        u8(P->d_as_descL[prev]), P->d_as_n + prev, u8(A->det[0].desc), cn + CN_NL, cap));
-        } else
-            LANE_TRY(match_knn2_two(A, A->det[0].desc, cn + CN_NQA, A->det[1].desc, cn + CN_NR,
-                                    P->d_as_descL[prev], P->d_as_n + prev, A->det[0].desc, cn + CN_NL, cap));
-        const GateArgs gate_b = { 1, cn, p.MIN_NUM_FEATURES, cap, A->d_as_n + curr, P->d_as_n + prev };       // VO:567
-        const GateArgs gate_c = { 2, cn, p.MIN_NUM_FEATURES, cap, nullptr, nullptr };                           // VO:626
-        LANE_TRY(match_ratio_compact2(A, ratio, cn + CN_NQA, A->d_matches[0], cn + CN_M, gate_b,
-                                      cn + CN_NQB, A->d_matches[1], cn + CN_TRAW, gate_c, cap, cap));
-        gp.g[1] = gp.g[0];
-    } else {
-        const int currB = B->plan.curr;
-        LANE_TRY(match_two_pairs(A, B, P->d_as_descL[prev], P->d_as_n + prev, P->d_as_n + prev, curr, currB, ratio, p.MIN_NUM_FEATURES));
-        // the second pair's triangular points: rows of the first pair's set, through its stereo matches, from its keypoint lists
-        gp.g[1] = GatherArgs{ B->d_matches[0], B->d_matches[1], B->d_counts, B->det[0].kps, B->det[1].kps, B->det[0].desc,
-                              B->d_as_kpsL[currB], B->d_as_kpsR[currB], B->d_as_descL[currB], B->loop_words(), A->det[0].kps, A->det[1].kps,
-                              B->d_x1, B->d_x2, B->d_xc, (cap + 15) / 16, A->d_matches[0] };
-    }
+    if (A->use_binary()) {                                                                 // VOU:520-524: Hamming on the padded rows
+        auto u8 = [](const float* d) { return reinterpret_cast<const uint8_t*>(d); };
+        LANE_TRY(match_knn2_bin_two(A, BIN_HAMMING, u8(A->det[0].desc), cn + CN_NQA, u8(A->det[1].desc), cn + CN_NR,
+                                    u8(P->d_as_descL[prev]), P->d_as_n + prev, u8(A->det[0].desc), cn + CN_NL, cap));
+    } else
+        LANE_TRY(match_knn2_two(A, A->det[0].desc, cn + CN_NQA, A->det[1].desc, cn + CN_NR,
+                                P->d_as_descL[prev], P->d_as_n + prev, A->det[0].desc, cn + CN_NL, cap));
+    const GateArgs gate_b = { 1, cn, p.MIN_NUM_FEATURES, cap, A->d_as_n + curr, P->d_as_n + prev };           // VO:567
+    const GateArgs gate_c = { 2, cn, p.MIN_NUM_FEATURES, cap, nullptr, nullptr };                               // VO:626
+    LANE_TRY(match_ratio_compact2(A, ratio, cn + CN_NQA, A->d_matches[0], cn + CN_M, gate_b,
+                                  cn + CN_NQB, A->d_matches[1], cn + CN_TRAW, gate_c, cap, cap));
     const double I[9] = {1,0,0,0,1,0,0,0,1}, z[3] = {0,0,0};
-    if (B) {
-        {
-            StageTimer t(A, ST_GATHER);
-            hipLaunchKernelGGL(k_gather_stereo_step, dim3((cap + 15) / 16 + (cap + 255) / 256, 2), dim3(256), 0, st, gp);
-        }
-        UVO_HIP_TRY(c, hipGetLastError());
-        // triangulation + extract_3Dpoints (VO:631-632) of both pairs on the point pairs just gathered; the rows of the second pair's set
-        // for a pair that follows alone (the first pair's set is read by the second only)
-        Range r_tri("uvo:triangulatePoints + extract_3Dpoints");
-        LANE_TRY(pose_triangulate_extract3d(A, 0, c->sh->P_eye_left, c->sh->P_right, I, z, c->sh->R_right, c->sh->t_right, c->sh->K_left, c->sh->K_right, cn + CN_T, cap,
-                                            A->h_countsA[0], B, B->h_countsA[0]));              // the counters land in pinned memory, no copy queued
-        LANE_TRY(pose_as_triangulate(B, st, B->plan.curr, B->d_as_n + B->plan.curr, cap, c->sh->P_eye_left, c->sh->P_right, I, z, c->sh->R_right, c->sh->t_right, c->sh->K_left, c->sh->K_right));
-        UVO_HIP_TRY(c, hipEventRecord(A->evAS, st));
-        UVO_HIP_TRY(c, hipEventRecord(B->evAS, st));
-    } else {
-        // one launch: this pair's set (VO:569-579) and its rows triangulated for the next pair; extract_3Dpoints (VO:632) on the rows of
-        // the previous pair's set that the triangular matches select (VO:631's points, triangulated in that pair's tail)
-        Range r_tri("uvo:select + triangulatePoints + extract_3Dpoints");
-        LANE_TRY(pose_stereo_tail(A, P, prev, curr, 0, c->sh->P_eye_left, c->sh->P_right, I, z, c->sh->R_right, c->sh->t_right, c->sh->K_left, c->sh->K_right, A->h_countsA[0]));
-        UVO_HIP_TRY(c, hipEventRecord(A->evAS, st));
-    }
+    // one launch: this pair's set (VO:569-579) and its rows triangulated for the next pair; extract_3Dpoints (VO:632) on the rows of
+    // the previous pair's set that the triangular matches select (VO:631's points, triangulated in that pair's tail)
+    Range r_tri("uvo:select + triangulatePoints + extract_3Dpoints");
+    LANE_TRY(pose_stereo_tail(A, P, prev, curr, 0, c->sh->P_eye_left, c->sh->P_right, I, z, c->sh->R_right, c->sh->t_right, c->sh->K_left, c->sh->K_right, A->h_countsA[0]));
+    UVO_HIP_TRY(c, hipEventRecord(A->evAS, st));
     }
     UVO_HIP_TRY(c, hipEventRecord(A->evA[1], st));                                          // end of stage A, for the pacing of later pairs (see uvo_ctx.h)
-    if (B) UVO_HIP_TRY(c, hipEventRecord(B->evA[1], st));
     if (trA) UVO_HIP_TRY(c, hipEventRecord(trA->ev[2], st));
-    if (trB) UVO_HIP_TRY(c, hipEventRecord(trB->ev[2], st));
     // The first RANSAC round without the host (pose.hip: k_pnp_*_spec), in two places:
     //  * the synchronous step (one pair in flight) queues it on this stream, right behind extract_3Dpoints, and the calling thread
     //    confirms it (0.80 -> 0.77 ms per pair at C3);
@@ -1582,39 +1484,29 @@ static uvo_status queue_stage_a(uvo_ctx* c, uvo_ctx* A, uvo_ctx* B)
     //    stage-A stream instead, the same kernels cost the pipeline a quarter of its rate (round 3: 4370 -> 3200 pairs/s).
     // UVO_PNP_SPEC=0 switches the round off (the host-driven stage then runs on the calling / collecting thread).
     static const int spec_env = getenv("UVO_PNP_SPEC") ? atoi(getenv("UVO_PNP_SPEC")) : 1;
-    const bool dev_b = !B && !A->inline_b && !c->timing && stage_b_on_device(c);
+    const bool dev_b = !A->inline_b && !c->timing && stage_b_on_device(c);
     A->dev_b = dev_b;
-    if (B) B->dev_b = false;
     // (the speculative round is EPnP with a five-point draw table: under SOLVEPNP_P3P the host-replayed stage serves the pair)
-    A->spec_queued = !B && spec_env != 0 && (A->inline_b || dev_b) && !c->timing && p.ITERATIONS_COUNT >= 1 && !c->pnp_p3p();
-    if (B) B->spec_queued = false;
+    A->spec_queued = spec_env != 0 && (A->inline_b || dev_b) && !c->timing && p.ITERATIONS_COUNT >= 1 && !c->pnp_p3p();
     hipStream_t sb = st;
     if (dev_b) { sb = A->pnp_stream; UVO_HIP_TRY(c, hipStreamWaitEvent(sb, A->evA[1], 0)); }
     if (A->spec_queued) LANE_TRY(pose_pnp_spec_launch(A, sb, c->sh->K_left, p.ITERATIONS_COUNT, (float)p.REPROJECTION_ERROR_THRESHOLD, p.CONFIDENCE, p.MIN_NUM_3DPOINTS));
     if (dev_b) UVO_HIP_TRY(c, hipEventRecord(A->evB, sb));                                  // what uvo_stereo_collect waits for
-    else {
-        UVO_HIP_TRY(c, hipEventRecord(A->evA[0], sb));                                      // what the lane's worker waits for
-        if (B) UVO_HIP_TRY(c, hipEventRecord(B->evA[0], sb));
-    }
+    else UVO_HIP_TRY(c, hipEventRecord(A->evA[0], sb));                                     // what the lane's worker waits for
     if (trA) trA->host_us[2] = uvo::now_us();
-    if (trB) trB->host_us[2] = uvo::now_us();
-    uvo_ctx* both[2] = { A, B };
-    for (uvo_ctx* L : both) {
-        if (!L) continue;
-        if (L->inline_b) {
-            // the synchronous step waits for its own pair: the calling thread polls the stream's end itself and finishes stage B inline
-            // (no worker wake-up, no condition variable: two thread hand-overs less on the pair's critical path)
-            UVO_HIP_TRY(c, hipEventRecord(L->evSync, sb));
-            L->job.kind = 0;
-        } else if (L->dev_b) {
-            L->job.kind = 0;                                   // nobody is woken: the round is on the device, collect finishes the pair
-        } else {   // hand stage B to the lane's worker
-            L->t_handover_us = uvo::now_us();
-            lane_hand_over(L, 0);
-        }
+    if (A->inline_b) {
+        // the synchronous step waits for its own pair: the calling thread polls the stream's end itself and finishes stage B inline
+        // (no worker wake-up, no condition variable: two thread hand-overs less on the pair's critical path)
+        UVO_HIP_TRY(c, hipEventRecord(A->evSync, sb));
+        A->job.kind = 0;
+    } else if (A->dev_b) {
+        A->job.kind = 0;                                       // nobody is woken: the round is on the device, collect finishes the pair
+    } else {   // hand stage B to the lane's worker
+        A->t_handover_us = uvo::now_us();
+        lane_hand_over(A, 0);
     }
     seg(11);                                                                               // matcher .. extract_3Dpoints launches, hand-over
-    if (uvo::g_bdbg) { uvo::g_bstat[6] += uvo::now_us() - t_sub; uvo::g_bstat[7] += B ? 2 : 1; }
+    if (uvo::g_bdbg) { uvo::g_bstat[6] += uvo::now_us() - t_sub; uvo::g_bstat[7] += 1; }
     return UVO_OK;
 #undef LANE_TRY
 }
@@ -1744,10 +1636,6 @@ static uvo_status stereo_collect_body(uvo_ctx* c, double dt, uvo_stereo_result* 
         return UVO_OK;
     }
     uvo_ctx* L = static_cast<uvo_ctx*>(c->sh->lanes[li]);
-    if (c->sh->stashed_lane == li) {                               // the pair was waiting for a partner that has not come: it goes alone, now
-        const uvo_status qs = queue_stage_a(c, L, nullptr);
-        if (qs != UVO_OK) return qs;
-    }
     if (L->inline_b) {
         L->inline_b = false;
         run_stage_b(L, uvo::poll_event(L->evSync) == hipSuccess);

@@ -62,15 +62,13 @@ __device__ __forceinline__ void extract3d_point(const float4 p, const uvo_point2
 
 // FILTER: the loops call triangulatePoints and extract_3Dpoints back to back on the same point pairs (VO:631-632, VO:355-356);
 // the per-point part of the latter then runs on the point just triangulated instead of in a launch of its own
-// per-lane arguments of the two kernels below: blockIdx.y selects the lane in a two-pair launch (uvo_stereo_submit, batch mode)
+// one lane's arguments of the two kernels below
 struct TriLane { const uvo_point2f* x1; const uvo_point2f* x2; const int* n_p; float4* out; double* cam1; int* flag; };
-struct TriLanes { TriLane l[2]; };
 struct Ex3Lane { const double* cam1; const int* flag; const uvo_point2f* xc; const int* n_p; int* tmp_idx; double* good_pts; int* good_idx; float* opts;
                  uvo_point2f* ipts; int* counts /* [1] = G */; int* counts_host /* pinned mirror of all the step's counters, or null */;
                  // the stereo loop's tail (k_stereo_tail): point i is row map[i].queryIdx of cam1 / flag / pts4 (the previous pair's set, triangulated
                  // row by row in that pair's own tail) and its current-image point is keypoint map[i].trainIdx of cL; null: point i is row i
                  const uvo_dmatch* map; const uvo_keypoint* cL; const float4* pts4; float4* out_pts4; int* tmp_row; };
-struct Ex3Lanes { Ex3Lane l[2]; };
 // cv::triangulatePoints for one point pair, by thread threadIdx.x < TT of its workgroup (the 4x4 Jacobi SVD's operands live in
 // LDS, one column of `lds` per thread)
 static const int kTriLdsDoubles = (16 + 16 + 16 + 4 + 4) * kTriThreads;
@@ -90,9 +88,8 @@ __device__ __forceinline__ float4 triangulate_point(const Mat34& P1, const Mat34
     return make_float4((float)Vt[12], (float)Vt[13], (float)Vt[14], (float)Vt[15]);
 }
 template <bool FILTER>
-__global__ __launch_bounds__(kTriThreads) void k_triangulate(Mat34 P1, Mat34 P2, TriLanes lanes, int n_imm, Cam c1, Cam c2, double tol)
+__global__ __launch_bounds__(kTriThreads) void k_triangulate(Mat34 P1, Mat34 P2, TriLane LN, int n_imm, Cam c1, Cam c2, double tol)
 {
-    const TriLane& LN = lanes.l[blockIdx.y];
     const uvo_point2f* x1 = LN.x1; const uvo_point2f* x2 = LN.x2; const int* n_p = LN.n_p; float4* out = LN.out; double* cam1 = LN.cam1; int* flag = LN.flag;
     const int n = n_p ? *n_p : n_imm;
     const int i = blockIdx.x * kTriThreads + threadIdx.x;
@@ -277,10 +274,10 @@ __device__ __forceinline__ void extract3d_block(const Ex3Lane& LN, int n_imm, in
     __syncthreads();
     publish(sm.s_base);
 }
-__global__ __launch_bounds__(1024) void k_extract3d_b(Ex3Lanes lanes, int n_imm, int min_pts, int force_seq)
+__global__ __launch_bounds__(1024) void k_extract3d_b(Ex3Lane LN, int n_imm, int min_pts, int force_seq)
 {
     __shared__ Ex3Smem sm;
-    extract3d_block(lanes.l[blockIdx.y], n_imm, min_pts, force_seq, sm);
+    extract3d_block(LN, n_imm, min_pts, force_seq, sm);
 }
 
 // ---------------------------------------------------------------- the tail of the stereo loop's stage A in ONE launch (round 4)
@@ -965,29 +962,23 @@ uvo_status pose_triangulate(Ctx* c, const double* P1, const double* P2, const in
     if (n_max <= 0) return UVO_OK;
     Mat34 a, b; memcpy(a.v, P1, sizeof(a.v)); memcpy(b.v, P2, sizeof(b.v));
     StageTimer t(c, ST_TRIANGULATE);
-    TriLanes tl; tl.l[0] = tl.l[1] = tri_lane(c, d_n, false);
-    hipLaunchKernelGGL(k_triangulate<false>, dim3((n_max + kTriThreads - 1) / kTriThreads), dim3(kTriThreads), 0, c->stream, a, b, tl, n_max, Cam(), Cam(), 0.0);
+    hipLaunchKernelGGL(k_triangulate<false>, dim3((n_max + kTriThreads - 1) / kTriThreads), dim3(kTriThreads), 0, c->stream, a, b, tri_lane(c, d_n, false), n_max, Cam(), Cam(), 0.0);
     UVO_HIP_TRY(c, hipGetLastError());
     return UVO_OK;
 }
 // triangulatePoints + extract_3Dpoints on the same point pairs (d_x1, d_x2), as both loops call them: two launches instead of three.
-// c2 != nullptr: the same for a second lane's pair in the same two launches (its count is c2's CN_T, its mirror counts_host2); the
-// kernels go to c's stream.
 uvo_status pose_triangulate_extract3d(Ctx* c, int slot, const double* P1, const double* P2, const double* R1, const double* t1,
                                       const double* R2, const double* t2, const double* K1, const double* K2, const int* d_n, int n_max,
-                                      int* counts_host, Ctx* c2, int* counts_host2)
+                                      int* counts_host)
 {
-    const int nl = c2 ? 2 : 1;
     if (n_max > 0) {
         Mat34 a, b; memcpy(a.v, P1, sizeof(a.v)); memcpy(b.v, P2, sizeof(b.v));
         StageTimer t(c, ST_TRIANGULATE);
-        TriLanes tl; tl.l[0] = tri_lane(c, d_n, true); tl.l[1] = c2 ? tri_lane(c2, c2->d_counts + CN_T, true) : tl.l[0];
-        hipLaunchKernelGGL(k_triangulate<true>, dim3((n_max + kTriThreads - 1) / kTriThreads, nl), dim3(kTriThreads), 0, c->stream,
-                           a, b, tl, n_max, make_cam(R1, t1, K1), make_cam(R2, t2, K2), c->p.REPROJECTION_TOLERANCE);
+        hipLaunchKernelGGL(k_triangulate<true>, dim3((n_max + kTriThreads - 1) / kTriThreads), dim3(kTriThreads), 0, c->stream,
+                           a, b, tri_lane(c, d_n, true), n_max, make_cam(R1, t1, K1), make_cam(R2, t2, K2), c->p.REPROJECTION_TOLERANCE);
     }
     StageTimer t(c, ST_EXTRACT3D);
-    Ex3Lanes el; el.l[0] = ex3_lane(c, slot, d_n, counts_host); el.l[1] = c2 ? ex3_lane(c2, slot, c2->d_counts + CN_T, counts_host2) : el.l[0];
-    hipLaunchKernelGGL(k_extract3d_b, dim3(1, nl), dim3(1024), 0, c->stream, el, n_max, c->p.MIN_NUM_3DPOINTS, extract3d_force_seq());
+    hipLaunchKernelGGL(k_extract3d_b, dim3(1), dim3(1024), 0, c->stream, ex3_lane(c, slot, d_n, counts_host), n_max, c->p.MIN_NUM_3DPOINTS, extract3d_force_seq());
     UVO_HIP_TRY(c, hipGetLastError());
     return UVO_OK;
 }
@@ -1009,8 +1000,7 @@ uvo_status pose_triangulate_extract3d_pick(Ctx* c, const double* P1, const doubl
     StageTimer t(c, ST_EXTRACT3D);
     Ex3Lane e = ex3_lane(c, 0, d_n, nullptr);
     e.xc = d_in2;
-    Ex3Lanes el; el.l[0] = el.l[1] = e;
-    hipLaunchKernelGGL(k_extract3d_b, dim3(1, 1), dim3(1024), 0, c->stream, el, n_max, c->p.MIN_NUM_3DPOINTS, extract3d_force_seq());
+    hipLaunchKernelGGL(k_extract3d_b, dim3(1), dim3(1024), 0, c->stream, e, n_max, c->p.MIN_NUM_3DPOINTS, extract3d_force_seq());
     UVO_HIP_TRY(c, hipGetLastError());
     return UVO_OK;
 }
@@ -1040,8 +1030,7 @@ uvo_status pose_stereo_tail(Ctx* a, Ctx* p, int prev, int curr, int slot, const 
     else {
         ta.out_pts4 = nullptr; ta.p4_blocks = 0;
         StageTimer t(a, ST_EXTRACT3D);
-        Ex3Lanes el; el.l[0] = el.l[1] = ta.ex;
-        hipLaunchKernelGGL(k_extract3d_b, dim3(1, 1), dim3(1024), 0, a->stream, el, cap, a->p.MIN_NUM_3DPOINTS, extract3d_force_seq());
+        hipLaunchKernelGGL(k_extract3d_b, dim3(1), dim3(1024), 0, a->stream, ta.ex, cap, a->p.MIN_NUM_3DPOINTS, extract3d_force_seq());
     }
     StageTimer t(a, ST_TRIANGULATE);
     hipLaunchKernelGGL(k_stereo_tail, dim3(ta.fused + ta.tri_blocks + ta.p4_blocks + ta.gather_blocks), dim3(kTailThreads), 0, a->stream, m1, m2,
@@ -1076,8 +1065,7 @@ uvo_status pose_extract3d(Ctx* c, int slot, const double* R1, const double* t1, 
         hipLaunchKernelGGL(k_extract3d_a, dim3((n_max + 255) / 256), dim3(256), 0, c->stream, c->d_pts4, c->d_x1, c->d_x2,
                            make_cam(R1, t1, K1), make_cam(R2, t2, K2), c->p.REPROJECTION_TOLERANCE, d_n, n_max, c->d_cam1, c->d_flag);
     }
-    Ex3Lanes el; el.l[0] = el.l[1] = ex3_lane(c, slot, d_n, counts_host);
-    hipLaunchKernelGGL(k_extract3d_b, dim3(1), dim3(1024), 0, c->stream, el, n_max, c->p.MIN_NUM_3DPOINTS, extract3d_force_seq());
+    hipLaunchKernelGGL(k_extract3d_b, dim3(1), dim3(1024), 0, c->stream, ex3_lane(c, slot, d_n, counts_host), n_max, c->p.MIN_NUM_3DPOINTS, extract3d_force_seq());
     UVO_HIP_TRY(c, hipGetLastError());
     return UVO_OK;
 }

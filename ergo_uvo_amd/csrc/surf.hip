@@ -45,15 +45,9 @@ struct DescArgs { const uint8_t* img[2]; uvo_keypoint* kps[2]; float* desc[2]; c
                   const AreaTab* tabs; const int* iscale;        // [kMaxWin + 1][21] resize tables, [kMaxWin + 1] integer scale (0: general path)
                   int extended;                                  // SURF_EXTENDED: 128 elements per descriptor row (8 sums per cell)
                   const int32_t* sum[2]; const float* ori_w; int* ori_drop; };   // orientation assignment (SURF_UPRIGHT = false): integral images, sample weights
-// Everything of the detector that belongs to ONE pipeline lane (one stereo pair: two images).  Every kernel of the stage takes a
-// LanePair and indexes it with the high bit of its image index -- blockIdx.y (or .z / .x where the kernel counts images there)
-// runs over 2 * nimg in a two-pair launch: the detector stages of two consecutive pairs of the stream, on two lanes' buffers, in
-// ONE launch each (uvo_stereo_submit, batch mode: the thin kernels -- scans, rank sort, finish passes -- take as long for four
-// images as for two).  A single pair is a LanePair whose entries are the same.
+// Everything of the detector that belongs to ONE pipeline lane (one stereo pair: two images, or a mono frame: one).  Every kernel of
+// the stage takes it by value; the image index is blockIdx.y (or .z / .x where the kernel counts images there).
 struct LaneArgs { ImgPair ip; int32_t* part; SurvOut sv; CandOut out; SortArgs sa; DescArgs da; uint8_t* patch; const int4* big_in; int4* big_out; int* big_large; };
-struct LanePair { LaneArgs a[2]; };
-#define UVO_LANE_IM(idx) ((int)(idx) & 1)
-#define UVO_LANE_OF(lp, idx) ((lp).a[(int)(idx) >> 1])
 // The integral image in three launches that move 4 + 4 + 33 MB for a 1080p pair (image twice, result once):
 //   k_integral_strip_sums   a workgroup per strip of 8 image rows: row prefixes in registers, their column sums over the strip
 //   k_integral_strip_scan   exclusive scan of those sums over the strips (a 135 x 1921 matrix at 1080p)
@@ -113,10 +107,10 @@ __device__ __forceinline__ void strip_row_prefix(const uint8_t* img, int w, int 
 }
 __device__ __forceinline__ int packed_px(unsigned lo, unsigned hi, int k) { return (int)(((k < 4 ? lo : hi) >> (8 * (k & 3))) & 255u); }
 
-__global__ __launch_bounds__(256) void k_integral_strip_sums(LanePair lp, int w, int h, int cstride, int nstrip)
+__global__ __launch_bounds__(256) void k_integral_strip_sums(LaneArgs LA, int w, int h, int cstride, int nstrip)
 {
-    const LaneArgs& LA = UVO_LANE_OF(lp, blockIdx.y); const ImgPair& ip = LA.ip; int32_t* part = LA.part;
-    const int strip = blockIdx.x, im = UVO_LANE_IM(blockIdx.y), tid = threadIdx.x;
+    const ImgPair& ip = LA.ip; int32_t* part = LA.part;
+    const int strip = blockIdx.x, im = blockIdx.y, tid = threadIdx.x;
     __shared__ int wt[kStripRows][4];
     int carry[kStripRows];
 #pragma unroll
@@ -140,10 +134,10 @@ __global__ __launch_bounds__(256) void k_integral_strip_sums(LanePair lp, int w,
 }
 
 // part[im][s][x] <- sum of part[im][0 .. s-1][x]: 32 columns x 8 groups of strips per workgroup
-__global__ __launch_bounds__(256) void k_integral_strip_scan(LanePair lp, int cstride, int nstrip, int w)
+__global__ __launch_bounds__(256) void k_integral_strip_scan(LaneArgs LA, int cstride, int nstrip, int w)
 {
-    int32_t* part = UVO_LANE_OF(lp, blockIdx.y).part;
-    const int tid = threadIdx.x, xl = tid & 31, g = tid >> 5, x = blockIdx.x * 32 + xl, im = UVO_LANE_IM(blockIdx.y);
+    int32_t* part = LA.part;
+    const int tid = threadIdx.x, xl = tid & 31, g = tid >> 5, x = blockIdx.x * 32 + xl, im = blockIdx.y;
     __shared__ int gsum[8][32];
     const int per = (nstrip + 7) / 8, s0 = g * per, s1 = min(nstrip, s0 + per);
     int32_t* p = part + (size_t)im * nstrip * cstride + x;
@@ -160,10 +154,10 @@ __global__ __launch_bounds__(256) void k_integral_strip_scan(LanePair lp, int cs
     for (int sI = s0; sI < s1; sI++) { const int v = p[(size_t)sI * cstride]; p[(size_t)sI * cstride] = acc; acc += v; }
 }
 
-__global__ __launch_bounds__(256) void k_integral_strip_final(LanePair lp, int w, int h, int cstride, int nstrip)
+__global__ __launch_bounds__(256) void k_integral_strip_final(LaneArgs LA, int w, int h, int cstride, int nstrip)
 {
-    const LaneArgs& LA = UVO_LANE_OF(lp, blockIdx.y); const ImgPair& ip = LA.ip; const int32_t* part = LA.part;
-    const int strip = blockIdx.x, im = UVO_LANE_IM(blockIdx.y), tid = threadIdx.x;
+    const ImgPair& ip = LA.ip; const int32_t* part = LA.part;
+    const int strip = blockIdx.x, im = blockIdx.y, tid = threadIdx.x;
     const int sw = w + 1, y0 = strip * kStripRows;
     __shared__ int wt[kStripRows][4];
     __shared__ __align__(16) int rowbuf[kStripRows / 2][kStripCols];
@@ -784,9 +778,9 @@ __device__ __forceinline__ void nms_survivors(const float* __restrict__ sdet, un
 // arithmetic, as k_hessian_layer_debug); lane 0 makes the comparison against them and runs findMaximaInLayer's tail.  The
 // workgroup's keypoints are collected in LDS and appended with one atomic per image.
 static const int kFinishPerWg = 16;
-__global__ __launch_bounds__(256) void k_hessian_finish(LanePair lp, const OctavePat* __restrict__ ops, int w, int h)
+__global__ __launch_bounds__(256) void k_hessian_finish(LaneArgs LA, const OctavePat* __restrict__ ops, int w, int h)
 {
-    const LaneArgs& LA = lp.a[blockIdx.y]; const SurvOut& sv = LA.sv; const ImgPair& ip = LA.ip; const CandOut& out = LA.out;
+    const SurvOut& sv = LA.sv; const ImgPair& ip = LA.ip; const CandOut& out = LA.out;
     __shared__ uvo_keypoint s_kp[2][kFinishPerWg];
     __shared__ int s_cnt[2], s_base[2];
     const int grp = threadIdx.x >> 4, k = threadIdx.x & 15;
@@ -936,21 +930,20 @@ __device__ __forceinline__ void hessian_nms_c_tile(const ImgPair& ip, int w, int
     nms_survivors<TW, TH, NT>(sdet, reinterpret_cast<unsigned*>(stile + THs * STEP * PW), op, thr, px0, py0, im, sv);
 }
 template <int O, int TW, int TH, int NT>
-__global__ __launch_bounds__(NT) void k_hessian_nms_c(LanePair lp, int w, int h, OctavePat op, float thr)
+__global__ __launch_bounds__(NT) void k_hessian_nms_c(LaneArgs LA, int w, int h, OctavePat op, float thr)
 {
     extern __shared__ __align__(16) unsigned char smem[];
-    const LaneArgs& LA = UVO_LANE_OF(lp, blockIdx.z);
-    hessian_nms_c_tile<O, TW, TH, NT>(LA.ip, w, h, op, thr, LA.sv, blockIdx.x, blockIdx.y, UVO_LANE_IM(blockIdx.z), smem);
+    hessian_nms_c_tile<O, TW, TH, NT>(LA.ip, w, h, op, thr, LA.sv, blockIdx.x, blockIdx.y, blockIdx.z, smem);
 }
 
 // Octaves 2 and 3: det layers from the de-interleaved planes, det planes in LDS, survivors as above.
 template <int O, int TW, int TH, int NT>
-__global__ __launch_bounds__(NT) void k_hessian_nms_p(LanePair lp, int w, int h, OctavePat op, float thr)
+__global__ __launch_bounds__(NT) void k_hessian_nms_p(LaneArgs LA, int w, int h, OctavePat op, float thr)
 {
     __shared__ float sdet[3 * TH * TW];
     __shared__ unsigned s_list[NmsLds<TW, TH>::kWords];
-    const LaneArgs& LA = UVO_LANE_OF(lp, blockIdx.z); const ImgPair& ip = LA.ip; const SurvOut& sv = LA.sv;
-    const int im = UVO_LANE_IM(blockIdx.z);
+    const ImgPair& ip = LA.ip; const SurvOut& sv = LA.sv;
+    const int im = blockIdx.z;
     const int px0 = blockIdx.x * (TW - 2) - 1, py0 = blockIdx.y * (TH - 2) - 1;
     det_layer_p<O, 1, TW, TH, NT>(ip.planes[im], ip.pw, ip.pstride, sdet, op, px0, py0, thr);
     det_layer_p<O, 2, TW, TH, NT>(ip.planes[im], ip.pw, ip.pstride, sdet, op, px0, py0, thr);
@@ -999,16 +992,16 @@ struct HessGrid { int nbx0, nb0, nbx1, nb1; P23Grid g; };          // tiles per 
 // turn-over costs per tile -- 93 / 103 / 105 us against 84: a slot bound to a fixed run of tiles loses the balance that "whichever
 // slot frees up takes the next tile" gives; the same lesson as the resident-workgroup queues)
 template <int TW, int TH>
-__global__ __launch_bounds__(kP23Threads) void k_hessian_nms_all(LanePair lp, int w, int h, HessDims hd, float thr,
+__global__ __launch_bounds__(kP23Threads) void k_hessian_nms_all(LaneArgs LA, int w, int h, HessDims hd, float thr,
                                                                  const uint32_t* __restrict__ order)
 {
     extern __shared__ __align__(16) unsigned char smem[];
-    const LaneArgs& LA = UVO_LANE_OF(lp, blockIdx.y); const ImgPair& ip = LA.ip;
+    const ImgPair& ip = LA.ip;
     // the survivor list's address, counter and capacity are read here, with the other arguments, rather than by scalar loads of their own
     // behind the tile's last barriers
     SurvOut sv = LA.sv;
     asm volatile("" : "+s"(sv.list), "+s"(sv.count), "+s"(sv.cap));
-    const int im = UVO_LANE_IM(blockIdx.y);
+    const int im = blockIdx.y;
     const unsigned e = order[blockIdx.x];
     const int kind = e >> 30, bx = e & 0x3FFF, by = (e >> 14) & 0x3FFF;
     hess_stamp(0); hess_stamp(4, kind);
@@ -1087,11 +1080,10 @@ static const int kOrderBinsPer = kOrderBuckets / kOrderThreads;  // buckets per 
 static_assert(kOrderBuckets % kOrderThreads == 0 && kBigBins == kOrderThreads, "k_order scans kOrderBinsPer buckets and one window bin per thread");
 static_assert(kOrderCap <= 65536, "bucket members are 16-bit candidate indices");
 
-__global__ __launch_bounds__(1024) void k_big_sort(LanePair lp, int cap, const int* __restrict__ iscale_tab)
+__global__ __launch_bounds__(1024) void k_big_sort(LaneArgs LA, int cap, const int* __restrict__ iscale_tab)
 {
-    const LaneArgs& LA = UVO_LANE_OF(lp, blockIdx.x);
     const int4* __restrict__ in = LA.big_in; int4* __restrict__ out = LA.big_out; const int* __restrict__ big_n = LA.da.big_n; int* __restrict__ big_large = LA.big_large;
-    const int im = UVO_LANE_IM(blockIdx.x), tid = threadIdx.x;
+    const int im = blockIdx.x, tid = threadIdx.x;
     if (min(LA.sa.cand_n[im], cap) <= kOrderCap) return;       // k_order's image
     const int n = min(big_n[im], cap);
     __shared__ int hist[kBigBins], scan[kBigBins];
@@ -1147,11 +1139,10 @@ __device__ __forceinline__ int wave_incl_scan(int v)
     return v;
 }
 
-__global__ __launch_bounds__(kOrderThreads) void k_order(LanePair lp, const int* __restrict__ iscale_tab)
+__global__ __launch_bounds__(kOrderThreads) void k_order(LaneArgs LA, const int* __restrict__ iscale_tab)
 {
-    const LaneArgs& LA = UVO_LANE_OF(lp, blockIdx.y);
     const SortArgs& a = LA.sa;
-    const int im = UVO_LANE_IM(blockIdx.y), tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int im = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int n = min(a.cand_n[im], a.cap);
     if (n > kOrderCap) return;                                   // (uniform) the fallback launches order this image
     __shared__ unsigned long long s_k1[kOrderCap];
@@ -1263,10 +1254,10 @@ __global__ __launch_bounds__(kOrderThreads) void k_order(LanePair lp, const int*
     }
 }
 
-__global__ __launch_bounds__(256) void k_rank_partial(LanePair lp)
+__global__ __launch_bounds__(256) void k_rank_partial(LaneArgs LA)
 {
-    const SortArgs& a = UVO_LANE_OF(lp, blockIdx.y).sa;
-    const int im = UVO_LANE_IM(blockIdx.y), tid = threadIdx.x;
+    const SortArgs& a = LA.sa;
+    const int im = blockIdx.y, tid = threadIdx.x;
     const int n = min(a.cand_n[im], a.cap);
     if (n <= kOrderCap) return;                                  // k_order's image
     __shared__ SortKey tile[kSortChunk];
@@ -1302,10 +1293,10 @@ __global__ __launch_bounds__(256) void k_rank_partial(LanePair lp)
     }
 }
 
-__global__ __launch_bounds__(256) void k_rank_scatter(LanePair lp)
+__global__ __launch_bounds__(256) void k_rank_scatter(LaneArgs LA)
 {
-    const SortArgs& a = UVO_LANE_OF(lp, blockIdx.y).sa;
-    const int im = UVO_LANE_IM(blockIdx.y);
+    const SortArgs& a = LA.sa;
+    const int im = blockIdx.y;
     const int n = min(a.cand_n[im], a.cap);
     if (n <= kOrderCap) return;                                  // k_order's image
     const int me = blockIdx.x * 256 + threadIdx.x;
@@ -2078,26 +2069,30 @@ __device__ __forceinline__ void descriptor64_big(const DescArgs& a, int w, int h
 // small-window keypoint each.  The large-window part stalls on its per-tap dependency chains, the small-window part on its
 // barriers; resident together they keep the VALU busier than one after the other (and a launch is saved).
 // (8 waves per SIMD: the compiler would settle at 66 VGPRs = 7 waves)
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_descriptor64(LanePair lp, int w, int h, int nbig, int part, int nim, int order)
+// The lane's arguments arrive as a one-entry array that the kernel indexes with yy >> 1 (0: a launch has at most two images).  With the
+// fields at constant offsets of the argument block the compiler loads them at entry, spills 46 SGPRs instead of 37 and needs 24 bytes of
+// scratch instead of 16 under the 64-VGPR cap; behind a run-time index each field is loaded where it is used.
+struct DescLane { LaneArgs a[1]; };
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_descriptor64(DescLane dl, int w, int h, int nbig, int part, int nimg, int order)
 {
     // The launch is one row of workgroups; `order` says who comes first (the hardware starts workgroups in index order, and with
     // lifetimes of 4 to 14 us that order decides what is resident together): 0: image by image, each image's large-window waves before
     // its small-window workgroups (rounds 2-4); 1: every image's large-window waves, then the small-window workgroups image by image;
     // 2: the same with the small-window workgroups of the images alternating
-    const int nsmall = (int)gridDim.x / nim - nbig;
+    const int nsmall = (int)gridDim.x / nimg - nbig;
     int id = blockIdx.x, yy, bx; bool big;
     if (order == 0) { yy = id / (nbig + nsmall); bx = id - yy * (nbig + nsmall); big = bx < nbig; if (!big) bx -= nbig; }
-    else if (id < nim * nbig) { yy = id / nbig; bx = id - yy * nbig; big = true; }
-    else { id -= nim * nbig; big = false; if (order == 1) { yy = id / nsmall; bx = id - yy * nsmall; } else { yy = id % nim; bx = id / nim; } }
-    const LaneArgs& LA = UVO_LANE_OF(lp, yy); const DescArgs& a = LA.da; uint8_t* __restrict__ patch = LA.patch;
+    else if (id < nimg * nbig) { yy = id / nbig; bx = id - yy * nbig; big = true; }
+    else { id -= nimg * nbig; big = false; if (order == 1) { yy = id / nsmall; bx = id - yy * nsmall; } else { yy = id % nimg; bx = id / nimg; } }
+    const LaneArgs& LA = dl.a[yy >> 1]; const DescArgs& a = LA.da; uint8_t* __restrict__ patch = LA.patch;
     // part (UVO_DESC_PART, measurement only -- the other class of keypoints gets no descriptor): 1 = large windows only, 2 = small only
-    if (big) { if (part != 2) descriptor64_big(a, w, h, patch, bx, nbig, UVO_LANE_IM(yy)); }
-    else if (part != 1) descriptor64_small(a, w, h, bx, nsmall, UVO_LANE_IM(yy));
+    if (big) { if (part != 2) descriptor64_big(a, w, h, patch, bx, nbig, yy & 1); }
+    else if (part != 1) descriptor64_small(a, w, h, bx, nsmall, yy & 1);
 }
-__global__ __launch_bounds__(256) void k_descriptor64_big_finish(LanePair lp)
+__global__ __launch_bounds__(256) void k_descriptor64_big_finish(LaneArgs LA)
 {
-    const LaneArgs& LA = UVO_LANE_OF(lp, blockIdx.y); const DescArgs& a = LA.da; const uint8_t* __restrict__ patch = LA.patch;
-    const int im = UVO_LANE_IM(blockIdx.y), tid = threadIdx.x;
+    const DescArgs& a = LA.da; const uint8_t* __restrict__ patch = LA.patch;
+    const int im = blockIdx.y, tid = threadIdx.x;
     const int nb = a.big_n[im];
     __shared__ int PATCH[21][21];
     for (int e = blockIdx.x; e < nb; e += gridDim.x) {
@@ -2178,39 +2173,31 @@ static LaneArgs lane_args(Ctx* c, int nimg, int gate_min_features)
     a.big_in = c->d_big_par; a.big_out = c->d_big_par + (size_t)2 * c->cap; a.big_large = c->d_counts + CN_BIGL0;
     return a;
 }
-// one lane, or the two lanes of a two-pair launch (c2; both hold image pairs of the same size, kernels go to c's stream)
-static LanePair lane_pair(Ctx* c, Ctx* c2, int nimg, int gate_min_features)
-{
-    LanePair lp;
-    lp.a[0] = lane_args(c, nimg, gate_min_features);
-    lp.a[1] = c2 ? lane_args(c2, nimg, gate_min_features) : lp.a[0];
-    return lp;
-}
 
-static uvo_status surf_integral_lanes(Ctx* c, const LanePair& lp, int nim)       // nim: images over all lanes of the launch
+static uvo_status surf_integral_launch(Ctx* c, const LaneArgs& LA, int nimg)
 {
     const int w = c->img_w, h = c->img_h, sw = w + 1;
     const int nstrip = (h + kStripRows - 1) / kStripRows, cstride = c->colpart_stride;
     StageTimer t(c, ST_INTEGRAL);
-    hipLaunchKernelGGL(k_integral_strip_sums, dim3(nstrip, nim), dim3(256), 0, c->stream, lp, w, h, cstride, nstrip);
-    hipLaunchKernelGGL(k_integral_strip_scan, dim3((sw + 31) / 32, nim), dim3(256), 0, c->stream, lp, cstride, nstrip, w);
-    hipLaunchKernelGGL(k_integral_strip_final, dim3(nstrip, nim), dim3(256), 0, c->stream, lp, w, h, cstride, nstrip);
+    hipLaunchKernelGGL(k_integral_strip_sums, dim3(nstrip, nimg), dim3(256), 0, c->stream, LA, w, h, cstride, nstrip);
+    hipLaunchKernelGGL(k_integral_strip_scan, dim3((sw + 31) / 32, nimg), dim3(256), 0, c->stream, LA, cstride, nstrip, w);
+    hipLaunchKernelGGL(k_integral_strip_final, dim3(nstrip, nimg), dim3(256), 0, c->stream, LA, w, h, cstride, nstrip);
     UVO_HIP_TRY(c, hipGetLastError());
     return UVO_OK;
 }
-uvo_status surf_integral(Ctx* c, int nimg) { return surf_integral_lanes(c, lane_pair(c, nullptr, nimg, -1), nimg); }
+uvo_status surf_integral(Ctx* c, int nimg) { return surf_integral_launch(c, lane_args(c, nimg, -1), nimg); }
 
 template <int O, int TW, int TH, int NT>
-static hipError_t launch_hessian_p(Ctx* c, const LanePair& lp, int nim, const OctavePat& op, float thr)
+static hipError_t launch_hessian_p(Ctx* c, const LaneArgs& LA, int nimg, const OctavePat& op, float thr)
 {
     const int w = c->img_w, h = c->img_h;
-    dim3 grid((op.cols + TW - 3) / (TW - 2), (op.rows + TH - 3) / (TH - 2), nim);
-    hipLaunchKernelGGL((k_hessian_nms_p<O, TW, TH, NT>), grid, dim3(NT), 0, c->stream, lp, w, h, op, thr);
+    dim3 grid((op.cols + TW - 3) / (TW - 2), (op.rows + TH - 3) / (TH - 2), nimg);
+    hipLaunchKernelGGL((k_hessian_nms_p<O, TW, TH, NT>), grid, dim3(NT), 0, c->stream, LA, w, h, op, thr);
     return hipGetLastError();
 }
 
 template <int O, int TW, int TH, int NT>
-static hipError_t launch_hessian_c(Ctx* c, const LanePair& lp, int nim, const OctavePat& op, float thr)
+static hipError_t launch_hessian_c(Ctx* c, const LaneArgs& LA, int nimg, const OctavePat& op, float thr)
 {
     using OC = OctC<O>;
     constexpr int STEP = OC::STEP;
@@ -2218,7 +2205,7 @@ static hipError_t launch_hessian_c(Ctx* c, const LanePair& lp, int nim, const Oc
     constexpr int PW = OctTile<O, TW>::PW;
     const int w = c->img_w, h = c->img_h;
     const size_t lds = sizeof(float) * 3 * TW * TH + sizeof(int32_t) * (size_t)THs * STEP * PW + sizeof(unsigned) * NmsLds<TW, TH>::kWords;
-    dim3 grid((op.cols + TW - 3) / (TW - 2), (op.rows + TH - 3) / (TH - 2), nim);
+    dim3 grid((op.cols + TW - 3) / (TW - 2), (op.rows + TH - 3) / (TH - 2), nimg);
     auto kern = k_hessian_nms_c<O, TW, TH, NT>;
     static bool attr_dev[64] = {false};                       // once per device (a process may hold contexts on several)
     bool& attr_set = attr_dev[c->device & 63];
@@ -2227,7 +2214,7 @@ static hipError_t launch_hessian_c(Ctx* c, const LanePair& lp, int nim, const Oc
         if (e != hipSuccess) return e;
         attr_set = true;
     }
-    hipLaunchKernelGGL(kern, grid, dim3(NT), lds, c->stream, lp, w, h, op, thr);
+    hipLaunchKernelGGL(kern, grid, dim3(NT), lds, c->stream, LA, w, h, op, thr);
     return hipGetLastError();
 }
 
@@ -2307,17 +2294,12 @@ uvo_status surf_prepare(Ctx* c, int w, int h)
     return UVO_OK;
 }
 
-// c2 != nullptr: the detector stages of TWO lanes (two consecutive stereo pairs of one stream, same image size) in one launch
-// each, queued on c's stream; results land in each lane's own buffers exactly as two calls would leave them.
-uvo_status surf_detect_lanes(Ctx* c, Ctx* c2, int nimg, int gate_min_features)
+uvo_status surf_detect(Ctx* c, int nimg, int gate_min_features)
 {
     const int w = c->img_w, h = c->img_h;
-    if (c2 && (nimg != 2 || c2->img_w != w || c2->img_h != h || !c->p.SURF_UPRIGHT)) { c->err = "two-pair launch: upright SURF on two image pairs of one size"; return UVO_INVALID_ARG; }
     UVO_TRY(surf_prepare(c, w, h));
-    if (c2) { const uvo_status st2 = surf_prepare(c2, w, h); if (st2 != UVO_OK) { c->err = c2->err; return st2; } }
-    const LanePair lp = lane_pair(c, c2, nimg, gate_min_features);
-    const int nim = c2 ? 2 * nimg : nimg, nlanes = c2 ? 2 : 1;
-    UVO_TRY(surf_integral_lanes(c, lp, nim));
+    const LaneArgs LA = lane_args(c, nimg, gate_min_features);
+    UVO_TRY(surf_integral_launch(c, LA, nimg));
     const float thr = (float)c->p.SURF_MIN_HESSIAN;
     {
         OctavePat ops[4];
@@ -2358,7 +2340,7 @@ uvo_status surf_detect_lanes(Ctx* c, Ctx* c2, int nimg, int gate_min_features)
             }
             Ctx::TraceRec* trh = (c->trace_on && c->trace_cur >= 0) ? &c->trace[c->trace_cur] : nullptr;      // uvo_trace_row::dev_ms[6], [7]
             if (trh) (void)hipEventRecord(trh->ev[6], c->stream);
-            hipLaunchKernelGGL(kern, dim3(total, nim), dim3(kP23Threads), lds_launch, c->stream, lp, w, h, hd, thr, c->d_hess_order);
+            hipLaunchKernelGGL(kern, dim3(total, nimg), dim3(kP23Threads), lds_launch, c->stream, LA, w, h, hd, thr, c->d_hess_order);
             if (trh) { (void)hipEventRecord(trh->ev[7], c->stream); trh->det_marked = true; }
             if (stamps_path && d_stamps && c->lane_id == 0) {        // (measurement: synchronous, every launch rewrites the file)
                 std::vector<long long> hs(stamps_n);
@@ -2366,7 +2348,7 @@ uvo_status surf_detect_lanes(Ctx* c, Ctx* c2, int nimg, int gate_min_features)
                 (void)hipMemcpy(hs.data(), d_stamps, sizeof(long long) * stamps_n, hipMemcpyDeviceToHost);
                 if (FILE* f = fopen(stamps_path, "w")) {
                     fprintf(f, "block,im,kind,t_start,t_filled,t_det,t_end,t_scan,t_scanbar,t_atomic\n");
-                    for (int y = 0; y < nim; y++) for (int b = 0; b < total; b++) { const long long* r = hs.data() + ((size_t)y * total + b) * 8; fprintf(f, "%d,%d,%lld,%lld,%lld,%lld,%lld,%lld,%lld,%lld\n", b, y, r[4], r[0], r[1], r[2], r[3], r[5], r[6], r[7]); }
+                    for (int y = 0; y < nimg; y++) for (int b = 0; b < total; b++) { const long long* r = hs.data() + ((size_t)y * total + b) * 8; fprintf(f, "%d,%d,%lld,%lld,%lld,%lld,%lld,%lld,%lld,%lld\n", b, y, r[4], r[0], r[1], r[2], r[3], r[5], r[6], r[7]); }
                     fclose(f);
                 }
             }
@@ -2379,15 +2361,15 @@ uvo_status surf_detect_lanes(Ctx* c, Ctx* c2, int nimg, int gate_min_features)
             // tile shapes chosen by pipelined throughput (tools/probe/ab.sh): octave 0 64 x 24 samples = 40 KB of LDS (18 KB det planes,
             // 19 KB integral tile, 3 KB survivor list), octave 1 32 x 24 = 59 KB (9 KB + 48 KB: the 54-pixel templates make the halo
             // most of the tile)
-            if (o == 0)      e = launch_hessian_c<0, 64, 24, 512>(c, lp, nim, op, thr);
-            else if (o == 1) e = launch_hessian_c<1, 32, 24, 512>(c, lp, nim, op, thr);
-            else if (o == 2) e = launch_hessian_p<2, 32, 16, 512>(c, lp, nim, op, thr);
-            else             e = launch_hessian_p<3, 16, 16, 256>(c, lp, nim, op, thr);
+            if (o == 0)      e = launch_hessian_c<0, 64, 24, 512>(c, LA, nimg, op, thr);
+            else if (o == 1) e = launch_hessian_c<1, 32, 24, 512>(c, LA, nimg, op, thr);
+            else if (o == 2) e = launch_hessian_p<2, 32, 16, 512>(c, LA, nimg, op, thr);
+            else             e = launch_hessian_p<3, 16, 16, 256>(c, LA, nimg, op, thr);
             UVO_HIP_TRY(c, e);
         }
         {   // the survivors of every octave: outer-layer determinants, last comparison, keypoints
             StageTimer t(c, ST_HESSIAN_O0 + c->p.SURF_OCTAVES_NUMBER - 1);
-            hipLaunchKernelGGL(k_hessian_finish, dim3((c->surv_cap + kFinishPerWg - 1) / kFinishPerWg, nlanes), dim3(256), 0, c->stream, lp, static_cast<const OctavePat*>(c->d_octpat), w, h);
+            hipLaunchKernelGGL(k_hessian_finish, dim3((c->surv_cap + kFinishPerWg - 1) / kFinishPerWg), dim3(256), 0, c->stream, LA, static_cast<const OctavePat*>(c->d_octpat), w, h);
             UVO_HIP_TRY(c, hipGetLastError());
         }
         static const int probe_thin = getenv("UVO_PROBE_THIN_US") ? atoi(getenv("UVO_PROBE_THIN_US")) : 0, probe_fat = getenv("UVO_PROBE_FAT_US") ? atoi(getenv("UVO_PROBE_FAT_US")) : 0;
@@ -2400,12 +2382,12 @@ uvo_status surf_detect_lanes(Ctx* c, Ctx* c2, int nimg, int gate_min_features)
     }
     {
         StageTimer t(c, ST_SORT);
-        hipLaunchKernelGGL(k_order, dim3(1, nim), dim3(kOrderThreads), 0, c->stream, lp, c->d_area_iscale);
+        hipLaunchKernelGGL(k_order, dim3(1, nimg), dim3(kOrderThreads), 0, c->stream, LA, c->d_area_iscale);
         if (c->cap > kOrderCap) {                              // the counts live on the device: each of these returns at once for an image k_order ordered
             const int tiles_max = ((c->cap + 255) / 256) * ((c->cap + kSortChunk - 1) / kSortChunk);
-            hipLaunchKernelGGL(k_rank_partial, dim3(tiles_max < 512 ? tiles_max : 512, nim), dim3(256), 0, c->stream, lp);
-            hipLaunchKernelGGL(k_rank_scatter, dim3((c->cap + 255) / 256, nim), dim3(256), 0, c->stream, lp);
-            hipLaunchKernelGGL(k_big_sort, dim3(nim), dim3(1024), 0, c->stream, lp, c->cap, c->d_area_iscale);
+            hipLaunchKernelGGL(k_rank_partial, dim3(tiles_max < 512 ? tiles_max : 512, nimg), dim3(256), 0, c->stream, LA);
+            hipLaunchKernelGGL(k_rank_scatter, dim3((c->cap + 255) / 256, nimg), dim3(256), 0, c->stream, LA);
+            hipLaunchKernelGGL(k_big_sort, dim3(nimg), dim3(1024), 0, c->stream, LA, c->cap, c->d_area_iscale);
         }
         UVO_HIP_TRY(c, hipGetLastError());
     }
@@ -2417,7 +2399,7 @@ uvo_status surf_detect_lanes(Ctx* c, Ctx* c2, int nimg, int gate_min_features)
             static const int desc_part = getenv("UVO_DESC_PART") ? atoi(getenv("UVO_DESC_PART")) : 0;      // measurement only
             static const char* dstamps_path = UVO_STAMPS ? getenv("UVO_DESC_STAMPS") : nullptr;
             static long long* d_dstamps = nullptr; const size_t dstamps_n = (size_t)4 * 16384 * 8;
-            const bool dstamp = dstamps_path && c->lane_id == 0 && nim == 2;
+            const bool dstamp = dstamps_path && c->lane_id == 0 && nimg == 2;
             if (dstamp) {
                 if (!d_dstamps) { (void)hipMalloc(reinterpret_cast<void**>(&d_dstamps), sizeof(long long) * dstamps_n); (void)hipMemcpyToSymbol(HIP_SYMBOL(g_desc_stamps), &d_dstamps, sizeof(d_dstamps)); }
                 (void)hipMemsetAsync(d_dstamps, 0, sizeof(long long) * dstamps_n, c->stream);
@@ -2434,7 +2416,7 @@ uvo_status surf_detect_lanes(Ctx* c, Ctx* c2, int nimg, int gate_min_features)
             static const int desc_order = getenv("UVO_DESC_ORDER") ? atoi(getenv("UVO_DESC_ORDER")) : 2;            // measurement
             static const int nbig_env = getenv("UVO_DESC_NBIG") ? atoi(getenv("UVO_DESC_NBIG")) : 0;
             const int nbig_l = nbig_env > 0 ? nbig_env : nbig;
-            hipLaunchKernelGGL(k_descriptor64, dim3((nbig_l + nsmall) * nim), dim3(256), lds_small > lds_big ? lds_small : lds_big, c->stream, lp, w, h, nbig_l, desc_part, nim, desc_order);
+            hipLaunchKernelGGL(k_descriptor64, dim3((nbig_l + nsmall) * nimg), dim3(256), lds_small > lds_big ? lds_small : lds_big, c->stream, DescLane{ { LA } }, w, h, nbig_l, desc_part, nimg, desc_order);
             if (dstamp && d_dstamps) {                        // (measurement: synchronous, every launch rewrites the file)
                 std::vector<long long> hs(dstamps_n);
                 (void)hipStreamSynchronize(c->stream);
@@ -2450,10 +2432,10 @@ uvo_status surf_detect_lanes(Ctx* c, Ctx* c2, int nimg, int gate_min_features)
                     fclose(f);
                 }
             }
-            hipLaunchKernelGGL(k_descriptor64_big_finish, dim3(1024, nim), dim3(256), 0, c->stream, lp);
+            hipLaunchKernelGGL(k_descriptor64_big_finish, dim3(1024, nimg), dim3(256), 0, c->stream, LA);
         } else {
             // orientation assignment, then every descriptor from its rotated window (not the shipped configuration)
-            const DescArgs& da = lp.a[0].da;
+            const DescArgs& da = LA.da;
             const size_t lds_rot = sizeof(float) * 21 * (kMaxWin + 1);
             static bool rot_attr_dev[64] = {false};
             bool& rot_attr = rot_attr_dev[c->device & 63];
@@ -2465,7 +2447,6 @@ uvo_status surf_detect_lanes(Ctx* c, Ctx* c2, int nimg, int gate_min_features)
     }
     return UVO_OK;
 }
-uvo_status surf_detect(Ctx* c, int nimg, int gate_min_features) { return surf_detect_lanes(c, nullptr, nimg, gate_min_features); }
 
 uvo_status surf_hessian_layer_debug(Ctx* c, int octave, int layer, float* det, float* trace)
 {

@@ -10,7 +10,6 @@
 #include <deque>
 #include <stdint.h>
 #include "../../include/uvo_hip.h"
-#include "uvo_experimental.h"
 
 namespace uvo {
 
@@ -71,12 +70,11 @@ struct Shared {
     int next_lane = 0;                           // lane of the next submitted pair
     int prev_lane = 0, prev_buf = 0;             // where the previous pair's as-set lives
     bool prev_sync = true;                       // that set was written synchronously (init step), no event to wait for
-    int stashed_lane = -1;                       // lane of the pair that waits for its partner (-1: none)
     int inflight[kMaxDepth]; int n_pending = 0;  // lanes of the submitted, not yet collected pairs (FIFO)
     long long n_submitted = 0, n_collected = 0;
     int last_lane = 0;
     long long plan_seq = 0;                      // pipelined entries planned so far (never reset); Ctx::assigned_seq is the lane's side
-    long long a_launch = 0;                      // stage-A launch sets queued so far (a two-pair set counts once): set t runs on A slot t mod (a_overlap + 1)
+    long long a_launch = 0;                      // stage-A launch sets queued so far: set t runs on A slot t mod (a_overlap + 1)
     bool in_sync_step = false;                   // the submit in progress is uvo_stereo_step's (one pair in flight)
     // keypoints per image of the last pair / frame whose counts reached the host (0: none yet): sizes the descriptor launch's
     // small-window part -- a grid of max_kpts workgroups spends a sixth of the launch's wave-time on workgroups that find no keypoint
@@ -114,11 +112,6 @@ struct Shared {
     double cpu_budget = 0;                       // logical CPUs this process may keep busy (host_cpu_budget(), ctx.hip)
     int a_overlap = 2;                           // stage As (detect .. extract_3Dpoints) allowed side by side (env UVO_A_OVERLAP, 0 = no limit)
     int a_overlap_mono = 4;                      // the same for mono frames (one image each; env UVO_A_OVERLAP_MONO)
-    // Two-pair launches (uvo_stereo_set_batch(c, 2); env UVO_BATCH): uvo_stereo_submit holds every first pair of two back until the
-    // next one arrives and queues the stage As of both -- lanes i and i + 1 -- as ONE set of launches on lane i's stream.  A pair
-    // waiting alone is queued by the first collect that needs it.  Results are those of single launches, pair for pair.
-    int batch = 1;                               // pairs per launch set (1 or 2)
-    int a_overlap2 = 2;                          // two-pair launch sets allowed side by side (env UVO_A_OVERLAP2)
     int max_b = 3;                               // PnP stages allowed at once (env UVO_MAX_B) ..
     int max_b_mono = 10;                         // ... and mono pose stages (env UVO_MAX_B_MONO): 2 ms of host-orchestrated, latency-bound kernels each (the
                                                  // five-point solver keeps one wave per SIMD busy for 0.9 ms), so many of them side by side cost little
@@ -354,8 +347,7 @@ uvo_status surf_upload(Ctx* c, int slot, const uint8_t* gray, int w, int h, int 
 uvo_status surf_integral(Ctx* c, int nimg);
 uvo_status surf_build_area_tables(Ctx* c);
 uvo_status surf_prepare(Ctx* c, int w, int h);                           // per-image-size tables of this lane (idempotent)
-uvo_status surf_detect(Ctx* c, int nimg, int gate_min_features = -1);
-uvo_status surf_detect_lanes(Ctx* c, Ctx* c2, int nimg, int gate_min_features);     // c2: a second lane's pair in the same launches (or nullptr)   // integral -> ... -> sorted kps + descriptors in c->det[];
+uvo_status surf_detect(Ctx* c, int nimg, int gate_min_features = -1);     // integral -> ... -> sorted kps + descriptors in c->det[];
                                                                         // gate_min_features >= 0: also evaluate VO:556 into d_counts[CN_NQA]
 uvo_status surf_hessian_layer_debug(Ctx* c, int octave, int layer, float* det, float* trace);
 // match.hip
@@ -375,16 +367,13 @@ uvo_status match_knn2_two(Ctx* c, const float* d_q0, const int* d_nq0, const flo
                           const float* d_q1, const int* d_nq1, const float* d_t1, const int* d_nt1, int n_max);
 uvo_status match_ratio_compact2(Ctx* c, float ratio, const int* d_nq0, uvo_dmatch* d_out0, int* d_nout0, const GateArgs& g0,
                                 const int* d_nq1, uvo_dmatch* d_out1, int* d_nout1, const GateArgs& g1, int n_max, int out_cap);
-uvo_status match_two_pairs(Ctx* a, Ctx* b, const float* d_prev_desc, const int* d_prev_n, const int* d_prev_as_n, int curr_a, int curr_b,
-                           float ratio, int min_features);
 uvo_status match_ratio_compact(Ctx* c, const int* d_nq, int nq_max, float ratio, uvo_dmatch* d_out, int* d_nout, int out_cap,
                                const GateArgs* gate = nullptr);
 // pose.hip
 uvo_status pose_triangulate(Ctx* c, const double* P1, const double* P2, const int* d_n, int n_max);
 uvo_status pose_triangulate_extract3d(Ctx* c, int slot, const double* P1, const double* P2, const double* R1, const double* t1,
                                       const double* R2, const double* t2, const double* K1, const double* K2, const int* d_n, int n_max,
-                                      int* counts_host = nullptr,      // counts_host: pinned mirror of d_counts written by the last kernel
-                                      Ctx* c2 = nullptr, int* counts_host2 = nullptr);   // c2: a second lane's pair in the same launches
+                                      int* counts_host = nullptr);     // counts_host: pinned mirror of d_counts written by the last kernel
 // The tail of the stereo loop's stage A in one launch: lane `a` gathers its "after stereo match" set (buffer curr) and triangulates
 // its rows, and runs extract_3Dpoints on the rows of lane p's set (buffer prev) that its triangular matches select (VO:569-579, 631-632).
 uvo_status pose_stereo_tail(Ctx* a, Ctx* p, int prev, int curr, int slot, const double* P1, const double* P2, const double* R1, const double* t1,

@@ -27,6 +27,34 @@ def test_library_exports_every_declared_symbol():
     assert set(_lib.EXPORTS) == set(names)
 
 
+def _defined_dynamic_symbols(path):
+    """Names of the defined symbols of an ELF64 little-endian shared object's .dynsym (what a dlsym can find)."""
+    import struct
+    b = open(path, "rb").read()
+    assert b[:6] == b"\x7fELF\x02\x01", "an ELF64 little-endian file"
+    shoff, = struct.unpack_from("<Q", b, 0x28)
+    shentsize, shnum = struct.unpack_from("<HH", b, 0x3A)
+    sections = [struct.unpack_from("<IIQQQQIIQQ", b, shoff + i * shentsize) for i in range(shnum)]
+    names = set()
+    for sh in sections:
+        if sh[1] != 11:                                   # SHT_DYNSYM
+            continue
+        stroff = sections[sh[6]][4]                       # sh_link: its string table
+        for off in range(sh[4], sh[4] + sh[5], sh[9]):
+            st_name, st_info, _, st_shndx = struct.unpack_from("<IBBH", b, off)
+            if st_shndx != 0 and (st_info >> 4) in (1, 2):    # defined; STB_GLOBAL or STB_WEAK
+                names.add(b[stroff + st_name:b.index(b"\0", stroff + st_name)].decode())
+    return names
+
+
+def test_library_exports_no_undeclared_uvo_symbol():
+    """The converse: every uvo_* symbol the built library exports is declared in include/uvo_hip.h."""
+    from ergo_uvo_amd import _lib
+    _lib.lib()
+    exported = {n for n in _defined_dynamic_symbols(_lib.LIB_PATH) if n.startswith("uvo_")}
+    assert exported == set(_declared_functions()), sorted(exported ^ set(_declared_functions()))
+
+
 def test_pod_layouts_match_opencv_types():
     import ergo_uvo_amd as uvo
     assert uvo.KP_DTYPE.itemsize == 28 and uvo.DM_DTYPE.itemsize == 16          # cv::KeyPoint, cv::DMatch

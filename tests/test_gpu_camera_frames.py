@@ -359,11 +359,9 @@ def test_refusals_name_their_cause_and_leave_the_context_usable(uvo, node_cams, 
 
 # ------------------------------------------------------------------ the two entries of a step share its body and its refusals
 def test_per_call_options_of_a_frames_entry_do_not_live_in_the_context(uvo, node_cams, scene_small):
-    """Two-pair launches on (stereo_set_batch(2)) and a producer stream declared, frames entries and grey entries interleaved, three
-    pairs in flight.  A frames entry goes alone and does not wait for the producer a second time; the grey entries around it still
-    pair up -- pairs 2, 3 and 7, 8 are two consecutive grey pairs right after a frames pair -- and a grey pair that waits for a
-    partner when a frames pair arrives (pair 5) goes alone.  Every result equals the synchronous run of the same sequence on a fresh
-    context with one pair per launch, field for field (the comparison of test_frames_and_grey_entries_mix_in_one_sequence)."""
+    """A producer stream declared, frames entries and grey entries interleaved, three pairs in flight.  A frames entry does not wait
+    for the producer a second time.  Every result equals the synchronous run of the same sequence on a fresh context, field for
+    field (the comparison of test_frames_and_grey_entries_mix_in_one_sequence)."""
     import torch
     _, camL, camR = node_cams
     kinds = "FFGGFGFGG"
@@ -380,7 +378,6 @@ def test_per_call_options_of_a_frames_entry_do_not_live_in_the_context(uvo, node
         assert sum(f[0] for f in want) >= 4, "the compared runs hold too few valid estimates"
         with torch.cuda.stream(producer):                                # the frames entries' inputs are produced on the declared stream
             frames = [None if k == "G" else (torch.from_numpy(_gray3(L)).cuda(), torch.from_numpy(_gray3(R)).cuda()) for k, (L, R) in zip(kinds, seq)]
-        c.stereo_set_batch(2)
         c.set_producer_stream(producer)
         got, sub = [], 0
         for i in range(len(seq)):

@@ -407,6 +407,94 @@ def test_pipelined_submit_collect_equals_step(ctx, scene_small):
     ctx.stereo_set_depth(2)
 
 
+# ---- the pipelined path against the synchronous step over gate failures and every submit / collect order (640 x 360, 4096 keypoints) ----
+def _fields(r):
+    return (r.valid, r.initialized, r.n_left, r.n_right, r.n_stereo_matches, r.n_tri_matches, r.n_good3d, r.n_inliers,
+            tuple(r.rvec), tuple(r.tvec), tuple(r.t_prev_curr), tuple(r.velocity))
+
+
+_WHAT = ("kps_left", "kps_right", "desc_left", "desc_right", "matches_stereo", "matches_tri", "points4d", "good_pts", "good_idx", "inliers")
+
+
+def _snapshot(c):
+    return {w: c.stereo_get(w).copy() for w in _WHAT}
+
+
+def _same(a, b):
+    return all(a[w].shape == b[w].shape and np.array_equal(a[w].view(np.uint8), b[w].view(np.uint8)) for w in _WHAT)
+
+
+@pytest.fixture(scope="module")
+def scene_four(scene_small):
+    from ergo_uvo_amd import synth
+    return list(scene_small) + [synth.stereo_pair(synth.Scene(123, 640), 3, 640, 360)]
+
+
+@pytest.fixture()
+def small_ctx():
+    import ergo_uvo_amd as uvo
+    c = uvo.Context(uvo.Params.stereo(SURF_MIN_HESSIAN=1500), 0, 640, 360, 4096)
+    yield c
+    c.close()
+
+
+def _run_sync(c, rig, seq):
+    c.stereo_set_rig(rig.K_left, rig.K_right, rig.R_right, rig.t_right)
+    out = []
+    for L, R in seq:
+        r = c.stereo_step(L, R, 0.05)
+        out.append((_fields(r), _snapshot(c)))
+    return out
+
+
+def _run_piped(c, rig, seq, depth, burst):
+    """submit up to `burst` pairs ahead (<= depth), collect one, ...: burst 1 keeps one pair in flight."""
+    c.stereo_set_depth(depth)
+    c.stereo_set_rig(rig.K_left, rig.K_right, rig.R_right, rig.t_right)
+    out, sub = [], 0
+    while len(out) < len(seq):
+        while sub < len(seq) and sub - len(out) < burst:
+            c.stereo_submit(*seq[sub]); sub += 1
+        r = c.stereo_collect(0.05)
+        out.append((_fields(r), _snapshot(c)))
+    return out
+
+
+def test_pipelined_pairs_equal_the_synchronous_step_over_gate_failures(small_ctx, scene_four):
+    """Fifteen pairs with gate failures first and second in a row, two blanks in succession, a half-blank pair and an odd tail, over
+    depths and submit / collect orders: result fields equal the synchronous step's, the ten stereo_get arrays bitwise from pair 1 on."""
+    import ergo_uvo_amd as uvo
+    from ergo_uvo_amd import synth
+    rig = synth.stereo_rig(640)
+    blank = (np.full_like(scene_four[0][0], 90), np.full_like(scene_four[0][1], 90))
+    half = (scene_four[1][0], blank[1])                       # features on the left only: VO:556 fails on the right count
+    seq = [scene_four[k] for k in (0, 1, 2, 3, 2)] + [blank, scene_four[1], scene_four[0], half, scene_four[2], blank, blank, scene_four[3], scene_four[2], scene_four[1]]
+    with pytest.raises(uvo.UvoError):
+        small_ctx.stereo_set_batch(2)                         # the two-pair launch path was removed ...
+    small_ctx.stereo_set_batch(1)                             # ... and one pair per launch set is what there is
+    want = _run_sync(small_ctx, rig, seq)
+    assert sum(f[0][0] for f in want) >= 7 and any(f[0][0] == 0 and f[0][1] == 1 for f in want[1:])
+    for depth, burst in ((2, 2), (4, 4), (6, 6), (6, 3), (5, 5), (3, 2), (4, 1), (2, 1)):
+        got = _run_piped(small_ctx, rig, seq, depth, burst)
+        for i, (g, w) in enumerate(zip(got, want)):
+            assert g[0] == w[0], (depth, burst, i, g[0], w[0])
+            if i == 0:
+                continue                         # the init pair ran on lane 0, which the first pipelined pair has taken by the time it is collected
+            assert _same(g[1], w[1]), (depth, burst, i, [k for k in _WHAT if not np.array_equal(g[1][k], w[1][k])])
+
+
+def test_pipelined_pairs_equal_the_synchronous_step_with_oriented_surf(small_ctx, scene_four):
+    """Oriented SURF (not the shipped configuration) through the pipeline at depth 4, four pairs ahead: fields as the synchronous run's."""
+    import ergo_uvo_amd as uvo
+    from ergo_uvo_amd import synth
+    rig = synth.stereo_rig(640)
+    seq = [scene_four[k] for k in (0, 1, 2, 1, 0, 3)]
+    small_ctx.set_params(uvo.Params.stereo(SURF_MIN_HESSIAN=1500, SURF_UPRIGHT=0))
+    want = [f[0] for f in _run_sync(small_ctx, rig, seq)]
+    got = [f[0] for f in _run_piped(small_ctx, rig, seq, 4, 4)]
+    assert got == want
+
+
 def test_failure_paths_through_the_pipeline(ctx, oracle, scene_small):
     """Frames without features in the middle of a sequence: the gate ladder (VO:556/567/626/634/665), the state kept on
     failure and the empty "after stereo match" sets handed to the next pair must behave as in the reference's loop --

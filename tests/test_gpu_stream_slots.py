@@ -19,7 +19,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 W, H, N_PAIRS, N_FRAMES, MIN_HESSIAN = 640, 360, 14, 4, 1500
 CHILD_LIMIT_S = 120                      # a child takes a few seconds; the limit only ends one that hangs
-ENV_KEYS = ("GPU_MAX_HW_QUEUES", "UVO_STAGE_B", "UVO_A_OVERLAP", "UVO_A_OVERLAP2", "UVO_MAX_B", "UVO_A_STREAMS", "UVO_B_STREAMS", "UVO_STREAM_SLOTS", "UVO_BATCH", "UVO_WORKER_WAIT",
+ENV_KEYS = ("GPU_MAX_HW_QUEUES", "UVO_STAGE_B", "UVO_A_OVERLAP", "UVO_MAX_B", "UVO_A_STREAMS", "UVO_B_STREAMS", "UVO_STREAM_SLOTS", "UVO_WORKER_WAIT",
             "UVO_CPU_BUDGET", "UVO_PIPELINE_DEPTH", "UVO_STREAM_POOL", "UVO_STREAM_ORDER", "UVO_PNP_PRIORITY", "UVO_PNP_SPEC", "UVO_HIP_LIB")
 
 
@@ -59,7 +59,7 @@ def _pipelined(ctx, rig, seq, depth):
 
 
 def _child(spec):
-    """spec: {"stage_b": [modes], "depths": [depth of every idle-to-idle sequence, in order], "batch": 1 | 2, "contexts": n}"""
+    """spec: {"stage_b": [modes], "depths": [depth of every idle-to-idle sequence, in order], "contexts": n}"""
     import numpy as np
     import ergo_uvo_amd as uvo
     from ergo_uvo_amd import synth
@@ -74,7 +74,6 @@ def _child(spec):
                 want = _synchronous(ctx, rig, seq)
                 assert sum(r[0] for r in want[0]) >= N_PAIRS // 2, [r[:8] for r in want[0]]      # the sequence is a real one: poses, not gate failures
                 assert all(len(a) == r[7] for a, r in zip(want[1], want[0]))
-            ctx.stereo_set_batch(spec.get("batch", 1))
             for mode in spec["stage_b"]:
                 os.environ["UVO_STAGE_B"] = mode                  # read by the library at every uvo_stereo_set_depth
                 for depth in spec["depths"]:
@@ -100,8 +99,6 @@ CASES += [
     ("4 queues, depth 6 -> 3 -> 6 between idle sequences", {"GPU_MAX_HW_QUEUES": "4"}, {"stage_b": BOTH, "depths": [6, 3, 6]}),
     ("4 queues, a second context after the first was closed", {"GPU_MAX_HW_QUEUES": "4"}, {"stage_b": BOTH, "depths": [6], "contexts": 2}),
     ("4 queues, no stage-A limit (UVO_A_OVERLAP=0)", {"GPU_MAX_HW_QUEUES": "4", "UVO_A_OVERLAP": "0"}, {"stage_b": BOTH, "depths": [6]}),
-    ("4 queues, two-pair launch sets", {"GPU_MAX_HW_QUEUES": "4"}, {"stage_b": ["worker"], "depths": [6, 5], "batch": 2}),
-    ("16 queues, two-pair launch sets", {"GPU_MAX_HW_QUEUES": "16"}, {"stage_b": ["worker"], "depths": [6], "batch": 2}),
 ]
 _stopped = []                            # why no further child is started: an earlier one faulted or ran into its time limit
 

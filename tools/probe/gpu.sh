@@ -7,8 +7,7 @@
 #   bench20 [n] [bench args]    the driver's form n times (--steps 20 --warmup 5 + args, e.g. --no-trace), value + blocks
 #   ab <steps>                  previous build (ergo_uvo_amd/lib_ab/libuvo_hip_old.so) against the current one, interleaved
 #   sweep <steps>               overlap / depth / PnP-slot settings of the one-pair pipeline
-#   batch <steps>               one- and two-pair launch sets over depth / overlap settings
-#   prof <tag> [sync|pipe|batch2]  rocprofv3 --kernel-trace --stats of a synchronous run / the pipelined bench / two-pair launch sets
+#   prof <tag> [sync|pipe]      rocprofv3 --kernel-trace --stats of a synchronous run / the pipelined bench
 #   hess-split <tag>            per-octave detection kernels (UVO_HESSIAN_SPLIT=1) and the merged launch, old build and new
 #   pmc <tag> <kernel pattern> [split]   counter passes (separate --pmc runs: SQ set 1, SQ set 2, FETCH_SIZE, WRITE_SIZE) of a synchronous run
 #   ctx-reuse [pairs]           five contexts in a row, stream pool on and off
@@ -43,15 +42,10 @@ step() {
              LBL=default brun --steps $n --depth 6; UVO_A_OVERLAP=3 LBL="A_OVERLAP=3 depth 6" brun --steps $n --depth 6; UVO_A_OVERLAP=3 LBL="A_OVERLAP=3 depth 8" brun --steps $n --depth 8
              UVO_MAX_B=4 LBL="MAX_B=4" brun --steps $n --depth 6; UVO_MAX_B=2 LBL="MAX_B=2" brun --steps $n --depth 6
              LBL="depth 8" brun --steps $n --depth 8; LBL="depth 7" brun --steps $n --depth 7; LBL=default brun --steps $n --depth 6 ;;
-    batch)   n=${1:-300}
-             LBL="batch 1 depth 6" brun --steps $n --batch 1 --depth 6; LBL="batch 2 depth 6" brun --steps $n --batch 2 --depth 6; LBL="batch 2 depth 8" brun --steps $n --batch 2 --depth 8
-             UVO_A_OVERLAP2=1 LBL="batch 2 depth 6 A_OVERLAP2=1" brun --steps $n --batch 2 --depth 6; UVO_A_OVERLAP2=1 LBL="batch 2 depth 4 A_OVERLAP2=1" brun --steps $n --batch 2 --depth 4
-             LBL="batch 1 depth 6" brun --steps $n --batch 1 --depth 6 ;;
     prof)    t=$1; kind=${2:-sync}
              case $kind in
                sync)   rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_${t}_sync -- python3 tools/prof_stereo.py 24 > gpurun_out/prof_${t}_sync.log 2>&1 || return 1; python tools/probe/kstats.py prof_${t}_sync 26 ;;
                pipe)   rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_${t}_pipe -- python3 bench.py --steps 200 --blocks 1 --timed-only > gpurun_out/prof_${t}_pipe.log 2>&1 || return 1; python tools/probe/kstats.py prof_${t}_pipe 26 ;;
-               batch2) UVO_A_OVERLAP2=1 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_${t}_batch2 -- python3 bench.py --steps 60 --blocks 1 --timed-only --batch 2 > gpurun_out/prof_${t}_batch2.log 2>&1 || return 1; python tools/probe/kstats.py prof_${t}_batch2 26 ;;
              esac ;;
     hess-split) t=$1
              for v in old new; do
