@@ -261,6 +261,33 @@ class Context:
             raise ValueError("orb_set_pattern: 256 x (x0, y0, x1, y1)")
         self._check(self._lib.uvo_orb_set_pattern(self._h, _p(pat)))
 
+    def orb_set_ranking(self, where):
+        """Where ORB's two retainBest rankings per level run: "device" / 1 (k_rb_rank, one launch per ranking) or "host" / 0 (the host
+        replay over downloaded responses).  The results do not depend on it; the fused steps take the master context's value."""
+        where = {"host": 0, "device": 1}.get(where, where)
+        self._check(self._lib.uvo_orb_set_ranking(self._h, int(where)))
+
+    def retain_best(self, responses, keep, where="device", starts=None):
+        """Test hook: KeyPointsFilter::retainBest's order on response segments.  Segment l is responses[starts[l]:starts[l + 1]] (default:
+        one segment, everything) ranked for keep[l]; returns (order, out_start, depth_limit_hits): order[out_start[l]:out_start[l + 1]] holds
+        the positions in `responses` that segment l keeps, in retainBest's order; depth_limit_hits[l] = 1 where introselect's depth limit
+        was reached.  where="device" is the launch orb_detect makes, "host" the host replay."""
+        r = np.ascontiguousarray(responses, np.float32).reshape(-1)
+        st = np.ascontiguousarray([0, r.size] if starts is None else starts, np.int32).reshape(-1)
+        kp = np.ascontiguousarray(keep, np.int32).reshape(-1)
+        nseg = st.size - 1
+        if kp.size != nseg:
+            raise ValueError("retain_best: one keep per segment")
+        if nseg >= 1 and int(st[-1]) > r.size:
+            raise ValueError("retain_best: starts reach past the responses")
+        where = {"host": 0, "device": 1}.get(where, where)
+        cap = max(int(r.size), 1)
+        order = np.empty(cap, np.int32)
+        out_start = np.zeros(max(nseg, 0) + 1, np.int32)
+        hits = np.zeros(max(nseg, 1), np.int32)
+        self._check(self._lib.uvo_retain_best(self._h, _p(r), _p(st), _p(kp), int(nseg), int(where), _p(order), cap, _p(out_start), _p(hits)))
+        return order[:out_start[nseg]].copy(), out_start, hits[:nseg]
+
     def orb_detect(self, img, cap=None, descriptors=True, width=None):
         """detect_features, FEATURE_DETECTOR == "ORB" (VO_utility.cpp:100-105): ORB::create(10000, 1.2, 8, 31, 0, 2, HARRIS_SCORE, 31, 10)
         ->detectAndCompute.  Returns (keypoints, n x 32 uint8 rBRIEF rows) -- rows for match_features_hamming; descriptors need

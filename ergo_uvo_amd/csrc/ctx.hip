@@ -857,6 +857,23 @@ try {
     UVO_TRY(need_idle(c, "uvo_orb_set_pattern"));
     return orb_set_pattern(c, pattern);
 } UVO_ABI_CATCH(c)
+// where both retainBest rankings of every level run: 0 the host replay, 1 k_rb_rank (orb.hip); the master context's value serves the lanes
+extern "C" uvo_status uvo_orb_set_ranking(uvo_ctx* c, int where)
+try {
+    if (!c) return UVO_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    UVO_TRY(need_idle(c, "uvo_orb_set_ranking"));
+    return orb_set_ranking(c, where);
+} UVO_ABI_CATCH(c)
+extern "C" uvo_status uvo_retain_best(uvo_ctx* c, const float* responses, const int* start, const int* keep, int nseg, int where, int* order, int cap,
+                                      int* out_start, int* depth_limit_hits)
+try {
+    if (!c) return UVO_INVALID_ARG;
+    if (!responses || !start || !keep || !order || !out_start || cap < 0) return fail(c, UVO_INVALID_ARG, "uvo_retain_best: responses, start, keep, order and out_start are required");
+    (void)hipSetDevice(c->device);
+    UVO_TRY(need_idle(c, "uvo_retain_best"));
+    return orb_retain_best(c, responses, start, keep, nseg, where, order, cap, out_start, depth_limit_hits);
+} UVO_ABI_CATCH(c)
 extern "C" uvo_status uvo_orb_detect(uvo_ctx* c, const uint8_t* gray, int w, int h, int stride, int mem, uvo_keypoint* kps, uint8_t* desc, int cap, int* n)
 try {
     if (!c || !n || !gray) return UVO_INVALID_ARG;

@@ -18,15 +18,22 @@
 //                      angle, coordinates rounded half to even
 // KeyPointsFilter::retainBest runs twice per level (on the FAST scores for twice the level's share, on the Harris responses for the
 // share).  Its surviving SET is a threshold on the n-th largest response, but the ORDER it leaves -- which is the order of the output
-// keypoints -- is that of libstdc++'s std::nth_element + std::partition, a sequential algorithm: the host replays it on the response
-// arrays (4 bytes per keypoint down, 4 bytes per survivor up; the images never leave the device), like the RANSAC scans of the pose
-// stages.
+// keypoints -- is that of libstdc++'s std::nth_element + std::partition, a sequential algorithm stated pass by pass:
+//   k_rb_rank          both rankings, one launch each for all levels (uvo_orb_set_ranking 1, the default): introselect's Hoare passes
+//                      as stopper lists + independent swaps + a closed-form cut (uvo_retain_best_dev.h), the tail partition likewise
+// or, with uvo_orb_set_ranking 0, the host replays it on the response arrays (uvo_retain_best.h: 4 bytes per keypoint down, 4 bytes per
+// survivor up; the images never leave the device), like the RANSAC scans of the pose stages.
 // THE SAMPLING TABLE IS AN INPUT (uvo_orb_set_pattern): OpenCV's bit_pattern_31_ (1024 integers learned offline) cannot be restated
 // and the reference holds no copy; without a table the detector returns keypoints and refuses descriptors.
 #include "uvo_ctx.h"
 #include "uvo_math.h"
+#define UVO_RB_TRACE           // the header counts rb_heap_select's calls: uvo_retain_best reports them (depth_limit_hits)
 #include "uvo_retain_best.h"   // RbItem, retain_best_order: the host replay of KeyPointsFilter::retainBest's order
+#include "uvo_retain_best_dev.h"   // the arithmetic of k_rb_rank, the same order on the device
+#include <limits.h>
 #include <float.h>
+#include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 #include <math.h>
 #include <vector>
@@ -42,6 +49,9 @@ struct OrbLevels {                                                  // by value 
     float scale[kOrbMaxLevels];
 };
 struct OrbPrefix { int n; int start[kOrbMaxLevels + 1]; };          // list positions at which each level's keypoints start
+static const int kOrbRankDefault = 1;                               // device: profiles/orb_device_rank.json
+// d_rank, in ints: k_rb_rank's ticket, counts and flags; the Harris list's OrbPrefix (n, start[17]); the final list's starts; both rankings' flags
+enum { RK_META = 0, RK_P1 = 48, RK_P2 = 68, RK_HIT1 = 88, RK_HIT2 = 104, RK_BACK_END = 120, RK_INTS = 128 };
 struct OrbWs {
     OrbParams p;
     bool has_pattern = false;
@@ -60,7 +70,19 @@ struct OrbWs {
     uvo_keypoint* d_kps = nullptr; uint8_t* d_desc = nullptr;
     int* h_int = nullptr; float* h_f = nullptr;                     // pinned
     std::vector<int> fin;                                           // host: the final ranking (source of an asynchronous copy: kept until the next call)
+    // uvo_orb_set_ranking: 1 = both retainBest rankings by k_rb_rank, 0 = by the host replay (the master context's value serves every lane)
+    int rank_dev = kOrbRankDefault;
+    RbdItem* d_items = nullptr; int* d_la = nullptr; int* d_lb = nullptr;      // k_rb_rank's items and stopper lists, fast_cap each
+    int* d_rank = nullptr;                                          // RK_INTS words: k_rb_rank's own, then what it leaves (level starts, depth-limit flags)
+    long depth_limit_hits = 0;                                      // segments that reached introselect's depth limit on the device, since the context was made
 };
+static int orb_rank_from_env()                                      // UVO_ORB_RANK=host|device: the initial setting, for measurements (tools/probe/README.md)
+{
+    const char* e = getenv("UVO_ORB_RANK");
+    if (e && strcmp(e, "host") == 0) return 0;
+    if (e && strcmp(e, "device") == 0) return 1;
+    return kOrbRankDefault;
+}
 static const char* const kOrbNoTable = "uvo_orb_detect: descriptors need the sampling table -- OpenCV's bit_pattern_31_ (orb.cpp), 256 x (x0, y0, x1, y1) -- through uvo_orb_set_pattern; pass desc = NULL for keypoints only";
 const char* const kOrbLoopNoTable = "ORB in the fused steps: the descriptors need the sampling table -- OpenCV's bit_pattern_31_ (orb.cpp), 256 x (x0, y0, x1, y1) -- through uvo_orb_set_pattern";
 
@@ -166,10 +188,8 @@ __global__ __launch_bounds__(1024) void k_orb_row_scan(const int* __restrict__ c
 __device__ __forceinline__ int orb_level_of(const OrbPrefix& P, int j) { int l = 0; while (l + 1 < P.n && j >= P.start[l + 1]) l++; return l; }
 
 // HarrisResponses(pyramid, layers, keypoints, 7, 0.04f) for list entry j (the FAST keypoint sel[j])
-__global__ __launch_bounds__(256) void k_orb_harris(OrbLevels L, OrbPrefix P, const int* __restrict__ sel, int n, const uint32_t* __restrict__ pos, float* __restrict__ resp)
+__device__ __forceinline__ void orb_harris_at(const OrbLevels& L, const OrbPrefix& P, const int* __restrict__ sel, const uint32_t* __restrict__ pos, float* __restrict__ resp, int j)
 {
-    const int j = blockIdx.x * 256 + threadIdx.x;
-    if (j >= n) return;
     const int l = orb_level_of(P, j), step = L.stride[l];
     const uint32_t pp = pos[sel[j]];
     const uint8_t* c0 = L.img[l] + (size_t)(pp >> 16) * step + (pp & 0xffffu);
@@ -187,6 +207,20 @@ __global__ __launch_bounds__(256) void k_orb_harris(OrbLevels L, OrbPrefix P, co
     const float scale_sq_sq = scale * scale * scale * scale;
     resp[j] = ((float)a * (float)b - (float)c * (float)c - 0.04f * ((float)a + (float)b) * ((float)a + (float)b)) * scale_sq_sq;
 }
+__global__ __launch_bounds__(256) void k_orb_harris(OrbLevels L, OrbPrefix P, const int* __restrict__ sel, int n, const uint32_t* __restrict__ pos, float* __restrict__ resp)
+{
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= n) return;
+    orb_harris_at(L, P, sel, pos, resp, j);
+}
+// the same with the list's level starts where k_rb_rank left them (device ranking): the grid covers an upper bound of the list
+__global__ __launch_bounds__(256) void k_orb_harris_dev(OrbLevels L, const OrbPrefix* __restrict__ Pd, const int* __restrict__ sel, const uint32_t* __restrict__ pos, float* __restrict__ resp)
+{
+    const OrbPrefix P = *Pd;
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= P.start[P.n]) return;
+    orb_harris_at(L, P, sel, pos, resp, j);
+}
 
 __device__ __forceinline__ float orb_atan2_deg(float y, float x)     // cv::fastAtan2 (as surf.hip's fast_atan2_deg)
 {
@@ -203,11 +237,9 @@ __device__ __forceinline__ float orb_atan2_deg(float y, float x)     // cv::fast
 struct OrbUmax { int u[40]; };
 // The final keypoints: entry i is Harris-list entry fin[i]; ICAngles over the disc of half_k (32 lanes per keypoint, lane = column),
 // pt *= the level's scale, size = patchSize * scale, octave = the level.
-__global__ __launch_bounds__(256) void k_orb_keypoints(OrbLevels L, OrbPrefix P, OrbUmax um, int half_k, int patch, const int* __restrict__ fin, int n,
-                                                       const int* __restrict__ sel, const uint32_t* __restrict__ pos, const float* __restrict__ resp, uvo_keypoint* __restrict__ kps)
+__device__ __forceinline__ void orb_keypoint_at(const OrbLevels& L, const OrbPrefix& P, const OrbUmax& um, int half_k, int patch, const int* __restrict__ fin, int i, int lane,
+                                                const int* __restrict__ sel, const uint32_t* __restrict__ pos, const float* __restrict__ resp, uvo_keypoint* __restrict__ kps)
 {
-    const int i = blockIdx.x * 8 + (threadIdx.x >> 5), lane = threadIdx.x & 31;
-    if (i >= n) return;                                             // (a whole 32-lane group leaves together)
     const int j = fin[i], l = orb_level_of(P, j), step = L.stride[l];
     const uint32_t pp = pos[sel[j]];
     const int px = (int)(pp & 0xffffu), py = (int)(pp >> 16);
@@ -233,6 +265,21 @@ __global__ __launch_bounds__(256) void k_orb_keypoints(OrbLevels L, OrbPrefix P,
         k.octave = l; k.class_id = -1;
         kps[i] = k;
     }
+}
+__global__ __launch_bounds__(256) void k_orb_keypoints(OrbLevels L, OrbPrefix P, OrbUmax um, int half_k, int patch, const int* __restrict__ fin, int n,
+                                                       const int* __restrict__ sel, const uint32_t* __restrict__ pos, const float* __restrict__ resp, uvo_keypoint* __restrict__ kps)
+{
+    const int i = blockIdx.x * 8 + (threadIdx.x >> 5), lane = threadIdx.x & 31;
+    if (i >= n) return;                                             // (a whole 32-lane group leaves together)
+    orb_keypoint_at(L, P, um, half_k, patch, fin, i, lane, sel, pos, resp, kps);
+}
+__global__ __launch_bounds__(256) void k_orb_keypoints_dev(OrbLevels L, const OrbPrefix* __restrict__ Pd, OrbUmax um, int half_k, int patch, const int* __restrict__ fin, int n,
+                                                           const int* __restrict__ sel, const uint32_t* __restrict__ pos, const float* __restrict__ resp, uvo_keypoint* __restrict__ kps)
+{
+    const OrbPrefix P = *Pd;                                        // the Harris list's level starts, left on the device by the first ranking
+    const int i = blockIdx.x * 8 + (threadIdx.x >> 5), lane = threadIdx.x & 31;
+    if (i >= n) return;
+    orb_keypoint_at(L, P, um, half_k, patch, fin, i, lane, sel, pos, resp, kps);
 }
 
 struct OrbTaps { int k[7]; };
@@ -300,6 +347,119 @@ __global__ __launch_bounds__(256) void k_orb_describe(OrbLevels L, const int8_t*
     desc[(size_t)i * kOrbDescBytes + lane] = (uint8_t)val;
 }
 
+// ------------------------------------------------------------------------------------------------ retainBest on the device
+// k_rb_rank: KeyPointsFilter::retainBest's ORDER (uvo_retain_best.h; arithmetic and proof: uvo_retain_best_dev.h) for up to 16 segments in
+// one launch, one workgroup of 16 waves per segment: segment l ranks resp[start[l] .. start[l + 1]) for keep.k[l] and leaves the old
+// positions (global: start[l] + index) of what retainBest keeps, in its order, compacted at order[out_start[l] ..).  Every introselect
+// round is one pass over the (response, index) items in memory: each wave lists the stoppers of its share of the range (ballots), the
+// k-th swap pairs the k-th left stopper with the k-th right stopper from the right, and the cut is a closed form.  The median of
+// three, the insertion sort of the last three items and -- past the depth limit, which natural images do not reach -- heap select are
+// one lane's.  The workgroup that finishes last (one agent-scope release per workgroup, one ticket, one acquire) sums the counts and
+// gathers every segment's order.
+struct RbKeep { int k[kOrbMaxLevels]; };
+struct RbShared { int cntL[kRbdWaves], cntR[kRbdWaves], prefL[kRbdWaves + 1], prefR[kRbdWaves + 1]; int K, last; };
+enum { RB_TICKET = 0, RB_COUNT = 4, RB_HIT = 4 + kOrbMaxLevels, RB_META_INTS = 4 + 2 * kOrbMaxLevels };   // the launch's own words (ticket zeroed before every launch)
+
+template <int MODE>
+__device__ __forceinline__ int rb_pass(RbdItem* v, int* A, int* B, int lo, int hi, float pv, RbShared& sh)
+{
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int chunk = rbd_chunk(hi - lo), b = lo + wave * chunk, e = min(b + chunk, hi);
+    const unsigned long long below = (1ull << lane) - 1ull;
+    int nl = 0, nr = 0;
+    for (int p0 = b; p0 < e; p0 += kRbdLanes) {
+        const int p = p0 + lane;
+        bool sl = false, sr = false;
+        if (p < e) { const float x = v[p].r; sl = rbd_left_stop<MODE>(x, pv); sr = rbd_right_stop<MODE>(x, pv); }
+        const unsigned long long bl = __ballot(sl), br = __ballot(sr);
+        if (sl) A[b + nl + __popcll(bl & below)] = p;                // (rank < the wave's count <= e - b: inside the wave's own share)
+        if (sr) B[b + nr + __popcll(br & below)] = p;
+        nl += __popcll(bl); nr += __popcll(br);
+    }
+    if (lane == 0) { sh.cntL[wave] = nl; sh.cntR[wave] = nr; }
+    __syncthreads();
+    if (tid == 0) {
+        int l = 0, r = 0;
+        for (int w = 0; w < kRbdWaves; w++) { sh.prefL[w] = l; sh.prefR[w] = r; l += sh.cntL[w]; r += sh.cntR[w]; }
+        sh.prefL[kRbdWaves] = l; sh.prefR[kRbdWaves] = r; sh.K = 0;
+    }
+    __syncthreads();
+    const int totL = sh.prefL[kRbdWaves], totR = sh.prefR[kRbdWaves], kmax = min(totL, totR);
+    int mine = 0;
+    for (int k = tid; k < kmax; k += kRbdThreads) {
+        const int pa = A[rbd_list_at(lo, chunk, sh.prefL, k)], pb = B[rbd_list_at(lo, chunk, sh.prefR, totR - 1 - k)];
+        if (pa < pb) { const RbdItem x = v[pa], y = v[pb]; v[pa] = y; v[pb] = x; mine++; }
+    }
+    if (MODE == 1) { __syncthreads(); return totR; }
+    if (mine) atomicAdd(&sh.K, mine);
+    __syncthreads();
+    const int K = sh.K;
+    const bool has_a = K < totL, has_b = K > 0;
+    const int a_K = has_a ? A[rbd_list_at(lo, chunk, sh.prefL, K)] : INT_MAX, b_Km1 = has_b ? B[rbd_list_at(lo, chunk, sh.prefR, totR - K)] : hi;
+    __syncthreads();                                                 // (sh is the next pass's)
+    return rbd_cut(has_a, a_K, has_b, b_Km1, hi);
+}
+
+__global__ __launch_bounds__(1024) void k_rb_rank(const float* __restrict__ resp, const int* __restrict__ start, RbKeep keep, int nseg, RbdItem* items, int* la, int* lb,
+                                                  int* meta, int* order, int cap, int* out_start, int* hits)
+{
+    __shared__ RbShared sh;
+    const int seg = blockIdx.x, tid = threadIdx.x;
+    const int s0 = start[seg], n = start[seg + 1] - s0, kp = keep.k[seg];
+    RbdItem* v = items + s0;
+    for (int q = tid; q < n; q += kRbdThreads) { RbdItem x; x.r = resp[s0 + q]; x.i = q; v[q] = x; }
+    int count = n, hit = 0;
+    if (n > kp && kp == 0) count = 0;
+    else if (n > kp) {
+        int* A = la + s0; int* B = lb + s0;
+        __syncthreads();
+        int first = 0, last = n, depth = rbd_depth(n);
+        const int nth = kp - 1;
+        while (last - first > 3) {
+            if (depth == 0) { hit = 1; break; }
+            --depth;
+            if (tid == 0) {
+                const int at0 = first + 1, at1 = first + (last - first) / 2, at2 = last - 1;
+                const int pick = rbd_median_pick(v[at0].r, v[at1].r, v[at2].r);
+                rbd_swap(v + first, v + (pick == 0 ? at0 : pick == 1 ? at1 : at2));
+            }
+            __syncthreads();
+            const int cut = rb_pass<0>(v, A, B, first + 1, last, v[first].r, sh);
+            if (rbd_take_right(cut, nth)) first = cut; else last = cut;
+        }
+        if (tid == 0) {
+            if (hit) { rbd_heap_select(v + first, v + nth + 1, v + last); rbd_swap(v + first, v + nth); }
+            else rbd_insertion(v + first, v + last);
+        }
+        __syncthreads();
+        count = kp + rb_pass<1>(v, A, B, kp, n, v[nth].r, sh);
+    }
+    // ---- publish this segment; the last workgroup to arrive gathers all of them ----
+    if (tid == 0) {
+        __hip_atomic_store(meta + RB_COUNT + seg, count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(meta + RB_HIT + seg, hit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                 // every storing wave, before the barrier
+    __syncthreads();
+    if (tid == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // (the write-back has landed before the ticket is drawn)
+        const int ticket = __hip_atomic_fetch_add(meta + RB_TICKET, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        sh.last = ticket == nseg - 1;
+        if (sh.last) { __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+    }
+    __syncthreads();
+    if (!sh.last) return;
+    int run = 0;
+    for (int l = 0; l < nseg; l++) {
+        const int c = __hip_atomic_load(meta + RB_COUNT + l, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), sl = start[l];
+        if (tid == 0) { out_start[l] = run; hits[l] = __hip_atomic_load(meta + RB_HIT + l, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+        if (run + c <= cap) for (int q = tid; q < c; q += kRbdThreads) order[run + q] = sl + items[sl + q].i;    // (past cap: the host reads out_start and refuses)
+        run += c;
+    }
+    if (tid == 0) out_start[nseg] = run;
+}
+
 // ------------------------------------------------------------------------------------------------ host
 namespace {
 // resize.cpp interpolationLinear<uint8_t>::getCoeffs over one axis: source offset and the 8.8 weight of the right / lower neighbour.  An
@@ -324,6 +484,8 @@ static void orb_free_sized(OrbWs* s)
 {
     (void)hipFree(s->d_pix); (void)hipFree(s->d_tab); (void)hipFree(s->d_rows); (void)hipFree(s->d_pos); (void)hipFree(s->d_score); (void)hipFree(s->d_sel);
     (void)hipFree(s->d_resp); (void)hipFree(s->d_fin); (void)hipFree(s->d_kps); (void)hipFree(s->d_desc); (void)hipHostFree(s->h_int); (void)hipHostFree(s->h_f);
+    (void)hipFree(s->d_items); (void)hipFree(s->d_la); (void)hipFree(s->d_lb); (void)hipFree(s->d_rank);
+    s->d_items = nullptr; s->d_la = nullptr; s->d_lb = nullptr; s->d_rank = nullptr;
     s->d_pix = nullptr; s->d_tab = nullptr; s->d_rows = nullptr; s->d_pos = nullptr; s->d_score = nullptr; s->d_sel = nullptr; s->d_resp = nullptr; s->d_fin = nullptr;
     s->d_kps = nullptr; s->d_desc = nullptr; s->h_int = nullptr; s->h_f = nullptr;
     s->w = s->h = 0;
@@ -339,7 +501,7 @@ void orb_ws_free(Ctx* c)
 }
 static OrbWs* orb_state(Ctx* c)
 {
-    if (!c->orb_ws) c->orb_ws = new OrbWs();
+    if (!c->orb_ws) { c->orb_ws = new OrbWs(); static_cast<OrbWs*>(c->orb_ws)->rank_dev = orb_rank_from_env(); }
     return static_cast<OrbWs*>(c->orb_ws);
 }
 // ORB_Impl::detectAndCompute's level geometry and computeKeyPoints' shares (orb.cpp), tables and buffers for one image size
@@ -401,7 +563,16 @@ static uvo_status orb_plan(Ctx* c, OrbWs* s, int w, int h)
          hipMalloc(reinterpret_cast<void**>(&s->d_kps), sizeof(uvo_keypoint) * (size_t)s->cap) == hipSuccess &&
          hipMalloc(reinterpret_cast<void**>(&s->d_desc), (size_t)kOrbDescBytes * s->cap) == hipSuccess &&
          hipHostMalloc(reinterpret_cast<void**>(&s->h_int), sizeof(int) * ((size_t)s->fast_cap + 64)) == hipSuccess &&
-         hipHostMalloc(reinterpret_cast<void**>(&s->h_f), sizeof(float) * (size_t)s->fast_cap) == hipSuccess;
+         hipHostMalloc(reinterpret_cast<void**>(&s->h_f), sizeof(float) * (size_t)s->fast_cap) == hipSuccess &&
+         hipMalloc(reinterpret_cast<void**>(&s->d_items), sizeof(RbdItem) * (size_t)s->fast_cap) == hipSuccess &&
+         hipMalloc(reinterpret_cast<void**>(&s->d_la), sizeof(int) * (size_t)s->fast_cap) == hipSuccess &&
+         hipMalloc(reinterpret_cast<void**>(&s->d_lb), sizeof(int) * (size_t)s->fast_cap) == hipSuccess &&
+         hipMalloc(reinterpret_cast<void**>(&s->d_rank), sizeof(int) * RK_INTS) == hipSuccess;
+    if (ok) {
+        int init[RK_INTS] = {0};
+        init[RK_P1] = L.n;                                           // OrbPrefix::n of the Harris list; k_rb_rank writes its starts
+        ok = hipMemcpy(s->d_rank, init, sizeof(init), hipMemcpyHostToDevice) == hipSuccess;
+    }
     if (ok && !tab.empty()) ok = hipMemcpy(s->d_tab, tab.data(), sizeof(uint16_t) * tab.size(), hipMemcpyHostToDevice) == hipSuccess;
     if (!ok) { orb_free_sized(s); c->err = "ORB workspace allocation failed"; return UVO_HIP_ERROR; }
     uint8_t* q = s->d_pix;
@@ -443,7 +614,67 @@ uvo_status orb_set_pattern(Ctx* c, const int* pattern)
 // detectAndCompute on `gray` (device or host) with workspace s (planned for w x h) and the sampling table `pattern` (device; null: keypoints
 // only): the keypoints and their rows are left in s->d_kps / s->d_desc, *n_out = the count; when it exceeds the list's capacity nothing
 // past the host ranking is computed and the call still returns UVO_OK
-static uvo_status orb_run(Ctx* c, OrbWs* s, hipStream_t st, const uint8_t* gray, int w, int h, int stride, int mem, const int8_t* pattern, int* n_out)
+static OrbTaps orb_blur_taps()
+{
+    OrbTaps kk;
+    // getGaussianKernel(7, 2, CV_32F) x 2^8 rounded: the 8-bit filter engine's integer taps
+    double t[7], sum = 0;
+    for (int i = 0; i < 7; i++) { const double x = i - 3; t[i] = exp(-0.5 / (2.0 * 2.0) * x * x); sum += t[i]; }
+    for (int i = 0; i < 7; i++) kk.k[i] = cv_round_f((float)(t[i] * (1. / sum)) * 256.f);
+    return kk;
+}
+// one launch of k_rb_rank on stream st: segment l = resp[start[l] .. start[l + 1]) (start on the device), keep[l] on the host
+static uvo_status rb_launch(Ctx* c, hipStream_t st, const float* resp, const int* d_start, const int* keep, int nseg, RbdItem* items, int* la, int* lb, int* meta,
+                            int* order, int cap, int* out_start, int* hits)
+{
+    RbKeep K; memset(&K, 0, sizeof(K));
+    for (int l = 0; l < nseg; l++) K.k[l] = keep[l];
+    UVO_HIP_TRY(c, hipMemsetAsync(meta, 0, 16, st));                 // the ticket's block
+    hipLaunchKernelGGL(k_rb_rank, dim3(nseg), dim3(kRbdThreads), 0, st, resp, d_start, K, nseg, items, la, lb, meta, order, cap, out_start, hits);
+    return UVO_OK;
+}
+// orb_run from the FAST corners' level starts on, with both rankings on the device: nothing that grows with the number of corners
+// crosses to the host; the level starts and the depth-limit flags (RK_P1 .. RK_BACK_END, 288 bytes) come back once, for the grid sizes
+static uvo_status orb_run_device(Ctx* c, OrbWs* s, hipStream_t st, const OrbLevels& L, int n_fast, const int8_t* pattern, int* n_out)
+{
+    const OrbParams& p = s->p;
+    if (n_fast == 0) return UVO_OK;
+    const int margin = std::max(p.edgeThreshold, 3), R = s->total_rows;
+    int* d_cnt = s->d_rows; int* d_off = s->d_rows + R; int* d_lvl = s->d_rows + 2 * R + 1;
+    int* rk = s->d_rank;
+    OrbPrefix* d_P1 = reinterpret_cast<OrbPrefix*>(rk + RK_P1);
+    hipLaunchKernelGGL(k_orb_nms_rows<true>, dim3((R + 3) / 4), dim3(256), 0, st, L, margin, d_cnt, d_off, s->d_pos, s->d_score);
+    int keep[kOrbMaxLevels];
+    // retainBest(keypoints, 2 * featuresNum) on the FAST scores, every level in one launch: d_sel and the Harris list's starts
+    for (int l = 0; l < L.n; l++) keep[l] = 2 * s->want[l];
+    UVO_TRY(rb_launch(c, st, s->d_score, d_lvl, keep, L.n, s->d_items, s->d_la, s->d_lb, rk + RK_META, s->d_sel, s->fast_cap, d_P1->start, rk + RK_HIT1));
+    hipLaunchKernelGGL(k_orb_harris_dev, dim3((n_fast + 255) / 256), dim3(256), 0, st, L, d_P1, s->d_sel, s->d_pos, s->d_resp);      // (the list is no longer than n_fast)
+    // retainBest(keypoints, featuresNum) on the Harris responses: d_fin and the final list's starts
+    for (int l = 0; l < L.n; l++) keep[l] = s->want[l];
+    UVO_TRY(rb_launch(c, st, s->d_resp, d_P1->start, keep, L.n, s->d_items, s->d_la, s->d_lb, rk + RK_META, s->d_fin, s->fast_cap, rk + RK_P2, rk + RK_HIT2));
+    UVO_HIP_TRY(c, hipMemcpyAsync(s->h_int, rk + RK_P1, sizeof(int) * (RK_BACK_END - RK_P1), hipMemcpyDeviceToHost, st));
+    if (pattern) {                                                  // (the blurred levels do not wait for the rankings)
+        const OrbTaps kk = orb_blur_taps();
+        for (int l = 0; l < L.n; l++)
+            hipLaunchKernelGGL(k_orb_blur, dim3((L.w[l] + 63) / 64, (L.h[l] + 15) / 16), dim3(256), 0, st, L.img[l], L.w[l], L.h[l], L.stride[l], kk, L.blur[l]);
+    }
+    UVO_HIP_TRY(c, hipStreamSynchronize(st));
+    UVO_HIP_TRY(c, hipGetLastError());
+    const int* back = s->h_int;
+    for (int l = 0; l < L.n; l++) s->depth_limit_hits += back[RK_HIT1 - RK_P1 + l] + back[RK_HIT2 - RK_P1 + l];
+    const int n = back[RK_P2 - RK_P1 + L.n];
+    *n_out = n;
+    static const bool dbg = getenv("UVO_DBG_PHASE") != nullptr;      // (as AKAZE's host-clock phases: tools/probe/README.md)
+    if (dbg) fprintf(stderr, "orb: %d FAST corners, %d after the first ranking, %d keypoints; %ld ranking segments past the depth limit so far\n", n_fast, back[1 + L.n], n, s->depth_limit_hits);
+    if (n > s->cap || n == 0) return UVO_OK;
+    OrbUmax um; memcpy(um.u, s->umax, sizeof(um.u));
+    hipLaunchKernelGGL(k_orb_keypoints_dev, dim3((n + 7) / 8), dim3(256), 0, st, L, d_P1, um, p.patchSize / 2, p.patchSize, s->d_fin, n, s->d_sel, s->d_pos, s->d_resp, s->d_kps);
+    if (pattern) hipLaunchKernelGGL(k_orb_describe, dim3((n + 7) / 8), dim3(256), 0, st, L, pattern, s->d_kps, n, s->d_desc);
+    UVO_HIP_TRY(c, hipGetLastError());
+    return UVO_OK;
+}
+
+static uvo_status orb_run(Ctx* c, OrbWs* s, hipStream_t st, const uint8_t* gray, int w, int h, int stride, int mem, const int8_t* pattern, int rank_dev, int* n_out)
 {
     *n_out = 0;
     OrbLevels L = s->L;
@@ -469,6 +700,7 @@ static uvo_status orb_run(Ctx* c, OrbWs* s, hipStream_t st, const uint8_t* gray,
     memcpy(lvl, s->h_int, sizeof(int) * (L.n + 1));
     const int n_fast = lvl[L.n];
     if (n_fast > s->fast_cap) { c->err = "ORB: more FAST corners than the list holds"; return UVO_CAPACITY; }
+    if (rank_dev) return orb_run_device(c, s, st, L, n_fast, pattern, n_out);
     std::vector<int> sel;
     OrbPrefix P1; memset(&P1, 0, sizeof(P1)); P1.n = L.n;
     std::vector<RbItem> tmp;
@@ -500,12 +732,7 @@ static uvo_status orb_run(Ctx* c, OrbWs* s, hipStream_t st, const uint8_t* gray,
     UVO_HIP_TRY(c, hipMemcpyAsync(s->d_fin, fin.data(), sizeof(int) * n, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_orb_keypoints, dim3((n + 7) / 8), dim3(256), 0, st, L, P1, um, p.patchSize / 2, p.patchSize, s->d_fin, n, s->d_sel, s->d_pos, s->d_resp, s->d_kps);
     if (pattern) {
-        OrbTaps kk;
-        {   // getGaussianKernel(7, 2, CV_32F) x 2^8 rounded: the 8-bit filter engine's integer taps
-            double t[7], sum = 0;
-            for (int i = 0; i < 7; i++) { const double x = i - 3; t[i] = exp(-0.5 / (2.0 * 2.0) * x * x); sum += t[i]; }
-            for (int i = 0; i < 7; i++) kk.k[i] = cv_round_f((float)(t[i] * (1. / sum)) * 256.f);
-        }
+        const OrbTaps kk = orb_blur_taps();
         for (int l = 0; l < L.n; l++)
             hipLaunchKernelGGL(k_orb_blur, dim3((L.w[l] + 63) / 64, (L.h[l] + 15) / 16), dim3(256), 0, st, L.img[l], L.w[l], L.h[l], L.stride[l], kk, L.blur[l]);
         hipLaunchKernelGGL(k_orb_describe, dim3((n + 7) / 8), dim3(256), 0, st, L, pattern, s->d_kps, n, s->d_desc);
@@ -522,7 +749,7 @@ uvo_status orb_detect(Ctx* c, const uint8_t* gray, int w, int h, int stride, int
     if (desc && !s->has_pattern) { c->err = kOrbNoTable; return UVO_INVALID_ARG; }
     UVO_TRY(orb_plan(c, s, w, h));
     hipStream_t st = c->stream;
-    UVO_TRY(orb_run(c, s, st, gray, w, h, stride, mem, desc ? s->d_pattern : nullptr, n_out));
+    UVO_TRY(orb_run(c, s, st, gray, w, h, stride, mem, desc ? s->d_pattern : nullptr, s->rank_dev, n_out));
     const int n = *n_out;
     if (n > s->cap) { c->err = "ORB: more keypoints tie at the per-level cuts than the output list has room for"; return UVO_CAPACITY; }
     if ((kps || desc) && n > cap) { c->err = "uvo_orb_detect: output capacity too small"; return UVO_CAPACITY; }
@@ -557,7 +784,7 @@ uvo_status orb_detect_lane(Ctx* c, int slot, int* n)
     UVO_TRY(orb_prepare_lane(c, w, h));                                       // (a no-op once the lane is primed)
     OrbWs* s = static_cast<OrbWs*>(c->orb_ws);
     const OrbWs* ms = static_cast<const OrbWs*>(c->sh->lanes[0]->orb_ws);
-    UVO_TRY(orb_run(c, s, c->stream, c->img[slot], w, h, w, UVO_MEM_DEVICE, ms->d_pattern, n));
+    UVO_TRY(orb_run(c, s, c->stream, c->img[slot], w, h, w, UVO_MEM_DEVICE, ms->d_pattern, ms->rank_dev, n));
     if (*n > c->cap || *n == 0) return UVO_OK;
     UVO_HIP_TRY(c, hipMemcpyAsync(c->det[slot].kps, s->d_kps, sizeof(uvo_keypoint) * (size_t)*n, hipMemcpyDeviceToDevice, c->stream));
     return pad_binary_rows(c, c->stream, s->d_desc, *n, kOrbDescBytes, reinterpret_cast<uint8_t*>(c->det[slot].desc));
@@ -574,6 +801,63 @@ uvo_status orb_level_plane(Ctx* c, int level, int what, uint8_t* out, int cap_by
     if ((size_t)cap_bytes < n) { c->err = "uvo_orb_plane: output capacity too small"; return UVO_CAPACITY; }
     const uint8_t* src = what == 0 ? s->L.img[level] : what == 1 ? s->L.blur[level] : s->L.score[level];
     UVO_HIP_TRY(c, hipMemcpy(out, src, n, hipMemcpyDeviceToHost));
+    return UVO_OK;
+}
+
+
+uvo_status orb_set_ranking(Ctx* c, int where)
+{
+    if (where != 0 && where != 1) { c->err = "uvo_orb_set_ranking: 0 (the host replays retainBest's order) or 1 (k_rb_rank on the device)"; return UVO_INVALID_ARG; }
+    orb_state(c)->rank_dev = where;
+    return UVO_OK;
+}
+// the test hook behind uvo_retain_best: host buffers in and out; where = 1 is the launch orb_run_device makes
+uvo_status orb_retain_best(Ctx* c, const float* responses, const int* start, const int* keep, int nseg, int where, int* order, int cap, int* out_start, int* hits)
+{
+    if (nseg < 1 || nseg > kOrbMaxLevels) { c->err = "uvo_retain_best: 1 .. 16 segments"; return UVO_INVALID_ARG; }
+    if (where != 0 && where != 1) { c->err = "uvo_retain_best: where = 0 (host) or 1 (device)"; return UVO_INVALID_ARG; }
+    if (start[0] < 0) { c->err = "uvo_retain_best: start[0] is negative"; return UVO_INVALID_ARG; }
+    for (int l = 0; l < nseg; l++) {
+        if (start[l + 1] < start[l]) { c->err = "uvo_retain_best: start decreases"; return UVO_INVALID_ARG; }
+        if (keep[l] < 0) { c->err = "uvo_retain_best: a negative keep"; return UVO_INVALID_ARG; }
+    }
+    const int total = start[nseg];
+    int hit[kOrbMaxLevels] = {0};
+    if (where == 0) {
+        std::vector<int> out;
+        std::vector<RbItem> tmp;
+        for (int l = 0; l < nseg; l++) {
+            out_start[l] = (int)out.size();
+            const long before = rb_heap_select_calls;
+            retain_best_order(responses + start[l], start[l + 1] - start[l], keep[l], start[l], &tmp, &out);
+            hit[l] = (int)(rb_heap_select_calls - before);
+        }
+        out_start[nseg] = (int)out.size();
+        if ((int)out.size() > cap) { c->err = "uvo_retain_best: output capacity too small"; return UVO_CAPACITY; }
+        if (!out.empty()) memcpy(order, out.data(), sizeof(int) * out.size());
+    } else {
+        const size_t nn = (size_t)std::max(total, 1), ncap = (size_t)std::max(cap, 1);
+        float* d_r = nullptr; RbdItem* d_items = nullptr; int *d_la = nullptr, *d_lb = nullptr, *d_order = nullptr, *d_w = nullptr;
+        enum { W_META = 0, W_START = 48, W_OUT = 68, W_HIT = 88, W_INTS = 104 };
+        int hw[W_INTS] = {0};
+        memcpy(hw + W_START, start, sizeof(int) * (nseg + 1));
+        bool ok = hipMalloc(reinterpret_cast<void**>(&d_r), sizeof(float) * nn) == hipSuccess && hipMalloc(reinterpret_cast<void**>(&d_items), sizeof(RbdItem) * nn) == hipSuccess &&
+                  hipMalloc(reinterpret_cast<void**>(&d_la), sizeof(int) * nn) == hipSuccess && hipMalloc(reinterpret_cast<void**>(&d_lb), sizeof(int) * nn) == hipSuccess &&
+                  hipMalloc(reinterpret_cast<void**>(&d_order), sizeof(int) * ncap) == hipSuccess && hipMalloc(reinterpret_cast<void**>(&d_w), sizeof(hw)) == hipSuccess;
+        hipStream_t st = c->stream;
+        ok = ok && hipMemcpyAsync(d_w, hw, sizeof(hw), hipMemcpyHostToDevice, st) == hipSuccess &&
+             (total == 0 || hipMemcpyAsync(d_r, responses, sizeof(float) * total, hipMemcpyHostToDevice, st) == hipSuccess);
+        uvo_status rc = ok ? rb_launch(c, st, d_r, d_w + W_START, keep, nseg, d_items, d_la, d_lb, d_w + W_META, d_order, cap, d_w + W_OUT, d_w + W_HIT) : UVO_HIP_ERROR;
+        ok = ok && rc == UVO_OK && hipGetLastError() == hipSuccess && hipMemcpyAsync(hw, d_w, sizeof(hw), hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
+        const int m = ok ? hw[W_OUT + nseg] : 0;
+        if (ok && m > 0 && m <= cap) ok = hipMemcpy(order, d_order, sizeof(int) * m, hipMemcpyDeviceToHost) == hipSuccess;
+        (void)hipFree(d_r); (void)hipFree(d_items); (void)hipFree(d_la); (void)hipFree(d_lb); (void)hipFree(d_order); (void)hipFree(d_w);
+        if (!ok) { c->err = "uvo_retain_best: a HIP call failed"; return UVO_HIP_ERROR; }
+        memcpy(out_start, hw + W_OUT, sizeof(int) * (nseg + 1));
+        memcpy(hit, hw + W_HIT, sizeof(int) * nseg);
+        if (m > cap) { c->err = "uvo_retain_best: output capacity too small"; return UVO_CAPACITY; }
+    }
+    if (hits) memcpy(hits, hit, sizeof(int) * nseg);
     return UVO_OK;
 }
 

@@ -421,6 +421,8 @@ void sift_ws_free(Ctx* c);
 void orb_ws_free(Ctx* c);
 uvo_status orb_configure(Ctx* c, int nfeatures, float scaleFactor, int nlevels, int edgeThreshold, int patchSize, int fastThreshold);
 uvo_status orb_set_pattern(Ctx* c, const int* pattern);
+uvo_status orb_set_ranking(Ctx* c, int where);
+uvo_status orb_retain_best(Ctx* c, const float* responses, const int* start, const int* keep, int nseg, int where, int* order, int cap, int* out_start, int* hits);
 uvo_status orb_detect(Ctx* c, const uint8_t* gray, int w, int h, int stride, int mem, uvo_keypoint* kps, uint8_t* desc, int cap, int* n_out);
 uvo_status orb_level_plane(Ctx* c, int level, int what, uint8_t* out, int cap_bytes, int* ow, int* oh);
 bool orb_has_pattern(Ctx* c);

@@ -45,7 +45,7 @@ void rb_sift(RbItem* first, ptrdiff_t hole, ptrdiff_t len, RbItem value)      //
     first[hole] = value;
 }
 #ifdef UVO_RB_TRACE
-long rb_heap_select_calls = 0;                                   // tests/cpp/retain_best_host.cpp: proof that the depth limit was reached
+long rb_heap_select_calls = 0;                                   // tests/cpp/retain_best_host.cpp: proof that the depth limit was reached; orb.hip: uvo_retain_best's depth_limit_hits
 #endif
 void rb_heap_select(RbItem* first, RbItem* middle, RbItem* last)
 {

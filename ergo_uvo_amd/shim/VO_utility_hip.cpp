@@ -75,6 +75,8 @@ struct State {
     int device = 0, max_w = 1920, max_h = 1200, max_kpts = 8192;
     std::vector<int> orb_pattern;                 // OpenCV's bit_pattern_31_ (set_orb_pattern / UVO_ORB_PATTERN_FILE); empty = not supplied
     bool orb_pattern_sent = false;                // ... and handed to the current context
+    int orb_ranking = -1;                         // set_orb_ranking: 0 host, 1 device; -1 = the library's default
+    bool orb_ranking_sent = false;
 } g;
 
 [[noreturn]] void raise(uvo_status st, const char* where)
@@ -162,7 +164,14 @@ void shutdown()
 {
     std::lock_guard<std::mutex> lk(g.mu);
     if (g.ctx) { uvo_ctx_destroy(g.ctx); g.ctx = nullptr; }
-    g.orb_pattern_sent = false; g.pnp_method = 1;
+    g.orb_pattern_sent = false; g.orb_ranking_sent = false; g.pnp_method = 1;
+}
+void set_orb_ranking(int where)
+{
+    if (where != 0 && where != 1) throw Error(UVO_INVALID_ARG, "set_orb_ranking: 0 (host) or 1 (device)");
+    std::lock_guard<std::mutex> lk(g.mu);
+    g.orb_ranking = where;
+    g.orb_ranking_sent = false;
 }
 void set_orb_pattern(const int* pattern1024)
 {
@@ -328,6 +337,7 @@ Mat get_image(const Mat& current_img, const Mat& cameraMatrix, const Mat& distor
 static void orb_pattern_to(uvo_ctx* c)
 {
     std::lock_guard<std::mutex> lk(g.mu);
+    if (g.orb_ranking >= 0 && !g.orb_ranking_sent) { SHIM_TRY(uvo_orb_set_ranking(c, g.orb_ranking), "uvo_orb_set_ranking"); g.orb_ranking_sent = true; }
     if (g.orb_pattern.empty())
         if (const char* path = getenv("UVO_ORB_PATTERN_FILE"))
             if (FILE* f = fopen(path, "r")) {

@@ -114,8 +114,10 @@ uvo_status uvo_ctx_set_feature_detector(uvo_ctx* c, const char* name);
  *            32-byte rows.  The stereo loop matches them by Hamming distance (VO_utility.cpp:520-524); the mono loop's 7-argument
  *            match_features builds BFMatcher(NORM_L2) whatever the detector (VO_utility.cpp:551-573): exact L2 of the bytes.
  *   "ORB" is accepted without a sampling table; the first step then fails with UVO_INVALID_ARG (the message names bit_pattern_31_).
- * The binary detectors' host stages (AKAZE's contrast factor and sequential duplicate suppression, ORB's retainBest rankings) run on the
- * thread that calls uvo_stereo_submit / uvo_mono_submit: with several pairs in flight they serialise the submissions' detection.  Each
+ * AKAZE's host stages (the contrast factor and the sequential duplicate suppression) run on the thread that calls uvo_stereo_submit /
+ * uvo_mono_submit: with several pairs in flight they serialise the submissions' detection.  ORB has no host stage with the rankings on
+ * the device (uvo_orb_set_ranking, the default): the submitting thread waits twice per image, for the FAST corners' level counts and for
+ * the final counts; with the rankings on the host it replays retainBest there, and the submissions' detection serialises likewise.  Each
  * lane keeps its own detector workspace, made by the first (synchronous) pair of a sequence; uvo_stereo_get("desc_left" / "desc_right")
  * returns the rows' bytes (61 or 32 per row).  Refused while pairs are in flight, and a change of detector while a VO sequence is running
  * (reset first).  A frame with more than max_kpts keypoints is a UVO_CAPACITY error, as for SURF: create the context with max_kpts >=
@@ -167,8 +169,9 @@ uvo_status uvo_akaze_plane(uvo_ctx* c, int level, int what, float* out, int cap_
  * others.  Rows of 32 bytes for uvo_match_knn2_ratio_hamming.  Keypoints in OpenCV's order: level by level, within a level the order
  * KeyPointsFilter::retainBest (libstdc++'s std::nth_element + std::partition) leaves; `size` = patchSize x 1.2^level, `angle` in
  * degrees (intensity centroid), `response` the Harris measure, `octave` the level.  Pyramid (INTER_LINEAR_EXACT), FAST-9/16 scores and
- * maxima, Harris responses, angles, the 7 x 7 blur and the descriptors run on the device; the two retainBest rankings per level run
- * on the host over the response arrays.
+ * maxima, Harris responses, angles, the 7 x 7 blur and the descriptors run on the device, and so do the two retainBest rankings per
+ * level (one launch each for all levels: k_rb_rank reproduces libstdc++'s introselect + partition order pass by pass) unless
+ * uvo_orb_set_ranking(c, 0) sends them to the host replay over the response arrays.
  * THE SAMPLING TABLE IS THE CALLER'S: with patchSize 31 OpenCV reads its 256 test pairs from `bit_pattern_31_` (orb.cpp: 1024 integers
  * learned offline), which this library cannot restate and the reference does not hold.  uvo_orb_set_pattern takes it in OpenCV's own
  * layout -- x0, y0, x1, y1 per descriptor bit, |coordinate| <= patchSize / 2 -- and keeps it for the context (NULL forgets it).  Without a
@@ -177,6 +180,19 @@ uvo_status uvo_akaze_plane(uvo_ctx* c, int level, int what, float* out, int cap_
  * The fused steps take the same detector after uvo_ctx_set_loop_detector(c, "ORB"), with this context's parameters and table. */
 uvo_status uvo_orb_configure(uvo_ctx* c, int nfeatures, float scale_factor, int nlevels, int edge_threshold, int patch_size, int fast_threshold);
 uvo_status uvo_orb_set_pattern(uvo_ctx* c, const int* pattern /* 1024 ints or NULL */);
+/* Where the two retainBest rankings of every level run: 1 = on the device (default; no per-corner copy between the pyramid and the
+ * descriptors, 288 bytes of level starts and flags come back for the grid sizes), 0 = the host replay (4 bytes per corner down, 4 per
+ * survivor up, twice).  The results do not depend on the value.  Anything else is UVO_INVALID_ARG; refused while entries are in flight.
+ * The fused steps take the master context's value, as they take its uvo_orb_configure. */
+uvo_status uvo_orb_set_ranking(uvo_ctx* c, int where);
+/* test hook: KeyPointsFilter::retainBest's order on nseg (1 .. 16) segments of a response array: segment l is
+ * responses[start[l] .. start[l + 1]) ranked for keep[l].  order[out_start[l] .. out_start[l + 1]) receives the positions in `responses`
+ * (start[l] + index) that segment l keeps, in the order std::nth_element + std::partition leave; out_start is the running sum of the
+ * counts; depth_limit_hits[l] (may be NULL) = 1 where introselect's depth limit was reached (heap select ran).  where = 1 launches the
+ * kernel uvo_orb_detect launches, once for all segments; where = 0 runs the host replay.  Host buffers.  nseg outside 1 .. 16, a
+ * decreasing start or a negative keep: UVO_INVALID_ARG; more than `cap` positions: UVO_CAPACITY.  Idle contexts only. */
+uvo_status uvo_retain_best(uvo_ctx* c, const float* responses, const int* start /* nseg + 1 */, const int* keep /* nseg */, int nseg, int where,
+                           int* order, int cap, int* out_start /* nseg + 1 */, int* depth_limit_hits /* nseg, or NULL */);
 uvo_status uvo_orb_detect(uvo_ctx* c, const uint8_t* gray, int w, int h, int stride, int mem, uvo_keypoint* kps, uint8_t* desc, int cap, int* n);
 /* test hook: level `level` of the last uvo_orb_detect as bytes to a host buffer: what = 0 the resized image (levels >= 1), 1 its blurred
  * copy (after a call with descriptors), 2 its FAST score map (0 = no corner) */

@@ -87,6 +87,9 @@ uvo_ctx* context();
 void     shutdown();
 // OpenCV's bit_pattern_31_ for the "ORB" branch of detect_features: 1024 ints, x0, y0, x1, y1 per descriptor bit (nullptr forgets it)
 void     set_orb_pattern(const int* pattern1024);
+// where the "ORB" branch's retainBest rankings run: 1 the device, 0 the host replay (uvo_orb_set_ranking); results do not depend on it.
+// Kept across a rebuilt context, as the table is.
+void     set_orb_ranking(int where);
 
 // Replacements for the cv:: functions the node loops call directly (visual_odometry.h:355, 631, 647-648, 673).
 void triangulatePoints(const uvocv::Mat& projMatr1, const uvocv::Mat& projMatr2, const std::vector<uvocv::Point2f>& projPoints1,
