@@ -17,7 +17,7 @@
 //                   (near-duplicate descriptors) is scanned row by row.  Those rows are evaluated in OpenCV's
 //                   order (the 16 lanes hold the 16 accumulators of normL2Sqr_) and the two smallest by (distance,
 //                   train index) are kept -- exactly what BFMatcher's insertion rule leaves after the full scan.
-// k_match_compact : ratio test + ordered stream compaction of the surviving matches (single workgroup scan).
+// k_match_compact : ratio test + ordered stream compaction of the surviving matches (one workgroup, one scan per 4096 queries).
 //
 // Margin: the split-bf16 contraction differs from the real t.q by less than (2^-15 + 2^-16) sum|t_k q_k| <= 2.3e-5 (|q|^2 + |t|^2),
 // so S' by twice that; OpenCV's float sum is within ~64 ulp of the real squared distance and the index bits cost 2^-16 of
@@ -347,46 +347,64 @@ __global__ __launch_bounds__(256) void k_match_resolve(MatchBatch mb)
     }
 }
 
-// ratio test + ordered compaction, one workgroup of 1024 threads; with two problems they are compacted one after the other (the
+// ratio test + ordered compaction, one workgroup of kCompactThreads threads; with two problems they are compacted one after the other (the
 // second's query count is the one the first's gate has just written: VO:567 decides whether the triangular matches are used)
 struct CompactProb { const int* knn_idx; const float* knn_dist; const int* nq_p; int nq_imm; uvo_dmatch* out; int* nout; int out_cap; GateArgs g; };
 struct CompactBatch { CompactProb p[2]; int np; float ratio; };
-__global__ __launch_bounds__(1024) void k_match_compact(CompactBatch cb)
+static const int kCompactThreads = 1024;
+__global__ __launch_bounds__(kCompactThreads) void k_match_compact(CompactBatch cb)
 {
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    __shared__ int wtot[16];
-    __shared__ int s_base;
+    constexpr int NT = kCompactThreads, NW = NT / 64;
+    // kRun passes of NT queries (4096 in all) are scanned together: every wave leaves the popcount of each of its kRun ballots (64 words,
+    // pass-major = query order), and after ONE barrier every wave scans those 64 words for itself, a word per lane.  The words are
+    // double-buffered, so the next block of 4096 queries (there is none at the loops' sizes) needs no second barrier either.
+    constexpr int kRun = 64 / NW;
+    static_assert(kRun * NW == 64, "one popcount word per lane of a wave");
+    __shared__ int wtot[2][64];
+    int buf = 0;
     for (int pi = 0; pi < cb.np; pi++) {
         const CompactProb& P = cb.p[pi];
-        const int* knn_idx = P.knn_idx; const float* knn_dist = P.knn_dist;
+        const int2* knn_idx = reinterpret_cast<const int2*>(P.knn_idx); const float2* knn_dist = reinterpret_cast<const float2*>(P.knn_dist);
         uvo_dmatch* out = P.out; const int out_cap = P.out_cap; const GateArgs g = P.g; const float ratio = cb.ratio;
-        if (tid == 0) s_base = 0;
-        __syncthreads();
         const int nq = P.nq_p ? *P.nq_p : P.nq_imm;
-        for (int base = 0; base < nq; base += 1024) {
-            int q = base + tid;
-            bool keep = false; int i0 = -1; float d0 = 0.f;
-            if (q < nq) {
-                i0 = knn_idx[2*q]; int i1 = knn_idx[2*q + 1];
-                d0 = knn_dist[2*q]; float d1 = knn_dist[2*q + 1];
-                keep = i0 >= 0 && i1 >= 0 && d0 < ratio * d1;
+        int sbase = 0;                                                  // matches kept so far: the same on every thread
+        for (int base = 0; base < nq; base += kRun * NT, buf ^= 1) {
+            bool keep[kRun]; int i0[kRun], before[kRun]; float d0[kRun];
+#pragma unroll
+            for (int j = 0; j < kRun; j++) {
+                const int q = base + j * NT + tid;
+                keep[j] = false; i0[j] = -1; d0[j] = 0.f;
+                if (q < nq) {
+                    const int2 ii = knn_idx[q]; const float2 dd = knn_dist[q];
+                    i0[j] = ii.x; d0[j] = dd.x;
+                    keep[j] = ii.x >= 0 && ii.y >= 0 && dd.x < ratio * dd.y;
+                }
             }
-            unsigned long long bal = __ballot(keep);
-            int before = __popcll(bal & ((1ull << lane) - 1ull));
-            if (lane == 0) wtot[wv] = __popcll(bal);
-            __syncthreads();
-            int off = s_base;
-            for (int k = 0; k < wv; k++) off += wtot[k];
-            if (keep) {
-                int pos = off + before;
-                if (pos < out_cap) { uvo_dmatch m; m.queryIdx = q; m.trainIdx = i0; m.imgIdx = 0; m.distance = d0; out[pos] = m; }
+#pragma unroll
+            for (int j = 0; j < kRun; j++) {
+                const unsigned long long bal = __ballot(keep[j]);
+                before[j] = __popcll(bal & ((1ull << lane) - 1ull));
+                if (lane == 0) wtot[buf][j * NW + wv] = __popcll(bal);
             }
             __syncthreads();
-            if (tid == 0) { int t = 0; for (int k = 0; k < 16; k++) t += wtot[k]; s_base += t; }
-            __syncthreads();
+            const int own = wtot[buf][lane];
+            int incl = own;                                             // inclusive prefix sum over the wave's 64 lanes
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o); if (lane >= o) incl += t; }
+            const int excl = incl - own;
+#pragma unroll
+            for (int j = 0; j < kRun; j++) {
+                const int off = __shfl(excl, j * NW + wv);
+                if (keep[j]) {
+                    const int pos = sbase + off + before[j];
+                    if (pos < out_cap) { uvo_dmatch m; m.queryIdx = base + j * NT + tid; m.trainIdx = i0[j]; m.imgIdx = 0; m.distance = d0[j]; out[pos] = m; }
+                }
+            }
+            sbase += __shfl(incl, 63);
         }
         if (tid == 0) {
-            *P.nout = s_base;                // may exceed out_cap: the host reports UVO_CAPACITY
+            *P.nout = sbase;                 // may exceed out_cap: the host reports UVO_CAPACITY
             int* cn = g.cn;
             if (g.mode == 1) {             // VO:567: results_match_curr.size() > MIN_NUM_FEATURES, else the "after stereo match" sets stay empty
                 int M = cn[CN_NQA] > 0 ? cn[CN_M] : 0;
@@ -430,8 +448,11 @@ static uvo_status match_launch(Ctx* c, const MatchBatch& mb, int np, int nq_max,
         // in turn; four in flight, the first batch together with the query's own loads: 20.3 -> 17.8 us (eight in flight: 128
         // VGPRs, three waves per SIMD, fewer resident workgroups than tiles, 20.3).  Measured without effect: the four 32-row
         // blocks of a chunk unrolled two at a time (22.5 us before the grid change; all four: 155 VGPRs, two waves per SIMD, 24.7).
+        // Measured and rejected (profiles/match_chunk_walk.json): workgroups that keep a chunk in LDS and walk its
+        // query tiles, at 256 ... 1152 workgroups -- 18.5 us at best against 18.0 here, and slower inside the pipeline.  A tile's time is
+        // not its staging but the top-4 bookkeeping (~850 VALU instructions per wave), which every form pays once per tile.
         static const int gtot = getenv("UVO_MATCH_GRID") ? atoi(getenv("UVO_MATCH_GRID")) : 1152;
-        const int gmax = gtot / np;
+        const int gmax = gtot / np > 0 ? gtot / np : 1;
         dim3 grid(tiles_max < gmax ? tiles_max : gmax, np);
         static bool attr_dev[64] = {false};                   // more than 64 KB of LDS (D = 128) has to be asked for, once per device
         bool& attr_set = attr_dev[c->device & 63];
@@ -483,7 +504,7 @@ uvo_status match_ratio_compact(Ctx* c, const int* d_nq, int nq_max, float ratio,
     if (gate) g = *gate;
     cb.p[0] = CompactProb{ c->d_knn_idx, c->d_knn_dist, d_nq, nq_max, d_out, d_nout, out_cap, g };
     cb.p[1] = cb.p[0]; cb.np = 1; cb.ratio = ratio;
-    hipLaunchKernelGGL(k_match_compact, dim3(1), dim3(1024), 0, c->stream, cb);
+    hipLaunchKernelGGL(k_match_compact, dim3(1), dim3(kCompactThreads), 0, c->stream, cb);
     UVO_HIP_TRY(c, hipGetLastError());
     return UVO_OK;
 }
@@ -497,7 +518,7 @@ uvo_status match_ratio_compact2(Ctx* c, float ratio, const int* d_nq0, uvo_dmatc
     cb.p[0] = CompactProb{ c->d_knn_idx, c->d_knn_dist, d_nq0, n_max, d_out0, d_nout0, out_cap, g0 };
     cb.p[1] = CompactProb{ c->d_knn_idx + (size_t)2 * c->cap, c->d_knn_dist + (size_t)2 * c->cap, d_nq1, n_max, d_out1, d_nout1, out_cap, g1 };
     cb.np = 2; cb.ratio = ratio;
-    hipLaunchKernelGGL(k_match_compact, dim3(1), dim3(1024), 0, c->stream, cb);
+    hipLaunchKernelGGL(k_match_compact, dim3(1), dim3(kCompactThreads), 0, c->stream, cb);
     UVO_HIP_TRY(c, hipGetLastError());
     return UVO_OK;
 }

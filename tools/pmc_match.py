@@ -12,8 +12,8 @@ for r in csv.DictReader(open(f)):
         acc[r["Counter_Name"]].append(float(r["Counter_Value"]))
 avg = {k: sum(v) / len(v) for k, v in acc.items()}
 n = len(next(iter(acc.values())))
-res = {"kernel": "uvo::k_match_mfma (v_mfma_f32_32x32x16_bf16 on bf16 hi/lo splits: shortlist of the brute-force matcher, fixed grid of 768 workgroups walking the tiles), "
-                 "C3 stereo pair, both calls averaged",
+res = {"kernel": "uvo::k_match_mfma (v_mfma_f32_32x32x16_bf16 on bf16 hi/lo splits: shortlist of the brute-force matcher, fixed grid of 1152 workgroups -- UVO_MATCH_GRID -- walking the tiles, "
+                 "both matches of the loop in one launch), C3 stereo pair",
        "command": "rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_INSTS_VALU_MFMA_MOPS_BF16 SQ_INSTS_MFMA -- python3 tools/prof_stereo.py 6",
        "launches_sampled": n, "counters_avg_per_launch": avg}
 if "SQ_VALU_MFMA_BUSY_CYCLES" in avg and "SQ_BUSY_CU_CYCLES" in avg:
