@@ -267,6 +267,40 @@ class Context:
         where = {"host": 0, "device": 1}.get(where, where)
         self._check(self._lib.uvo_orb_set_ranking(self._h, int(where)))
 
+    def akaze_set_suppression(self, where):
+        """Where AKAZE's sequential stages (contrast factor, duplicate suppression, refinement) run: "host" / 0 (the host scans of the
+        candidate list) or "device" / 1 (k_ak_scan, k_ak_refine; the fused steps then queue their detection without a host wait).  The
+        results do not depend on it; the fused steps take the master context's value."""
+        where = {"host": 0, "device": 1}.get(where, where)
+        self._check(self._lib.uvo_akaze_set_suppression(self._h, int(where)))
+
+    def akaze_suppress(self, w, h, level, x, y, v9, where="device", cap=None):
+        """Test hook: the scans and the refinement akaze_detect runs, on a candidate list in any order, for the level plan of a w x h
+        image.  v9: n x 9 response neighbourhoods (row-major, v9[:, 4] the value).  Returns (marks, keypoints): marks[q, p] = candidate
+        q's mark after phase p + 1, keypoints what Do_Subpixel_Refinement leaves, in OpenCV's order."""
+        level = np.ascontiguousarray(level, np.int32).reshape(-1)
+        x = np.ascontiguousarray(x, np.int32).reshape(-1)
+        y = np.ascontiguousarray(y, np.int32).reshape(-1)
+        v9 = np.ascontiguousarray(v9, np.float32).reshape(-1, 9)
+        n = level.size
+        if x.size != n or y.size != n or v9.shape[0] != n:
+            raise ValueError("akaze_suppress: level, x, y and v9 describe the same candidates")
+        where = {"host": 0, "device": 1}.get(where, where)
+        cap = max(n, 1) if cap is None else int(cap)
+        marks = np.zeros((max(n, 1), 3), np.uint8)
+        kps = np.zeros(max(cap, 1), KP_DTYPE)
+        nk = C.c_int(0)
+        self._check(self._lib.uvo_akaze_suppress(self._h, int(w), int(h), _p(level), _p(x), _p(y), _p(v9), int(n), int(where), _p(marks), _p(kps), cap, C.byref(nk)))
+        return marks[:n].copy(), kps[:nk.value].copy()
+
+    def akaze_stats(self):
+        """Figures of the last AKAZE detection on this context's own lane, or of the last akaze_suppress: dict(n_candidates, rounds (the
+        largest round count of a scan, per phase; zeros on the host), host_waits (stream waits of the calling thread))."""
+        nc, hw = C.c_int(0), C.c_int(0)
+        rounds = np.zeros(3, np.int32)
+        self._check(self._lib.uvo_akaze_stats(self._h, C.byref(nc), _p(rounds), C.byref(hw)))
+        return {"n_candidates": nc.value, "rounds": [int(v) for v in rounds], "host_waits": hw.value}
+
     def retain_best(self, responses, keep, where="device", starts=None):
         """Test hook: KeyPointsFilter::retainBest's order on response segments.  Segment l is responses[starts[l]:starts[l + 1]] (default:
         one segment, everything) ranked for keep[l]; returns (order, out_start, depth_limit_hits): order[out_start[l]:out_start[l + 1]] holds

@@ -18,11 +18,18 @@
 //   k_ak_candidates                strict 3 x 3 maxima above the threshold inside the level's border, with their neighbourhood
 //   k_ak_orientation               Compute_Main_Orientation, one wave per keypoint (samples, counting sort and window sums in LDS)
 //   k_ak_mldb                      the M-LDB descriptor, 32 lanes per keypoint (one per grid cell of the 2x2 + 3x3 + 4x4 grids)
+//   k_ak_kcontrast                 compute_kcontrast's last step on the histogram, into the device word the conductance kernels read
+//   k_ak_cand_count / _scan / _emit  the same candidates IN ORDER (level by level, row-major): per-workgroup counts, one scan, an ordered scatter
+//   k_ak_scan                      one phase of the duplicate suppression, a workgroup per level (uvo_akaze_suppress_dev.h)
+//   k_ak_refine                    Do_Subpixel_Refinement per surviving candidate, compacted in candidate order, the count left on the device
 // What OpenCV does SEQUENTIALLY -- the row-major scan that suppresses weaker maxima within sigma_size of a stronger one, the two
-// sweeps across neighbouring scales (FindKeypointsSameScale, Find_Scale_Space_Extrema), the 2 x 2 sub-pixel solve -- runs on the host
-// over the candidate list (a few thousand 40-byte records; the planes stay on the device), like the RANSAC scans of the pose stages.
+// sweeps across neighbouring scales (FindKeypointsSameScale, Find_Scale_Space_Extrema), the 2 x 2 sub-pixel solve -- is DEFINED by the
+// host scans of uvo_akaze_suppress.h over the candidate list (a few thousand 48-byte records; the planes stay on the device).
+// uvo_akaze_set_suppression chooses where it runs: 0 those host scans (three waits of the calling thread per image: histogram, candidate
+// count, candidate records), 1 the device form above, which queues without a wait inside the fused steps.  Results do not depend on it.
 #include "uvo_ctx.h"
 #include "uvo_math.h"
+#include "uvo_akaze_suppress.h"
 #include <float.h>
 #include <string.h>
 #include <math.h>
@@ -33,8 +40,8 @@ namespace uvo {
 
 double now_us();                                                  // pose.hip / ctx.hip: steady clock, microseconds
 static const int kAkMaxLevels = 16, kAkDescBytes = 61, kAkCandCap = 1 << 18;
+static const int kAkazeSuppressDefault = 1;                       // uvo_akaze_set_suppression's initial value: the device (124 against 66 stereo pairs/s at depth 6)
 struct AkLevel { int w, h, octave, sublevel, sigma_size, border, nsteps; float esigma, etime, octave_ratio; float tau[64]; };
-struct AkCand { int x, y; float v[9]; int pad; };             // a strict maximum and its 3 x 3 neighbourhood (row-major, v[4] = the maximum); pad = its evolution level
 struct AkTab { int si; float alpha; };
 
 struct AkazeWs {
@@ -50,12 +57,24 @@ struct AkazeWs {
     uvo_keypoint* d_kps = nullptr; uint8_t* d_desc = nullptr; // outputs (cap: max_kpts, grown by the single-image path when a frame has more)
     AkTab* xtab[kAkMaxLevels] = {nullptr}; AkTab* ytab[kAkMaxLevels] = {nullptr}; int* xofs[kAkMaxLevels] = {nullptr}; int* yofs[kAkMaxLevels] = {nullptr};   // general INTER_AREA tables of the octave changes that are not exact halvings (built with the workspace)
     float* d_kc = nullptr; float* h_kc = nullptr;             // compute_kcontrast's result: pinned source, device copy the conductance kernels read
-    hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; // the launch chain from the first evolution step to the last level's candidates, captured once per image size
-    std::vector<uint8_t> mask[kAkMaxLevels]; std::vector<float> val[kAkMaxLevels];               // host: keypoint mask and Ldet at candidates
-    std::vector<std::vector<AkCand>> cands;
-    std::vector<uint64_t> keys;                               // host: sort keys of the candidate list
+    hipGraph_t graph[2] = {nullptr, nullptr}; hipGraphExec_t exec[2] = {nullptr, nullptr};   // the launch chain from the first evolution step to the last level's candidates, captured once per image size: [0] candidates in atomicAdd order (the host sorts), [1] emitted in order
+    AksHost hs;                                               // host: the definition's marks, value planes and per-level candidate lists (uvo_akaze_suppress.h)
     std::vector<uvo_keypoint> out;                            // host: the refined keypoints (source of an asynchronous copy: kept until the next call)
+    // ---- the device form (uvo_akaze_set_suppression 1) ----
+    AksLevels L;                                              // the plan as the scans read it
+    int blk_base[kAkMaxLevels + 1] = {0};                     // ordered emission: the first workgroup of each level's candidate grid; [n] = their number
+    int* d_blk = nullptr;                                     // [blk_base[n] + 1] per-workgroup counts, then their exclusive scan
+    uint32_t* d_pos = nullptr; float* d_val = nullptr;        // per candidate, in order: (y << 16) | x, the response
+    uint8_t* d_mark = nullptr; uint8_t* d_state = nullptr;    // 3 x kAkCandCap marks (one plane per phase), kAkCandCap round states
+    int* d_sup = nullptr; int* h_sup = nullptr;               // SUP_* words (h_sup pinned)
+    int cand_cap = kAkCandCap;                                // the candidates one image may have (the lists hold kAkCandCap; UVO_AKAZE_CAND_CAP lowers it for tests of the overflow path)
+    int stat_ncand = 0, stat_rounds[3] = {0, 0, 0}, stat_waits = 0, stat_dev = 0;    // uvo_akaze_stats: the last detection (stat_dev: the figures are in d_sup)
 };
+// d_sup: the candidates found (may exceed the list), the candidates listed, the levels' starts in the list, per image slot of a lane the
+// keypoint count (what the kernels after the refinement consume: always a count of written keypoints) and, apart from it, the flag "more
+// candidates were found than the list holds" (read by k_binary_publish_dev and the host only), the largest round count per phase
+enum { SUP_FOUND = 0, SUP_N = 1, SUP_START = 2, SUP_NK = SUP_START + kAkMaxLevels + 1, SUP_OVF = SUP_NK + 2, SUP_ROUNDS = SUP_OVF + 2, SUP_INTS = SUP_ROUNDS + 3 };
+static_assert(sizeof(AksKp) == sizeof(uvo_keypoint) && kAksMaxLevels == kAkMaxLevels, "AksKp mirrors uvo_keypoint");
 
 // ---- fed.cpp: fed_tau_by_process_time(T, 1, 0.25f, true, tau) ----
 static bool fed_is_prime(int number)
@@ -297,6 +316,147 @@ __global__ __launch_bounds__(256) void k_ak_candidates(const float* __restrict__
     c.v[6] = next[x - 1]; c.v[7] = next[x]; c.v[8] = next[x + 1];
     out[slot] = c;
 }
+// ---- the same candidates IN ORDER, level by level and row-major (uvo_akaze_set_suppression 1): every level's candidate grid in one launch,
+// workgroup b = 256 consecutive columns of one row of level l (blk_base[l] <= b < blk_base[l + 1]; a level whose border leaves nothing has
+// no workgroup), so workgroup order, then thread order, IS the visiting order: count per workgroup, one exclusive scan, ordered scatter ----
+struct AkCandPlan { const float* ldet[kAkMaxLevels]; int w[kAkMaxLevels], h[kAkMaxLevels], border[kAkMaxLevels], gx[kAkMaxLevels], blk_base[kAkMaxLevels + 1]; int n; float thr; };
+__device__ __forceinline__ bool ak_cand_test(const AkCandPlan& P, int b, int* level, int* xo, int* yo)
+{
+    int l = 0;
+    while (l + 1 < P.n && b >= P.blk_base[l + 1]) l++;
+    const int lb = b - P.blk_base[l], border = P.border[l], w = P.w[l], h = P.h[l];
+    const int x = border + (lb % P.gx[l]) * 256 + (int)threadIdx.x, y = border + lb / P.gx[l];
+    *level = l; *xo = x; *yo = y;
+    if (x >= w - border || y >= h - border) return false;
+    const float* curr = P.ldet[l] + (size_t)y * w; const float* prev = curr - w; const float* next = curr + w;
+    const float value = curr[x];
+    if (value <= P.thr) return false;
+    if (value <= curr[x - 1] || value <= curr[x + 1]) return false;
+    if (value <= prev[x - 1] || value <= prev[x] || value <= prev[x + 1]) return false;
+    if (value <= next[x - 1] || value <= next[x] || value <= next[x + 1]) return false;
+    return true;
+}
+__global__ __launch_bounds__(256) void k_ak_cand_count(AkCandPlan P, int* __restrict__ blk)
+{
+    int l, x, y;
+    const int n = __syncthreads_count(ak_cand_test(P, blockIdx.x, &l, &x, &y) ? 1 : 0);
+    if (threadIdx.x == 0) blk[blockIdx.x] = n;
+}
+// one workgroup: blk[0, nblk) -> its exclusive scan, blk[nblk] = the total; the levels' starts, clamped to the list's capacity
+__global__ __launch_bounds__(1024) void k_ak_cand_scan(AkCandPlan P, int* blk, int nblk, int cap, int* __restrict__ sup)
+{
+    __shared__ int s_sum[1024];
+    const int t = threadIdx.x, chunk = (nblk + 1023) / 1024, lo = min(t * chunk, nblk), hi = min(lo + chunk, nblk);
+    int sum = 0;
+    for (int i = lo; i < hi; i++) sum += blk[i];
+    s_sum[t] = sum;
+    __syncthreads();
+    for (int d = 1; d < 1024; d <<= 1) {                              // inclusive scan of the threads' sums
+        const int v = t >= d ? s_sum[t - d] : 0;
+        __syncthreads();
+        s_sum[t] += v;
+        __syncthreads();
+    }
+    int run = s_sum[t] - sum;
+    for (int i = lo; i < hi; i++) { const int v = blk[i]; blk[i] = run; run += v; }
+    if (t == 1023) blk[nblk] = s_sum[1023];
+    __syncthreads();
+    const int total = blk[nblk];
+    if (t == 0) { sup[SUP_FOUND] = total; sup[SUP_N] = min(total, cap); }
+    if (t <= kAkMaxLevels) sup[SUP_START + t] = min(t < P.n ? blk[P.blk_base[t]] : total, cap);
+}
+__global__ __launch_bounds__(256) void k_ak_cand_emit(AkCandPlan P, const int* __restrict__ blk, AkCand* __restrict__ out, uint32_t* __restrict__ pos, float* __restrict__ val, int cap)
+{
+    __shared__ int s_w[4];
+    int l, x, y;
+    const bool is = ak_cand_test(P, blockIdx.x, &l, &x, &y);
+    const unsigned long long m = __ballot(is);
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (lane == 0) s_w[wv] = __popcll(m);
+    __syncthreads();
+    if (!is) return;
+    int slot = blk[blockIdx.x] + __popcll(m & ((1ull << lane) - 1ull));
+    for (int k = 0; k < wv; k++) slot += s_w[k];
+    if (slot >= cap) return;
+    const int w = P.w[l];
+    const float* curr = P.ldet[l] + (size_t)y * w; const float* prev = curr - w; const float* next = curr + w;
+    AkCand c;
+    c.x = x; c.y = y; c.pad = l;
+    c.v[0] = prev[x - 1]; c.v[1] = prev[x]; c.v[2] = prev[x + 1]; c.v[3] = curr[x - 1]; c.v[4] = curr[x]; c.v[5] = curr[x + 1];
+    c.v[6] = next[x - 1]; c.v[7] = next[x]; c.v[8] = next[x + 1];
+    out[slot] = c; pos[slot] = aks_pos(x, y); val[slot] = c.v[4];
+}
+// compute_kcontrast's last step, where the histogram is
+__global__ void k_ak_kcontrast(const int* __restrict__ hist, int total, int nbins, float* __restrict__ kc)
+{
+    if (threadIdx.x == 0 && blockIdx.x == 0) *kc = aks_kcontrast(__int_as_float(hist[0]), hist + 1, total, nbins);
+}
+// ---- one phase of the duplicate suppression (uvo_akaze_suppress_dev.h): workgroup wg runs the scan of level wg, in rounds; every loop is
+// bounded by a list range, and a workgroup waits for nothing but its own barriers.  mark: three planes of kAkCandCap bytes (phase 0, 1, 2);
+// a phase reads the scanning level's marks from the previous plane and writes the target level's into its own, which it first fills (zero
+// in phase 0, the previous plane's after) -- each level's range of a plane has exactly one writing workgroup. ----
+__global__ __launch_bounds__(1024) void k_ak_scan(int phase, AksLevels L, const uint32_t* __restrict__ pos, const float* __restrict__ val, uint8_t* mark, uint8_t* state, int* sup)
+{
+    __shared__ int s_left;
+    const int wg = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
+    int copy_level;
+    const AksScan sc = aks_scan_of(phase, wg, L, &copy_level);
+    const int* start = sup + SUP_START;
+    const uint8_t* mprev = mark + (size_t)(phase ? phase - 1 : 0) * kAkCandCap;
+    uint8_t* mt = mark + (size_t)phase * kAkCandCap;
+    if (copy_level >= 0) for (int q = start[copy_level] + tid; q < start[copy_level + 1]; q += nt) mt[q] = mprev[q];
+    if (sc.own < 0) return;                                             // (the whole workgroup)
+    const int a = start[sc.own], b = start[sc.own + 1], ta = start[sc.tgt], tb = start[sc.tgt + 1];
+    const int tw = L.lv[sc.tgt].w, th = L.lv[sc.tgt].h;
+    if (tid == 0) s_left = 0;
+    __syncthreads();
+    int mine = 0;
+    if (phase == 0) for (int q = a + tid; q < b; q += nt) { mt[q] = 0; state[q] = AKS_UNDECIDED; mine++; }
+    else {
+        for (int p = ta + tid; p < tb; p += nt) mt[p] = mprev[p];
+        for (int q = a + tid; q < b; q += nt) { const bool act = mprev[q] != 0; state[q] = act ? AKS_UNDECIDED : AKS_DECIDED; mine += act; }
+    }
+    if (mine) atomicAdd(&s_left, mine);
+    __syncthreads();
+    int rounds = 0;
+    for (int it = 0; it < b - a; ++it) {                                // (each round decides at least the earliest undecided candidate)
+        if (s_left == 0) break;                                         // (read by all between two barriers: the same for all)
+        for (int q = a + tid; q < b; q += nt) if (state[q] == AKS_UNDECIDED && aks_ready(pos, state, a, q, sc)) state[q] = AKS_READY;     // (READY reads as "not decided" to the others)
+        __syncthreads();
+        int dec = 0;
+        for (int q = a + tid; q < b; q += nt) if (state[q] == AKS_READY) { aks_decide(phase, pos, val, mt, ta, tb, q, sc, tw, th); state[q] = AKS_DECIDED; dec++; }
+        if (dec) atomicSub(&s_left, dec);
+        __syncthreads();
+        rounds++;
+    }
+    if (tid == 0) atomicMax(&sup[SUP_ROUNDS + phase], rounds);
+}
+// Do_Subpixel_Refinement per candidate that kept its mark, compacted in candidate order into out[0, cap); the count (also past cap: the
+// caller compares) goes to sup[SUP_NK + nk_slot]; sup[SUP_OVF + nk_slot] = more candidates were found than the list (cand_cap) holds
+__global__ __launch_bounds__(1024) void k_ak_refine(AksLevels L, const AkCand* __restrict__ cand, const uint8_t* __restrict__ m3, int* sup, uvo_keypoint* __restrict__ out, int cap, int nk_slot, int cand_cap)
+{
+    __shared__ int s_w[16];
+    __shared__ int s_base;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, n = sup[SUP_N];
+    if (tid == 0) s_base = 0;
+    __syncthreads();
+    for (int q0 = 0; q0 < n; q0 += 1024) {
+        const int q = q0 + tid;
+        bool keep = false;
+        AksKp k;
+        if (q < n && m3[q] != 0) { const AkCand cd = cand[q]; keep = aks_refine(cd, L.lv[cd.pad], cd.pad, &k); }
+        const unsigned long long m = __ballot(keep);
+        if (lane == 0) s_w[wv] = __popcll(m);
+        __syncthreads();
+        int slot = s_base + __popcll(m & ((1ull << lane) - 1ull)), tot = 0;
+        for (int i = 0; i < 16; i++) { if (i < wv) slot += s_w[i]; tot += s_w[i]; }
+        if (keep && slot < cap) { uvo_keypoint o; o.x = k.x; o.y = k.y; o.size = k.size; o.angle = k.angle; o.response = k.response; o.octave = k.octave; o.class_id = k.class_id; out[slot] = o; }
+        __syncthreads();
+        if (tid == 0) s_base += tot;
+        __syncthreads();
+    }
+    if (tid == 0) { sup[SUP_NK + nk_slot] = s_base; sup[SUP_OVF + nk_slot] = sup[SUP_FOUND] > cand_cap ? 1 : 0; }
+}
 
 __device__ __forceinline__ float ak_atan2_deg(float y, float x)      // cv::fastAtan2 (as surf.hip's fast_atan2_deg)
 {
@@ -335,8 +495,12 @@ constexpr AkOriTab ak_make_ori_tab()
     return t;
 }
 __device__ const AkOriTab kAkOriTab = ak_make_ori_tab();
-__global__ __launch_bounds__(256) void k_ak_orientation(AkPlanes pl, uvo_keypoint* __restrict__ kps, int n)
+// (d_n, when given: the count on the device, n its bound -- the grid is sized from n and a workgroup past the count returns at once; only the
+// first min(count, n) keypoints were written by k_ak_refine, so nothing else is ever read)
+__global__ __launch_bounds__(256) void k_ak_orientation(AkPlanes pl, uvo_keypoint* __restrict__ kps, int n, const int* __restrict__ d_n)
 {
+    if (d_n) n = min(n, *d_n);
+    if ((int)blockIdx.x * 4 >= n) return;
     constexpr int ang_size = 109, slices = 42, win = 7;
     __shared__ float sX[4][ang_size + 3], sY[4][ang_size + 3];
     __shared__ unsigned char sBin[4][ang_size + 3], sOrd[4][ang_size + 3];
@@ -399,8 +563,11 @@ __global__ __launch_bounds__(256) void k_ak_orientation(AkPlanes pl, uvo_keypoin
 // MLDB_Full_Descriptor_Invoker: grids of 2 x 2, 3 x 3 and 4 x 4 cells over the rotated 20 x 20-sample pattern (cell sides 10, 7, 5 samples),
 // per cell the means of Lt and of the rotated derivatives; every pair of cells of a grid compared channel by channel: 3 (6 + 36 + 120) =
 // 486 bits.  Lane c of the keypoint's 32 owns cell c (0..3 | 4..12 | 13..28) and sums its samples in OpenCV's order; lane 0 packs.
-__global__ __launch_bounds__(256) void k_ak_mldb(AkPlanes pl, const uvo_keypoint* __restrict__ kps, int n, uint8_t* __restrict__ desc)
+// (d_n as k_ak_orientation's; rows of `stride` bytes, zero past the 61)
+__global__ __launch_bounds__(256) void k_ak_mldb(AkPlanes pl, const uvo_keypoint* __restrict__ kps, int n, const int* __restrict__ d_n, uint8_t* __restrict__ desc, int stride)
 {
+    if (d_n) n = min(n, *d_n);
+    if ((int)blockIdx.x * 8 >= n) return;
     __shared__ int s_val[8][29 * 3];
     const int g = threadIdx.x >> 5, lane = threadIdx.x & 31, q = blockIdx.x * 8 + g;
     if (q < n && lane < 29) {
@@ -453,7 +620,8 @@ __global__ __launch_bounds__(256) void k_ak_mldb(AkPlanes pl, const uvo_keypoint
                     for (int j = i + 1; j < val_count; j++) { d[dpos >> 3] |= (uint8_t)((ival > iv[3 * j + pos]) << (dpos & 7)); dpos++; }
                 }
         }
-        for (int i = 0; i < kAkDescBytes; i++) desc[(size_t)q * kAkDescBytes + i] = d[i];
+        for (int i = 0; i < kAkDescBytes; i++) desc[(size_t)q * stride + i] = d[i];
+        for (int i = kAkDescBytes; i < stride; i++) desc[(size_t)q * stride + i] = 0;
     }
 }
 
@@ -466,8 +634,8 @@ void akaze_ws_free(Ctx* c)
     for (float* p : s->s) (void)hipFree(p);
     (void)hipFree(s->img); (void)hipFree(s->img8); (void)hipFree(s->hist); (void)hipFree(s->cand); (void)hipFree(s->cand_n); (void)hipFree(s->d_kps); (void)hipFree(s->d_desc);
     for (int i = 0; i < kAkMaxLevels; i++) { (void)hipFree(s->xtab[i]); (void)hipFree(s->ytab[i]); (void)hipFree(s->xofs[i]); (void)hipFree(s->yofs[i]); }
-    if (s->exec) (void)hipGraphExecDestroy(s->exec);
-    if (s->graph) (void)hipGraphDestroy(s->graph);
+    for (int g = 0; g < 2; g++) { if (s->exec[g]) (void)hipGraphExecDestroy(s->exec[g]); if (s->graph[g]) (void)hipGraphDestroy(s->graph[g]); }
+    (void)hipFree(s->d_blk); (void)hipFree(s->d_pos); (void)hipFree(s->d_val); (void)hipFree(s->d_mark); (void)hipFree(s->d_state); (void)hipFree(s->d_sup); (void)hipHostFree(s->h_sup);
     (void)hipFree(s->d_kc); (void)hipHostFree(s->h_kc);
     (void)hipHostFree(s->h_cand); (void)hipHostFree(s->h_hist);
     delete s;
@@ -483,21 +651,33 @@ static AkazeWs* akaze_ws(Ctx* c, int w, int h)
     c->akaze_ws = s;
     s->w = w; s->h = h; s->cap = c->cap;
     s->n = akaze_plan(w, h, s->lv);
+    if (const char* e = getenv("UVO_AKAZE_CAND_CAP")) s->cand_cap = std::min(std::max(atoi(e), 1), kAkCandCap);      // (read per workspace: tools/probe/README.md)
     bool ok = true;
     auto alloc = [&](float** p, size_t n) { ok = ok && hipMalloc(reinterpret_cast<void**>(p), sizeof(float) * n) == hipSuccess; };
     const size_t npx = (size_t)w * h;
     for (int i = 0; i < s->n; i++) {
         const size_t n = (size_t)s->lv[i].w * s->lv[i].h;
         alloc(&s->Lt[i], n); alloc(&s->Lsmooth[i], n); alloc(&s->Lx[i], n); alloc(&s->Ly[i], n); alloc(&s->Ldet[i], n);
-        s->mask[i].resize(n); s->val[i].resize(n);
     }
+    for (int i = 0; i < s->n; i++) {                                // the plan as the scans read it; the candidate grids of the ordered emission
+        const AkLevel& lv = s->lv[i];
+        s->L.lv[i] = AksLevel{ lv.w, lv.h, lv.sigma_size, lv.octave, lv.octave_ratio, lv.esigma };
+        const bool none = lv.border + 1 >= lv.h || lv.w - 2 * lv.border <= 0 || lv.h - 2 * lv.border <= 0;
+        s->blk_base[i + 1] = s->blk_base[i] + (none ? 0 : ((lv.w - 2 * lv.border + 255) / 256) * (lv.h - 2 * lv.border));
+    }
+    s->L.n = s->n;
+    aks_host_init(&s->hs, s->L);
     alloc(&s->img, npx);
     for (float*& p : s->s) alloc(&p, npx);
     ok = ok && hipMalloc(reinterpret_cast<void**>(&s->img8), npx) == hipSuccess && hipMalloc(reinterpret_cast<void**>(&s->hist), sizeof(int) * 512) == hipSuccess &&
          hipMalloc(reinterpret_cast<void**>(&s->cand), sizeof(AkCand) * kAkCandCap) == hipSuccess && hipMalloc(reinterpret_cast<void**>(&s->cand_n), sizeof(int) * kAkMaxLevels) == hipSuccess &&
          hipMalloc(reinterpret_cast<void**>(&s->d_kps), sizeof(uvo_keypoint) * (size_t)s->cap) == hipSuccess && hipMalloc(reinterpret_cast<void**>(&s->d_desc), (size_t)kAkDescBytes * s->cap) == hipSuccess &&
          hipMalloc(reinterpret_cast<void**>(&s->d_kc), sizeof(float)) == hipSuccess && hipHostMalloc(reinterpret_cast<void**>(&s->h_kc), sizeof(float)) == hipSuccess &&
-         hipHostMalloc(reinterpret_cast<void**>(&s->h_cand), sizeof(AkCand) * kAkCandCap) == hipSuccess && hipHostMalloc(reinterpret_cast<void**>(&s->h_hist), sizeof(int) * 512) == hipSuccess;
+         hipHostMalloc(reinterpret_cast<void**>(&s->h_cand), sizeof(AkCand) * kAkCandCap) == hipSuccess && hipHostMalloc(reinterpret_cast<void**>(&s->h_hist), sizeof(int) * 512) == hipSuccess &&
+         hipMalloc(reinterpret_cast<void**>(&s->d_blk), sizeof(int) * ((size_t)s->blk_base[s->n] + 1)) == hipSuccess && hipMalloc(reinterpret_cast<void**>(&s->d_pos), sizeof(uint32_t) * kAkCandCap) == hipSuccess &&
+         hipMalloc(reinterpret_cast<void**>(&s->d_val), sizeof(float) * kAkCandCap) == hipSuccess && hipMalloc(reinterpret_cast<void**>(&s->d_mark), (size_t)3 * kAkCandCap) == hipSuccess &&
+         hipMalloc(reinterpret_cast<void**>(&s->d_state), (size_t)kAkCandCap) == hipSuccess && hipMalloc(reinterpret_cast<void**>(&s->d_sup), sizeof(int) * SUP_INTS) == hipSuccess &&
+         hipHostMalloc(reinterpret_cast<void**>(&s->h_sup), sizeof(int) * SUP_INTS) == hipSuccess && hipMemset(s->d_sup, 0, sizeof(int) * SUP_INTS) == hipSuccess;
     // resize(Lt[i - 1], Lt[i], INTER_AREA) at an octave change: exact halving has a kernel of its own; other size ratios (odd sizes) take
     // resizeArea_'s tables, which depend on the sizes alone
     for (int i = 1; i < s->n && ok; i++) {
@@ -514,7 +694,6 @@ static AkazeWs* akaze_ws(Ctx* c, int w, int h)
              hipMemcpy(s->xofs[i], xo.data(), sizeof(int) * xo.size(), hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(s->yofs[i], yo.data(), sizeof(int) * yo.size(), hipMemcpyHostToDevice) == hipSuccess;
     }
     if (!ok) { akaze_ws_free(c); return nullptr; }
-    s->cands.resize(kAkMaxLevels);
     return s;
 }
 static void gauss_kernel(int n, double sigma, AkKernel* kk)       // getGaussianKernel(n, sigma, CV_32F): double, normalised, cast
@@ -543,24 +722,8 @@ static void area_tab(int ssize, int dsize, double scale, std::vector<AkTab>* tab
     }
     (*ofs)[dsize] = (int)tab->size();
 }
-// find_neighbor_point (AKAZEFeatures.cpp): a keypoint of `mask` within search_radius (L2) of (x, y), scanning the square window row-major
-static bool find_neighbor_point(int x, int y, const std::vector<uint8_t>& mask, int cols, int rows, int search_radius, int* idx)
-{
-    // (the marks are sparse: eight mask bytes are tested at a time and only a non-zero word is walked byte by byte, in the same order)
-    const int j0 = std::max(x - search_radius, 0), j1 = std::min(x + search_radius, cols), r2 = search_radius * search_radius;
-    for (int i = std::max(y - search_radius, 0); i < std::min(y + search_radius, rows); ++i) {
-        const uint8_t* curr = mask.data() + (size_t)i * cols;
-        const int dy = i - y;
-        for (int j = j0; j < j1;) {
-            if (j1 - j >= 8) { uint64_t wd; memcpy(&wd, curr + j, 8); if (wd == 0) { j += 8; continue; } }
-            if (curr[j] != 0) { const int dx = j - x; if (dx * dx + dy * dy <= r2) { *idx = i * cols + j; return true; } }
-            ++j;
-        }
-    }
-    return false;
-}
-
-static uvo_status akaze_record(Ctx* c, AkazeWs* s, hipStream_t st)
+// ordered: the candidates by k_ak_cand_count / _scan / _emit (in visiting order, with pos and val) instead of k_ak_candidates' atomicAdd order
+static uvo_status akaze_record(Ctx* c, AkazeWs* s, hipStream_t st, bool ordered)
 {
     const dim3 blk(256);
     auto grid = [](int ww, int hh) { return dim3((ww + 255) / 256, hh); };
@@ -587,7 +750,7 @@ static uvo_status akaze_record(Ctx* c, AkazeWs* s, hipStream_t st)
         }
         if (cur != s->Lt[i]) UVO_HIP_TRY(c, hipMemcpyAsync(s->Lt[i], cur, sizeof(float) * (size_t)lw * lh, hipMemcpyDeviceToDevice, st));
     }
-    UVO_HIP_TRY(c, hipMemsetAsync(s->cand_n, 0, sizeof(int) * kAkMaxLevels, st));
+    if (!ordered) UVO_HIP_TRY(c, hipMemsetAsync(s->cand_n, 0, sizeof(int) * kAkMaxLevels, st));
     for (int i = 0; i < s->n; i++) {
         const AkLevel& lv = s->lv[i];
         const int lw = lv.w, lh = lv.h, r = lv.sigma_size;
@@ -597,9 +760,20 @@ static uvo_status akaze_record(Ctx* c, AkazeWs* s, hipStream_t st)
         hipLaunchKernelGGL(k_ak_sep_deriv, grid(lw, lh), blk, 0, st, s->Lsmooth[i], lw, lh, 0, r, s->Ly[i]);
         hipLaunchKernelGGL(k_ak_sep_deriv, grid(lw, lh), blk, 0, st, s->Ly[i], lw, lh, 0, r, s->s[2]);        // Lyy
         hipLaunchKernelGGL(k_ak_det, dim3((lw * lh + 255) / 256), blk, 0, st, s->s[0], s->s[1], s->s[2], lw * lh, (float)(r * r * r * r), s->Ldet[i]);
-        if (lv.border + 1 >= lh || lw - 2 * lv.border <= 0 || lh - 2 * lv.border <= 0) continue;              // "if border is too big we shouldn't search any keypoints"
+        if (ordered || lv.border + 1 >= lh || lw - 2 * lv.border <= 0 || lh - 2 * lv.border <= 0) continue;   // "if border is too big we shouldn't search any keypoints"
         // every level appends to one list (the record carries its level); cand_n[0] counts them all
-        hipLaunchKernelGGL(k_ak_candidates, grid(lw - 2 * lv.border, lh - 2 * lv.border), blk, 0, st, s->Ldet[i], lw, lh, lv.border, 0.001f, i, s->cand, s->cand_n, kAkCandCap);
+        hipLaunchKernelGGL(k_ak_candidates, grid(lw - 2 * lv.border, lh - 2 * lv.border), blk, 0, st, s->Ldet[i], lw, lh, lv.border, 0.001f, i, s->cand, s->cand_n, s->cand_cap);
+    }
+    if (ordered) {
+        AkCandPlan P;
+        memset(&P, 0, sizeof(P));
+        for (int i = 0; i < s->n; i++) { P.ldet[i] = s->Ldet[i]; P.w[i] = s->lv[i].w; P.h[i] = s->lv[i].h; P.border[i] = s->lv[i].border; P.gx[i] = std::max(1, (s->lv[i].w - 2 * s->lv[i].border + 255) / 256); }
+        for (int i = 0; i <= s->n; i++) P.blk_base[i] = s->blk_base[i];
+        P.n = s->n; P.thr = 0.001f;
+        const int nblk = s->blk_base[s->n];
+        if (nblk > 0) hipLaunchKernelGGL(k_ak_cand_count, dim3(nblk), blk, 0, st, P, s->d_blk);
+        hipLaunchKernelGGL(k_ak_cand_scan, dim3(1), dim3(1024), 0, st, P, s->d_blk, nblk, s->cand_cap, s->d_sup);
+        if (nblk > 0) hipLaunchKernelGGL(k_ak_cand_emit, dim3(nblk), blk, 0, st, P, s->d_blk, s->cand, s->d_pos, s->d_val, s->cand_cap);
     }
     return UVO_OK;
 }
@@ -609,31 +783,65 @@ static bool akaze_use_graph()
     return on;
 }
 // the chain captured on stream st (thread-local capture mode) and instantiated, once per workspace
-static uvo_status akaze_capture(Ctx* c, AkazeWs* s, hipStream_t st)
+static uvo_status akaze_capture(Ctx* c, AkazeWs* s, hipStream_t st, int ordered)
 {
-    if (s->exec) return UVO_OK;
+    if (s->exec[ordered]) return UVO_OK;
     UVO_HIP_TRY(c, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-    const uvo_status rs = akaze_record(c, s, st);
+    const uvo_status rs = akaze_record(c, s, st, ordered != 0);
     hipGraph_t g = nullptr;
     const hipError_t ee = hipStreamEndCapture(st, &g);
     if (rs != UVO_OK || ee != hipSuccess || !g) { if (g) (void)hipGraphDestroy(g); if (rs == UVO_OK) c->err = std::string("AKAZE: graph capture: ") + hipGetErrorString(ee); return rs != UVO_OK ? rs : UVO_HIP_ERROR; }
-    s->graph = g;
-    UVO_HIP_TRY(c, hipGraphInstantiate(&s->exec, s->graph, nullptr, nullptr, 0));
+    s->graph[ordered] = g;
+    UVO_HIP_TRY(c, hipGraphInstantiate(&s->exec[ordered], s->graph[ordered], nullptr, nullptr, 0));
     return UVO_OK;
 }
 
-// detectAndCompute on `gray` (device or host): the keypoints and their M-LDB rows are left in s->d_kps / s->d_desc, *n_out = the count.  When
-// the count exceeds the workspace's capacity, `grow` reallocates the two output buffers to hold it (the single-image operator: AKAZE has no
-// upper bound on its count -- 17 850 on a 1080p frame); without it nothing past the host stages is computed and the call still returns
-// UVO_OK (the fused steps, whose lane buffers max_kpts sizes)
-static uvo_status akaze_run(Ctx* c, AkazeWs* s, hipStream_t st, const uint8_t* gray, int w, int h, int stride, int mem, bool grow, int* n_out)
+// the three scans and the refinement on the ordered list in s->cand / d_pos / d_val with d_sup[SUP_N, SUP_START ..] (left by the ordered
+// emission, or uploaded by the test hook): keypoints to dst[0, cap), their count to d_sup[SUP_NK + nk_slot].  Five launches, no wait.
+static uvo_status akaze_suppress_launch(Ctx* c, AkazeWs* s, hipStream_t st, uvo_keypoint* dst, int cap, int nk_slot, bool scans = true)
+{
+    if (scans) {
+        UVO_HIP_TRY(c, hipMemsetAsync(s->d_sup + SUP_ROUNDS, 0, sizeof(int) * 3, st));
+        for (int ph = 0; ph < 3; ph++) hipLaunchKernelGGL(k_ak_scan, dim3(s->n), dim3(1024), 0, st, ph, s->L, s->d_pos, s->d_val, s->d_mark, s->d_state, s->d_sup);
+    }
+    hipLaunchKernelGGL(k_ak_refine, dim3(1), dim3(1024), 0, st, s->L, s->cand, s->d_mark + (size_t)2 * kAkCandCap, s->d_sup, dst, cap, nk_slot, s->cand_cap);
+    UVO_HIP_TRY(c, hipGetLastError());
+    return UVO_OK;
+}
+// the definition on a candidate list in any order: the host scans of uvo_akaze_suppress.h; marks (n x 3, or null): each candidate's mark after each phase
+static void akaze_suppress_host(AkazeWs* s, const AkCand* list, int n_cand, uint8_t* marks)
+{
+    aks_host_order(&s->hs, list, n_cand);
+    aks_host_within(&s->hs);
+    if (marks) aks_host_marks(&s->hs, list, n_cand, marks, 3);
+    aks_host_sweep_lower(&s->hs);
+    if (marks) aks_host_marks(&s->hs, list, n_cand, marks + 1, 3);
+    aks_host_sweep_upper(&s->hs);
+    if (marks) aks_host_marks(&s->hs, list, n_cand, marks + 2, 3);
+    aks_host_refine(&s->hs, &s->out);
+}
+
+// where a lane's detection leaves its results under suppression setting 1: the lane's keypoints and 64-byte rows, written straight from the kernels
+struct AkLaneOut { uvo_keypoint* kps; uint8_t* rows; int cap, slot; };
+// detectAndCompute on `gray` (device or host), *n_out = the count.
+//   where = 0 (the host scans): the keypoints and their M-LDB rows are left in s->d_kps / s->d_desc.  When the count exceeds the workspace's
+//     capacity, `grow` reallocates the two output buffers to hold it (the single-image operator: AKAZE has no upper bound on its count --
+//     17 850 on a 1080p frame); without it nothing past the host stages is computed and the call still returns UVO_OK (the fused steps,
+//     whose lane buffers max_kpts sizes).  Three waits.
+//   where = 1 (the device form), lane = null: the same outputs and contract, ONE wait (the count, which sizes the output buffers).
+//   where = 1, lane given: everything is queued and nothing waited for; the keypoints and padded rows go to the lane's buffers, the count stays in
+//     d_sup[SUP_NK + lane->slot] (possibly past lane->cap) and a candidate overflow raises d_sup[SUP_OVF + lane->slot]: nothing is written
+//     past either list, and the step's count readback reports UVO_CAPACITY for either, each by its name; *n_out = -1.
+static uvo_status akaze_run(Ctx* c, AkazeWs* s, hipStream_t st, const uint8_t* gray, int w, int h, int stride, int mem, bool grow, int where, const AkLaneOut* lane, int* n_out)
 {
     *n_out = 0;
     const dim3 blk(256);
     auto grid = [](int ww, int hh) { return dim3((ww + 255) / 256, hh); };
     static const bool dbg = getenv("UVO_DBG_PHASE") != nullptr;                                            // host wall clock of the call's phases
-    double tph[8] = {0}; int nph = 0;
-    auto stamp = [&]() { if (dbg && nph < 8) tph[nph++] = uvo::now_us(); };
+    double tph[8] = {0}; int nph = 0, waits = 0;
+    auto stamp = [&]() { if (dbg && nph < 8) tph[nph++] = uvo::now_us(); };     // (at the call's own waits only: the device form has one, for the count, and none inside a fused step)
+    auto wait = [&]() { waits++; return hipStreamSynchronize(st); };
+    if (where == 1 && (w > 65535 || h > 65535)) { c->err = "AKAZE: the device suppression packs positions into 16 bits a side"; return UVO_INVALID_ARG; }
     stamp();
     // ---- Create_Nonlinear_Scale_Space ----
     const uint8_t* d_img8 = gray;
@@ -646,12 +854,12 @@ static uvo_status akaze_run(Ctx* c, AkazeWs* s, hipStream_t st, const uint8_t* g
     AkKernel k9, k5;
     { int ks = cv_ceil_d((double)(2.0f * (1.0f + (1.6f - 0.8f) / (0.3f)))); ks |= 1; gauss_kernel(ks, (double)1.6f, &k9); }
     gauss_kernel(5, (double)1.0f, &k5);
-    // last frame's keypoint marks (the masks are whole planes: clearing the few thousand marked entries, not 11 MB of planes per frame)
-    for (int i = 0; i < s->n; i++) { for (const AkCand& cd : s->cands[i]) s->mask[i][(size_t)cd.y * s->lv[i].w + cd.x] = 0; s->cands[i].clear(); }
+    aks_host_clear(&s->hs);
     hipLaunchKernelGGL(k_ak_blur_rows, grid(w, h), blk, 0, st, s->img, w, h, k9, s->s[0]);
     hipLaunchKernelGGL(k_ak_blur_cols, grid(w, h), blk, 0, st, s->s[0], w, h, k9, s->Lsmooth[0]);
     UVO_HIP_TRY(c, hipMemcpyAsync(s->Lt[0], s->Lsmooth[0], sizeof(float) * (size_t)w * h, hipMemcpyDeviceToDevice, st));
     float kcontrast = 0.f;
+    bool kc_on_device = false;
     if (s->n > 1) {                                                  // compute_kcontrast on the image blurred with sigma 1
         hipLaunchKernelGGL(k_ak_blur_rows, grid(w, h), blk, 0, st, s->img, w, h, k5, s->s[0]);
         hipLaunchKernelGGL(k_ak_blur_cols, grid(w, h), blk, 0, st, s->s[0], w, h, k5, s->s[1]);
@@ -663,141 +871,112 @@ static uvo_status akaze_run(Ctx* c, AkazeWs* s, hipStream_t st, const uint8_t* g
             hipLaunchKernelGGL(k_ak_gradmax, dim3((w - 2 + 255) / 256, (h - 2 + 15) / 16), blk, 0, st, s->s[2], s->s[3], w, h, s->hist);
             hipLaunchKernelGGL(k_ak_gradhist, dim3((w - 2 + 1023) / 1024, h - 2), blk, 0, st, s->s[2], s->s[3], w, h, nbins, s->hist);
         }
-        UVO_HIP_TRY(c, hipMemcpyAsync(s->h_hist, s->hist, sizeof(int) * 512, hipMemcpyDeviceToHost, st));
-        UVO_HIP_TRY(c, hipStreamSynchronize(st));
-        float hmax; memcpy(&hmax, &s->h_hist[0], 4);
-        const int* hist = s->h_hist + 1;
         const int total = (w - 2) * (h - 2);
-        kcontrast = 0.03f;
-        if (total > 0 && hmax != 0.0f) {
-            const int nthreshold = (int)((total - hist[0]) * 0.7f);
-            int nelements = 0;
-            for (int k = 1; k < nbins; k++) {
-                if (nelements >= nthreshold) { kcontrast = (float)hmax * k / nbins; break; }
-                nelements = nelements + hist[k];
-            }
+        if (where == 1) { hipLaunchKernelGGL(k_ak_kcontrast, dim3(1), dim3(64), 0, st, s->hist, total, nbins, s->d_kc); kc_on_device = true; }
+        else {
+            UVO_HIP_TRY(c, hipMemcpyAsync(s->h_hist, s->hist, sizeof(int) * 512, hipMemcpyDeviceToHost, st));
+            UVO_HIP_TRY(c, wait());
+            float hmax; memcpy(&hmax, &s->h_hist[0], 4);
+            kcontrast = aks_kcontrast(hmax, s->h_hist + 1, total, nbins);
         }
     }
     stamp();
-    *s->h_kc = kcontrast;
-    UVO_HIP_TRY(c, hipMemcpyAsync(s->d_kc, s->h_kc, sizeof(float), hipMemcpyHostToDevice, st));
+    if (!kc_on_device) {
+        *s->h_kc = kcontrast;
+        UVO_HIP_TRY(c, hipMemcpyAsync(s->d_kc, s->h_kc, sizeof(float), hipMemcpyHostToDevice, st));
+    }
     // ---- the evolution (levels 1 ..), Compute_Determinant_Hessian_Response and the candidates of every level: ~600 small launches (166 FED
     // steps, 80 derivative passes at 1080p) whose arguments depend on the image SIZE only -- captured once per workspace as a HIP graph
     // and replayed with one call per frame.  Measured: the chain is bound by the DEVICE (600 kernels of 3-6 us back to back: 3.2 ms at
     // 1080p either way; whole call 1.46 ms as a graph against 1.56 ms launch by launch at 640 x 360, level at 1080p); what the graph
     // buys is the host thread, idle instead of issuing launches for 3 ms. ----
     if (akaze_use_graph()) {
-        UVO_TRY(akaze_capture(c, s, st));
-        UVO_HIP_TRY(c, hipGraphLaunch(s->exec, st));
-    } else UVO_TRY(akaze_record(c, s, st));
-    int n_cand = 0;
-    UVO_HIP_TRY(c, hipMemcpyAsync(s->h_hist, s->cand_n, sizeof(int), hipMemcpyDeviceToHost, st));
-    UVO_HIP_TRY(c, hipStreamSynchronize(st));
-    n_cand = s->h_hist[0];
-    if (n_cand > kAkCandCap) { c->err = "AKAZE: more local maxima than the candidate list holds"; return UVO_CAPACITY; }
-    if (n_cand) {
-        UVO_HIP_TRY(c, hipMemcpyAsync(s->h_cand, s->cand, sizeof(AkCand) * n_cand, hipMemcpyDeviceToHost, st));
-        UVO_HIP_TRY(c, hipStreamSynchronize(st));
-        // level by level, row-major inside a level -- the order the scans visit them: one sort of 64-bit keys (level, y, x, list position)
-        std::vector<uint64_t>& keys = s->keys;
-        keys.resize((size_t)n_cand);
-        for (int q = 0; q < n_cand; q++) { const AkCand& cd = s->h_cand[q]; keys[(size_t)q] = ((uint64_t)cd.pad << 58) | ((uint64_t)cd.y << 40) | ((uint64_t)cd.x << 22) | (uint64_t)q; }
-        std::sort(keys.begin(), keys.end());
-        for (int q = 0; q < n_cand; q++) { const AkCand& cd = s->h_cand[keys[(size_t)q] & 0x3fffffu]; s->cands[cd.pad].push_back(cd); }
+        UVO_TRY(akaze_capture(c, s, st, where));
+        UVO_HIP_TRY(c, hipGraphLaunch(s->exec[where], st));
+    } else UVO_TRY(akaze_record(c, s, st, where == 1));
+    AkPlanes pl;
+    memset(&pl, 0, sizeof(pl));
+    for (int i = 0; i < s->n; i++) { pl.Lt[i] = s->Lt[i]; pl.Lx[i] = s->Lx[i]; pl.Ly[i] = s->Ly[i]; pl.w[i] = s->lv[i].w; pl.h[i] = s->lv[i].h; pl.ratio[i] = s->lv[i].octave_ratio; }
+    s->stat_dev = where;
+    int n_cand = 0, n = 0;
+    if (where == 1 && lane) {
+        // ---- the fused steps: suppression, refinement, orientation and M-LDB by counts read on the device (grids from the lane's capacity) ----
+        const int* d_n = s->d_sup + SUP_NK + lane->slot;
+        UVO_TRY(akaze_suppress_launch(c, s, st, lane->kps, lane->cap, lane->slot));
+        hipLaunchKernelGGL(k_ak_orientation, dim3((lane->cap + 3) / 4), dim3(256), 0, st, pl, lane->kps, lane->cap, d_n);
+        hipLaunchKernelGGL(k_ak_mldb, dim3((lane->cap + 7) / 8), dim3(256), 0, st, pl, lane->kps, lane->cap, d_n, lane->rows, 4 * kBinRowWords);
+        UVO_HIP_TRY(c, hipGetLastError());
+        s->stat_waits = waits;
+        *n_out = -1;
+        return UVO_OK;
     }
-    UVO_HIP_TRY(c, hipGetLastError());
-    stamp();
-    // ---- FindKeypointsSameScale's sequential half, Find_Scale_Space_Extrema's two sweeps (host, candidate lists) ----
-    for (int i = 0; i < s->n; i++) {
-        const AkLevel& lv = s->lv[i];
-        for (const AkCand& cd : s->cands[i]) {
-            const float value = cd.v[4];
-            s->val[i][(size_t)cd.y * lv.w + cd.x] = value;
-            int idx = 0;
-            if (find_neighbor_point(cd.x, cd.y, s->mask[i], lv.w, lv.h, lv.sigma_size, &idx)) {
-                if (value > s->val[i][idx]) s->mask[i][idx] = 0;
-                else continue;
-            }
-            s->mask[i][(size_t)cd.y * lv.w + cd.x] = 1;
+    if (where == 1) {
+        UVO_TRY(akaze_suppress_launch(c, s, st, s->d_kps, s->cap, 0));
+        UVO_HIP_TRY(c, hipMemcpyAsync(s->h_sup, s->d_sup, sizeof(int) * SUP_INTS, hipMemcpyDeviceToHost, st));
+        UVO_HIP_TRY(c, wait());
+        n_cand = s->h_sup[SUP_FOUND];
+        s->stat_ncand = n_cand; s->stat_waits = waits;
+        if (n_cand > s->cand_cap) { c->err = kAkazeCandOverflow; return UVO_CAPACITY; }
+        n = s->h_sup[SUP_NK];
+        stamp();
+    } else {
+        UVO_HIP_TRY(c, hipMemcpyAsync(s->h_hist, s->cand_n, sizeof(int), hipMemcpyDeviceToHost, st));
+        UVO_HIP_TRY(c, wait());
+        n_cand = s->h_hist[0];
+        s->stat_ncand = n_cand; s->stat_waits = waits; s->stat_rounds[0] = s->stat_rounds[1] = s->stat_rounds[2] = 0;
+        if (n_cand > s->cand_cap) { c->err = kAkazeCandOverflow; return UVO_CAPACITY; }
+        if (n_cand) {
+            UVO_HIP_TRY(c, hipMemcpyAsync(s->h_cand, s->cand, sizeof(AkCand) * n_cand, hipMemcpyDeviceToHost, st));
+            UVO_HIP_TRY(c, wait());
+            s->stat_waits = waits;
         }
+        UVO_HIP_TRY(c, hipGetLastError());
+        stamp();
+        // ---- FindKeypointsSameScale's sequential half, Find_Scale_Space_Extrema's two sweeps, Do_Subpixel_Refinement (host, candidate lists) ----
+        akaze_suppress_host(s, s->h_cand, n_cand, nullptr);
+        n = (int)s->out.size();
+        stamp();
     }
-    for (int i = 1; i < s->n; i++) {
-        const AkLevel& lv = s->lv[i]; const AkLevel& lp = s->lv[i - 1];
-        const int diff_ratio = (int)lv.octave_ratio / (int)lp.octave_ratio, search_radius = lv.sigma_size * diff_ratio;
-        for (const AkCand& cd : s->cands[i]) {
-            const size_t j = (size_t)cd.y * lv.w + cd.x;
-            if (s->mask[i][j] == 0) continue;
-            int idx = 0;
-            if (find_neighbor_point(cd.x * diff_ratio, cd.y * diff_ratio, s->mask[i - 1], lp.w, lp.h, search_radius, &idx))
-                if (s->val[i][j] > s->val[i - 1][idx]) s->mask[i - 1][idx] = 0;
-        }
-    }
-    for (int i = s->n - 2; i >= 0; i--) {
-        const AkLevel& lv = s->lv[i]; const AkLevel& ln = s->lv[i + 1];
-        const int diff_ratio = (int)ln.octave_ratio / (int)lv.octave_ratio, search_radius = ln.sigma_size;
-        for (const AkCand& cd : s->cands[i]) {
-            const size_t j = (size_t)cd.y * lv.w + cd.x;
-            if (s->mask[i][j] == 0) continue;
-            int idx = 0;
-            if (find_neighbor_point(cd.x / diff_ratio, cd.y / diff_ratio, s->mask[i + 1], ln.w, ln.h, search_radius, &idx))
-                if (s->val[i][j] > s->val[i + 1][idx]) s->mask[i + 1][idx] = 0;
-        }
-    }
-    // ---- Do_Subpixel_Refinement (host: a 2 x 2 solve per keypoint on the neighbourhood the candidate record carries) ----
-    std::vector<uvo_keypoint>& out = s->out;
-    out.clear();
-    for (int i = 0; i < s->n; i++) {
-        const AkLevel& e = s->lv[i];
-        const float ratio = e.octave_ratio;
-        for (const AkCand& cd : s->cands[i]) {
-            if (s->mask[i][(size_t)cd.y * e.w + cd.x] == 0) continue;
-            uvo_keypoint k;
-            k.x = cd.x * e.octave_ratio; k.y = cd.y * e.octave_ratio;
-            k.size = e.esigma * 1.5f;
-            k.angle = -1; k.response = cd.v[4]; k.octave = e.octave; k.class_id = i;
-            const float* v = cd.v;                                   // v[3 * (dy + 1) + (dx + 1)]
-            const float Dx = 0.5f * (v[5] - v[3]);
-            const float Dy = 0.5f * (v[7] - v[1]);
-            const float Dxx = v[5] + v[3] - 2.0f * v[4];
-            const float Dyy = v[7] + v[1] - 2.0f * v[4];
-            const float Dxy = 0.25f * (v[8] + v[0] - v[2] - v[6]);
-            // solve(Matx22f, Vec2f, DECOMP_LU): lapack.cpp's 2 x 2 CV_32F branch -- determinant and numerators in double, the result
-            // cast to float; a zero determinant leaves dst = 0
-            float dx = 0.0f, dy = 0.0f;
-            double det = (double)Dxx * Dyy - (double)Dxy * Dxy;
-            if (det != 0) { det = 1. / det; dx = (float)(((double)(-Dx) * Dyy - (double)(-Dy) * Dxy) * det); dy = (float)(((double)(-Dy) * Dxx - (double)(-Dx) * Dxy) * det); }
-            if (fabsf(dx) > 1.0f || fabsf(dy) > 1.0f) continue;
-            k.x += dx * ratio + .5f * (ratio - 1.f);
-            k.y += dy * ratio + .5f * (ratio - 1.f);
-            k.angle = 0.0f;
-            k.size *= 2.0f;
-            out.push_back(k);
-        }
-    }
-    const int n = (int)out.size();
     *n_out = n;
-    stamp();
     if (n == 0 || (n > s->cap && !grow)) return UVO_OK;
-    if (n > s->cap) {                                                // (the stream is idle here: synchronised after the candidate copy; the
+    if (n > s->cap) {                                                // (the stream is idle here: synchronised after the count's copy; the
         (void)hipFree(s->d_kps); (void)hipFree(s->d_desc);          // outputs are not part of the captured graph)
         s->d_kps = nullptr; s->d_desc = nullptr; s->cap = 0;
         const int ncap = (n + 4095) & ~4095;
         if (hipMalloc(reinterpret_cast<void**>(&s->d_kps), sizeof(uvo_keypoint) * (size_t)ncap) != hipSuccess ||
             hipMalloc(reinterpret_cast<void**>(&s->d_desc), (size_t)kAkDescBytes * ncap) != hipSuccess) { c->err = "AKAZE: growing the output buffers failed"; return UVO_HIP_ERROR; }
         s->cap = ncap;
+        if (where == 1) UVO_TRY(akaze_suppress_launch(c, s, st, s->d_kps, s->cap, 0, false));         // (the marks are still there: the refinement again, into the buffer that holds them all)
     }
     // ---- Compute_Keypoints_Orientation, MLDB descriptors ----
-    AkPlanes pl;
-    memset(&pl, 0, sizeof(pl));
-    for (int i = 0; i < s->n; i++) { pl.Lt[i] = s->Lt[i]; pl.Lx[i] = s->Lx[i]; pl.Ly[i] = s->Ly[i]; pl.w[i] = s->lv[i].w; pl.h[i] = s->lv[i].h; pl.ratio[i] = s->lv[i].octave_ratio; }
-    UVO_HIP_TRY(c, hipMemcpyAsync(s->d_kps, out.data(), sizeof(uvo_keypoint) * n, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_ak_orientation, dim3((n + 3) / 4), dim3(256), 0, st, pl, s->d_kps, n);
-    hipLaunchKernelGGL(k_ak_mldb, dim3((n + 7) / 8), dim3(256), 0, st, pl, s->d_kps, n, s->d_desc);
+    if (where == 0) UVO_HIP_TRY(c, hipMemcpyAsync(s->d_kps, s->out.data(), sizeof(uvo_keypoint) * n, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_ak_orientation, dim3((n + 3) / 4), dim3(256), 0, st, pl, s->d_kps, n, (const int*)nullptr);
+    hipLaunchKernelGGL(k_ak_mldb, dim3((n + 7) / 8), dim3(256), 0, st, pl, s->d_kps, n, (const int*)nullptr, s->d_desc, kAkDescBytes);
     UVO_HIP_TRY(c, hipGetLastError());
     if (dbg) UVO_HIP_TRY(c, hipStreamSynchronize(st));
     stamp();
-    if (dbg && nph == 5) fprintf(stderr, "[uvo] akaze phases (ms): contrast %.3f | evolution + responses + candidates (%d) %.3f | host suppression + refinement %.3f | orientation + M-LDB (%d keypoints) %.3f\n",
-                                 (tph[1] - tph[0]) * 1e-3, n_cand, (tph[2] - tph[1]) * 1e-3, (tph[3] - tph[2]) * 1e-3, n, (tph[4] - tph[3]) * 1e-3);
+    if (dbg && where == 1 && nph == 4) fprintf(stderr, "[uvo] akaze phases (ms), device suppression: queueing up to the contrast factor %.3f | evolution + responses + ordered candidates (%d) + suppression + refinement, to the count's wait %.3f | orientation + M-LDB (%d keypoints) %.3f\n",
+                                               (tph[1] - tph[0]) * 1e-3, n_cand, (tph[2] - tph[1]) * 1e-3, n, (tph[3] - tph[2]) * 1e-3);
+    if (dbg && where == 0 && nph == 5) fprintf(stderr, "[uvo] akaze phases (ms): contrast %.3f | evolution + responses + candidates (%d) %.3f | %s suppression + refinement %.3f | orientation + M-LDB (%d keypoints) %.3f\n",
+                                 (tph[1] - tph[0]) * 1e-3, n_cand, (tph[2] - tph[1]) * 1e-3, "host", (tph[3] - tph[2]) * 1e-3, n, (tph[4] - tph[3]) * 1e-3);
+    return UVO_OK;
+}
+static int akaze_suppress_from_env()                                // UVO_AKAZE_SUPPRESS=host|device: the initial setting, for measurements (tools/probe/README.md)
+{
+    const char* e = getenv("UVO_AKAZE_SUPPRESS");
+    if (e && strcmp(e, "host") == 0) return 0;
+    if (e && strcmp(e, "device") == 0) return 1;
+    return kAkazeSuppressDefault;
+}
+static int akaze_where(Ctx* c)                                      // the context's setting (-1: not set yet)
+{
+    if (c->akaze_suppress < 0) c->akaze_suppress = akaze_suppress_from_env();
+    return c->akaze_suppress;
+}
+uvo_status akaze_set_suppression(Ctx* c, int where)
+{
+    if (where != 0 && where != 1) { c->err = "uvo_akaze_set_suppression: 0 (the host scans of the candidate list) or 1 (the device form: k_ak_scan, k_ak_refine)"; return UVO_INVALID_ARG; }
+    c->akaze_suppress = where;
     return UVO_OK;
 }
 uvo_status akaze_detect(Ctx* c, const uint8_t* gray, int w, int h, int stride, int mem, uvo_keypoint* kps, uint8_t* desc, int cap, int* n_out)
@@ -807,7 +986,7 @@ uvo_status akaze_detect(Ctx* c, const uint8_t* gray, int w, int h, int stride, i
     AkazeWs* s = akaze_ws(c, w, h);
     if (!s) { c->err = "AKAZE workspace allocation failed"; return UVO_HIP_ERROR; }
     hipStream_t st = c->stream;
-    UVO_TRY(akaze_run(c, s, st, gray, w, h, stride, mem, true, n_out));
+    UVO_TRY(akaze_run(c, s, st, gray, w, h, stride, mem, true, akaze_where(c), nullptr, n_out));
     const int n = *n_out;
     if ((kps || desc) && n > cap) { c->err = "uvo_akaze_detect: output capacity too small"; return UVO_CAPACITY; }
     if (n == 0) return UVO_OK;
@@ -818,26 +997,117 @@ uvo_status akaze_detect(Ctx* c, const uint8_t* gray, int w, int h, int stride, i
 }
 
 // ---- detect_features' AKAZE branch inside the fused steps.  The lane's workspace is made (and its evolution graph captured on the
-// lane's stream) when a sequence starts, not in it; both images of a pair go through it in turn -- the host stages between the launches
-// (contrast factor, duplicate suppression, refinement) wait for the device, so nothing is gained by a second one.
+// lane's stream) when a sequence starts, not in it; both images of a pair go through it in turn.  Under suppression setting 0 the host
+// stages between the launches (contrast factor, duplicate suppression, refinement) wait for the device; under setting 1 the whole
+// detection is queued and the count stays on the device (*d_n), as the SURF branch's does.
 uvo_status akaze_prepare_lane(Ctx* c, int w, int h)
 {
     AkazeWs* s = akaze_ws(c, w, h);
     if (!s) { c->err = "AKAZE workspace allocation failed"; return UVO_HIP_ERROR; }
-    if (akaze_use_graph()) UVO_TRY(akaze_capture(c, s, c->stream));
+    if (akaze_use_graph()) UVO_TRY(akaze_capture(c, s, c->stream, akaze_where(c->sh->lanes[0])));
     return UVO_OK;
 }
-uvo_status akaze_detect_lane(Ctx* c, int slot, int* n)
+uvo_status akaze_detect_lane(Ctx* c, int slot, int* n, const int** d_n, const int** d_ovf)
 {
     const int w = c->img_w, h = c->img_h;
-    *n = 0;
+    *n = 0; *d_n = nullptr; *d_ovf = nullptr;
     if (w < 16 || h < 16) { c->err = "AKAZE: image too small"; return UVO_INVALID_ARG; }
     UVO_TRY(akaze_prepare_lane(c, w, h));                                    // (a no-op once the lane is primed)
     AkazeWs* s = static_cast<AkazeWs*>(c->akaze_ws);
-    UVO_TRY(akaze_run(c, s, c->stream, c->img[slot], w, h, w, UVO_MEM_DEVICE, false, n));
+    const int where = akaze_where(c->sh->lanes[0]);                          // the master context's value serves every lane
+    if (where == 1) {
+        const AkLaneOut lo = { c->det[slot].kps, reinterpret_cast<uint8_t*>(c->det[slot].desc), c->cap, slot };
+        UVO_TRY(akaze_run(c, s, c->stream, c->img[slot], w, h, w, UVO_MEM_DEVICE, false, 1, &lo, n));
+        *d_n = s->d_sup + SUP_NK + slot; *d_ovf = s->d_sup + SUP_OVF + slot;
+        return UVO_OK;
+    }
+    UVO_TRY(akaze_run(c, s, c->stream, c->img[slot], w, h, w, UVO_MEM_DEVICE, false, 0, nullptr, n));
     if (*n > c->cap || *n == 0) return UVO_OK;
     UVO_HIP_TRY(c, hipMemcpyAsync(c->det[slot].kps, s->d_kps, sizeof(uvo_keypoint) * (size_t)*n, hipMemcpyDeviceToDevice, c->stream));
     return pad_binary_rows(c, c->stream, s->d_desc, *n, kAkDescBytes, reinterpret_cast<uint8_t*>(c->det[slot].desc));
+}
+// uvo_akaze_suppress: the scans and the refinement of uvo_akaze_detect on the caller's candidate list (any order), for the plan of a w x h image
+uvo_status akaze_suppress(Ctx* c, int w, int h, const int* level, const int* x, const int* y, const float* v9, int n, int where, uint8_t* marks, uvo_keypoint* kps, int cap, int* n_kps)
+{
+    *n_kps = 0;
+    if (where != 0 && where != 1) { c->err = "uvo_akaze_suppress: where = 0 (host) or 1 (device)"; return UVO_INVALID_ARG; }
+    if (w < 16 || h < 16 || w > c->max_w || h > c->max_h || w > 65535 || h > 65535) { c->err = "uvo_akaze_suppress: image size outside the context's limits"; return UVO_INVALID_ARG; }
+    if (n < 0) { c->err = "uvo_akaze_suppress: a negative candidate count"; return UVO_INVALID_ARG; }
+    if (n > kAkCandCap) { c->err = "uvo_akaze_suppress: more candidates than the candidate list holds (262144)"; return UVO_INVALID_ARG; }
+    if (n > 0 && (!level || !x || !y || !v9)) { c->err = "uvo_akaze_suppress: level, x, y and v9 are required"; return UVO_INVALID_ARG; }
+    AkazeWs* s = akaze_ws(c, w, h);
+    if (!s) { c->err = "AKAZE workspace allocation failed"; return UVO_HIP_ERROR; }
+    std::vector<AkCand> list((size_t)n);
+    for (int q = 0; q < n; q++) {
+        if (level[q] < 0 || level[q] >= s->n) { c->err = "uvo_akaze_suppress: a candidate's level is outside the image's plan"; return UVO_INVALID_ARG; }
+        if (x[q] < 0 || y[q] < 0 || x[q] >= s->lv[level[q]].w || y[q] >= s->lv[level[q]].h) { c->err = "uvo_akaze_suppress: a candidate's position is outside its level"; return UVO_INVALID_ARG; }
+        AkCand& cd = list[(size_t)q];
+        cd.x = x[q]; cd.y = y[q]; cd.pad = level[q];
+        memcpy(cd.v, v9 + (size_t)9 * q, sizeof(float) * 9);
+    }
+    std::vector<uint64_t> keys((size_t)n);                                   // (level, y, x, list position): the visiting order, and duplicates side by side
+    for (int q = 0; q < n; q++) keys[(size_t)q] = ((uint64_t)level[q] << 58) | ((uint64_t)y[q] << 40) | ((uint64_t)x[q] << 22) | (uint64_t)q;
+    std::sort(keys.begin(), keys.end());
+    for (int q = 1; q < n; q++) if ((keys[(size_t)q] >> 22) == (keys[(size_t)q - 1] >> 22)) { c->err = "uvo_akaze_suppress: two candidates on one cell of one level"; return UVO_INVALID_ARG; }
+    hipStream_t st = c->stream;
+    s->stat_dev = where; s->stat_ncand = n; s->stat_waits = 0;
+    s->stat_rounds[0] = s->stat_rounds[1] = s->stat_rounds[2] = 0;
+    int nk = 0;
+    std::vector<uvo_keypoint> dev_out;
+    if (where == 0) {
+        aks_host_clear(&s->hs);
+        akaze_suppress_host(s, list.data(), n, marks);
+        nk = (int)s->out.size();
+    } else {
+        // the ordered list, as k_ak_cand_emit leaves it
+        std::vector<uint32_t> pos((size_t)n); std::vector<float> val((size_t)n);
+        int* hs = s->h_sup;
+        memset(hs, 0, sizeof(int) * SUP_INTS);
+        hs[SUP_FOUND] = hs[SUP_N] = n;
+        for (int l = 0; l <= kAkMaxLevels; l++) hs[SUP_START + l] = n;
+        for (int q = n - 1; q >= 0; q--) {
+            const AkCand& cd = list[keys[(size_t)q] & 0x3fffffu];
+            s->h_cand[q] = cd; pos[(size_t)q] = aks_pos(cd.x, cd.y); val[(size_t)q] = cd.v[4];
+            for (int l = cd.pad; l >= 0 && hs[SUP_START + l] > q; l--) hs[SUP_START + l] = q;
+        }
+        const int dcap = std::max(cap, 1);
+        uvo_keypoint* d_out = nullptr;
+        if (hipMalloc(reinterpret_cast<void**>(&d_out), sizeof(uvo_keypoint) * (size_t)dcap) != hipSuccess) { c->err = "uvo_akaze_suppress: allocation failed"; return UVO_HIP_ERROR; }
+        bool ok = hipMemcpyAsync(s->d_sup, hs, sizeof(int) * SUP_INTS, hipMemcpyHostToDevice, st) == hipSuccess;
+        if (n) ok = ok && hipMemcpyAsync(s->cand, s->h_cand, sizeof(AkCand) * n, hipMemcpyHostToDevice, st) == hipSuccess &&
+                    hipMemcpyAsync(s->d_pos, pos.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, st) == hipSuccess &&
+                    hipMemcpyAsync(s->d_val, val.data(), sizeof(float) * n, hipMemcpyHostToDevice, st) == hipSuccess;
+        ok = ok && hipStreamSynchronize(st) == hipSuccess;                    // (pos and val are pageable and local)
+        const uvo_status rc = ok ? akaze_suppress_launch(c, s, st, d_out, cap, 0) : UVO_HIP_ERROR;
+        std::vector<uint8_t> dm((size_t)3 * std::max(n, 1));
+        ok = ok && rc == UVO_OK && hipMemcpyAsync(hs, s->d_sup, sizeof(int) * SUP_INTS, hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
+        for (int ph = 0; ph < 3 && ok && n; ph++) ok = hipMemcpy(dm.data() + (size_t)ph * n, s->d_mark + (size_t)ph * kAkCandCap, (size_t)n, hipMemcpyDeviceToHost) == hipSuccess;
+        nk = ok ? hs[SUP_NK] : 0;
+        if (ok && nk > 0 && nk <= cap) { dev_out.resize((size_t)nk); ok = hipMemcpy(dev_out.data(), d_out, sizeof(uvo_keypoint) * (size_t)nk, hipMemcpyDeviceToHost) == hipSuccess; }
+        (void)hipFree(d_out);
+        if (!ok) { if (rc == UVO_OK) c->err = "uvo_akaze_suppress: a HIP call failed"; return rc != UVO_OK ? rc : UVO_HIP_ERROR; }
+        if (marks) for (int q = 0; q < n; q++) for (int ph = 0; ph < 3; ph++) marks[(size_t)3 * (keys[(size_t)q] & 0x3fffffu) + ph] = dm[(size_t)ph * n + q];
+    }
+    *n_kps = nk;
+    if (nk > cap) { c->err = "uvo_akaze_suppress: more keypoints than the output holds"; return UVO_CAPACITY; }
+    if (nk) memcpy(kps, where == 0 ? s->out.data() : dev_out.data(), sizeof(uvo_keypoint) * (size_t)nk);
+    return UVO_OK;
+}
+// uvo_akaze_stats: the last detection (or hook call) of this context's workspace
+uvo_status akaze_stats(Ctx* c, int* n_candidates, int* rounds, int* host_waits)
+{
+    AkazeWs* s = static_cast<AkazeWs*>(c->akaze_ws);
+    if (!s) { c->err = "uvo_akaze_stats: no AKAZE detection has run on this context"; return UVO_INVALID_ARG; }
+    if (s->stat_dev) {
+        UVO_HIP_TRY(c, hipStreamSynchronize(c->stream));
+        UVO_HIP_TRY(c, hipMemcpy(s->h_sup, s->d_sup, sizeof(int) * SUP_INTS, hipMemcpyDeviceToHost));
+        s->stat_ncand = s->h_sup[SUP_FOUND];
+        for (int p = 0; p < 3; p++) s->stat_rounds[p] = s->h_sup[SUP_ROUNDS + p];
+    }
+    if (n_candidates) *n_candidates = s->stat_ncand;
+    if (rounds) for (int p = 0; p < 3; p++) rounds[p] = s->stat_rounds[p];
+    if (host_waits) *host_waits = s->stat_waits;
+    return UVO_OK;
 }
 // intermediates for the parity tests: what = 0 Lt, 1 Lsmooth, 2 Lx, 3 Ly, 4 Ldet of `level` after the last akaze_detect
 uvo_status akaze_plane(Ctx* c, int level, int what, float* out, int cap_floats, int* ow, int* oh)

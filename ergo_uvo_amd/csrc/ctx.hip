@@ -660,13 +660,16 @@ static uvo_status check_cand_overflow(uvo_ctx* c, int nimg)
     if (c->h_counts[CN_ORI_DROP] != 0)
         return fail(c, UVO_INVALID_ARG, "SURF orientation: a keypoint had no gradient sample inside the image; OpenCV drops such keypoints, which this build does not do");
     for (int i = 0; i < nimg; i++)
+        if (c->h_counts[CN_CAND0 + i] == kCandListOverflow && c->loop_detector() == 2) return fail(c, UVO_CAPACITY, kAkazeCandOverflow);
+    for (int i = 0; i < nimg; i++)
         if (c->h_counts[CN_CAND0 + i] > c->cap)
             return fail(c, UVO_CAPACITY, "SURF found more keypoints than the context's max_kpts; results would be order-dependent");
     return UVO_OK;
 }
 
 // detect_features' AKAZE / ORB branch (VOU:93-105) inside the fused steps: each image through the lane's detector in turn (their host stages
-// -- AKAZE's contrast factor and duplicate suppression, ORB's retainBest rankings -- run on this thread and wait for the device), then the
+// -- AKAZE's contrast factor and duplicate suppression under uvo_akaze_set_suppression 0, ORB's retainBest rankings under
+// uvo_orb_set_ranking 0 -- run on this thread and wait for the device; AKAZE under setting 1 queues everything and hands back device counts), then the
 // counts are published where the SURF detector leaves its own: min(n, max_kpts) in d_counts[CN_NL + i], n in d_counts[CN_CAND0 + i] (more
 // than max_kpts is reported by the caller's overflow check; no list is cut), and the VO:556 gate evaluated on the device
 __global__ void k_binary_publish(int n0, int n1, int* cn, int cap, int nimg, int gate_min_features)
@@ -681,11 +684,28 @@ __global__ void k_binary_publish(int n0, int n1, int* cn, int cap, int nimg, int
     if (gate_min_features >= 0 && nimg == 2)                           // VO:556: both images need >= MIN_NUM_FEATURES keypoints, else no stereo matching
         cn[CN_NQA] = (cn[CN_NL] >= gate_min_features && cn[CN_NR] >= gate_min_features) ? cn[CN_NL] : 0;
 }
+// the same with the counts where AKAZE's device suppression leaves them (uvo_akaze_set_suppression 1): nothing of the detection came back to the host
+// (a candidate-list overflow -- d_ovf -- publishes no keypoints at all and leaves kCandListOverflow for the host's count check)
+__global__ void k_binary_publish_dev(const int* d_n0, const int* d_n1, const int* d_ovf0, const int* d_ovf1, int* cn, int cap, int nimg, int gate_min_features)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    for (int i = 0; i < nimg; i++) {
+        const bool ovf = (i ? *d_ovf1 : *d_ovf0) != 0;
+        const int n = ovf ? 0 : (i ? *d_n1 : *d_n0);
+        cn[CN_CAND0 + i] = ovf ? kCandListOverflow : n;
+        cn[CN_NL + i] = n < cap ? n : cap;
+    }
+    cn[CN_ORI_DROP] = 0;
+    if (gate_min_features >= 0 && nimg == 2)
+        cn[CN_NQA] = (cn[CN_NL] >= gate_min_features && cn[CN_NR] >= gate_min_features) ? cn[CN_NL] : 0;
+}
 static uvo_status binary_detect_lane(Ctx* c, int nimg, int gate_min_features)
 {
     int n[2] = {0, 0};
-    for (int i = 0; i < nimg; i++) UVO_TRY(c->loop_detector() == 2 ? akaze_detect_lane(c, i, &n[i]) : orb_detect_lane(c, i, &n[i]));
-    hipLaunchKernelGGL(k_binary_publish, dim3(1), dim3(64), 0, c->stream, n[0], n[1], c->d_counts, c->cap, nimg, gate_min_features);
+    const int* d_n[2] = {nullptr, nullptr}; const int* d_ovf[2] = {nullptr, nullptr};
+    for (int i = 0; i < nimg; i++) UVO_TRY(c->loop_detector() == 2 ? akaze_detect_lane(c, i, &n[i], &d_n[i], &d_ovf[i]) : orb_detect_lane(c, i, &n[i]));
+    if (d_n[0]) hipLaunchKernelGGL(k_binary_publish_dev, dim3(1), dim3(64), 0, c->stream, d_n[0], d_n[nimg - 1], d_ovf[0], d_ovf[nimg - 1], c->d_counts, c->cap, nimg, gate_min_features);
+    else hipLaunchKernelGGL(k_binary_publish, dim3(1), dim3(64), 0, c->stream, n[0], n[1], c->d_counts, c->cap, nimg, gate_min_features);
     UVO_HIP_TRY(c, hipGetLastError());
     return UVO_OK;
 }
@@ -839,6 +859,32 @@ try {
     (void)hipSetDevice(c->device);
     UVO_TRY(need_idle(c, "uvo_akaze_plane"));
     return akaze_plane(c, level, what, out, cap_floats, w, h);
+} UVO_ABI_CATCH(c)
+
+// where the AKAZE branch's sequential stages run (contrast factor, duplicate suppression, refinement): 0 the host scans, 1 the device form
+// (akaze.hip); the master context's value serves the lanes
+extern "C" uvo_status uvo_akaze_set_suppression(uvo_ctx* c, int where)
+try {
+    if (!c) return UVO_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    UVO_TRY(need_idle(c, "uvo_akaze_set_suppression"));
+    return akaze_set_suppression(c, where);
+} UVO_ABI_CATCH(c)
+extern "C" uvo_status uvo_akaze_suppress(uvo_ctx* c, int w, int h, const int* level, const int* x, const int* y, const float* v9, int n, int where, uint8_t* marks,
+                                         uvo_keypoint* kps, int cap, int* n_kps)
+try {
+    if (!c) return UVO_INVALID_ARG;
+    if (!n_kps || cap < 0 || (cap > 0 && !kps)) return fail(c, UVO_INVALID_ARG, "uvo_akaze_suppress: kps (cap > 0) and n_kps are required");
+    (void)hipSetDevice(c->device);
+    UVO_TRY(need_idle(c, "uvo_akaze_suppress"));
+    return akaze_suppress(c, w, h, level, x, y, v9, n, where, marks, kps, cap, n_kps);
+} UVO_ABI_CATCH(c)
+extern "C" uvo_status uvo_akaze_stats(uvo_ctx* c, int* n_candidates, int* rounds, int* host_waits)
+try {
+    if (!c) return UVO_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    UVO_TRY(need_idle(c, "uvo_akaze_stats"));
+    return akaze_stats(c, n_candidates, rounds, host_waits);
 } UVO_ABI_CATCH(c)
 
 // detect_features' ORB branch (VO_utility.cpp:100-105): ORB::create(10000, 1.2, 8, 31, 0, 2, HARRIS_SCORE, 31, 10)->detectAndCompute; 32-byte rBRIEF
@@ -2084,6 +2130,7 @@ static void run_mono_stage_b(uvo_ctx* L, bool stage_a_ok)
     auto hip_ok = [&](hipError_t e) { if (e != hipSuccess && j.st == UVO_OK) { j.st = UVO_HIP_ERROR; j.err = hipGetErrorString(e); } return e == hipSuccess; };
     const int* hc = L->h_countsA[0];
     const int cap = L->cap;
+    if (hc[CN_CAND0] == kCandListOverflow && L->loop_detector() == 2) { j.st = UVO_CAPACITY; j.err = kAkazeCandOverflow; return; }
     if (hc[CN_CAND0] > cap) { j.st = UVO_CAPACITY; j.err = "SURF found more keypoints than the context's max_kpts; results would be order-dependent"; return; }
     if (hc[CN_ORI_DROP] != 0) { j.st = UVO_INVALID_ARG; j.err = "SURF orientation: a keypoint had no gradient sample inside the image; OpenCV drops such keypoints, which this build does not do"; return; }
     const int n = hc[CN_NL], M = L->mono_matched ? hc[CN_M] : 0;

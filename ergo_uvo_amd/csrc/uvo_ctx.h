@@ -283,6 +283,7 @@ struct Ctx {
     void* codec_ws = nullptr;                    // CodecWs* (uvo_decode_image), allocated on first use
     void* orb_ws = nullptr;                      // OrbWs* (uvo_orb_detect): parameters, sampling table, buffers of the last image size
     void* akaze_ws = nullptr;                    // AkazeWs* (uvo_akaze_detect), allocated on first use per image size
+    int akaze_suppress = -1;                     // uvo_akaze_set_suppression: 0 the host scans, 1 the device form; -1 = not asked yet (akaze.hip: the default, or UVO_AKAZE_SUPPRESS)
     void* sift_ws[2] = {nullptr, nullptr};       // SiftWs* per image slot (uvo_sift_detect uses slot 0), allocated on first use
     // the last frame's intermediates for uvo_mono_get: keypoints (det[0].kps), matches (d_matches[0]) and, after the device-resident pose
     // chain, the good points (d_good_pts[0]) stay in the lane's device buffers -- counts here -- until someone asks
@@ -436,7 +437,14 @@ void akaze_ws_free(Ctx* c);
 uvo_status akaze_detect(Ctx* c, const uint8_t* gray, int w, int h, int stride, int mem, uvo_keypoint* kps, uint8_t* desc, int cap, int* n_out);
 uvo_status akaze_plane(Ctx* c, int level, int what, float* out, int cap_floats, int* ow, int* oh);
 uvo_status akaze_prepare_lane(Ctx* c, int w, int h);
-uvo_status akaze_detect_lane(Ctx* c, int slot, int* n);
+uvo_status akaze_detect_lane(Ctx* c, int slot, int* n, const int** d_n, const int** d_ovf);      // *d_n != null: the count and the candidate-overflow flag are on the device (suppression setting 1), *n = -1
+// k_binary_publish_dev leaves kCandListOverflow in d_counts[CN_CAND0 + i] (a word only the host reads on the binary branches) when image i had more
+// local maxima than AKAZE's candidate list holds; the count checks then report kAkazeCandOverflow, not the max_kpts message
+static const int kCandListOverflow = 0x7fffffff;
+static const char* const kAkazeCandOverflow = "AKAZE: more local maxima than the candidate list holds (a larger max_kpts does not help)";
+uvo_status akaze_set_suppression(Ctx* c, int where);
+uvo_status akaze_suppress(Ctx* c, int w, int h, const int* level, const int* x, const int* y, const float* v9, int n, int where, uint8_t* marks, uvo_keypoint* kps, int cap, int* n_kps);
+uvo_status akaze_stats(Ctx* c, int* n_candidates, int* rounds, int* host_waits);
 uvo_status sift_detect(Ctx* c, const uint8_t* gray, int w, int h, int stride, int mem, int nfeatures, int nL, double contrastThreshold,
                        double edgeThreshold, double sigma, uvo_keypoint* kps, float* desc, int cap, int* n_out);
 uvo_status sift_layer(Ctx* c, int octave, int layer, int dog, float* out, int cap_floats, int* ow, int* oh);

@@ -77,6 +77,8 @@ struct State {
     bool orb_pattern_sent = false;                // ... and handed to the current context
     int orb_ranking = -1;                         // set_orb_ranking: 0 host, 1 device; -1 = the library's default
     bool orb_ranking_sent = false;
+    int akaze_suppression = -1;                   // set_akaze_suppression: 0 host, 1 device; -1 = the library's default
+    bool akaze_suppression_sent = false;
 } g;
 
 [[noreturn]] void raise(uvo_status st, const char* where)
@@ -164,7 +166,7 @@ void shutdown()
 {
     std::lock_guard<std::mutex> lk(g.mu);
     if (g.ctx) { uvo_ctx_destroy(g.ctx); g.ctx = nullptr; }
-    g.orb_pattern_sent = false; g.orb_ranking_sent = false; g.pnp_method = 1;
+    g.orb_pattern_sent = false; g.orb_ranking_sent = false; g.akaze_suppression_sent = false; g.pnp_method = 1;
 }
 void set_orb_ranking(int where)
 {
@@ -172,6 +174,13 @@ void set_orb_ranking(int where)
     std::lock_guard<std::mutex> lk(g.mu);
     g.orb_ranking = where;
     g.orb_ranking_sent = false;
+}
+void set_akaze_suppression(int where)
+{
+    if (where != 0 && where != 1) throw Error(UVO_INVALID_ARG, "set_akaze_suppression: 0 (host) or 1 (device)");
+    std::lock_guard<std::mutex> lk(g.mu);
+    g.akaze_suppression = where;
+    g.akaze_suppression_sent = false;
 }
 void set_orb_pattern(const int* pattern1024)
 {
@@ -334,6 +343,11 @@ Mat get_image(const Mat& current_img, const Mat& cameraMatrix, const Mat& distor
 // The "ORB" branch (ORB::create(10000, 1.2, 8, 31, 0, 2, ORB::HARRIS_SCORE, 31, 10)->detectAndCompute, VOU:100-105: CV_8U rows of 32 bytes)
 // needs OpenCV's learned sampling table bit_pattern_31_, which cannot be restated: uvo_hip::set_orb_pattern(table) or a text file of its
 // 1024 integers named by UVO_ORB_PATTERN_FILE; without one the branch throws and says so.
+static void akaze_suppression_to(uvo_ctx* c)
+{
+    std::lock_guard<std::mutex> lk(g.mu);
+    if (g.akaze_suppression >= 0 && !g.akaze_suppression_sent) { SHIM_TRY(uvo_akaze_set_suppression(c, g.akaze_suppression), "uvo_akaze_set_suppression"); g.akaze_suppression_sent = true; }
+}
 static void orb_pattern_to(uvo_ctx* c)
 {
     std::lock_guard<std::mutex> lk(g.mu);
@@ -372,6 +386,7 @@ void detect_features(Mat img, vector<KeyPoint>& keypoints, Mat& descriptors)
         return;
     }
     if (akaze) {
+        akaze_suppression_to(c);
         // AKAZE has no cap on its count (17 850 keypoints on a 1080p frame): a frame with more than max_kpts is run again with room for all
         int cap = g.max_kpts;
         vector<uvo_keypoint> kps((size_t)cap);
@@ -691,6 +706,7 @@ void loop_set_detector()
 {
     uvo_ctx* c = ctx_now();
     if (FEATURE_DETECTOR == "ORB") orb_pattern_to(c);                         // the table first: the loop reads the context's
+    if (FEATURE_DETECTOR == "AKAZE") akaze_suppression_to(c);
     SHIM_TRY(uvo_ctx_set_loop_detector(c, FEATURE_DETECTOR.c_str()), "uvo_ctx_set_loop_detector");
 }
 void loop_set_depth(int depth) { SHIM_TRY(uvo_stereo_set_depth(ctx_now(), depth), "uvo_stereo_set_depth"); }

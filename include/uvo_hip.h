@@ -114,8 +114,10 @@ uvo_status uvo_ctx_set_feature_detector(uvo_ctx* c, const char* name);
  *            32-byte rows.  The stereo loop matches them by Hamming distance (VO_utility.cpp:520-524); the mono loop's 7-argument
  *            match_features builds BFMatcher(NORM_L2) whatever the detector (VO_utility.cpp:551-573): exact L2 of the bytes.
  *   "ORB" is accepted without a sampling table; the first step then fails with UVO_INVALID_ARG (the message names bit_pattern_31_).
- * AKAZE's host stages (the contrast factor and the sequential duplicate suppression) run on the thread that calls uvo_stereo_submit /
- * uvo_mono_submit: with several pairs in flight they serialise the submissions' detection.  ORB has no host stage with the rankings on
+ * AKAZE's sequential stages (the contrast factor, the duplicate suppression, the sub-pixel refinement) run where
+ * uvo_akaze_set_suppression puts them.  On the host (0) they run on the thread that calls uvo_stereo_submit /
+ * uvo_mono_submit, which waits three times per image: with several pairs in flight they serialise the submissions' detection.  On the
+ * device (1, the default) the whole detection is queued without a wait and its counts stay on the device, as the SURF branch's.  ORB has no host stage with the rankings on
  * the device (uvo_orb_set_ranking, the default): the submitting thread waits twice per image, for the FAST corners' level counts and for
  * the final counts; with the rankings on the host it replays retainBest there, and the submissions' detection serialises likewise.  Each
  * lane keeps its own detector workspace, made by the first (synchronous) pair of a sequence; uvo_stereo_get("desc_left" / "desc_right")
@@ -157,9 +159,29 @@ uvo_status uvo_sift_detect(uvo_ctx* c, const uint8_t* gray, int w, int h, int st
  * descriptors) -- DESCRIPTOR_MLDB at full length (486 bits: rows of 61 bytes, for uvo_match_knn2_ratio_hamming), 3 channels, threshold
  * 0.001, 4 octaves of 4 sublevels, DIFF_PM_G2.  Keypoints in OpenCV's order (evolution level by level, row-major), `size` the diameter,
  * `angle` in degrees, `class_id` the evolution level.  The non-linear scale space, the Hessian response, orientation and descriptors run
- * on the device; the sequential duplicate suppression of Find_Scale_Space_Extrema runs on the host over the candidate list.  The fused
- * steps take the same detector after uvo_ctx_set_loop_detector(c, "AKAZE"). */
+ * on the device; the contrast factor, the sequential duplicate suppression of Find_Scale_Space_Extrema and the sub-pixel refinement run
+ * over the candidate list on the host or on the device (uvo_akaze_set_suppression; this operator then waits once, for the count that
+ * sizes its buffers, instead of three times).  The fused steps take the same detector after uvo_ctx_set_loop_detector(c, "AKAZE"). */
 uvo_status uvo_akaze_detect(uvo_ctx* c, const uint8_t* gray, int w, int h, int stride, int mem, uvo_keypoint* kps, uint8_t* desc, int cap, int* n);
+/* Where AKAZE's sequential stages run: 0 = the host scans of the candidate list (the definition), 1 = the device (default): the contrast
+ * factor by one small kernel, the candidates emitted in visiting order, the three suppression phases as rounds of one workgroup per level,
+ * the refinement compacted in candidate order.  The results do not depend on the value.  Anything else is UVO_INVALID_ARG; refused while
+ * entries are in flight.  The fused steps take the master context's value, as for uvo_orb_set_ranking. */
+uvo_status uvo_akaze_set_suppression(uvo_ctx* c, int where);
+/* test hook: the scans and the refinement uvo_akaze_detect runs, on the caller's n candidates (ANY order) for the level plan of a w x h
+ * image: candidate q is the cell (x[q], y[q]) of evolution level level[q] with the 3 x 3 neighbourhood v9[9 q ..] of the response
+ * (row-major, v9[9 q + 4] the value).  marks (n x 3 bytes, or NULL): marks[3 q + p] = candidate q's mark after phase p + 1 (within the
+ * level; against the level below; against the level above), in the caller's order.  kps: what Do_Subpixel_Refinement leaves (angle 0,
+ * size doubled), in OpenCV's order.  where = 1 launches the kernels the detector launches; 0 runs the host scans.  Host buffers.
+ * UVO_INVALID_ARG: a level outside the plan, a position outside its level, two candidates on one cell of one level, n < 0, n above the
+ * candidate capacity (262144); UVO_CAPACITY: more than `cap` keypoints (*n_kps holds the count).  Idle contexts only. */
+uvo_status uvo_akaze_suppress(uvo_ctx* c, int w, int h, const int* level, const int* x, const int* y, const float* v9, int n, int where,
+                              uint8_t* marks /* n x 3, or NULL */, uvo_keypoint* kps, int cap, int* n_kps);
+/* Figures of the last AKAZE detection of the context's own lane (lane 0), or of its last uvo_akaze_suppress: the candidates found;
+ * rounds[3] = the largest round count of a scan, per phase (0 on the host); host_waits = the stream waits the detection made the calling
+ * thread perform (3 per image on the host, 1 for uvo_akaze_detect on the device, 0 for a fused step on the device).  Any pointer may be
+ * NULL.  Idle contexts only; UVO_INVALID_ARG before any AKAZE call. */
+uvo_status uvo_akaze_stats(uvo_ctx* c, int* n_candidates, int* rounds /* 3 */, int* host_waits);
 /* test hook: plane `what` (0 Lt, 1 Lsmooth, 2 Lx, 3 Ly -- the multiscale derivatives --, 4 Ldet) of evolution level `level` of the last
  * uvo_akaze_detect, row-major floats to a host buffer */
 uvo_status uvo_akaze_plane(uvo_ctx* c, int level, int what, float* out, int cap_floats, int* w, int* h);

@@ -90,6 +90,9 @@ void     set_orb_pattern(const int* pattern1024);
 // where the "ORB" branch's retainBest rankings run: 1 the device, 0 the host replay (uvo_orb_set_ranking); results do not depend on it.
 // Kept across a rebuilt context, as the table is.
 void     set_orb_ranking(int where);
+// where the "AKAZE" branch's contrast factor, duplicate suppression and refinement run: 1 the device, 0 the host scans
+// (uvo_akaze_set_suppression); results do not depend on it.  Kept across a rebuilt context.
+void     set_akaze_suppression(int where);
 
 // Replacements for the cv:: functions the node loops call directly (visual_odometry.h:355, 631, 647-648, 673).
 void triangulatePoints(const uvocv::Mat& projMatr1, const uvocv::Mat& projMatr2, const std::vector<uvocv::Point2f>& projPoints1,
