@@ -922,6 +922,23 @@ class Context:
         n = self._lib.uvo_mono_get(self._h, what.encode(), _p(buf), buf.nbytes)
         return buf[:max(n, 0)].copy()
 
+    def mono_set_pose_stage(self, where):
+        """Where estimate_relative_pose's attempts of the mono loop run: "host" / 0 (a first attempt with the essential matrix is
+        device-resident, homography-first frames and second attempts go through the host-pointer operators: the definition, and the
+        default) or "device" / 1 (every attempt device-resident; estimate_relative_pose on host points then takes the same chains).
+        The results do not depend on it; refused while frames are in flight; the master context's value serves every lane."""
+        where = {"host": 0, "device": 1}.get(where, where)
+        self._check(self._lib.uvo_mono_set_pose_stage(self._h, int(where)))
+
+    def mono_pose_stats(self) -> dict:
+        """Route figures of the last frame mono_step / mono_collect returned (or of the last estimate_relative_pose call):
+        dict(attempts=[E resident, H resident, E host-pointer, H host-pointer], first_method (1 essential, 0 homography, -1 the frame never
+        reached estimate_relative_pose), host_waits, uploads (point lists copied to the device), fallbacks)."""
+        att = np.zeros(4, np.int32)
+        fm, hw, up, fb = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        self._check(self._lib.uvo_mono_pose_stats(self._h, _p(att), C.byref(fm), C.byref(hw), C.byref(up), C.byref(fb)))
+        return {"attempts": [int(v) for v in att], "first_method": fm.value, "host_waits": hw.value, "uploads": up.value, "fallbacks": fb.value}
+
     # ------------------------------------------------------------------ timing
     def timing_enable(self, on: bool = True):
         self._check(self._lib.uvo_timing_enable(self._h, int(on)))

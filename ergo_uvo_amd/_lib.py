@@ -12,6 +12,9 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("UVO_HIP_LIB") or os.path.join(_HERE, "lib", "libuvo_hip.so")      # UVO_HIP_LIB: another build of the same ABI (A/B measurements)
+# UVO_HIP_LIB_LACKS=name,name: entries an OLDER build named by UVO_HIP_LIB does not have yet (a parent commit's library as the reference arm
+# of a measurement): they are not looked up, and calling one raises.  Ignored for the package's own library, which must be complete.
+LACKS = frozenset(n for n in os.environ.get("UVO_HIP_LIB_LACKS", "").split(",") if n) if os.environ.get("UVO_HIP_LIB") else frozenset()
 
 EXPORTS = [
     "uvo_params_default_stereo", "uvo_params_default_mono", "uvo_ctx_create", "uvo_ctx_destroy", "uvo_last_error",
@@ -21,7 +24,7 @@ EXPORTS = [
     "uvo_stereo_set_depth", "uvo_stereo_submit", "uvo_stereo_collect",
     "uvo_stereo_get", "uvo_find_essential_mat", "uvo_five_point_models", "uvo_solve_poly10", "uvo_homography_models", "uvo_recover_pose", "uvo_find_homography", "uvo_decompose_homography_mat",
     "uvo_recover_pose_homography", "uvo_select_estimation_method", "uvo_estimate_relative_pose", "uvo_mono_set_camera",
-    "uvo_mono_reset", "uvo_mono_step", "uvo_mono_submit", "uvo_mono_collect", "uvo_mono_get", "uvo_get_image",
+    "uvo_mono_reset", "uvo_mono_step", "uvo_mono_submit", "uvo_mono_collect", "uvo_mono_get", "uvo_mono_set_pose_stage", "uvo_mono_pose_stats", "uvo_get_image",
     "uvo_ctx_set_camera", "uvo_stereo_step_frames", "uvo_stereo_submit_frames", "uvo_mono_step_frames", "uvo_mono_submit_frames",
     "uvo_ctx_set_jpeg_entropy", "uvo_stereo_step_compressed", "uvo_stereo_submit_compressed", "uvo_mono_step_compressed", "uvo_mono_submit_compressed",
     "uvo_jpeg_coefficients", "uvo_jpeg_entropy_stats",
@@ -79,6 +82,9 @@ def lib() -> C.CDLL:
         _lib.uvo_akaze_set_suppression.argtypes = [C.c_void_p, C.c_int]
         _lib.uvo_akaze_suppress.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         _lib.uvo_akaze_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        for name, sig in (("uvo_mono_set_pose_stage", [C.c_void_p, C.c_int]), ("uvo_mono_pose_stats", [C.c_void_p] * 6)):
+            if name not in LACKS:
+                getattr(_lib, name).argtypes = sig
         _lib.uvo_retain_best.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         _lib.uvo_match_loop_knn2.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         _lib.uvo_device_alloc.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
@@ -94,5 +100,6 @@ def lib() -> C.CDLL:
         _lib.uvo_trace_read.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         _lib.uvo_trace_enable.argtypes = [C.c_void_p, C.c_int]
         for name in EXPORTS:
-            getattr(_lib, name)  # fail loudly if the ABI and the header drift apart
+            if name not in LACKS:
+                getattr(_lib, name)  # fail loudly if the ABI and the header drift apart
     return _lib

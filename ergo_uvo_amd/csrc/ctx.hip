@@ -641,6 +641,7 @@ hipError_t host_sync(Ctx* c, hipStream_t st)
 {
     // (an event of the lane's own and hipEventQuery -- a load of the signal; hipStreamQuery in a loop cost the 600-step form 6 % and put
     // millisecond gaps back: p99 of the collect gaps 0.95 ms against 0.33)
+    c->stat_waits++;                                       // (the lane's own thread: uvo_mono_pose_stats reports a stage's differences)
     if (c->wait_eff.load(std::memory_order_acquire) != 2) { const hipError_t e = hipEventRecord(c->evPoll, st); return e == hipSuccess ? poll_event(c->evPoll) : e; }     // every mode but block-all
     hipError_t e = hipEventRecord(c->evBlock, st);
     return e == hipSuccess ? hipEventSynchronize(c->evBlock) : e;
@@ -651,6 +652,7 @@ hipError_t host_sync(Ctx* c, hipStream_t st)
 static uvo_status read_counts(uvo_ctx* c)
 {
     UVO_HIP_TRY(c, hipMemcpyAsync(c->h_counts, c->d_counts, sizeof(int) * CN_TOTAL, hipMemcpyDeviceToHost, c->stream));
+    c->stat_waits++;
     UVO_HIP_TRY(c, hipStreamSynchronize(c->stream));
     return UVO_OK;
 }
@@ -1970,7 +1972,7 @@ extern "C" uvo_status uvo_recover_pose_homography(uvo_ctx* c, const double* H, c
 try {
     if (!c || !H || !p1 || !p2 || !K || !R || !t || !max_good || n < 0) return UVO_INVALID_ARG;
     (void)hipSetDevice(c->device);
-    return mono_recover_pose_homography(c, H, p1, p2, n, K, c->p.HOMOGRAPHY_DISTANCE, R, t, max_good);
+    return mono_recover_pose_homography(c, H, p1, p2, n, K, c->p.HOMOGRAPHY_DISTANCE, R, t, max_good, true);
 } UVO_ABI_CATCH(c)
 
 // MU:65-86 compute_median
@@ -2023,7 +2025,7 @@ static uvo_status estimate_once(uvo_ctx* c, const uvo_point2f* k1, const uvo_poi
                                      p.HOMOGRAPHY_CONFIDENCE, H, mask, &ok));
         *n_in = extract_inliers(k1, k2, mask, n, in1, in2);
         int good = 0;
-        if (ok) UVO_TRY(mono_recover_pose_homography(c, H, k1, k2, n, K, p.HOMOGRAPHY_DISTANCE, R, t, &good));
+        if (ok) UVO_TRY(mono_recover_pose_homography(c, H, k1, k2, n, K, p.HOMOGRAPHY_DISTANCE, R, t, &good, false));
     }
     int v = 0;
     for (int i = 0; i < n; i++) v += mask[i] != 0;
@@ -2042,6 +2044,39 @@ static const char* bad_outlier_methods(const uvo_params& p)
         return "outlier methods must be 4 (LMEDS) or 8 (RANSAC)";
     return nullptr;
 }
+// estimate_relative_pose (VOU:134-180) on host points through the device-resident chains (pose stage 1): the points are staged once
+// (mono_stage_points: what k_mono_prep leaves behind a frame's stage A), then each attempt is the chain the loop's stage B runs
+static uvo_status estimate_relative_pose_resident(uvo_ctx* c, const uvo_point2f* k1, const uvo_point2f* k2, int n, const double* K, int* use_essential, double* R, double* t,
+                                                  uvo_point2f* in1, uvo_point2f* in2, int* n_in, uint8_t* mask, int* success, Ctx::MonoPoseStats* ps)
+{
+    const uvo_params& p = c->p;
+    const uvo_point2f *h1 = nullptr, *h2 = nullptr;
+    UVO_TRY(mono_stage_points(c, k1, k2, n, K, &h1, &h2));
+    for (int attempt = 0; attempt < 2 && !*success; attempt++) {
+        MonoResident mr;
+        int valid_inliers = 0;
+        bool fetch = true;
+        if (*use_essential) {
+            ps->attempts[0]++;
+            UVO_TRY(mono_essential_resident(c, n, K, p.ESSENTIAL_OUTLIER_METHOD, p.ESSENTIAL_CONFIDENCE, p.ESSENTIAL_THRESHOLD, (int)p.ESSENTIAL_MAX_ITERS, &mr));
+            if (mr.ok) { memcpy(R, mr.R, sizeof(double) * 9); memcpy(t, mr.t, sizeof(double) * 3); memcpy(mask, mr.mask, (size_t)n); valid_inliers = mr.valid_inliers; }
+            else memset(mask, 0, (size_t)n);
+        } else {
+            ps->attempts[1]++;
+            UVO_TRY(mono_homography_resident(c, n, K, p.HOMOGRAPHY_OUTLIER_METHOD, p.HOMOGRAPHY_THRESHOLD, (int)p.HOMOGRAPHY_MAX_ITERS, p.HOMOGRAPHY_CONFIDENCE,
+                                             p.HOMOGRAPHY_DISTANCE, &mr));
+            memcpy(mask, mr.mask, (size_t)n);
+            valid_inliers = mr.valid_inliers;
+            if (mr.pose) { memcpy(R, mr.R, sizeof(double) * 9); memcpy(t, mr.t, sizeof(double) * 3); }
+            if (mr.fallback) { ps->fallbacks++; fetch = false; }
+        }
+        if (fetch) { *n_in = mr.n_in; UVO_TRY(mono_resident_inliers(c, mr.n_in, in1, in2)); }
+        else *n_in = extract_inliers(h1, h2, mask, n, in1, in2);
+        if (estimate_accepted(p, valid_inliers, n)) *success = 1;
+        else if (attempt == 0) *use_essential = !*use_essential;
+    }
+    return UVO_OK;
+}
 // estimate_relative_pose (VOU:134-180).  use_essential is the reference's global (in/out); R, t are in/out.
 extern "C" uvo_status uvo_estimate_relative_pose(uvo_ctx* c, const uvo_point2f* k1, const uvo_point2f* k2, int n, const double* K,
                                                  int* use_essential, double* R, double* t, uvo_point2f* in1, uvo_point2f* in2, int* n_in,
@@ -2054,8 +2089,17 @@ try {
     if (const char* why = bad_outlier_methods(p)) return fail(c, UVO_INVALID_ARG, why);
     bool estimate_completed = false, switch_method = false;
     *success = 0;
+    Ctx::MonoPoseStats ps;                                 // uvo_mono_pose_stats after an operator call speaks of that call
+    ps.first_method = *use_essential ? 1 : 0;
+    const unsigned waits0 = c->stat_waits, uploads0 = c->stat_uploads;
+    struct StatsAtExit { uvo_ctx* c; Ctx::MonoPoseStats& ps; unsigned w0, u0; ~StatsAtExit() { ps.host_waits = (int)(c->stat_waits - w0); ps.uploads = (int)(c->stat_uploads - u0); c->mono_pstats = ps; } } stats_at_exit{c, ps, waits0, uploads0};
+    if (c->sh->mono_pose_stage == 1) {
+        *n_in = 0;
+        return estimate_relative_pose_resident(c, k1, k2, n, K, use_essential, R, t, in1, in2, n_in, mask, success, &ps);
+    }
     while (!estimate_completed) {
         int valid_inliers = 0;
+        ps.attempts[*use_essential ? 2 : 3]++;
         UVO_TRY(estimate_once(c, k1, k2, n, K, *use_essential, R, t, in1, in2, n_in, mask, &valid_inliers));
         if (estimate_accepted(p, valid_inliers, n)) { *success = 1; estimate_completed = true; }
         else {
@@ -2064,6 +2108,27 @@ try {
             *use_essential = !*use_essential;
         }
     }
+    return UVO_OK;
+} UVO_ABI_CATCH(c)
+
+extern "C" uvo_status uvo_mono_set_pose_stage(uvo_ctx* c, int where)
+try {
+    if (!c) return UVO_INVALID_ARG;
+    if (where != 0 && where != 1)
+        return fail(c, UVO_INVALID_ARG, "uvo_mono_set_pose_stage: 0 (essential-first attempts resident, the rest through the host-pointer operators) or 1 (every attempt resident)");
+    if (c->sh->n_pending != 0) return fail(c, UVO_INVALID_ARG, "uvo_mono_set_pose_stage: the pose stage cannot change while frames are in flight (collect them first)");
+    c->sh->mono_pose_stage = where;
+    return UVO_OK;
+} UVO_ABI_CATCH(c)
+extern "C" uvo_status uvo_mono_pose_stats(uvo_ctx* c, int* attempts, int* first_method, int* host_waits, int* uploads, int* fallbacks)
+try {
+    if (!c) return UVO_INVALID_ARG;
+    const Ctx::MonoPoseStats& s = c->mono_pstats;
+    if (attempts) for (int i = 0; i < 4; i++) attempts[i] = s.attempts[i];
+    if (first_method) *first_method = s.first_method;
+    if (host_waits) *host_waits = s.host_waits;
+    if (uploads) *uploads = s.uploads;
+    if (fallbacks) *fallbacks = s.fallbacks;
     return UVO_OK;
 } UVO_ABI_CATCH(c)
 
@@ -2112,10 +2177,14 @@ __global__ __launch_bounds__(256) void k_gather_mono_pairs(const uvo_dmatch* __r
 
 // Stage B of one mono frame (VO:276-376 after the matching) on lane L's buffers and stream -- the lane's worker for a pipelined frame,
 // the calling thread for uvo_mono_step: fills job.mres / pose_written / sf_written.  The matched points are on the device (d_x1 / d_x2,
-// mirrored in pinned memory by k_mono_prep together with select_estimation_method's decision).  A frame whose method is the essential
-// matrix takes the device-resident chain (mono.hip: mono_essential_resident, two host syncs); homography-first frames and second
-// attempts (VOU:165-178) take the host-pointer operators on the pinned mirrors.  Keypoints, matches and good points are NOT copied to the
-// host: uvo_mono_get reads them from the lane's buffers when asked.
+// mirrored in pinned memory by k_mono_prep together with select_estimation_method's decision).  With the pose stage at 1
+// (uvo_mono_set_pose_stage) every attempt of estimate_relative_pose takes a device-resident chain (mono.hip:
+// mono_essential_resident, two host syncs; mono_homography_resident, three or four; nothing uploaded).  At 0 -- the definition, and the default -- only a
+// first attempt with the essential matrix does; homography-first frames and second attempts (VOU:165-178) take the host-pointer
+// operators on the pinned mirrors.  Either chain reads d_x1 / d_x2, q1 / q2 and the pinned mirrors and leaves their content as it is (the
+// homography chain's single-solution hand-over uploads the mirrors into d_x1 / d_x2 again: the same bytes), so a failed attempt leaves
+// the other method what it needs (mono.hip lists what the chains overwrite).  Keypoints, matches and good points are NOT
+// copied to the host: uvo_mono_get reads them from the lane's buffers when asked.
 static void run_mono_stage_b(uvo_ctx* L, bool stage_a_ok)
 {
     Ctx::BJob& j = L->job;
@@ -2123,6 +2192,9 @@ static void run_mono_stage_b(uvo_ctx* L, bool stage_a_ok)
     const uvo_params& p = L->p;
     j.st = UVO_OK; j.err.clear(); j.pose_written = j.sf_written = false;
     memset(&j.mres, 0, sizeof(j.mres));
+    j.pstats = Ctx::MonoPoseStats();
+    const unsigned waits0 = L->stat_waits, uploads0 = L->stat_uploads;
+    struct StatsAtExit { Ctx::BJob& j; uvo_ctx* L; unsigned w0, u0; ~StatsAtExit() { j.pstats.host_waits = (int)(L->stat_waits - w0); j.pstats.uploads = (int)(L->stat_uploads - u0); } } stats_at_exit{j, L, waits0, uploads0};
     L->mono_mask.clear(); L->mono_good_pts.clear();
     L->mono_dev_n = L->mono_dev_M = L->mono_dev_G = 0; L->mono_good_on_host = false;
     if (!stage_a_ok) { j.st = UVO_HIP_ERROR; j.err = "stage A of the frame failed"; return; }
@@ -2146,6 +2218,8 @@ static void run_mono_stage_b(uvo_ctx* L, bool stage_a_ok)
     int use_essential = mono_prep_method(L, M, &k1, &k2);                                  // VO:310-317 (select_estimation_method, on the device)
     if (use_essential < 0) { j.st = UVO_HIP_ERROR; j.err = "mono pose stage: select_estimation_method's kernel did not report"; return; }
     L->mono_mask.assign(M, 0);
+    j.pstats.first_method = use_essential;
+    const bool all_resident = L->sh->mono_pose_stage == 1;
     // R, t are in/out in the reference (kept when no estimator writes them): run on a sentinel and report whether they were written
     double R[9], t[3];
     const double kSentinel = -7.0e300;
@@ -2157,14 +2231,30 @@ static void run_mono_stage_b(uvo_ctx* L, bool stage_a_ok)
     std::vector<uvo_point2f> in1, in2;           // extract_inliers' output of a host-pointer attempt
     for (int attempt = 0; attempt < 2 && !success; attempt++) {                            // estimate_relative_pose (VOU:134-180)
         int valid_inliers = 0;
-        if (use_essential && attempt == 0) {
+        if (use_essential && (attempt == 0 || all_resident)) {
+            j.pstats.attempts[0]++;
             j.st = mono_essential_resident(L, M, K, p.ESSENTIAL_OUTLIER_METHOD, p.ESSENTIAL_CONFIDENCE, p.ESSENTIAL_THRESHOLD, (int)p.ESSENTIAL_MAX_ITERS, &mr);
             if (j.st != UVO_OK) { j.err = L->err; return; }
             n_in = mr.n_in;
             if (mr.ok) { memcpy(R, mr.R, sizeof(R)); memcpy(t, mr.t, sizeof(t)); memcpy(L->mono_mask.data(), mr.mask, (size_t)M); valid_inliers = mr.valid_inliers; }
             else memset(L->mono_mask.data(), 0, (size_t)M);
             resident = true;
+        } else if (!use_essential && all_resident) {
+            j.pstats.attempts[1]++;
+            j.st = mono_homography_resident(L, M, K, p.HOMOGRAPHY_OUTLIER_METHOD, p.HOMOGRAPHY_THRESHOLD, (int)p.HOMOGRAPHY_MAX_ITERS, p.HOMOGRAPHY_CONFIDENCE,
+                                            p.HOMOGRAPHY_DISTANCE, &mr);
+            if (j.st != UVO_OK) { j.err = L->err; return; }
+            n_in = mr.n_in; valid_inliers = mr.valid_inliers;
+            memcpy(L->mono_mask.data(), mr.mask, (size_t)M);                               // (zeros when findHomography produced nothing)
+            if (mr.pose) { memcpy(R, mr.R, sizeof(R)); memcpy(t, mr.t, sizeof(t)); }
+            resident = !mr.fallback;
+            if (mr.fallback) {                                                             // the definition's route from here: extract_inliers on the host, its pose tail below
+                j.pstats.fallbacks++;
+                in1.resize(M); in2.resize(M);
+                n_in = extract_inliers(k1, k2, L->mono_mask.data(), M, in1.data(), in2.data());
+            }
         } else {
+            j.pstats.attempts[use_essential ? 2 : 3]++;
             in1.resize(M); in2.resize(M);
             j.st = estimate_once(L, k1, k2, M, K, use_essential, R, t, in1.data(), in2.data(), &n_in, L->mono_mask.data(), &valid_inliers);
             if (j.st != UVO_OK) { j.err = L->err; return; }
@@ -2194,6 +2284,7 @@ static void run_mono_stage_b(uvo_ctx* L, bool stage_a_ok)
                 if (!hip_ok(hipMemcpyAsync(L->d_x1, in1.data(), sizeof(uvo_point2f) * n_in, hipMemcpyHostToDevice, st))) return;
                 if (!hip_ok(hipMemcpyAsync(L->d_x2, in2.data(), sizeof(uvo_point2f) * n_in, hipMemcpyHostToDevice, st))) return;
                 if (!hip_ok(hipMemcpyAsync(L->d_xc, in2.data(), sizeof(uvo_point2f) * n_in, hipMemcpyHostToDevice, st))) return;
+                L->stat_uploads += 3;
                 if ((j.st = pose_triangulate_extract3d(L, 0, P_prev, P_curr, I, z, R, t, K, K, nullptr, n_in)) != UVO_OK) { j.err = L->err; return; }   // VO:355-356
                 if ((j.st = read_counts(L)) != UVO_OK) { j.err = L->err; return; }
                 G = L->h_counts[CN_G];
@@ -2224,6 +2315,7 @@ static void run_mono_stage_b(uvo_ctx* L, bool stage_a_ok)
 static void apply_mono_result(uvo_ctx* c, const Ctx::BJob& j, double dt, uvo_mono_result* out)
 {
     *out = j.mres;
+    c->mono_pstats = j.pstats;
     if (j.mres.n_kps > 0) c->sh->kp_hint = j.mres.n_kps;          // sizes the descriptor launch's small-window grid of the frames to come
     if (j.pose_written) { memcpy(c->sh->mono_R, j.R, sizeof(c->sh->mono_R)); memcpy(c->sh->mono_t, j.t, sizeof(c->sh->mono_t)); }
     if (j.sf_written) c->sh->mono_SF = j.SF;
@@ -2267,6 +2359,7 @@ static uvo_status mono_step_body(uvo_ctx* c, const uint8_t* img, int w, int h, i
     const uvo_params& p = c->p;
     Range r_step("uvo:mono_step");
     memset(out, 0, sizeof(*out));
+    c->mono_pstats = Ctx::MonoPoseStats();
     c->mono_mask.clear(); c->mono_good_pts.clear();
     c->mono_dev_n = c->mono_dev_M = c->mono_dev_G = 0; c->mono_good_on_host = true;
     if (!o.producer_waited) UVO_TRY(wait_for_producer(c, c, mem));
@@ -2318,7 +2411,10 @@ static uvo_status mono_submit_body(uvo_ctx* c, const uint8_t* img, int w, int h,
         // (earlier init frames may still await their collect: they are complete, only their result is queued)
         uvo_mono_result r;
         memset(&r, 0, sizeof(r));
-        UVO_TRY(mono_step_body(c, img, w, h, stride, mem, range, 1.0, &r, o));             // nothing is published before initialisation
+        const Ctx::MonoPoseStats returned = c->mono_pstats;                                // uvo_mono_pose_stats speaks of the last frame RETURNED: the collect resets it
+        const uvo_status st_init = mono_step_body(c, img, w, h, stride, mem, range, 1.0, &r, o);   // nothing is published before initialisation
+        c->mono_pstats = returned;
+        UVO_TRY(st_init);
         c->sh->mono_init_results.push_back(r);
         c->sh->inflight[c->sh->n_pending++] = Shared::kInflightMonoInit; c->sh->n_submitted++;                // a synchronous init frame
         c->sh->prev_lane = 0; c->sh->next_lane = 1 % depth;
@@ -2378,6 +2474,7 @@ static uvo_status mono_collect_body(uvo_ctx* c, double dt, uvo_mono_result* out)
     if (li < 0) {                                          // a synchronous init frame (its state is already applied)
         *out = c->sh->mono_init_results.front();
         c->sh->mono_init_results.pop_front();
+        c->mono_pstats = Ctx::MonoPoseStats();
         return UVO_OK;
     }
     uvo_ctx* L = static_cast<uvo_ctx*>(c->sh->lanes[li]);

@@ -16,6 +16,7 @@
 //   k_model_mask    : mask of the winning model
 //   k_recover_pose  : cheirality test of the 4 (R,t) candidates
 #include "uvo_ctx.h"
+#include "uvo_h_vote.h"
 #include "uvo_mono.h"
 #include "uvo_epnp.h"
 #include <string.h>
@@ -759,6 +760,7 @@ struct MonoWs {                       // device workspace of the mono stage, own
     // the loop's pose stage with its points resident on the device (mono_essential_resident)
     uvo_point2f *in1 = nullptr, *in2 = nullptr;    // extract_inliers' output (cap each)
     int* pick = nullptr;                           // [0] best candidate of recoverPose, [1] n_in
+    float* zrows = nullptr;                        // recover_pose_homography's vote: the z row of each candidate (4 x cap; k_h_vote writes, k_h_pick counts)
     Pinned<uvo_point2f> h_x1, h_x2;                // the frame's matched points, mirrored by k_mono_prep
     Pinned<int> h_prep;                            // k_mono_prep: [0] use_essential of select_estimation_method, [1] M it saw
     Pinned<int> h_pick;                            // k_mono_pick: best, good[4], n_in, valid inliers; k_mono_scale: G, n_front
@@ -782,7 +784,7 @@ static MonoWs* mono_ws(Ctx* c)
               hipMalloc((void**)&w->masks, 5 * cap) == hipSuccess && hipMalloc((void**)&w->good, sizeof(int) * 4) == hipSuccess &&
               hipMalloc((void**)&w->best, sizeof(double) * 9) == hipSuccess &&
               hipMalloc((void**)&w->in1, sizeof(uvo_point2f) * cap) == hipSuccess && hipMalloc((void**)&w->in2, sizeof(uvo_point2f) * cap) == hipSuccess &&
-              hipMalloc((void**)&w->pick, sizeof(int) * 4) == hipSuccess;
+              hipMalloc((void**)&w->pick, sizeof(int) * 4) == hipSuccess && hipMalloc((void**)&w->zrows, sizeof(float) * 4 * (cap ? cap : 1)) == hipSuccess;
     if (!ok) { delete w; return nullptr; }
     ok = w->h_subsets.resize(kMaxHyp * 5) && w->h_nmodels.resize(kMaxHyp) && w->h_counts.resize(kMaxHyp * 10) &&
          w->h_medians.resize(kMaxHyp * 10) && w->h_models.resize((size_t)kMaxHyp * 90) &&
@@ -797,7 +799,7 @@ void mono_ws_free(Ctx* c)
 {
     MonoWs* w = static_cast<MonoWs*>(c->mono_ws);
     if (!w) return;
-    void* ptrs[] = { w->q1, w->q2, w->src, w->dst, w->subsets, w->models, w->nmodels, w->counts, w->medians, w->masks, w->good, w->best, w->in1, w->in2, w->pick };
+    void* ptrs[] = { w->q1, w->q2, w->src, w->dst, w->subsets, w->models, w->nmodels, w->counts, w->medians, w->masks, w->good, w->best, w->in1, w->in2, w->pick, w->zrows };
     for (void* p : ptrs) (void)hipFree(p);
     w->h_subsets.release(); w->h_nmodels.release(); w->h_counts.release(); w->h_medians.release(); w->h_models.release();
     w->h_q1.release(); w->h_q2.release(); w->h_src.release(); w->h_dst.release(); w->h_mask.release(); w->h_good.release();
@@ -946,6 +948,7 @@ uvo_status mono_find_essential(Ctx* c, const uvo_point2f* p1, const uvo_point2f*
     hipStream_t st = c->stream;
     UVO_HIP_TRY(c, hipMemcpyAsync(w->q1, q1.data(), sizeof(double) * 2 * n, hipMemcpyHostToDevice, st));
     UVO_HIP_TRY(c, hipMemcpyAsync(w->q2, q2.data(), sizeof(double) * 2 * n, hipMemcpyHostToDevice, st));
+    c->stat_uploads += 2;
     const bool lmeds = method != 8;
     int niters;
     if (n == modelPoints) niters = 1;
@@ -1119,6 +1122,7 @@ uvo_status mono_recover_pose(Ctx* c, const double* E, const uvo_point2f* p1, con
         hipStream_t st = c->stream;
         UVO_HIP_TRY(c, hipMemcpyAsync(w->q1, q1.data(), sizeof(double) * 2 * n, hipMemcpyHostToDevice, st));
         UVO_HIP_TRY(c, hipMemcpyAsync(w->q2, q2.data(), sizeof(double) * 2 * n, hipMemcpyHostToDevice, st));
+        c->stat_uploads += 2;
         memcpy(w->h_mask.data(), mask, (size_t)n);
         UVO_HIP_TRY(c, hipMemcpyAsync(w->masks + 4 * (size_t)c->cap, w->h_mask.data(), n, hipMemcpyHostToDevice, st));
         UVO_HIP_TRY(c, hipMemsetAsync(w->good, 0, sizeof(int) * 4, st));
@@ -1282,6 +1286,32 @@ static void lm_refine_homography(const float* M, const float* m, int count, doub
     memcpy(h, x, sizeof(x));
 }
 
+// findHomography's host pieces, shared by the host-pointer operator and the resident chain (mono_homography_resident)
+static int h_niters(bool lmeds, double confidence, int maxIters)
+{
+    if (lmeds) { int niters = ransac_update_num_iters(confidence, 0.45, 4, maxIters); return niters > 3 ? niters : 3; }
+    return maxIters > 1 ? maxIters : 1;
+}
+static double h_final_threshold(bool lmeds, double thr, int n, double min_median)
+{
+    if (!lmeds) return thr;
+    double sigma = 2.5 * 1.4826 * (1 + 5. / (n - 4)) * sqrt(min_median);
+    return sigma > 0.001 ? sigma : 0.001;
+}
+// compressElems by the mask (in1 / in2 -> src / dst, which may be the same arrays) and the refit on the k inliers: homography_kernel,
+// then the LM refinement.  Returns k; H is left alone when k == 0.
+static int h_compact_refit(const float* in1, const float* in2, int n, const uint8_t* mask, float* src, float* dst, double* H)
+{
+    double scratch[171]; int iscratch[18];
+    int k = 0;
+    for (int i = 0; i < n; i++) if (mask[i]) { src[2*k] = in1[2*i]; src[2*k+1] = in1[2*i+1]; dst[2*k] = in2[2*i]; dst[2*k+1] = in2[2*i+1]; k++; }
+    if (k > 0) {
+        homography_kernel(src, dst, k, H, SArr<1>{scratch}, SArr<1>{scratch + 81}, SArr<1>{scratch + 90}, iscratch);
+        lm_refine_homography(src, dst, k, H);
+    }
+    return k;
+}
+
 // cv::findHomography (VOU:152)
 uvo_status mono_find_homography(Ctx* c, const uvo_point2f* p1, const uvo_point2f* p2, int n, int method, double thr, int maxIters,
                                 double confidence, double* H, uint8_t* mask, int* ok)
@@ -1304,9 +1334,7 @@ uvo_status mono_find_homography(Ctx* c, const uvo_point2f* p1, const uvo_point2f
     } else {
         hipStream_t st = c->stream;
         const bool lmeds = method != 8;
-        int niters;
-        if (lmeds) { niters = ransac_update_num_iters(confidence, 0.45, modelPoints, maxIters); niters = niters > 3 ? niters : 3; }
-        else niters = maxIters > 1 ? maxIters : 1;
+        const int niters = h_niters(lmeds, confidence, maxIters);
         if (niters > kMaxHyp) { c->err = "max_iters exceeds the compiled hypothesis capacity (2048)"; return UVO_CAPACITY; }
         if (lmeds) UVO_TRY(lmeds_capacity(c, w, n));
         bool failed_first = false;
@@ -1314,6 +1342,7 @@ uvo_status mono_find_homography(Ctx* c, const uvo_point2f* p1, const uvo_point2f
         if (nsub > 0) {
             UVO_HIP_TRY(c, hipMemcpyAsync(w->src, src.data(), sizeof(float) * 2 * n, hipMemcpyHostToDevice, st));
             UVO_HIP_TRY(c, hipMemcpyAsync(w->dst, dst.data(), sizeof(float) * 2 * n, hipMemcpyHostToDevice, st));
+            c->stat_uploads += 2;
             UVO_HIP_TRY(c, hipMemcpyAsync(w->subsets, w->h_subsets.data(), sizeof(int) * 4 * nsub, hipMemcpyHostToDevice, st));
             // RANSAC in rounds, as mono_find_essential: the first kFirstRound subsets, the rest only if the adaptive count reaches past them
             // (at the shipped 0.1-px threshold the scan of a low-inlier frame never settles inside the first round, and the second launch
@@ -1351,11 +1380,7 @@ uvo_status mono_find_homography(Ctx* c, const uvo_point2f* p1, const uvo_point2f
                 }
             }
             if (win.hyp >= 0) {
-                double final_thr = thr;
-                if (lmeds) {
-                    double sigma = 2.5 * 1.4826 * (1 + 5. / (n - modelPoints)) * sqrt(win.min_median);
-                    final_thr = sigma > 0.001 ? sigma : 0.001;
-                }
+                const double final_thr = h_final_threshold(lmeds, thr, n, win.min_median);
                 const double* best = w->models + (size_t)win.hyp * 9;
                 hipLaunchKernelGGL(k_model_mask, dim3((n + 255) / 256), dim3(256), 0, st, 1, nullptr, nullptr, w->src, w->dst, n, best,
                                    (float)(final_thr * final_thr), w->masks);
@@ -1369,14 +1394,7 @@ uvo_status mono_find_homography(Ctx* c, const uvo_point2f* p1, const uvo_point2f
             }
         }
     }
-    if (result && n > 4) {
-        int k = 0;                                                       // compressElems
-        for (int i = 0; i < n; i++) if (mask[i]) { src[2*k] = src[2*i]; src[2*k+1] = src[2*i+1]; dst[2*k] = dst[2*i]; dst[2*k+1] = dst[2*i+1]; k++; }
-        if (k > 0) {
-            homography_kernel(src.data(), dst.data(), k, H, SArr<1>{scratch}, SArr<1>{scratch + 81}, SArr<1>{scratch + 90}, iscratch);
-            lm_refine_homography(src.data(), dst.data(), k, H);
-        }
-    }
+    if (result && n > 4) h_compact_refit(src.data(), dst.data(), n, mask, src.data(), dst.data(), H);
     if (!result) memset(mask, 0, n);
     *ok = result;
     return UVO_OK;
@@ -1509,55 +1527,64 @@ void projection_matrix(const double* R, const double* t, const double* K, double
     for (int i = 0; i < 3; i++) for (int j = 0; j < 4; j++) P[i*4 + j] = K[i*3]*Rt[j] + K[i*3+1]*Rt[4 + j] + K[i*3+2]*Rt[8 + j];
 }
 
+// the pose of candidate `cnd` of decomposeHomographyMat as recover_pose_homography returns it: its R, its t over |t| (VOU:615-620)
+static void h_candidate_pose(const double* Rs, const double* ts, int cnd, double* R, double* t)
+{
+    const double* tb = ts + 3*cnd;
+    double nrm = sqrt(tb[0]*tb[0] + tb[1]*tb[1] + tb[2]*tb[2]);
+    double inv = 1.0 / nrm;
+    memcpy(R, Rs + 9*cnd, sizeof(double)*9);
+    for (int k = 0; k < 3; k++) t[k] = tb[k] * inv;
+}
 // recover_pose_homography (VOU:581-624), including the reference's reinterpretation of two neighbouring
-// floats as one double at VOU:601-602 (the last column, read past the buffer there, is not counted).
+// floats as one double at VOU:601-602 (the last column, read past the buffer there, is not counted): the count and the choice are
+// uvo_h_vote.h's, as in the resident chain's k_h_pick.  The z rows of the candidates come
+//   one_launch = false  candidate by candidate: triangulatePoints (k_triangulate), a download of the points and a wait each, then
+//                       convert_from_homogeneous_coords (VOU:71-83) on the host -- the definition's route (estimate_once, pose stage 0)
+//   one_launch = true   from one launch for every candidate (pose.hip: k_h_vote, the conversion included) and one wait: the operator
+//                       uvo_recover_pose_homography
 uvo_status mono_recover_pose_homography(Ctx* c, const double* H, const uvo_point2f* p1, const uvo_point2f* p2, int n, const double* K,
-                                        double HOMOGRAPHY_DISTANCE, double* R, double* t, int* max_good_out)
+                                        double HOMOGRAPHY_DISTANCE, double* R, double* t, int* max_good_out, bool one_launch)
 {
     *max_good_out = 0;
     if (n > c->cap) { c->err = "point count exceeds the context's max_kpts"; return UVO_CAPACITY; }
+    MonoWs* w = mono_ws(c);
+    if (!w) { c->err = "mono workspace allocation failed"; return UVO_HIP_ERROR; }
     double Rs[36], ts[12], ns[12];
     int solutions = decompose_homography_mat(H, K, Rs, ts, ns);
     const double I[9] = {1,0,0,0,1,0,0,0,1}, z[3] = {0,0,0};
-    double proj_std[12];
+    double proj_std[12], P[kHVoteMaxCands][12];
     projection_matrix(I, z, K, proj_std);
-    int best = -1, max_good = 0;
-    std::vector<float4> p4(n > 0 ? n : 1);
-    std::vector<float> zrow(n + 1);
-    hipStream_t st = c->stream;
+    for (int i = 0; i < solutions; i++) projection_matrix(Rs + 9*i, ts + 3*i, K, P[i]);
+    int counts[kHVoteMaxCands] = {0, 0, 0, 0};
     if (n > 0) {
+        hipStream_t st = c->stream;
         UVO_HIP_TRY(c, hipMemcpyAsync(c->d_x1, p1, sizeof(uvo_point2f) * n, hipMemcpyHostToDevice, st));
         UVO_HIP_TRY(c, hipMemcpyAsync(c->d_x2, p2, sizeof(uvo_point2f) * n, hipMemcpyHostToDevice, st));
-    }
-    for (int i = 0; i < solutions; i++) {
-        double P[12];
-        projection_matrix(Rs + 9*i, ts + 3*i, K, P);
-        if (n > 0) {
-            UVO_TRY(pose_triangulate(c, proj_std, P, nullptr, n));
-            UVO_HIP_TRY(c, hipMemcpyAsync(p4.data(), c->d_pts4, sizeof(float4) * n, hipMemcpyDeviceToHost, st));
+        c->stat_uploads += 2;
+        std::vector<float> zrows((size_t)solutions * n);
+        if (one_launch) {
+            UVO_TRY(pose_h_vote(c, proj_std, &P[0][0], solutions, c->d_x1, c->d_x2, n, w->zrows, c->cap));
+            for (int i = 0; i < solutions; i++)
+                UVO_HIP_TRY(c, hipMemcpyAsync(zrows.data() + (size_t)i * n, w->zrows + (size_t)i * c->cap, sizeof(float) * n, hipMemcpyDeviceToHost, st));
             UVO_HIP_TRY(c, host_sync(c, st));
+        } else {
+            std::vector<float4> p4(n);
+            for (int i = 0; i < solutions; i++) {
+                UVO_TRY(pose_triangulate(c, proj_std, P[i], nullptr, n));
+                UVO_HIP_TRY(c, hipMemcpyAsync(p4.data(), c->d_pts4, sizeof(float4) * n, hipMemcpyDeviceToHost, st));
+                UVO_HIP_TRY(c, host_sync(c, st));
+                for (int j = 0; j < n; j++) {               // convert_from_homogeneous_coords (VOU:71-83): col / w in float
+                    float inv = (float)(1.0 / (double)p4[j].w);
+                    zrows[(size_t)i * n + j] = p4[j].z * inv + 0.f;
+                }
+            }
         }
-        for (int j = 0; j < n; j++) {                       // convert_from_homogeneous_coords (VOU:71-83): col / w in float
-            float inv = (float)(1.0 / (double)p4[j].w);
-            zrow[j] = p4[j].z * inv + 0.f;
-        }
-        int good = 0;
-        for (int j = 0; j + 1 < n; j++) {
-            uint32_t lo, hi; memcpy(&lo, &zrow[j], 4); memcpy(&hi, &zrow[j + 1], 4);
-            uint64_t bits = ((uint64_t)hi << 32) | lo;
-            double v; memcpy(&v, &bits, 8);
-            if (v > 0 && v < HOMOGRAPHY_DISTANCE) good++;
-        }
-        if (good > max_good) { best = i; max_good = good; }
+        for (int i = 0; i < solutions; i++) counts[i] = hv_row_count(zrows.data() + (size_t)i * n, n, HOMOGRAPHY_DISTANCE);      // VOU:601-602
     }
-    if (best != -1) {
-        const double* tb = ts + 3*best;
-        double nrm = sqrt(tb[0]*tb[0] + tb[1]*tb[1] + tb[2]*tb[2]);
-        double inv = 1.0 / nrm;
-        memcpy(R, Rs + 9*best, sizeof(double)*9);
-        for (int k = 0; k < 3; k++) t[k] = tb[k] * inv;
-    }
-    *max_good_out = max_good;
+    const int best = hv_choose(counts, solutions);
+    if (best != -1) h_candidate_pose(Rs, ts, best, R, t);
+    *max_good_out = best >= 0 ? counts[best] : 0;
     return UVO_OK;
 }
 
@@ -1578,15 +1605,17 @@ uvo_status mono_recover_pose_homography(Ctx* c, const double* H, const uvo_point
 //                   as an ordered compaction, the valid-inlier count), triangulatePoints + extract_3Dpoints on the compacted pairs
 //                   with the candidate chosen ON THE DEVICE, convert_3Dpoints_camera's z list -- the SECOND and last host sync.
 // Two syncs instead of eight; nothing is uploaded.  Frames whose first method is the homography, and second attempts after a failed
-// acceptance test (VO_utility.cpp:165-178), take the host-pointer operators as before, on the pinned mirrors.  Same kernels, same
-// operands, same order: the results are those of the host-pointer path bit for bit (tests/test_gpu_parity.py, test_gpu_configs.py).
+// acceptance test (VO_utility.cpp:165-178), take the host-pointer operators on the pinned mirrors when the pose stage is 0
+// (uvo_mono_set_pose_stage: the definition) and the chains -- this one, or mono_homography_resident at the end of this file -- when it
+// is 1.  Same kernels, same operands, same order: the results are those of the host-pointer path bit for bit (tests/test_gpu_parity.py,
+// test_gpu_configs.py, test_gpu_mono_resident.py).
 // ------------------------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(1024) void k_mono_prep(const uvo_point2f* __restrict__ x1, const uvo_point2f* __restrict__ x2, const int* __restrict__ count, int cap,
+__global__ __launch_bounds__(1024) void k_mono_prep(const uvo_point2f* __restrict__ x1, const uvo_point2f* __restrict__ x2, const int* __restrict__ count /* null: cap points */, int cap,
                                                     double ax, double bx, double ay, double by, int distance,
                                                     double* __restrict__ q1, double* __restrict__ q2, uvo_point2f* __restrict__ h_x1, uvo_point2f* __restrict__ h_x2,
                                                     int* __restrict__ h_prep)
 {
-    const int tid = threadIdx.x, M = min(*count, cap);
+    const int tid = threadIdx.x, M = count ? min(*count, cap) : cap;
     const double D = (double)distance;
     int lt = 0; double max_lt = -1.0, min_ge = DBL_MAX;
     for (int i = tid; i < M; i += 1024) {
@@ -1806,7 +1835,229 @@ uvo_status mono_essential_resident(Ctx* c, int n, const double* K, int method, d
     out->n_in = w->h_pick[5]; out->valid_inliers = w->h_pick[6]; out->good = w->h_pick[1 + best];
     out->G = w->h_pick[7]; out->n_front = w->h_pick[8];
     out->ok = lmeds && n != modelPoints ? (out->n_in >= modelPoints) : 1;
+    out->pose = out->ok;
     memcpy(out->R, rt.R[best], sizeof(out->R)); memcpy(out->t, rt.t[best], sizeof(out->t));
+    return UVO_OK;
+}
+
+// The host-pointer operator's way into the resident chains (uvo_estimate_relative_pose with the pose stage at 1): its points uploaded
+// once into d_x1 / d_x2, then k_mono_prep on exactly n of them -- q1 / q2 and the pinned mirrors as a frame's stage A leaves them.
+uvo_status mono_stage_points(Ctx* c, const uvo_point2f* p1, const uvo_point2f* p2, int n, const double* K, const uvo_point2f** k1, const uvo_point2f** k2)
+{
+    MonoWs* w = mono_ws(c);
+    if (!w) { c->err = "mono workspace allocation failed"; return UVO_HIP_ERROR; }
+    if (n <= 0 || n > c->cap) { c->err = "point count exceeds the context's max_kpts"; return UVO_CAPACITY; }
+    hipStream_t st = c->stream;
+    UVO_HIP_TRY(c, hipMemcpyAsync(c->d_x1, p1, sizeof(uvo_point2f) * n, hipMemcpyHostToDevice, st));
+    UVO_HIP_TRY(c, hipMemcpyAsync(c->d_x2, p2, sizeof(uvo_point2f) * n, hipMemcpyHostToDevice, st));
+    c->stat_uploads += 2;
+    const double fx = K[0], fy = K[4], cx = K[2], cy = K[5];
+    const double ax = 1. / fx, bx = -cx * ax, ay = 1. / fy, by = -cy * ay;
+    w->h_prep[0] = -1;
+    hipLaunchKernelGGL(k_mono_prep, dim3(1), dim3(1024), 0, st, c->d_x1, c->d_x2, (const int*)nullptr, n, ax, bx, ay, by, 0,
+                       w->q1, w->q2, w->h_x1.data(), w->h_x2.data(), w->h_prep.data());
+    UVO_HIP_TRY(c, hipGetLastError());
+    UVO_HIP_TRY(c, host_sync(c, st));
+    if (w->h_prep[0] < 0 || w->h_prep[1] != n) { c->err = "mono pose stage: the staging kernel did not report"; return UVO_HIP_ERROR; }
+    *k1 = w->h_x1.data(); *k2 = w->h_x2.data();
+    return UVO_OK;
+}
+
+// recover_pose_homography's vote and what follows it, one workgroup behind k_h_vote (pose.hip):
+//   the count of every candidate's z row by the reference's type-punned read (uvo_h_vote.h; VO_utility.cpp:601-602), neighbours taken
+//   from the WRITTEN rows because they cross k_h_vote's workgroups; the choice (first strictly greater than a maximum that starts at 0,
+//   -1 when every count is 0); extract_inliers (VO_utility.cpp:306-329) as the ordered compaction of x1 / x2 by findHomography's mask;
+//   the acceptance count, which in this branch is countNonZero of that same mask (VO_utility.cpp:154-157: the vote does not touch it).
+// pick[0] is the candidate the tail indexes with: never -1 -- without a winner it is 0 and pick[1], the tail's point count, is 0, so
+// k_triangulate_pick and extract_3Dpoints have nothing to do; the host reads the true choice from h_pick[0].
+__global__ __launch_bounds__(1024) void k_h_pick(const uvo_point2f* __restrict__ x1, const uvo_point2f* __restrict__ x2, int n, const uint8_t* __restrict__ hmask,
+                                                 const float* __restrict__ zrows, int row_stride, int ncand, double distance,
+                                                 uvo_point2f* __restrict__ in1, uvo_point2f* __restrict__ in2, int* __restrict__ pick, int* __restrict__ h_pick)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    __shared__ int wtot[16], s_base, s_good[kHVoteMaxCands];
+    if (tid < kHVoteMaxCands) s_good[tid] = 0;
+    if (tid == 0) s_base = 0;
+    __syncthreads();
+    n = n < row_stride ? n : row_stride;
+    ncand = ncand < kHVoteMaxCands ? ncand : kHVoteMaxCands;
+    for (int cnd = 0; cnd < ncand; cnd++) {
+        const float* z = zrows + (size_t)cnd * row_stride;
+        int good = 0;
+        for (int j = tid; j + 1 < n; j += 1024) good += hv_pair_good(z[j], z[j + 1], distance) ? 1 : 0;
+        for (int o = 32; o > 0; o >>= 1) good += __shfl_down(good, o);
+        if (lane == 0 && good) atomicAdd(&s_good[cnd], good);
+    }
+    for (int base = 0; base < n; base += 1024) {
+        const int i = base + tid;
+        const bool keep = i < n && hmask[i] != 0;
+        const unsigned long long bal = __ballot(keep);
+        const int before = __popcll(bal & ((1ull << lane) - 1ull));
+        if (lane == 0) wtot[wv] = __popcll(bal);
+        __syncthreads();
+        int off = s_base;
+        for (int k = 0; k < wv; k++) off += wtot[k];
+        if (keep) { in1[off + before] = x1[i]; in2[off + before] = x2[i]; }
+        __syncthreads();
+        if (tid == 0) { int tot = 0; for (int k = 0; k < 16; k++) tot += wtot[k]; s_base += tot; }
+        __syncthreads();
+    }
+    __syncthreads();                                                 // s_good is complete whether or not the loop above ran
+    if (tid == 0) {
+        int counts[kHVoteMaxCands];
+        for (int k = 0; k < kHVoteMaxCands; k++) counts[k] = s_good[k];
+        const int best = hv_choose(counts, ncand);
+        pick[0] = best < 0 ? 0 : best; pick[1] = best < 0 ? 0 : s_base;
+        h_pick[0] = best; h_pick[1] = counts[0]; h_pick[2] = counts[1]; h_pick[3] = counts[2]; h_pick[4] = counts[3]; h_pick[5] = s_base; h_pick[6] = s_base;
+    }
+}
+
+// findHomography + recover_pose_homography + triangulatePoints + extract_3Dpoints + convert_3Dpoints_camera on the n matched points
+// k_mono_prep left on the device (d_x1 / d_x2: uvo_point2f[n] is the float[2n] the homography kernels read) and mirrored in pinned
+// memory (h_x1 / h_x2).  Nothing is uploaded unless the attempt is handed over (below).  Host waits: the hypothesis scores (a second one when RANSAC's scan goes past the first
+// round, as mono_find_homography), the mask with the winning model, and the end of the chain -- three or four.
+//   on the host, on the pinned mirrors: the sampler's checkSubset; the refit on the inliers (homography_kernel on k points, then the LM
+//       refinement: their sums over the points are sequential in the definition, and that order is what the bits are);
+//       decomposeHomographyMat.
+//   without a wait in between: the candidates' vote (k_h_vote), count / choice / extract_inliers (k_h_pick), triangulatePoints +
+//       extract_3Dpoints under the candidate chosen on the device, convert_3Dpoints_camera's z list (k_mono_scale).
+// What the chain reads and whose CONTENT it leaves as it is: d_x1 / d_x2, q1 / q2, h_x1 / h_x2 -- an essential attempt may follow (or
+// precede) it on the same frame.  Not written at all but on the single-solution hand-over, where mono_recover_pose_homography uploads
+// h_x1 / h_x2 into d_x1 / d_x2 again (identical bytes: two uploads, one wait for its one candidate) and overwrites d_pts4.  What it overwrites: h_subsets, models / nmodels and their mirrors, h_counts / h_medians, masks (the row at 4 * cap), h_mask,
+// h_src / h_dst (the refit's compacted inliers), zrows, in1 / in2, pick, h_pick, h_zs and the lane's triangulation outputs (d_pts4,
+// d_cam1, d_flag, d_good_pts[0], CN_G) -- exactly what mono_essential_resident overwrites too, which reads only q1 / q2, d_x1 / d_x2.
+// out->fallback: a single-solution decomposition (ninf < epsilon: t = 0, normalised by a zero norm) is finished by the host-pointer
+// operator, and so is a vote no candidate won (R, t stay unwritten): the caller runs the host-pointer pose tail, as the definition does
+// (three uploads of the compacted inliers and two waits when the attempt is accepted).  "No upload, at most four waits" holds for the
+// attempts that are not handed over; uvo_mono_pose_stats counts the others as fallbacks with their waits and uploads.
+uvo_status mono_homography_resident(Ctx* c, int n, const double* K, int method, double thr, int maxIters, double confidence, double HOMOGRAPHY_DISTANCE,
+                                    MonoResident* out)
+{
+    memset(out, 0, sizeof(*out));
+    MonoWs* w = mono_ws(c);
+    if (!w) { c->err = "mono workspace allocation failed"; return UVO_HIP_ERROR; }
+    if (n > c->cap) { c->err = "point count exceeds the context's max_kpts"; return UVO_CAPACITY; }
+    out->mask = w->h_mask.data(); out->zs = w->h_zs.data();
+    uint8_t* mask = w->h_mask.data();
+    memset(mask, 0, (size_t)(n > 0 ? n : 0));
+    if (thr <= 0) thr = 3;
+    const int modelPoints = 4;
+    if (n < modelPoints) return UVO_OK;
+    const float* hx1 = reinterpret_cast<const float*>(w->h_x1.data()); const float* hx2 = reinterpret_cast<const float*>(w->h_x2.data());
+    const float* dx1 = reinterpret_cast<const float*>(c->d_x1); const float* dx2 = reinterpret_cast<const float*>(c->d_x2);
+    uint8_t* hmask = w->masks + 4 * (size_t)c->cap;
+    hipStream_t st = c->stream;
+    double H[9];
+    double scratch[171]; int iscratch[18];
+    int result = 0;
+    if (n == 4) {
+        memset(mask, 1, n);
+        UVO_HIP_TRY(c, hipMemsetAsync(hmask, 1, n, st));
+        result = homography_kernel(hx1, hx2, n, H, SArr<1>{scratch}, SArr<1>{scratch + 81}, SArr<1>{scratch + 90}, iscratch) > 0;
+    } else {
+        const bool lmeds = method != 8;
+        const int niters = h_niters(lmeds, confidence, maxIters);
+        if (niters > kMaxHyp) { c->err = "max_iters exceeds the compiled hypothesis capacity (2048)"; return UVO_CAPACITY; }
+        if (lmeds) UVO_TRY(lmeds_capacity(c, w, n));
+        bool failed_first = false;
+        const int nsub = make_subsets(w->h_subsets.data(), niters, modelPoints, n, lmeds ? 1000 : 10000, hx1, hx2, &failed_first);
+        if (nsub > 0) {
+            const int kFirstRound = 128;
+            const int first = (!lmeds && nsub > kFirstRound && !w->h_one_round) ? kFirstRound : nsub;
+            const int npow2 = next_pow2(n);
+            const float thr2 = (float)(thr * thr);
+            // a round of hypotheses: subsets read from pinned memory, counts / medians written to it, the model counts mirrored
+            auto round = [&](int from, int cnt) -> uvo_status {
+                hipLaunchKernelGGL(k_h_hyp, dim3((cnt + kHPerWg - 1) / kHPerWg), dim3(64), 0, st, dx1, dx2, w->h_subsets.data() + (size_t)4 * from, cnt,
+                                   w->models + (size_t)9 * from, w->nmodels + from);
+                hipLaunchKernelGGL(k_h_score, dim3(cnt), dim3(256), lmeds ? sizeof(float) * npow2 : 0, st, dx1, dx2, n, w->models + (size_t)9 * from, w->nmodels + from,
+                                   lmeds ? 1 : 0, thr2, npow2, w->h_counts.data() + from, w->h_medians.data() + from);
+                hipLaunchKernelGGL(k_mirror_words, dim3(std::min(64, (cnt + 255) / 256)), dim3(256), 0, st, w->nmodels + from, w->h_nmodels.data() + from, cnt);
+                UVO_HIP_TRY(c, hipGetLastError());
+                UVO_HIP_TRY(c, host_sync(c, st));
+                return UVO_OK;
+            };
+            UVO_TRY(round(0, first));
+            Winner win;
+            if (lmeds) win = replay_lmeds(w->h_nmodels.data(), w->h_medians.data(), 1, nsub);
+            else {
+                int settled = niters;
+                win = replay_ransac(w->h_nmodels.data(), w->h_counts.data(), 1, first, niters, n, modelPoints, confidence, &settled);
+                if (nsub > kFirstRound) w->h_one_round = settled > kFirstRound;          // as mono_find_homography: the scan's result is the same either way
+                if (first < nsub && settled > first) {
+                    UVO_TRY(round(first, nsub - first));
+                    win = replay_ransac(w->h_nmodels.data(), w->h_counts.data(), 1, nsub, niters, n, modelPoints, confidence);
+                }
+            }
+            if (win.hyp >= 0) {
+                const double final_thr = h_final_threshold(lmeds, thr, n, win.min_median);
+                const double* best = w->models + (size_t)win.hyp * 9;
+                hipLaunchKernelGGL(k_model_mask, dim3((n + 255) / 256), dim3(256), 0, st, 1, nullptr, nullptr, dx1, dx2, n, best,
+                                   (float)(final_thr * final_thr), hmask);
+                UVO_HIP_TRY(c, hipGetLastError());
+                UVO_HIP_TRY(c, hipMemcpyAsync(mask, hmask, n, hipMemcpyDeviceToHost, st));
+                UVO_HIP_TRY(c, hipMemcpyAsync(w->h_models.data(), best, sizeof(double) * 9, hipMemcpyDeviceToHost, st));
+                UVO_HIP_TRY(c, host_sync(c, st));
+                memcpy(H, w->h_models.data(), sizeof(double) * 9);
+                if (lmeds) { int good = 0; for (int i = 0; i < n; i++) good += mask[i]; result = good >= modelPoints; }
+                else result = 1;
+            }
+        }
+    }
+    int k = 0;
+    if (result && n > 4) k = h_compact_refit(hx1, hx2, n, mask, w->h_src.data(), w->h_dst.data(), H);      // on the pinned mirror, which stays as it is
+    else if (result) k = n;
+    if (!result) { memset(mask, 0, (size_t)n); return UVO_OK; }
+    out->ok = 1;
+    out->n_in = out->valid_inliers = k;                                      // extract_inliers' count = countNonZero(mask) (VOU:154-157)
+    // recover_pose_homography (VOU:581-624)
+    double Rs[36], ts[12], ns[12];
+    const int solutions = decompose_homography_mat(H, K, Rs, ts, ns);
+    if (solutions != kHVoteMaxCands) {                                       // the single-solution decomposition: the host-pointer operator's answer
+        int good = 0;
+        UVO_TRY(mono_recover_pose_homography(c, H, w->h_x1.data(), w->h_x2.data(), n, K, HOMOGRAPHY_DISTANCE, out->R, out->t, &good, false));
+        out->good = good; out->pose = good > 0; out->fallback = 1;
+        return UVO_OK;
+    }
+    const double I[9] = {1,0,0,0,1,0,0,0,1}, z[3] = {0,0,0};
+    double P_prev[12], P_vote[4][12], P_cand[4][12];
+    projection_matrix(I, z, K, P_prev);
+    PoseRt rt;
+    for (int cnd = 0; cnd < 4; cnd++) {
+        const double* tb = ts + 3*cnd;
+        projection_matrix(Rs + 9*cnd, tb, K, P_vote[cnd]);                   // the vote: the decomposition's own t (VOU:592)
+        h_candidate_pose(Rs, ts, cnd, rt.R[cnd], rt.t[cnd]);                 // the pose: t / |t| (VOU:615-620)
+        projection_matrix(rt.R[cnd], rt.t[cnd], K, P_cand[cnd]);
+    }
+    UVO_TRY(pose_h_vote(c, P_prev, &P_vote[0][0], solutions, c->d_x1, c->d_x2, n, w->zrows, c->cap));
+    w->h_pick[9] = 0;
+    hipLaunchKernelGGL(k_h_pick, dim3(1), dim3(1024), 0, st, c->d_x1, c->d_x2, n, hmask, w->zrows, c->cap, solutions, HOMOGRAPHY_DISTANCE,
+                       w->in1, w->in2, w->pick, w->h_pick.data());
+    UVO_HIP_TRY(c, hipGetLastError());
+    UVO_TRY(pose_triangulate_extract3d_pick(c, P_prev, &P_cand[0][0], &rt.R[0][0], &rt.t[0][0], K, w->pick, w->in1, w->in2, w->pick + 1, n));
+    hipLaunchKernelGGL(k_mono_scale, dim3(1), dim3(1024), 0, st, rt, w->pick, c->d_good_pts[0], c->d_counts + CN_G, w->h_zs.data(), w->h_pick.data());
+    UVO_HIP_TRY(c, hipGetLastError());
+    UVO_HIP_TRY(c, host_sync(c, st));
+    if (w->h_pick[9] != 1) { c->err = "mono pose stage: the device chain did not report"; return UVO_HIP_ERROR; }
+    const int best = w->h_pick[0];
+    if (w->h_pick[5] != k || best < -1 || best > 3) { c->err = "mono pose stage: the device's inlier count differs from the mask's"; return UVO_HIP_ERROR; }
+    if (best < 0) { out->fallback = 1; return UVO_OK; }                      // no winner: R, t unwritten (VOU:611)
+    out->good = w->h_pick[1 + best];
+    out->G = w->h_pick[7]; out->n_front = w->h_pick[8];
+    out->pose = 1;
+    memcpy(out->R, rt.R[best], sizeof(out->R)); memcpy(out->t, rt.t[best], sizeof(out->t));
+    return UVO_OK;
+}
+
+// extract_inliers' output of the resident chain that just ran (in1 / in2 on the device), for the host-pointer operator
+uvo_status mono_resident_inliers(Ctx* c, int n_in, uvo_point2f* in1, uvo_point2f* in2)
+{
+    MonoWs* w = static_cast<MonoWs*>(c->mono_ws);
+    if (!w || n_in < 0 || n_in > c->cap) { c->err = "mono pose stage: no resident inliers to read"; return UVO_INVALID_ARG; }
+    if (n_in == 0) return UVO_OK;
+    UVO_HIP_TRY(c, hipMemcpyAsync(in1, w->in1, sizeof(uvo_point2f) * n_in, hipMemcpyDeviceToHost, c->stream));
+    UVO_HIP_TRY(c, hipMemcpyAsync(in2, w->in2, sizeof(uvo_point2f) * n_in, hipMemcpyDeviceToHost, c->stream));
+    UVO_HIP_TRY(c, host_sync(c, c->stream));
     return UVO_OK;
 }
 

@@ -116,6 +116,22 @@ __global__ __launch_bounds__(kTriThreads) void k_triangulate_pick(Mat34 P1, Pose
     extract3d_point(X, LN.x1[i], LN.x2[i], c1, pc.c2[b], tol, LN.cam1, LN.flag, i);
 }
 
+// recover_pose_homography's vote (VO_utility.cpp:590-600): every candidate of decomposeHomographyMat (blockIdx.y) triangulates every point
+// pair under K [I | 0] and its own K [R | t]; convert_from_homogeneous_coords' float z (VO_utility.cpp:71-83: the column times
+// (float)(1.0 / (double)w), + 0.f) goes into the candidate's row of `zrows` (row_stride floats apart).  The count over neighbouring
+// entries crosses workgroup boundaries, so it is taken from the written rows by the kernel behind this one (mono.hip: k_h_pick).
+struct HVoteCands { Mat34 P2[4]; };
+__global__ __launch_bounds__(kTriThreads) void k_h_vote(Mat34 P1, HVoteCands hc, const uvo_point2f* __restrict__ x1, const uvo_point2f* __restrict__ x2, int n,
+                                                        float* __restrict__ zrows, int row_stride)
+{
+    const int cnd = blockIdx.y & 3, i = blockIdx.x * kTriThreads + threadIdx.x;
+    __shared__ double lds[kTriLdsDoubles];
+    if (i >= n || i >= row_stride) return;
+    const float4 p = triangulate_point(P1, hc.P2[cnd], x1[i], x2[i], lds);
+    const float inv = (float)(1.0 / (double)p.w);
+    zrows[(size_t)cnd * row_stride + i] = p.z * inv + 0.f;
+}
+
 // ---------------------------------------------------------------- extract_3Dpoints
 // stage A on caller-provided homogeneous points (uvo_extract_3d_points)
 __global__ __launch_bounds__(256) void k_extract3d_a(const float4* pts4, const uvo_point2f* k1, const uvo_point2f* k2,
@@ -1001,6 +1017,20 @@ uvo_status pose_triangulate_extract3d_pick(Ctx* c, const double* P1, const doubl
     Ex3Lane e = ex3_lane(c, 0, d_n, nullptr);
     e.xc = d_in2;
     hipLaunchKernelGGL(k_extract3d_b, dim3(1), dim3(1024), 0, c->stream, e, n_max, c->p.MIN_NUM_3DPOINTS, extract3d_force_seq());
+    UVO_HIP_TRY(c, hipGetLastError());
+    return UVO_OK;
+}
+
+// the vote's z rows of `ncand` (1 .. 4) candidates (P2x4: ncand x 12) on the n point pairs d_x1 / d_x2, one launch (k_h_vote)
+uvo_status pose_h_vote(Ctx* c, const double* P1, const double* P2x4, int ncand, const uvo_point2f* d_x1, const uvo_point2f* d_x2, int n, float* d_zrows, int row_stride)
+{
+    if (n <= 0) return UVO_OK;
+    if (ncand < 1 || ncand > 4 || n > row_stride) { c->err = "homography vote: candidate or point count outside the rows"; return UVO_INVALID_ARG; }
+    Mat34 a; memcpy(a.v, P1, sizeof(a.v));
+    HVoteCands hc;
+    for (int k = 0; k < 4; k++) memcpy(hc.P2[k].v, P2x4 + 12 * (k < ncand ? k : 0), sizeof(hc.P2[k].v));
+    StageTimer t(c, ST_TRIANGULATE);
+    hipLaunchKernelGGL(k_h_vote, dim3((n + kTriThreads - 1) / kTriThreads, ncand), dim3(kTriThreads), 0, c->stream, a, hc, d_x1, d_x2, n, d_zrows, row_stride);
     UVO_HIP_TRY(c, hipGetLastError());
     return UVO_OK;
 }

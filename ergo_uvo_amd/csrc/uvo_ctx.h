@@ -120,6 +120,10 @@ struct Shared {
     // cv::solvePnPRansac's `flags` (uvo_ctx_set_pnp_method): 1 EPnP; 3 DLS and 4 UPNP run EPnP in OpenCV 4.5; 2 P3P: a four-point RANSAC
     // kernel (k_pnp_hyp_p3p), the final refit stays EPnP.  uvo_ctx_set_params leaves it alone.
     int pnp_method = 1;
+    // uvo_mono_set_pose_stage: 0 = essential-first attempts resident, the rest through the host-pointer operators (the definition, and the
+    // default: profiles/mono_pose_resident.json); 1 = every attempt of estimate_relative_pose resident (mono.hip:
+    // mono_homography_resident)
+    int mono_pose_stage = 0;
     // ---- streams ----
     // The pipeline's HIP streams belong to the context, by role (0 stage A, 1 PnP) and concurrency slot; a lane's `stream` / `pnp_stream`
     // are handles assigned per entry (ctx.hip: "streams by role and slot"), never created or destroyed by the lane.
@@ -256,6 +260,11 @@ struct Ctx {
     int as_w = 0;                                // the as-buffer this lane writes next
     struct Pending { bool used = false; };
     Pending pending;                             // this lane's pair
+    // The mono pose stage's route counters: attempts = {E resident, H resident, E host-pointer, H host-pointer}; first_method 1 essential,
+    // 0 homography, -1 the frame never reached estimate_relative_pose; host waits and queued point-list uploads of the stage; fallbacks
+    struct MonoPoseStats { int attempts[4] = {0, 0, 0, 0}, first_method = -1, host_waits = 0, uploads = 0, fallbacks = 0; };
+    unsigned stat_waits = 0, stat_uploads = 0;   // running counts of this lane's host waits (host_sync, read_counts) and point-list uploads; they wrap (unsigned), the pose stage reads differences
+    MonoPoseStats mono_pstats;                   // of the last frame a mono entry returned (lane 0) / of the last operator call
     // stage-B worker of this lane
     struct BJob {
         int state = 0;                           // 0 idle, 1 queued, 2 done
@@ -267,6 +276,7 @@ struct Ctx {
         uvo_mono_result mres;                    // counters and flags of the frame (pose, SF, velocity are filled by collect)
         bool pose_written = false; double R[9], t[3];      // estimate_relative_pose wrote R, t (kept from the previous frame otherwise)
         bool sf_written = false; double SF = 0;
+        MonoPoseStats pstats;                    // which routes the frame's pose stage took (uvo_mono_pose_stats)
     } job;
     // mono pipeline: this lane's keypoints/descriptors are ready (evDet); the following frame has finished reading them (evPrevRead)
     hipEvent_t evDet = nullptr, evPrevRead = nullptr; bool prev_read_pending = false;
@@ -384,6 +394,7 @@ uvo_status pose_as_triangulate(Ctx* c, hipStream_t st, int buf, const int* d_n, 
                                const double* R2, const double* t2, const double* K1, const double* K2);
 uvo_status pose_triangulate_extract3d_pick(Ctx* c, const double* P1, const double* P2x4, const double* Rx4, const double* tx4, const double* K,
                                            const int* d_best, const uvo_point2f* d_in1, const uvo_point2f* d_in2, const int* d_n, int n_max);
+uvo_status pose_h_vote(Ctx* c, const double* P1, const double* P2x4, int ncand, const uvo_point2f* d_x1, const uvo_point2f* d_x2, int n, float* d_zrows, int row_stride);
 uvo_status pose_extract3d(Ctx* c, int slot, const double* R1, const double* t1, const double* R2, const double* t2,
                           const double* K1, const double* K2, const int* d_n, int n_max);
 uvo_status pose_reproject_errors(Ctx* c, const double* world, int n, const double* R, const double* t, const double* K,
@@ -463,12 +474,20 @@ uvo_status mono_find_homography(Ctx* c, const uvo_point2f* p1, const uvo_point2f
                                 double confidence, double* H, uint8_t* mask, int* ok);
 int decompose_homography_mat(const double* H, const double* K, double* Rs, double* ts, double* ns);
 // the mono loop's pose stage on the matched points left on the device (mono.hip, "RESIDENT ON THE DEVICE")
-struct MonoResident { int ok, n_in, valid_inliers, good, G, n_front; double E[9], R[9], t[3]; const uint8_t* mask; const double* zs; };   // mask, zs: pinned, valid until the lane's next frame
+// ok: the estimator produced a model; pose: R, t were written; fallback: the chain handed the attempt over to the host-pointer route
+// (homography only: a single-solution decomposition, or a vote no candidate won) -- the pose tail then runs on host-compacted inliers
+struct MonoResident { int ok, n_in, valid_inliers, good, G, n_front, pose, fallback; double E[9], R[9], t[3]; const uint8_t* mask; const double* zs; };   // mask, zs: pinned, valid until the lane's next frame
 uvo_status mono_prep_launch(Ctx* c, hipStream_t st, const double* K, int distance);
 int mono_prep_method(Ctx* c, int M, const uvo_point2f** k1, const uvo_point2f** k2);      // select_estimation_method's result (1 essential, 0 homography, -1 not reported) + the pinned point mirrors
 uvo_status mono_essential_resident(Ctx* c, int n, const double* K, int method, double prob, double threshold, int maxIters, MonoResident* out);
+uvo_status mono_homography_resident(Ctx* c, int n, const double* K, int method, double thr, int maxIters, double confidence, double HOMOGRAPHY_DISTANCE,
+                                    MonoResident* out);
+uvo_status mono_resident_inliers(Ctx* c, int n_in, uvo_point2f* in1, uvo_point2f* in2);      // what the chain that just ran left in in1 / in2 (device), to the host
+// the host-pointer operator's way in: its n points staged once into d_x1 / d_x2, then what k_mono_prep leaves (q1, q2, the pinned mirrors)
+uvo_status mono_stage_points(Ctx* c, const uvo_point2f* p1, const uvo_point2f* p2, int n, const double* K, const uvo_point2f** k1, const uvo_point2f** k2);
 uvo_status mono_recover_pose_homography(Ctx* c, const double* H, const uvo_point2f* p1, const uvo_point2f* p2, int n, const double* K,
-                                        double HOMOGRAPHY_DISTANCE, double* R, double* t, int* max_good);
+                                        double HOMOGRAPHY_DISTANCE, double* R, double* t, int* max_good,
+                                        bool one_launch);      // false: a launch and a wait per candidate (the definition's route); true: one launch, one wait
 void projection_matrix(const double* R, const double* t, const double* K, double* P);
 
 }  // namespace uvo

@@ -79,6 +79,8 @@ struct State {
     bool orb_ranking_sent = false;
     int akaze_suppression = -1;                   // set_akaze_suppression: 0 host, 1 device; -1 = the library's default
     bool akaze_suppression_sent = false;
+    int mono_pose_stage = -1;                     // set_mono_pose_stage: 0 the definition's routes, 1 every attempt resident; -1 = the library's default
+    bool mono_pose_stage_sent = false;
 } g;
 
 [[noreturn]] void raise(uvo_status st, const char* where)
@@ -111,6 +113,7 @@ uvo_ctx* ctx_now()
         g.applied = p;
     }
     if (PNP_METHOD_FLAG >= 1 && PNP_METHOD_FLAG <= 4) set_method_locked(PNP_METHOD_FLAG);
+    if (g.mono_pose_stage >= 0 && !g.mono_pose_stage_sent) { SHIM_TRY(uvo_mono_set_pose_stage(g.ctx, g.mono_pose_stage), "uvo_mono_set_pose_stage"); g.mono_pose_stage_sent = true; }
     return g.ctx;
 }
 
@@ -166,7 +169,7 @@ void shutdown()
 {
     std::lock_guard<std::mutex> lk(g.mu);
     if (g.ctx) { uvo_ctx_destroy(g.ctx); g.ctx = nullptr; }
-    g.orb_pattern_sent = false; g.orb_ranking_sent = false; g.akaze_suppression_sent = false; g.pnp_method = 1;
+    g.orb_pattern_sent = false; g.orb_ranking_sent = false; g.akaze_suppression_sent = false; g.mono_pose_stage_sent = false; g.pnp_method = 1;
 }
 void set_orb_ranking(int where)
 {
@@ -181,6 +184,13 @@ void set_akaze_suppression(int where)
     std::lock_guard<std::mutex> lk(g.mu);
     g.akaze_suppression = where;
     g.akaze_suppression_sent = false;
+}
+void set_mono_pose_stage(int where)
+{
+    if (where != 0 && where != 1) throw Error(UVO_INVALID_ARG, "set_mono_pose_stage: 0 (essential-first resident, the rest through the host-pointer operators) or 1 (every attempt resident)");
+    std::lock_guard<std::mutex> lk(g.mu);
+    g.mono_pose_stage = where;
+    g.mono_pose_stage_sent = false;
 }
 void set_orb_pattern(const int* pattern1024)
 {

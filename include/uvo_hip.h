@@ -377,6 +377,29 @@ uvo_status uvo_mono_submit(uvo_ctx* c, const uint8_t* img, int w, int h, int str
 uvo_status uvo_mono_collect(uvo_ctx* c, double dt, uvo_mono_result* out);
 /* last step's intermediates: "kps", "matches", "mask", "good_pts" */
 int        uvo_mono_get(uvo_ctx* c, const char* what, void* out, int cap_bytes);
+/* Where estimate_relative_pose's attempts (VO_utility.cpp:134-180) of the mono loop run.
+ *   0  a first attempt with the essential matrix is a device-resident chain (two host waits, nothing uploaded); a frame whose first
+ *      method is the homography, and every second attempt (VO_utility.cpp:165-178), go through the host-pointer operators
+ *      (uvo_find_homography / uvo_recover_pose_homography / uvo_find_essential_mat / uvo_recover_pose on the pinned point mirrors, then
+ *      three uploads for the triangulation).  This route is the definition, and the default.
+ *   1  every attempt is a device-resident chain: findHomography's hypothesis rounds and mask (VO_utility.cpp:152), the vote of
+ *      recover_pose_homography among decomposeHomographyMat's candidates including the type-punned count of VO_utility.cpp:601-602,
+ *      extract_inliers, triangulatePoints + extract_3Dpoints (visual_odometry.h:355-356) and convert_3Dpoints_camera's z list without
+ *      a host wait in between; at most four waits per homography attempt, nothing uploaded.  checkSubset, the refit with its LM
+ *      refinement and decomposeHomographyMat stay on the host.  A single-solution decomposition and a vote without a winner are
+ *      finished by route 0 from that point (counted as fallbacks).  uvo_estimate_relative_pose on host pointers then stages its points
+ *      once and takes the same chains.
+ * Results do not depend on the value.  1 is faster wherever a frame takes a homography attempt, synchronously and with fourteen frames
+ * in flight, and level with 0 on essential-only sequences; with six frames in flight at the shipped 0.1-px thresholds it measured level
+ * too (profiles/mono_pose_resident.json), which is why it is not the default.  Refused with UVO_INVALID_ARG for other values, and while frames are in flight.  The master
+ * context's value serves every lane. */
+uvo_status uvo_mono_set_pose_stage(uvo_ctx* c, int where);
+/* Route figures of the last frame uvo_mono_step / uvo_mono_collect (or their frames / compressed forms) returned, or of the last
+ * uvo_estimate_relative_pose call: attempts = {essential resident, homography resident, essential host-pointer, homography
+ * host-pointer}; first_method 1 essential, 0 homography, -1 when the frame never reached estimate_relative_pose; host_waits = waits of
+ * the calling / worker thread for the stream after stage A's counts were read; uploads = host-to-device copies of point lists the stage
+ * queued; fallbacks = resident homography attempts route 0 finished.  Any pointer may be NULL. */
+uvo_status uvo_mono_pose_stats(uvo_ctx* c, int* attempts /* 4 */, int* first_method, int* host_waits, int* uploads, int* fallbacks);
 
 /* ---- get_image (VO_utility.h:105 -> VO_utility.cpp:337-379), the preprocessing in front of detect_features:
  * cv::resize(INTER_AREA) to desired_width x (int)(h / (w / desired_width)) (skipped when the size already matches),

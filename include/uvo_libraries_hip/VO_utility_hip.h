@@ -93,6 +93,10 @@ void     set_orb_ranking(int where);
 // where the "AKAZE" branch's contrast factor, duplicate suppression and refinement run: 1 the device, 0 the host scans
 // (uvo_akaze_set_suppression); results do not depend on it.  Kept across a rebuilt context.
 void     set_akaze_suppression(int where);
+// where estimate_relative_pose's attempts run (uvo_mono_set_pose_stage): 1 every attempt a device-resident chain,
+// 0 only a first attempt with the essential matrix, the rest through the host-pointer operators (the definition, the library's default); results do not depend
+// on it.  Sent to the context at its next use (refused there while frames are in flight).  Kept across a rebuilt context.
+void     set_mono_pose_stage(int where);
 
 // Replacements for the cv:: functions the node loops call directly (visual_odometry.h:355, 631, 647-648, 673).
 void triangulatePoints(const uvocv::Mat& projMatr1, const uvocv::Mat& projMatr2, const std::vector<uvocv::Point2f>& projPoints1,
