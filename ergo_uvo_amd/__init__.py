@@ -261,6 +261,13 @@ class Context:
             raise ValueError("orb_set_pattern: 256 x (x0, y0, x1, y1)")
         self._check(self._lib.uvo_orb_set_pattern(self._h, _p(pat)))
 
+    def surf_set_detection_path(self, which):
+        """Which detection kernels serve SURF: "auto" / 0 (the tuned kernels where they apply -- SURF_OCTAVES_LAYERS 3, at most four octaves --
+        and the general scale-space kernels otherwise) or "general" / 1 (the general kernels and the wide-window descriptor launch for every
+        configuration).  The results do not depend on it; the fused steps take the master context's value."""
+        which = {"auto": 0, "general": 1}.get(which, which)
+        self._check(self._lib.uvo_surf_set_detection_path(self._h, int(which)))
+
     def orb_set_ranking(self, where):
         """Where ORB's two retainBest rankings per level run: "device" / 1 (k_rb_rank, one launch per ranking) or "host" / 0 (the host
         replay over downloaded responses).  The results do not depend on it; the fused steps take the master context's value."""

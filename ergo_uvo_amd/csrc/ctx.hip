@@ -522,7 +522,7 @@ static void destroy_one(uvo_ctx* c)
     sift_ws_free(c);
     akaze_ws_free(c);
     orb_ws_free(c);
-    void* ptrs[] = { c->d_hess_order, c->d_surv, c->d_octpat, c->d_colpart, c->d_DW, c->d_rank, c->d_big_par, c->d_big_patch, c->d_area_tabs, c->d_area_iscale, c->d_ori_w, c->d_mpart, c->d_mscratch, c->d_knn_idx, c->d_knn_dist, c->d_x1, c->d_x2, c->d_xc, c->d_pts4, c->d_cam1,
+    void* ptrs[] = { c->d_hess_order, c->d_gen_tab, c->d_gen_planes, c->d_surv, c->d_octpat, c->d_colpart, c->d_DW, c->d_rank, c->d_big_par, c->d_big_patch, c->d_area_tabs, c->d_area_iscale, c->d_ori_w, c->d_mpart, c->d_mscratch, c->d_knn_idx, c->d_knn_dist, c->d_x1, c->d_x2, c->d_xc, c->d_pts4, c->d_cam1,
                      c->d_flag, c->d_tmp_idx, c->d_tmp_row, c->d_good_pts[0], c->d_good_pts[1], c->d_good_idx[0], c->d_good_idx[1], c->d_opts[0], c->d_opts[1],
                      c->d_ipts[0], c->d_ipts[1], c->d_counts, c->d_countsB, c->d_subsets, c->d_models,
                      c->d_hcount, c->d_inliers, c->d_refit, c->d_pose };
@@ -912,6 +912,17 @@ try {
     (void)hipSetDevice(c->device);
     UVO_TRY(need_idle(c, "uvo_orb_set_ranking"));
     return orb_set_ranking(c, where);
+} UVO_ABI_CATCH(c)
+// which detection kernels serve SURF: 0 the tuned ones where they apply and the general scale-space path otherwise, 1 the general path (and the
+// wide-window descriptor launch) for every configuration; the master context's value serves the lanes
+extern "C" uvo_status uvo_surf_set_detection_path(uvo_ctx* c, int which)
+try {
+    if (!c) return UVO_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    UVO_TRY(need_idle(c, "uvo_surf_set_detection_path"));
+    if (which != 0 && which != 1) return fail(c, UVO_INVALID_ARG, "uvo_surf_set_detection_path: 0 (automatic: the tuned kernels where they apply) or 1 (the general scale-space kernels for every configuration)");
+    c->sh->surf_detection_path = which;
+    return UVO_OK;
 } UVO_ABI_CATCH(c)
 extern "C" uvo_status uvo_retain_best(uvo_ctx* c, const float* responses, const int* start, const int* keep, int nseg, int where, int* order, int cap,
                                       int* out_start, int* depth_limit_hits)

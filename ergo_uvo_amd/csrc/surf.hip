@@ -8,9 +8,13 @@
 //                             3x3x3 NMS + quadratic interpolation; box patterns compile-time; the integral tile is
 //                             staged in LDS (octaves 0-1) or read from the planes (2-3); det planes never leave LDS;
 //                             candidates are appended with one atomic per keypoint
+//   scale_space_det / scale_space_nms : every other configuration (nOctaves 1..8, nOctaveLayers 1..8), and any configuration under
+//                             uvo_surf_set_detection_path(1): determinant planes in global memory, run-time box patterns, the same
+//                             candidate list
 //   order (rank_partial / rank_scatter / big_sort above 8192 candidates) : deterministic ordering (OpenCV's
 //                             KeypointGreater) and the large-window list
 //   descriptor64_small / _big (+ _big_tabs, _big_finish) : INTER_AREA window resample + Haar gradients + 4x4x4 sums
+//   descriptor_wide<ROT> (+ _wide_finish) : the few windows wider than kMaxWin that other scale spaces than the shipped one produce
 // All float arithmetic keeps OpenCV's operation order (int box sum * float weight accumulated in
 // double; no FMA contraction) so results are bit-identical to the CPU restatement.
 #include "uvo_ctx.h"
@@ -320,9 +324,10 @@ __device__ __forceinline__ void solve3f(const float a[3][3], const float b[3], f
 
 // findMaximaInLayer's tail for one 3x3x3 maximum: centre, interpolateKeypoint, SURFInvoker's size check
 // (the caller appends).  `trace` is dx + dy of the centre sample.
-template <int STEP>
-__device__ __forceinline__ bool make_keypoint(float N9[3][9], float val0, float trace, int i, int j, int size, int ds, int octave,
-                                              int w, int h, uvo_keypoint* pkp)
+// (STEP is the octave's sample step: a constant in the tuned kernels through make_keypoint<STEP> below, a run-time value on the
+// general scale-space path, whose octaves go beyond step 8)
+__device__ __forceinline__ bool make_keypoint_step(float N9[3][9], float val0, float trace, int i, int j, int size, int ds, int octave,
+                                                   int w, int h, const int STEP, uvo_keypoint* pkp)
 {
     int sum_i = STEP * (i - (size / 2) / STEP);
     int sum_j = STEP * (j - (size / 2) / STEP);
@@ -352,6 +357,12 @@ __device__ __forceinline__ bool make_keypoint(float N9[3][9], float val0, float 
     if (h + 1 < grad_wav_size || w + 1 < grad_wav_size) return false;
     *pkp = kp;
     return true;
+}
+template <int STEP>
+__device__ __forceinline__ bool make_keypoint(float N9[3][9], float val0, float trace, int i, int j, int size, int ds, int octave,
+                                              int w, int h, uvo_keypoint* pkp)
+{
+    return make_keypoint_step(N9, val0, trace, i, j, size, ds, octave, w, h, STEP, pkp);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1040,6 +1051,120 @@ __global__ void k_hessian_layer_debug(const int32_t* gsum, int w, int h, LayerPa
 }
 
 // ------------------------------------------------------------------------------------------
+// The general scale space: any nOctaves 1..8 x nOctaveLayers 1..8 (fastHessianDetector as written: every layer's determinants as a
+// plane, then findMaximaInLayer over the planes).  The tuned kernels above are compile-time in the five layer sizes of an octave and
+// serve nOctaveLayers == 3, nOctaves <= 4; everything else -- and every configuration under uvo_surf_set_detection_path(1) -- runs
+//   k_scale_space_det   one determinant per sample of every layer that fits the image, from the run-time box patterns
+//                       (k_hessian_layer_debug's arithmetic), into the lane's plane workspace; positions outside a layer's
+//                       sampled region are written as zero, which is what the comparisons of the restatement read there
+//   k_scale_space_nms   3x3x3 strict maxima of the middle layers with findMaximaInLayer's margin, the keypoint tail, and the
+//                       append to the candidate list the tuned path fills (one atomic per wave and image)
+// Nothing here is tuned: a determinant is 32 global loads, and the planes make a round trip through memory.
+// ------------------------------------------------------------------------------------------
+static const int kGenMaxOctaves = 8, kGenMaxLayers = 8;
+struct GenLayer {
+    LayerPat lp;                   // samples_i = 0: the layer does not fit the image and has no plane
+    int step, rows, cols, octave;
+    int nms_margin;                // (size of the layer above / 2) / step + 1: findMaximaInLayer's, for a middle layer
+    int ds;                        // size - size of the layer below
+    long long off;                 // the plane's first float within an image's part of the workspace
+};
+struct GenTab { GenLayer L[kGenMaxOctaves * (kGenMaxLayers + 2)]; };
+static void make_gen_layer(int octave, int layer, int w, int h, GenLayer* g)
+{
+    const int step = 1 << octave, size = (9 + 6 * layer) << octave;
+    memset(g, 0, sizeof(*g));
+    make_pattern(size, &g->lp);
+    g->lp.margin = (size / 2) / step;
+    const bool fits = size <= h && size <= w;
+    g->lp.samples_i = fits ? 1 + (h - size) / step : 0;
+    g->lp.samples_j = fits ? 1 + (w - size) / step : 0;
+    g->step = step; g->rows = h / step; g->cols = w / step; g->octave = octave;
+    g->nms_margin = (((9 + 6 * (layer + 1)) << octave) / 2) / step + 1;
+    g->ds = 6 << octave;
+}
+
+__global__ __launch_bounds__(256) void k_scale_space_det(LaneArgs LA, const GenLayer* __restrict__ tab, float* __restrict__ planes, long long img_floats, int w)
+{
+    const GenLayer& g = tab[blockIdx.y];
+    if (g.lp.samples_i <= 0) return;
+    const int im = blockIdx.z, sw = w + 1;
+    const int32_t* __restrict__ gsum = LA.ip.sum[im];
+    float* __restrict__ det = planes + (size_t)im * img_floats + g.off;
+    const int n = g.rows * g.cols, cols = g.cols, step = g.step, margin = g.lp.margin;
+    for (int idx = blockIdx.x * 256 + threadIdx.x; idx < n; idx += gridDim.x * 256) {
+        const int i = idx / cols, j = idx - i * cols;
+        const int oi = i - margin, oj = j - margin;
+        float d = 0.f;
+        if (oi >= 0 && oi < g.lp.samples_i && oj >= 0 && oj < g.lp.samples_j) {
+            const int32_t* o = gsum + (size_t)(oi * step) * sw + oj * step;
+            float dx, dy, dxy;
+            haar_response(g.lp, [&](int yy, int xx) { return o[(size_t)yy * sw + xx]; }, &dx, &dy, &dxy);
+            d = dx * dy - 0.81f * dxy * dxy;
+        }
+        det[idx] = d;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_scale_space_nms(LaneArgs LA, const GenLayer* __restrict__ tab, const float* __restrict__ planes, long long img_floats,
+                                                         int nlayers, int w, int h, float thr)
+{
+    const CandOut& out = LA.out;
+    const int oct = blockIdx.y / nlayers, l = 1 + blockIdx.y % nlayers;
+    const GenLayer* g3 = tab + oct * (nlayers + 2) + l - 1;            // the layers below, at and above the maxima's
+    const GenLayer& g = g3[1];
+    if (g3[2].lp.samples_i <= 0) return;                               // the layer above does not fit: the margin leaves no sample (and it has no plane)
+    const int im = blockIdx.z, sw = w + 1, cols = g.cols, step = g.step, m = g.nms_margin;
+    const int ni = g.rows - 2 * m, nj = cols - 2 * m;
+    if (ni <= 0 || nj <= 0) return;
+    const int32_t* __restrict__ gsum = LA.ip.sum[im];
+    const float* __restrict__ base = planes + (size_t)im * img_floats;
+    const float* __restrict__ P[3] = { base + g3[0].off, base + g3[1].off, base + g3[2].off };
+    const int n = ni * nj, lane = threadIdx.x & 63;
+    for (int b0 = blockIdx.x * 256; b0 < n; b0 += gridDim.x * 256) {   // (uniform trip count: the ballot below sees whole waves)
+        const int idx = b0 + threadIdx.x;
+        bool ok = false;
+        uvo_keypoint kp;
+        if (idx < n) {
+            const int i = m + idx / nj, j = m + idx % nj;
+            const float val0 = P[1][(size_t)i * cols + j];
+            if (val0 > thr) {
+                float N9[3][9];
+#pragma unroll
+                for (int r = 0; r < 3; r++)
+#pragma unroll
+                    for (int q = 0; q < 9; q++) N9[r][q] = P[r][(size_t)(i + q / 3 - 1) * cols + (j + q % 3 - 1)];
+                bool is_max = true;
+#pragma unroll
+                for (int r = 0; r < 3; r++)
+#pragma unroll
+                    for (int q = 0; q < 9; q++) if (!(r == 1 && q == 4)) is_max = is_max && (val0 > N9[r][q]);
+                if (is_max) {
+                    // the trace plane of the restatement at the centre: dx + dy where the layer was sampled, else the plane's zero
+                    const int oi = i - g.lp.margin, oj = j - g.lp.margin;
+                    float trace = 0.f;
+                    if (oi >= 0 && oi < g.lp.samples_i && oj >= 0 && oj < g.lp.samples_j) {
+                        const int32_t* o = gsum + (size_t)(oi * step) * sw + oj * step;
+                        float dx, dy;
+                        haar_response(g.lp, [&](int yy, int xx) { return o[(size_t)yy * sw + xx]; }, &dx, &dy, nullptr);
+                        trace = dx + dy;
+                    }
+                    ok = make_keypoint_step(N9, val0, trace, i, j, g.lp.size, g.ds, g.octave, w, h, step, &kp);
+                }
+            }
+        }
+        const unsigned long long mk = __ballot(ok);
+        if (mk != 0) {
+            int pos = 0;
+            const int leader = __ffsll((long long)mk) - 1;
+            if (lane == leader) pos = atomicAdd(&out.count[im], __popcll(mk));
+            pos = __shfl(pos, leader) + __popcll(mk & ((1ull << lane) - 1ull));
+            if (ok && pos < out.cap) out.cand[im][pos] = kp;           // beyond the list: the count says so (UVO_CAPACITY), nothing is written
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // deterministic ordering: rank = number of keypoints that sort before this one under OpenCV's
 // KeypointGreater (response desc, size desc, octave desc, y desc, x asc).  The five fields are
 // packed into order-preserving integer keys so a comparison is three 64-bit compares; ranks are
@@ -1062,7 +1187,8 @@ __device__ __forceinline__ SortKey make_sort_key(const uvo_keypoint& kp)
 }
 
 static const int kSmallWin = 128;       // descriptor windows up to this size use the small-LDS kernel
-static const int kMaxWin = 740;         // (int)(21 * 264 * 1.2f / 9) = 739: the window of the largest octave-3 keypoint
+static const int kMaxWin = 740;         // (int)(21 * 264 * 1.2f / 9) = 739: the window of the largest octave-3 keypoint of the shipped 4 x 3 scale space;
+                                        // wider windows (more layers or octaves) stay out of the lists below and go to k_descriptor_wide
 // Large windows (fallback path) are listed in append order by k_rank_scatter and then sorted by descending window size (a (keypoint,
 // column) task of descriptor64_big costs about ceil(win/256) lane passes x ceil((win/21 + 2)/16) tap batches, 1..9 units),
 // which the task dealing of that kernel relies on.  Counting sort, one workgroup per image.
@@ -1175,7 +1301,7 @@ __global__ __launch_bounds__(kOrderThreads) void k_order(LaneArgs LA, const int*
             lo = min(lo, r); hi = max(hi, r);
             const float sc = kp[k].size * 1.2f / 9.0f;          // k_rank_scatter's window size
             const int win_size = (int)((20 + 1) * sc);
-            if (win_size > kSmallWin) { wbin[k] = min(kBigBins - 1, max(0, kBigBins - 1 - win_size)); atomicAdd(&s_win[wbin[k]], 1); }
+            if (win_size > kSmallWin && win_size <= kMaxWin) { wbin[k] = min(kBigBins - 1, max(0, kBigBins - 1 - win_size)); atomicAdd(&s_win[wbin[k]], 1); }      // (wider: k_descriptor_wide)
         }
     }
 #pragma unroll
@@ -1311,7 +1437,7 @@ __global__ __launch_bounds__(256) void k_rank_scatter(LaneArgs LA)
         // geometry every task of theirs needs (SURFInvoker: win_size, win_offset, start_x/start_y)
         const float sc = kp.size * 1.2f / 9.0f;
         const int win_size = (int)((20 + 1) * sc);
-        if (win_size > kSmallWin) {
+        if (win_size > kSmallWin && win_size <= kMaxWin) {                  // (wider: k_descriptor_wide)
             const float win_offset = -(float)(win_size - 1) / 2;
             big = true;
             par = make_int4(r, win_size, cv_round_f(kp.x + win_offset), cv_round_f(kp.y - win_offset));
@@ -1807,6 +1933,7 @@ __global__ __launch_bounds__(256) void k_descriptor_rot(DescArgs a, int w, int h
         const uvo_keypoint kp = a.kps[im][k];
         const float s = kp.size * 1.2f / 9.0f;
         const int win_size = (int)((20 + 1) * s);
+        if (win_size > kMaxWin) continue;                               // k_descriptor_wide<true>'s keypoint (uniform: before any barrier)
         const int bp = win_size | 1;
         const int iscale = a.iscale[min(win_size, kMaxWin)];
         if (tid < 21) tab[tid] = a.tabs[min(win_size, kMaxWin) * 21 + tid];
@@ -1893,6 +2020,178 @@ __global__ __launch_bounds__(256) void k_descriptor_rot(DescArgs a, int w, int h
     }
 }
 
+// Windows wider than kMaxWin (more layers or octaves than the shipped configuration: a keypoint's window reaches 2.8 x the image's
+// smaller side, about 3000 samples at 1080p).  They are few -- tens per 1080p frame -- and kept out of the large-window lists and of
+// k_descriptor_rot: the workgroups walk the ordered keypoints and resample the wide ones, upright (ROT = false) or from the rotated
+// window (ROT = true), a workgroup per destination row dy of the 21 x 21 patch (workgroup b takes row b % 21 of keypoints b / 21,
+// b / 21 + gridDim.x / 21, ..); k_descriptor_wide_finish turns the patches into descriptors.  The patch rows go to the large-window
+// patch scratch at the keypoint's own index: k_descriptor64_big_finish, earlier on the same stream, is done with it.
+// The LDS does not grow with the window: a destination row only needs the window rows i of its own taps, staged kWideRows at a
+// time -- buf[dx][i] = sum over the taps j of column dx of WIN[i][j] * alpha_j (resizeArea_'s table order; integer block sums where
+// the scale is an integer to within DBL_EPSILON: resizeAreaFast_) -- and thread dx accumulates PATCH[dy][dx] over them in order.
+// The tables are evaluated here in double (area_tab, as describe_keypoint does).  ROT: thread i walks its row's running double
+// sums over the whole window, as k_descriptor_rot does; a row's float start position is carried from row 0 by thread 0.
+static const int kWideRows = 128;
+template <bool ROT>
+__global__ __launch_bounds__(256) void k_descriptor_wide(DescArgs a, int w, int h, uint8_t* __restrict__ patch)
+{
+    const int im = blockIdx.y, tid = threadIdx.x;
+    const int n = *a.n[im];
+    __shared__ float buf[21][kWideRows + 1];
+    __shared__ float s_sx[kWideRows], s_sy[kWideRows];
+    __shared__ AreaTab tab[21];
+    const uint8_t* __restrict__ img = a.img[im];
+    const int dy = blockIdx.x % 21;
+    for (int k = blockIdx.x / 21; k < n; k += gridDim.x / 21) {
+        const uvo_keypoint kp = a.kps[im][k];
+        const float s = kp.size * 1.2f / 9.0f;
+        const int win_size = (int)((20 + 1) * s);
+        if (win_size <= kMaxWin) continue;                              // (uniform: before any barrier)
+        const double scale = 1. / ((double)21 / win_size);
+        const int isc = cv_round_d(scale);
+        const int iscale = fabs(scale - isc) < DBL_EPSILON ? isc : 0;  // non-zero: resizeAreaFast_
+        if (tid < 21) tab[tid] = area_tab(tid, win_size, scale);
+        const float win_offset = -(float)(win_size - 1) / 2;
+        // upright: WIN[i][j] = img(clamp(start_y - j), clamp(start_x + i))
+        const int start_x = cv_round_f(kp.x + win_offset), start_y = cv_round_f(kp.y - win_offset);
+        // rotated: SURFInvoker's sin_dir / cos_dir and the first row's start position (k_descriptor_rot)
+        float sin_dir = 0.f, cos_dir = 0.f;
+        float ck_x = 0.f, ck_y = 0.f;                                 // start position of window row 0
+        if (ROT) {
+            float descriptor_dir = kp.angle;
+            descriptor_dir *= (float)(3.14159265358979323846 / 180);
+            double sd, cd;
+            det_sincos((double)descriptor_dir, &sd, &cd);
+            sin_dir = -(float)sd; cos_dir = (float)cd;
+            ck_x = kp.x + win_offset * cos_dir + win_offset * sin_dir;
+            ck_y = kp.y - win_offset * sin_dir + win_offset * cos_dir;
+        }
+        __syncthreads();
+        // taps of destination index d (the same table serves rows and columns): [begin, end)
+        auto tap_begin = [&](int d) { return iscale ? d * iscale : (tab[d].has_first ? tab[d].sx1 - 1 : tab[d].sx1); };
+        auto tap_end = [&](int d) { return iscale ? (d + 1) * iscale : (tab[d].has_last ? tab[d].sx2 + 1 : tab[d].sx2); };
+        const int ncols1 = w - 1, nrows1 = h - 1;
+        {
+            const int r_begin = tap_begin(dy), r_end = tap_end(dy);
+            const AreaTab ty = tab[dy];
+            float vsum = 0.f; int visum = 0;                            // thread dx < 21: PATCH[dy][dx] so far
+            for (int r0 = r_begin; r0 < r_end; r0 += kWideRows) {
+                const int nr = min(kWideRows, r_end - r0);
+                if (ROT && tid == 0) {                                  // start_x += sin_dir; start_y += cos_dir, row after row (float), from row 0
+                    float x = ck_x, y = ck_y;
+                    for (int r = 0; r < r0 + nr; r++, x += sin_dir, y += cos_dir)
+                        if (r >= r0) { s_sx[r - r0] = x; s_sy[r - r0] = y; }
+                }
+                if (ROT) __syncthreads();
+                if (ROT) {
+                    if (tid < nr) {
+                        double pixel_x = s_sx[tid], pixel_y = s_sy[tid];
+                        int dx = 0;
+                        float b = 0.f;
+                        int isum = 0;
+                        AreaTab tx = tab[0];
+                        for (int j = 0; j < win_size; j++, pixel_x += cos_dir, pixel_y -= sin_dir) {
+                            const int ix = cv_floor_d(pixel_x), iy = cv_floor_d(pixel_y);
+                            int v;
+                            if ((unsigned)ix < (unsigned)ncols1 && (unsigned)iy < (unsigned)nrows1) {
+                                const float fa = (float)(pixel_x - ix), fb = (float)(pixel_y - iy);
+                                const uint8_t* ip = img + (size_t)iy * w + ix;
+                                v = cv_round_f(ip[0] * (1.f - fa) * (1.f - fb) + ip[1] * fa * (1.f - fb) + ip[w] * (1.f - fa) * fb + ip[w + 1] * fa * fb) & 255;
+                            } else {
+                                int x = cv_round_d(pixel_x), y = cv_round_d(pixel_y);
+                                x = x > 0 ? x : 0; x = x < ncols1 ? x : ncols1; y = y > 0 ? y : 0; y = y < nrows1 ? y : nrows1;
+                                v = img[(size_t)y * w + x];
+                            }
+                            if (iscale) {
+                                isum += v;
+                                if ((j + 1) % iscale == 0) { if (dx < 21) reinterpret_cast<int*>(&buf[dx][0])[tid] = isum; isum = 0; dx++; }
+                            } else {
+                                while (dx < 21) {                       // k_descriptor_rot's walk of the column table
+                                    const int c_begin = tx.has_first ? tx.sx1 - 1 : tx.sx1, c_end = tx.has_last ? tx.sx2 + 1 : tx.sx2;
+                                    if (j < c_begin) break;
+                                    if (j < c_end) {
+                                        const float alpha = j < tx.sx1 ? tx.a_first : (j < tx.sx2 ? tx.a_mid : tx.a_last);
+                                        b += v * alpha;
+                                    }
+                                    if (j + 1 >= c_end) {
+                                        buf[dx][tid] = b; b = 0.f; dx++;
+                                        if (dx < 21) tx = tab[dx];
+                                        continue;
+                                    }
+                                    break;
+                                }
+                            }
+                        }
+                    }
+                } else {
+                    for (int e = tid; e < 21 * nr; e += 256) {          // lanes along the window rows = image x
+                        const int dx = e / nr, il = e - dx * nr;
+                        int x = start_x + r0 + il; x = x > 0 ? x : 0; x = x < ncols1 ? x : ncols1;
+                        const int c_begin = tap_begin(dx), c_end = tap_end(dx);
+                        // taps fetched eight at a time (independent loads in flight; the row clamp makes every one of them valid),
+                        // accumulated in order, as descriptor64_big's scalar path does
+                        const AreaTab tx = tab[dx];
+                        float b = 0.f;
+                        int isum = 0;
+                        for (int c0 = c_begin; c0 < c_end; c0 += 8) {
+                            int v[8];
+#pragma unroll
+                            for (int q = 0; q < 8; q++) {
+                                int y = start_y - (c0 + q); y = y > 0 ? y : 0; y = y < nrows1 ? y : nrows1;
+                                v[q] = img[(size_t)y * w + x];
+                            }
+#pragma unroll
+                            for (int q = 0; q < 8; q++) {
+                                const int cc = c0 + q;
+                                if (cc >= c_end) continue;
+                                if (iscale) isum += v[q];
+                                else {
+                                    const float alpha = cc < tx.sx1 ? tx.a_first : (cc < tx.sx2 ? tx.a_mid : tx.a_last);
+                                    b += v[q] * alpha;
+                                }
+                            }
+                        }
+                        if (iscale) reinterpret_cast<int*>(&buf[dx][0])[il] = isum;
+                        else buf[dx][il] = b;
+                    }
+                }
+                __syncthreads();
+                if (tid < 21) {                                         // the vertical pass over these rows, in row order
+                    if (iscale) { for (int r = 0; r < nr; r++) visum += reinterpret_cast<const int*>(&buf[tid][0])[r]; }
+                    else for (int r = 0; r < nr; r++) {
+                        const int rr = r0 + r;
+                        const float beta = rr < ty.sx1 ? ty.a_first : (rr < ty.sx2 ? ty.a_mid : ty.a_last);
+                        vsum += beta * buf[tid][r];
+                    }
+                }
+                __syncthreads();                                        // buf and the start positions are reused
+            }
+            if (tid < 21) {
+                int result;
+                if (!iscale) result = sat_u8(vsum);
+                else if (iscale == 2) result = (visum + 2) >> 2;
+                else { const float sc = 1.f / (iscale * iscale); result = sat_u8(visum * sc); }
+                patch[((size_t)im * a.cap + k) * kPatchStride + dy * 21 + tid] = (uint8_t)result;
+            }
+        }
+        __syncthreads();                                                // tab is rewritten for the next keypoint
+    }
+}
+__global__ __launch_bounds__(256) void k_descriptor_wide_finish(DescArgs a, const uint8_t* __restrict__ patch)
+{
+    const int im = blockIdx.y, tid = threadIdx.x;
+    const int n = *a.n[im];
+    __shared__ int PATCH[21][21];
+    for (int k = blockIdx.x; k < n; k += gridDim.x) {
+        const float s = a.kps[im][k].size * 1.2f / 9.0f;
+        if ((int)((20 + 1) * s) <= kMaxWin) continue;                   // (uniform: before any barrier)
+        const uint8_t* src = patch + ((size_t)im * a.cap + k) * kPatchStride;
+        for (int o = tid; o < 441; o += 256) PATCH[o / 21][o % 21] = src[o];
+        __syncthreads();
+        describe_tail(a, im, k, PATCH);
+        __syncthreads();
+    }
+}
 
 // small windows: one workgroup per keypoint (block bx of nbx of the launch's small-window part)
 __device__ __forceinline__ void descriptor64_small(const DescArgs& a, int w, int h, int bx, int nbx, int im)
@@ -2242,12 +2541,63 @@ static bool merged_launch(const Ctx* c)
 // block order of the merged detection launch.  Idempotent; surf_detect calls it for the image at hand, and the pipeline calls it
 // for every lane as soon as the stream's image size is known, so that a lane's first pair does not pay two allocations, two
 // uploads and four host syncs inside somebody's timed loop.
+// which detection kernels serve this lane's configuration (uvo_surf_set_detection_path; the master context's value)
+static bool general_path(const Ctx* c)
+{
+    return c->sh->surf_detection_path == 1 || c->p.SURF_OCTAVES_LAYERS != 3 || c->p.SURF_OCTAVES_NUMBER > 4;
+}
+// the widest descriptor window a w x h image can produce under the lane's configuration: a keypoint of middle layer l is at most as
+// large as layer l + 1 (interpolateKeypoint moves the size by at most ds), and has maxima only where that layer fits the image
+static int widest_window(const Ctx* c, int w, int h)
+{
+    int win = 0;
+    for (int o = 0; o < c->p.SURF_OCTAVES_NUMBER; o++)
+        for (int l = 1; l <= c->p.SURF_OCTAVES_LAYERS; l++) {
+            const int size = (9 + 6 * (l + 1)) << o;
+            if (size > w || size > h) break;
+            const float sc = (float)size * 1.2f / 9.0f;
+            win = std::max(win, (int)((20 + 1) * sc));
+        }
+    return win;
+}
+// The general path's layer table and determinant planes (see k_scale_space_det): the table follows the image size and the
+// configuration, the planes are sized from max_w x max_h and the configuration, so a sequence allocates once.
+static uvo_status general_prepare(Ctx* c, int w, int h)
+{
+    const int no = c->p.SURF_OCTAVES_NUMBER, nl = c->p.SURF_OCTAVES_LAYERS + 2;
+    std::vector<unsigned char> raw(sizeof(GenTab), 0);
+    GenTab* tab = reinterpret_cast<GenTab*>(raw.data());
+    long long off = 0, need = 0;
+    for (int o = 0; o < no; o++) for (int l = 0; l < nl; l++) {
+        GenLayer* g = &tab->L[o * nl + l];
+        make_gen_layer(o, l, w, h, g);
+        g->off = off;
+        off += (long long)g->rows * g->cols;
+        need += (long long)(c->max_h >> o) * (c->max_w >> o);
+    }
+    if (c->h_gen_tab == raw && c->gen_planes_cap >= (size_t)need * 2) return UVO_OK;
+    UVO_HIP_TRY(c, hipStreamSynchronize(c->stream));                  // nothing may still read the old table or planes
+    if (!c->d_gen_tab) UVO_HIP_TRY(c, hipMalloc(&c->d_gen_tab, sizeof(GenTab)));
+    if (c->gen_planes_cap < (size_t)need * 2) {
+        if (c->d_gen_planes) (void)hipFree(c->d_gen_planes);
+        c->d_gen_planes = nullptr; c->gen_planes_cap = 0;
+        UVO_HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_gen_planes), sizeof(float) * (size_t)need * 2));
+        c->gen_planes_cap = (size_t)need * 2;
+    }
+    c->gen_img_floats = (long long)(c->gen_planes_cap / 2);
+    c->h_gen_tab = raw;
+    UVO_HIP_TRY(c, hipMemcpyAsync(c->d_gen_tab, c->h_gen_tab.data(), sizeof(GenTab), hipMemcpyHostToDevice, c->stream));
+    UVO_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return UVO_OK;
+}
+
 uvo_status surf_prepare(Ctx* c, int w, int h)
 {
-    if (c->p.SURF_OCTAVES_NUMBER < 1 || c->p.SURF_OCTAVES_NUMBER > 4 || c->p.SURF_OCTAVES_LAYERS != 3) {
-        c->err = "SURF: supported nOctaves 1..4, nOctaveLayers 3";
+    if (c->p.SURF_OCTAVES_NUMBER < 1 || c->p.SURF_OCTAVES_NUMBER > kGenMaxOctaves || c->p.SURF_OCTAVES_LAYERS < 1 || c->p.SURF_OCTAVES_LAYERS > kGenMaxLayers) {
+        c->err = "SURF: supported SURF_OCTAVES_NUMBER (nOctaves) 1..8 and SURF_OCTAVES_LAYERS (nOctaveLayers) 1..8";
         return UVO_INVALID_ARG;
     }
+    if (general_path(c)) return general_prepare(c, w, h);
     OctavePat ops[4];
     memset(ops, 0, sizeof(ops));
     for (int o = 0; o < c->p.SURF_OCTAVES_NUMBER; o++) make_octave(o, c->p.SURF_OCTAVES_LAYERS, w, h, &ops[o]);
@@ -2301,7 +2651,21 @@ uvo_status surf_detect(Ctx* c, int nimg, int gate_min_features)
     const LaneArgs LA = lane_args(c, nimg, gate_min_features);
     UVO_TRY(surf_integral_launch(c, LA, nimg));
     const float thr = (float)c->p.SURF_MIN_HESSIAN;
-    {
+    if (general_path(c)) {
+        const int no = c->p.SURF_OCTAVES_NUMBER, nl = c->p.SURF_OCTAVES_LAYERS;
+        const GenLayer* tab = static_cast<const GenLayer*>(c->d_gen_tab);
+        const int gx = std::min(1024, (w * h + 255) / 256);
+        {
+            StageTimer t(c, ST_HESSIAN_O0);
+            hipLaunchKernelGGL(k_scale_space_det, dim3(gx, no * (nl + 2), nimg), dim3(256), 0, c->stream, LA, tab, c->d_gen_planes, c->gen_img_floats, w);
+            UVO_HIP_TRY(c, hipGetLastError());
+        }
+        {
+            StageTimer t(c, ST_HESSIAN_O0 + 1);
+            hipLaunchKernelGGL(k_scale_space_nms, dim3(gx, no * nl, nimg), dim3(256), 0, c->stream, LA, tab, c->d_gen_planes, c->gen_img_floats, nl, w, h, thr);
+            UVO_HIP_TRY(c, hipGetLastError());
+        }
+    } else {
         OctavePat ops[4];
         memset(ops, 0, sizeof(ops));
         for (int o = 0; o < c->p.SURF_OCTAVES_NUMBER; o++) make_octave(o, c->p.SURF_OCTAVES_LAYERS, w, h, &ops[o]);
@@ -2394,6 +2758,10 @@ uvo_status surf_detect(Ctx* c, int nimg, int gate_min_features)
     {
         StageTimer t(c, ST_DESCRIPTOR);
         const size_t lds_small = sizeof(float) * 21 * ((kSmallWin + 3) | 1), lds_big = sizeof(float) * 4 * kBigRow;
+        // windows wider than kMaxWin: only where the configuration and the image size can produce one (never for the shipped configuration), or
+        // under uvo_surf_set_detection_path(1); the launch walks the ordered keypoints and describes the wide ones
+        const bool wide = c->sh->surf_detection_path == 1 || widest_window(c, w, h) > kMaxWin;
+        const int kWideGrid = 128;                             // keypoints walked side by side (x 21 destination rows)
         if (c->p.SURF_UPRIGHT) {
             const int nbig = 1024;                             // 8192 persistent waves for the large-window tasks (512: 80 us, 768..2048: 66-69 us)
             static const int desc_part = getenv("UVO_DESC_PART") ? atoi(getenv("UVO_DESC_PART")) : 0;      // measurement only
@@ -2433,6 +2801,10 @@ uvo_status surf_detect(Ctx* c, int nimg, int gate_min_features)
                 }
             }
             hipLaunchKernelGGL(k_descriptor64_big_finish, dim3(1024, nimg), dim3(256), 0, c->stream, LA);
+            if (wide) {
+                hipLaunchKernelGGL(k_descriptor_wide<false>, dim3(21 * kWideGrid, nimg), dim3(256), 0, c->stream, LA.da, w, h, LA.patch);
+                hipLaunchKernelGGL(k_descriptor_wide_finish, dim3(kWideGrid, nimg), dim3(256), 0, c->stream, LA.da, LA.patch);
+            }
         } else {
             // orientation assignment, then every descriptor from its rotated window (not the shipped configuration)
             const DescArgs& da = LA.da;
@@ -2442,6 +2814,10 @@ uvo_status surf_detect(Ctx* c, int nimg, int gate_min_features)
             if (!rot_attr) { UVO_HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_descriptor_rot), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_rot)); rot_attr = true; }
             hipLaunchKernelGGL(k_surf_orientation, dim3((c->cap + 3) / 4, nimg), dim3(256), 0, c->stream, da, w, h);
             hipLaunchKernelGGL(k_descriptor_rot, dim3(2048, nimg), dim3(256), lds_rot, c->stream, da, w, h);
+            if (wide) {
+                hipLaunchKernelGGL(k_descriptor_wide<true>, dim3(21 * kWideGrid, nimg), dim3(256), 0, c->stream, da, w, h, LA.patch);
+                hipLaunchKernelGGL(k_descriptor_wide_finish, dim3(kWideGrid, nimg), dim3(256), 0, c->stream, da, LA.patch);
+            }
         }
         UVO_HIP_TRY(c, hipGetLastError());
     }
@@ -2451,15 +2827,19 @@ uvo_status surf_detect(Ctx* c, int nimg, int gate_min_features)
 uvo_status surf_hessian_layer_debug(Ctx* c, int octave, int layer, float* det, float* trace)
 {
     const int w = c->img_w, h = c->img_h;
-    if (octave < 0 || octave > 3 || layer < 0 || layer > 4 || w <= 0) { c->err = "hessian_layer: bad octave/layer or no image"; return UVO_INVALID_ARG; }
-    OctavePat op;
-    make_octave(octave, 3, w, h, &op);
+    if (octave < 0 || octave >= kGenMaxOctaves || layer < 0 || layer > c->p.SURF_OCTAVES_LAYERS + 1 || w <= 0) {
+        c->err = "hessian_layer: octave 0..7, layer 0..SURF_OCTAVES_LAYERS + 1 of the context's parameters, after an image";
+        return UVO_INVALID_ARG;
+    }
+    GenLayer op;
+    make_gen_layer(octave, layer, w, h, &op);
     size_t n = (size_t)op.rows * op.cols;
+    if (n == 0) return UVO_OK;                                        // the octave's step exceeds the image: no sample, nothing to write
     float *d_det = nullptr, *d_tr = nullptr;
     UVO_HIP_TRY(c, hipMalloc(&d_det, sizeof(float) * n * 2));
     d_tr = d_det + n;
     UVO_HIP_TRY(c, hipMemsetAsync(d_det, 0, sizeof(float) * n * 2, c->stream));
-    const LayerPat& lp = op.L[layer];
+    const LayerPat& lp = op.lp;
     if (lp.samples_i > 0) {
         dim3 g((lp.samples_j + 255) / 256, lp.samples_i);
         hipLaunchKernelGGL(k_hessian_layer_debug, g, dim3(256), 0, c->stream, c->d_sum[0], w, h, lp, op.step, op.rows, op.cols, d_det, d_tr);

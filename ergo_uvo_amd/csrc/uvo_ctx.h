@@ -124,6 +124,9 @@ struct Shared {
     // default: profiles/mono_pose_resident.json); 1 = every attempt of estimate_relative_pose resident (mono.hip:
     // mono_homography_resident)
     int mono_pose_stage = 0;
+    // uvo_surf_set_detection_path: 0 = the tuned detection kernels where they apply (nOctaveLayers == 3, nOctaves <= 4), the general scale-space
+    // kernels otherwise; 1 = the general kernels, and the wide-window descriptor launch, for every configuration.  Results do not depend on it.
+    int surf_detection_path = 0;
     // ---- streams ----
     // The pipeline's HIP streams belong to the context, by role (0 stage A, 1 PnP) and concurrency slot; a lane's `stream` / `pnp_stream`
     // are handles assigned per entry (ctx.hip: "streams by role and slot"), never created or destroyed by the lane.
@@ -160,6 +163,11 @@ struct Ctx {
     std::vector<unsigned char> h_octpat;         // what d_octpat holds
     uint32_t* d_hess_order = nullptr; size_t d_hess_order_cap = 0;       // merged detection launch: octave and tile (column, row) of every block
     std::vector<uint32_t> h_hess_order; int hess_order_key[3] = {0, 0, 0};
+    // the general scale-space path (surf.hip: k_scale_space_det / _nms), made when this lane first meets a configuration the tuned kernels do not
+    // serve (or uvo_surf_set_detection_path(1)): the layer table of the current image size and configuration, and the determinant planes of
+    // both images, sized from max_w x max_h and the configuration
+    void* d_gen_tab = nullptr; std::vector<unsigned char> h_gen_tab;
+    float* d_gen_planes = nullptr; size_t gen_planes_cap = 0; long long gen_img_floats = 0;
     int4* d_big_par = nullptr; int* d_big_n = nullptr;   // [2][cap] (sorted index, win, start_x, start_y) of large-window keypoints in append order, then [2][cap] by descending win; [2] counts
     struct AreaTab* d_area_tabs = nullptr;       // [kMaxWin + 1][21] INTER_AREA resize tables of every descriptor window size (surf_build_area_tables)
     float* d_ori_w = nullptr;                    // 13 x 13 Gaussian weights of the orientation samples (SURF_UPRIGHT = false)

@@ -144,9 +144,18 @@ uvo_status uvo_ctx_set_pnp_method(uvo_ctx* c, int flag);
  * desc is n x 64 f32, or n x 128 when the context's SURF_EXTENDED is set.  SURF_UPRIGHT = 0 runs the orientation assignment
  * and samples the descriptor window rotated (keypoint.angle = the orientation, 270 when upright).  Overwrites outputs (as
  * detectAndCompute does).  The matcher, the gathers and the stereo / mono steps take the row width from the context's
- * SURF_EXTENDED (64 or 128 floats) end to end. */
+ * SURF_EXTENDED (64 or 128 floats) end to end.
+ * The scale space is SURF::create's: SURF_OCTAVES_NUMBER 1..8 octaves of SURF_OCTAVES_LAYERS 1..8 middle layers (anything else is
+ * UVO_INVALID_ARG at the first detection).  SURF_OCTAVES_LAYERS == 3 with up to four octaves -- the shipped configurations -- runs the
+ * tuned detection kernels; every other pair runs the general scale-space kernels, which keep every layer's determinants as planes in a
+ * workspace the context (each pipeline lane) allocates when it first meets such a configuration, sized from max_w x max_h.  Keypoints
+ * whose descriptor window is wider than the shipped configuration's widest (740 samples) are described by a kernel pair of their own. */
 uvo_status uvo_surf_detect(uvo_ctx* c, const uint8_t* gray, int w, int h, int stride, int mem,
                            uvo_keypoint* kps, float* desc, int cap, int* n);
+/* Which detection kernels serve the SURF branch: 0 = automatic (the default): the tuned kernels where they apply, the general scale-space
+ * kernels otherwise; 1 = the general kernels, and the wide-window descriptor launch, for every configuration.  The results do not depend on
+ * the value.  Anything else is UVO_INVALID_ARG; refused while entries are in flight.  The master context's value serves every lane. */
+uvo_status uvo_surf_set_detection_path(uvo_ctx* c, int which);
 /* ---- detect_features, FEATURE_DETECTOR == "SIFT" (VO_utility.cpp:107-112):
  *     SIFT::create(10000, 3, 0.03, 10, 1.6)->detectAndCompute(img, noArray(), keypoints, descriptors)
  * the five arguments of SIFT::create are passed through (nfeatures <= 0 keeps every keypoint).  gray as for uvo_surf_detect.
@@ -223,7 +232,8 @@ uvo_status uvo_orb_plane(uvo_ctx* c, int level, int what, uint8_t* out, int cap_
  * octave `octave` (0 = the doubled image) of the last uvo_sift_detect, row-major floats to a host buffer; out = NULL reports the size */
 uvo_status uvo_sift_layer(uvo_ctx* c, int octave, int layer, int dog, float* out, int cap_floats, int* w, int* h);
 /* test hooks into the detector's first stages (host outputs): integral image (h+1)x(w+1) s32 of the
- * last image given to uvo_surf_detect / uvo_integral, and one Hessian det/trace layer of it */
+ * last image given to uvo_surf_detect / uvo_integral, and one Hessian det/trace layer of it: octave 0..7, layer 0 ..
+ * SURF_OCTAVES_LAYERS + 1 of the context's parameters, (h >> octave) x (w >> octave) floats each */
 uvo_status uvo_integral(uvo_ctx* c, const uint8_t* gray, int w, int h, int stride, int mem, int32_t* sum);
 uvo_status uvo_hessian_layer(uvo_ctx* c, int octave, int layer, float* det, float* trace);
 
