@@ -4,10 +4,11 @@
 // Pipeline per image (both images of a stereo pair go through every launch together, blockIdx.z):
 //   integral_rows / integral_colsum / integral_colfinal : u8 -> s32 integral image (HBM-bound), row-major and
 //                             de-interleaved by (row & 3, col & 3) for the coarse octaves
-//   hessian_nms_c<O> (O = 0, 1) / hessian_nms_p<O> (O = 2, 3) : per octave, fused box-filter Hessian (5 layers) +
-//                             3x3x3 NMS + quadratic interpolation; box patterns compile-time; the integral tile is
+//   hessian_nms_all / hessian_finish : nOctaveLayers = 3 with nOctaves 1..4, every octave's tiles in one launch: fused box-filter
+//                             Hessian (3 middle layers) + 3x3x3 NMS; box patterns compile-time; the integral tile is
 //                             staged in LDS (octaves 0-1) or read from the planes (2-3); det planes never leave LDS;
-//                             candidates are appended with one atomic per keypoint
+//                             survivors are appended with one atomic per tile, and hessian_finish evaluates their outer-layer
+//                             neighbours, interpolates and appends the keypoints
 //   scale_space_det / scale_space_nms : every other configuration (nOctaves 1..8, nOctaveLayers 1..8), and any configuration under
 //                             uvo_surf_set_detection_path(1): determinant planes in global memory, run-time box patterns, the same
 //                             candidate list
@@ -557,41 +558,12 @@ __device__ __forceinline__ ImgRsrc img_rsrc(const uint8_t* img, int bytes)
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(img), 0, bytes, 0x00020000);      // raw buffer, dword data format (gfx9 family)
 }
 
-// The same layer from the de-interleaved planes in global memory (octaves 2 and 3: the integral tile of one
-// workgroup would not fit LDS).  Sample (oi, oj) has its top-left at pixel (STEP*oi, STEP*oj); corner (dy, dx) is in
-// plane (dy & 3, dx & 3) at [STEP/4*oi + dy/4][STEP/4*oj + dx/4]: plane and offsets are compile-time, lanes along oj.
-template <int O, int L, int TW, int TH, int NT, class OP>
-__device__ __forceinline__ void det_layer_p(const int32_t* __restrict__ planes, int pw, int pstride, float* __restrict__ sdet,
-                                            const OP& op, int px0, int py0, float skip_thr)
-{
-    using OC = OctC<O>;
-    constexpr int STEP = OC::STEP, SIZE = OC::size(L), Q = STEP / 4;
-    static_assert(STEP % 4 == 0, "plane variant needs a step that is a multiple of 4");
-    using LC = LayerC<SIZE>;
-    // The planes are read through a buffer resource: a corner's address is the lane's sample offset (one VGPR) + a scalar offset
-    // (plane and row of the corner: SALU arithmetic on pw / pstride) + the column as the instruction's immediate, instead of a
-    // 64-bit flat address (a VGPR pair and a v_lshl_add_u64) per corner.
-    const ImgRsrc rs = img_rsrc(reinterpret_cast<const uint8_t*>(planes), 16 * pstride * 4);
-#define SVP(dy, dx) (int)__builtin_amdgcn_raw_buffer_load_b32(rs, voff + 4 * ((dx) >> 2) + plane_written<(dy), (dx)>(), 4 * ((((dy) & 3) * 4 + ((dx) & 3)) * pstride + ((dy) >> 2) * pw), 0)
-    UVO_HESSIAN_CONSTS(LC);
-    const auto& lp = op.L[L];
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int it = 0; it < (TW * TH + NT - 1) / NT; it++) {
-        const int sidx = tid + it * NT;
-        if ((it + 1) * NT > TW * TH && sidx >= TW * TH) break;
-        const int ry = sidx / TW, rx = sidx - ry * TW;
-        const int oi = py0 + ry - OC::margin(L), oj = px0 + rx - OC::margin(L);
-        float det = 0.f;
-        if (oi >= 0 && oi < lp.samples_i && oj >= 0 && oj < lp.samples_j) {
-            const int voff = 4 * ((oi * Q) * pw + oj * Q);
-            UVO_HESSIAN_DET(SVP, det)
-        }
-        sdet[((L - 1) * TH + ry) * TW + rx] = det;
-    }
-#undef SVP
-}
-
+// Octaves 2 and 3 read the de-interleaved planes in global memory (the integral tile of one workgroup would not fit LDS).
+// Sample (oi, oj) has its top-left at pixel (STEP*oi, STEP*oj); corner (dy, dx) is in plane (dy & 3, dx & 3) at
+// [STEP/4*oi + dy/4][STEP/4*oj + dx/4]: plane and offsets are compile-time, lanes along oj.  The planes are read through a buffer
+// resource: a corner's address is the lane's sample offset (one VGPR) + a scalar offset (plane and row of the corner: SALU
+// arithmetic on pw / pstride) + the column as the instruction's immediate, instead of a 64-bit flat address (a VGPR pair and a
+// v_lshl_add_u64) per corner.
 // The three middle layers of a plane-octave sample in TWO memory round trips instead of six (the merged launch): first the sixteen
 // Dx / Dy corners of all three layers -- 48 independent buffer loads per lane, issued together -- then, for the layers whose dx * dy
 // can still beat the threshold, their Dxy corners together.  A plane tile used to live ~13 us in its workgroup slot, almost all of it
@@ -675,22 +647,6 @@ __device__ __forceinline__ void det_layers_p3(const int32_t* __restrict__ planes
 template <int TW, int TH>
 struct NmsLds { static constexpr int kList = 3 * ((TW - 1) / 2) * ((TH - 1) / 2), kWords = kList + 2; };
 
-// UVO_HESS_STAMPS=<file> (measurement): wall-clock stamps (100 MHz) of every workgroup's phases in the last detection launch --
-// start, integral tile in LDS, box sums done, end -- with the tile kind, written as CSV when the context goes
-// The stamps exist in the measurement build only (make STAMPS=1 -> lib_ab/libuvo_hip_stamps.so, tools/probe/gpu.sh stamps): reading the
-// pointer costs a scalar load and an s_waitcnt lgkmcnt(0) per stamp, which also drains the LDS reads in flight -- the descriptor launch
-// measured 66 us with its stamps compiled in and switched off, 58 us without them.
-#ifndef UVO_STAMPS
-#define UVO_STAMPS 0
-#endif
-__device__ long long* g_hess_stamps = nullptr;
-__device__ __forceinline__ void hess_stamp(int k, long long v = -1)
-{
-#if UVO_STAMPS
-    long long* st = g_hess_stamps;
-    if (st && threadIdx.x == 0) st[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 8 + k] = v >= 0 ? v : (long long)wall_clock64();
-#endif
-}
 // the survivor count of a tile starts at zero: called before the barrier that precedes nms_survivors (one barrier less per tile: under
 // three workgroups per CU a barrier costs the wait for the slowest of eight time-sliced waves)
 template <int TW, int TH>
@@ -754,15 +710,12 @@ __device__ __forceinline__ void nms_survivors(const float* __restrict__ sdet, un
         }
     }
     }
-    hess_stamp(5);
     __syncthreads();
-    hess_stamp(6);
     const int nloc = s_n[0];
     // one global atomic per workgroup (a device-scope increment of one address costs ~7 ns chip-wide, and its wave a round trip)
     if (nloc == 0) return;
     if (tid == 0) s_n[1] = atomicAdd(sv.count, nloc);
     __syncthreads();
-    hess_stamp(7);
     const int base = s_n[1];
     // a record is 32 words (im, octave, L, i, j, 27 neighbourhood values): 32 lanes write one word each (one thread per survivor
     // writing its 128 bytes took ~1 us of a tile's life)
@@ -879,7 +832,15 @@ __global__ __launch_bounds__(256) void k_hessian_finish(LaneArgs LA, const Octav
 
 // quads a thread has in flight during the tile fill: the whole tile in one round trip when that takes at most six per thread
 #define UVO_FILL(quads, nt) (((quads) + (nt) - 1) / (nt) <= 6 ? ((quads) + (nt) - 1) / (nt) : 4)
-// One tile of octave 0 or 1 (tile bx, by of image im): the body of k_hessian_nms_c and of the octave-0 blocks of k_hessian_nms_c0_p23
+// One tile of octave 0 or 1 (tile bx, by of image im) in k_hessian_nms_all.  Its dynamic LDS: the det planes of layers 1..3, the
+// integral tile, the survivor list -- in that order.
+template <int O, int TW, int TH>
+constexpr size_t hessian_c_tile_lds()
+{
+    using OC = OctC<O>;
+    constexpr int THs = (TH - 1) * OC::STEP + (OC::HI - OC::LO) + 1;
+    return sizeof(float) * 3 * TW * TH + sizeof(int32_t) * (size_t)THs * OC::STEP * OctTile<O, TW>::PW + sizeof(unsigned) * NmsLds<TW, TH>::kWords;
+}
 template <int O, int TW, int TH, int NT, class OP>
 __device__ __forceinline__ void hessian_nms_c_tile(const ImgPair& ip, int w, int h, const OP& op, float thr, const SurvOut& sv,
                                                    int bx, int by, int im, unsigned char* smem)
@@ -932,40 +893,15 @@ __device__ __forceinline__ void hessian_nms_c_tile(const ImgPair& ip, int w, int
     }
     nms_zero<TW, TH>(reinterpret_cast<unsigned*>(stile + THs * STEP * PW));
     __syncthreads();
-    hess_stamp(1);
     det_layer_c<O, 1, TW, TH, NT>(stile, sdet, op, px0, py0, thr);
     det_layer_c<O, 2, TW, TH, NT>(stile, sdet, op, px0, py0, thr);
     det_layer_c<O, 3, TW, TH, NT>(stile, sdet, op, px0, py0, thr);
     __syncthreads();
-    hess_stamp(2);
     nms_survivors<TW, TH, NT>(sdet, reinterpret_cast<unsigned*>(stile + THs * STEP * PW), op, thr, px0, py0, im, sv);
 }
-template <int O, int TW, int TH, int NT>
-__global__ __launch_bounds__(NT) void k_hessian_nms_c(LaneArgs LA, int w, int h, OctavePat op, float thr)
-{
-    extern __shared__ __align__(16) unsigned char smem[];
-    hessian_nms_c_tile<O, TW, TH, NT>(LA.ip, w, h, op, thr, LA.sv, blockIdx.x, blockIdx.y, blockIdx.z, smem);
-}
 
-// Octaves 2 and 3: det layers from the de-interleaved planes, det planes in LDS, survivors as above.
-template <int O, int TW, int TH, int NT>
-__global__ __launch_bounds__(NT) void k_hessian_nms_p(LaneArgs LA, int w, int h, OctavePat op, float thr)
-{
-    __shared__ float sdet[3 * TH * TW];
-    __shared__ unsigned s_list[NmsLds<TW, TH>::kWords];
-    const ImgPair& ip = LA.ip; const SurvOut& sv = LA.sv;
-    const int im = blockIdx.z;
-    const int px0 = blockIdx.x * (TW - 2) - 1, py0 = blockIdx.y * (TH - 2) - 1;
-    det_layer_p<O, 1, TW, TH, NT>(ip.planes[im], ip.pw, ip.pstride, sdet, op, px0, py0, thr);
-    det_layer_p<O, 2, TW, TH, NT>(ip.planes[im], ip.pw, ip.pstride, sdet, op, px0, py0, thr);
-    det_layer_p<O, 3, TW, TH, NT>(ip.planes[im], ip.pw, ip.pstride, sdet, op, px0, py0, thr);
-    nms_zero<TW, TH>(s_list);
-    __syncthreads();
-    nms_survivors<TW, TH, NT>(sdet, s_list, op, thr, px0, py0, im, sv);
-}
-
-// Octaves 2 and 3 in one launch (block b walks octave 2's tiles, then octave 3's): both are latency-bound on plane reads and
-// neither fills the chip (5120 and 2560 waves); side by side they take about what octave 2 took alone.
+// One tile of octave 2 or 3: det layers from the de-interleaved planes, det planes in LDS, survivors as above.  Both are
+// latency-bound on plane reads and neither fills the chip (5120 and 2560 waves at 1080p).
 static const int kP23Threads = 512;
 struct P23Grid { int nbx2, nb2, nbx3, nb3; };
 template <class OP>
@@ -979,14 +915,12 @@ __device__ __forceinline__ void hessian_nms_p23_tile(const ImgPair& ip, const OP
         det_layers_p3<2, TW2, TH2, kP23Threads>(ip.planes[im], ip.pw, ip.pstride, sdet, op2, px0, py0, thr);
         nms_zero<TW2, TH2>(s_list);
         __syncthreads();
-        hess_stamp(2);
         nms_survivors<TW2, TH2, kP23Threads>(sdet, s_list, op2, thr, px0, py0, im, sv);
     } else {
         const int px0 = bx * (TW3 - 2) - 1, py0 = by * (TH3 - 2) - 1;
         det_layers_p3<3, TW3, TH3, kP23Threads>(ip.planes[im], ip.pw, ip.pstride, sdet, op3, px0, py0, thr);
         nms_zero<TW3, TH3>(s_list);
         __syncthreads();
-        hess_stamp(2);
         nms_survivors<TW3, TH3, kP23Threads>(sdet, s_list, op3, thr, px0, py0, im, sv);
     }
 }
@@ -998,7 +932,6 @@ static const int kP23SdetFloats = 3 * 16 * 32;
 // three blocks per CU -- the octave-0 / plane mix runs as fast with three as with four, 63 us, but not with two, 81 us).  The
 // patterns come from the device copy of the table (four of them exceed the 4 KB of kernel arguments).
 static const int kO1TileRows = 18;             // sample rows of an octave-1 tile in the merged launch
-struct HessGrid { int nbx0, nb0, nbx1, nb1; P23Grid g; };          // tiles per kind
 // (Measured and not kept, round 4: two to four consecutive tiles of a kind per workgroup, to save the ~1.9 us a workgroup slot's
 // turn-over costs per tile -- 93 / 103 / 105 us against 84: a slot bound to a fixed run of tiles loses the balance that "whichever
 // slot frees up takes the next tile" gives; the same lesson as the resident-workgroup queues)
@@ -1015,27 +948,15 @@ __global__ __launch_bounds__(kP23Threads) void k_hessian_nms_all(LaneArgs LA, in
     const int im = blockIdx.y;
     const unsigned e = order[blockIdx.x];
     const int kind = e >> 30, bx = e & 0x3FFF, by = (e >> 14) & 0x3FFF;
-    hess_stamp(0); hess_stamp(4, kind);
     if (kind == 0) hessian_nms_c_tile<0, TW, TH, kP23Threads>(ip, w, h, hd.o[0], thr, sv, bx, by, im, smem);
     else if (kind == 1) hessian_nms_c_tile<1, 32, kO1TileRows, kP23Threads>(ip, w, h, hd.o[1], thr, sv, bx, by, im, smem);
     else {
         float* sdet = reinterpret_cast<float*>(smem);
         hessian_nms_p23_tile(ip, hd.o[2], hd.o[3], thr, sv, kind == 3, bx, by, im, sdet, reinterpret_cast<unsigned*>(sdet + kP23SdetFloats));
     }
-    hess_stamp(3);
 }
 
 // debug / parity hook: one det+trace layer written to global planes (rows x cols)
-// Measurement only (tools/probe/gpu.sh sens): a kernel of known duration in the middle of stage A -- one wave ("thin") or three
-// workgroups per CU holding a detection tile's LDS ("fat") -- to read off how the pipeline's cadence follows either kind of time.
-__global__ __launch_bounds__(256) void k_probe_hold(int ticks)
-{
-    extern __shared__ int probe_lds[];
-    if (threadIdx.x == 0) probe_lds[0] = ticks;
-    const long long t0 = wall_clock64();
-    while (wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(16);
-}
-
 __global__ void k_hessian_layer_debug(const int32_t* gsum, int w, int h, LayerPat lp, int step, int rows, int cols,
                                       float* det, float* trace)
 {
@@ -1553,15 +1474,6 @@ __device__ __forceinline__ void describe_tail(const DescArgs& a, int im, int k, 
 // windows), PX = 2 and PX = 1 for windows up to 127 / 64 pixels so that small windows do not idle three quarters of the lanes.
 // ------------------------------------------------------------------------------------------
 static const int kTapBatch = 16;           // image rows a lane of descriptor64_big has in flight
-// UVO_DESC_STAMPS=<file> (measurement): wall-clock stamps (100 MHz) of the phases of every small-window workgroup of the last descriptor launch
-__device__ long long* g_desc_stamps = nullptr;
-__device__ __forceinline__ void desc_stamp(int im, int k, int slot, long long v = -1)
-{
-#if UVO_STAMPS
-    long long* st = g_desc_stamps;
-    if (st && threadIdx.x == 0) st[((size_t)im * 16384 + (k & 16383)) * 8 + slot] = v >= 0 ? v : (long long)wall_clock64();
-#endif
-}
 // (Round 4, measured and removed: staging a small window's bytes in LDS first -- every load of the workgroup in flight at once -- and
 // running the horizontal pass from there.  Stamps: table + barrier 1.2 us and horizontal pass 5.3 us became staging 4.0 us + LDS pass
 // 3.9 us; the small-window half of the launch alone 30.0 -> 34.3 us.)
@@ -1730,13 +1642,11 @@ __device__ __forceinline__ ColTask col_task(const AreaTab& ty, int dx, int start
 __device__ __forceinline__ void describe_keypoint(const DescArgs& a, int w, int h, int k, int im)
 {
     const int tid = threadIdx.x;
-    desc_stamp(im, k, 0);
     const uvo_keypoint kp = a.kps[im][k];
     const float size = kp.size;
     const float s = size * 1.2f / 9.0f;
     const int win_size = (int)((20 + 1) * s);
     if (win_size > kSmallWin) return;                  // large windows: descriptor64_big
-    desc_stamp(im, k, 1); desc_stamp(im, k, 6, win_size);
     extern __shared__ __align__(16) unsigned char smem_desc[];
     float* buf = reinterpret_cast<float*>(smem_desc);                 // [21][bp]
     const int bp = (win_size + 3) | 1;                                // odd pitch: the vertical pass walks 21 columns bank-conflict-free (+3: area_column's alignment shift)
@@ -1772,7 +1682,6 @@ __device__ __forceinline__ void describe_keypoint(const DescArgs& a, int w, int 
     } else {
         if (tid < 21) tab[tid] = area_tab(tid, win_size, scale);
         __syncthreads();
-        desc_stamp(im, k, 2);
         // horizontal pass of resizeArea_ (over WIN columns j = image rows), lanes along WIN rows i = image x: wave wv takes the
         // destination columns dx = wv, wv + 4, .. through the shared column core (round 3): a column's taps are the same for
         // every lane, so row clamps, offsets and weights are scalar work and a lane's pixel costs cvt + mul + add.  (Round 2 ran
@@ -1793,7 +1702,6 @@ __device__ __forceinline__ void describe_keypoint(const DescArgs& a, int w, int 
             }
         }
         __syncthreads();
-        desc_stamp(im, k, 3);
         // vertical pass (over WIN rows i)
         for (int o = tid; o < 441; o += 256) {
             int dy = o / 21, dx = o - dy * 21;
@@ -1807,9 +1715,7 @@ __device__ __forceinline__ void describe_keypoint(const DescArgs& a, int w, int 
         }
     }
     __syncthreads();
-    desc_stamp(im, k, 4); if (area_fast) desc_stamp(im, k, 7, 2);
     describe_tail(a, im, k, PATCH);
-    desc_stamp(im, k, 5);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2248,8 +2154,6 @@ __device__ __forceinline__ void descriptor64_big(const DescArgs& a, int w, int h
         }
         if (t >= ntask) continue;
         const int e = entry_of(t);
-        const bool st_on = UVO_STAMPS && g_desc_stamps != nullptr && lane == 0;
-        if (st_on) { long long* sp = g_desc_stamps + ((size_t)(2 + im) * 16384 + (t & 16383)) * 8; sp[0] = wall_clock64(); sp[6] = par.y & 0xFFFF; sp[7] = (t < nt1 ? 1 : 3) + 10 * (par.y >> 16 != 0); }
         const int ncols = t < nt1 ? 1 : 3, dx0 = t < nt1 ? t - e * 21 : 3 * ((t - nt1) - (e - nl) * 7);
         const int bstride = 256;                              // floats between the column buffers of a three-column task (kTripleWin + 8 <= 256)
         // the task is the same for every lane: scalar registers, so that row clamps, row addresses and tap weights are SALU work
@@ -2349,7 +2253,6 @@ __device__ __forceinline__ void descriptor64_big(const DescArgs& a, int w, int h
                 }
             }
             __builtin_amdgcn_wave_barrier();
-            if (st_on) g_desc_stamps[((size_t)(2 + im) * 16384 + (t & 16383)) * 8 + 1] = wall_clock64();
             if (lane < 21 * ncols) {                        // vertical passes of the task's columns, 21 lanes each
                 const int d = lane / 21, dy = lane - d * 21;
                 const float* bufrow = bufrow0 + d * bstride + (vec_ok ? (start_x & 3) : 0);      // area_column's alignment shift
@@ -2361,7 +2264,6 @@ __device__ __forceinline__ void descriptor64_big(const DescArgs& a, int w, int h
             }
         }
         __builtin_amdgcn_wave_barrier();
-        if (st_on) g_desc_stamps[((size_t)(2 + im) * 16384 + (t & 16383)) * 8 + 2] = wall_clock64();
     }
 }
 // Both window classes in one launch: blocks [0, nbig) are the persistent waves of the large-window tasks, the rest take one
@@ -2372,21 +2274,19 @@ __device__ __forceinline__ void descriptor64_big(const DescArgs& a, int w, int h
 // fields at constant offsets of the argument block the compiler loads them at entry, spills 46 SGPRs instead of 37 and needs 24 bytes of
 // scratch instead of 16 under the 64-VGPR cap; behind a run-time index each field is loaded where it is used.
 struct DescLane { LaneArgs a[1]; };
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_descriptor64(DescLane dl, int w, int h, int nbig, int part, int nimg, int order)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_descriptor64(DescLane dl, int w, int h, int nbig, int nimg)
 {
-    // The launch is one row of workgroups; `order` says who comes first (the hardware starts workgroups in index order, and with
-    // lifetimes of 4 to 14 us that order decides what is resident together): 0: image by image, each image's large-window waves before
-    // its small-window workgroups (rounds 2-4); 1: every image's large-window waves, then the small-window workgroups image by image;
-    // 2: the same with the small-window workgroups of the images alternating
+    // The launch is one row of workgroups (the hardware starts workgroups in index order, and with lifetimes of 4 to 14 us that order
+    // decides what is resident together): every image's nbig large-window workgroups first, image by image, then the small-window
+    // workgroups with the images alternating
     const int nsmall = (int)gridDim.x / nimg - nbig;
-    int id = blockIdx.x, yy, bx; bool big;
-    if (order == 0) { yy = id / (nbig + nsmall); bx = id - yy * (nbig + nsmall); big = bx < nbig; if (!big) bx -= nbig; }
-    else if (id < nimg * nbig) { yy = id / nbig; bx = id - yy * nbig; big = true; }
-    else { id -= nimg * nbig; big = false; if (order == 1) { yy = id / nsmall; bx = id - yy * nsmall; } else { yy = id % nimg; bx = id / nimg; } }
+    int id = blockIdx.x, yy, bx;
+    const bool big = id < nimg * nbig;
+    if (big) { yy = id / nbig; bx = id - yy * nbig; }
+    else { id -= nimg * nbig; yy = id % nimg; bx = id / nimg; }
     const LaneArgs& LA = dl.a[yy >> 1]; const DescArgs& a = LA.da; uint8_t* __restrict__ patch = LA.patch;
-    // part (UVO_DESC_PART, measurement only -- the other class of keypoints gets no descriptor): 1 = large windows only, 2 = small only
-    if (big) { if (part != 2) descriptor64_big(a, w, h, patch, bx, nbig, yy & 1); }
-    else if (part != 1) descriptor64_small(a, w, h, bx, nsmall, yy & 1);
+    if (big) descriptor64_big(a, w, h, patch, bx, nbig, yy & 1);
+    else descriptor64_small(a, w, h, bx, nsmall, yy & 1);
 }
 __global__ __launch_bounds__(256) void k_descriptor64_big_finish(LaneArgs LA)
 {
@@ -2486,38 +2386,20 @@ static uvo_status surf_integral_launch(Ctx* c, const LaneArgs& LA, int nimg)
 }
 uvo_status surf_integral(Ctx* c, int nimg) { return surf_integral_launch(c, lane_args(c, nimg, -1), nimg); }
 
-template <int O, int TW, int TH, int NT>
-static hipError_t launch_hessian_p(Ctx* c, const LaneArgs& LA, int nimg, const OctavePat& op, float thr)
+// A kernel's dynamic LDS limit, raised once per device (a process may hold contexts on several): `done` is the call site's static
+// bool[64]
+template <class K>
+static hipError_t raise_dynamic_lds(const Ctx* c, K kern, size_t bytes, bool (&done)[64])
 {
-    const int w = c->img_w, h = c->img_h;
-    dim3 grid((op.cols + TW - 3) / (TW - 2), (op.rows + TH - 3) / (TH - 2), nimg);
-    hipLaunchKernelGGL((k_hessian_nms_p<O, TW, TH, NT>), grid, dim3(NT), 0, c->stream, LA, w, h, op, thr);
-    return hipGetLastError();
+    bool& set = done[c->device & 63];
+    if (set) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    set = e == hipSuccess;
+    return e;
 }
 
-template <int O, int TW, int TH, int NT>
-static hipError_t launch_hessian_c(Ctx* c, const LaneArgs& LA, int nimg, const OctavePat& op, float thr)
-{
-    using OC = OctC<O>;
-    constexpr int STEP = OC::STEP;
-    constexpr int THs = (TH - 1) * STEP + (OC::HI - OC::LO) + 1;
-    constexpr int PW = OctTile<O, TW>::PW;
-    const int w = c->img_w, h = c->img_h;
-    const size_t lds = sizeof(float) * 3 * TW * TH + sizeof(int32_t) * (size_t)THs * STEP * PW + sizeof(unsigned) * NmsLds<TW, TH>::kWords;
-    dim3 grid((op.cols + TW - 3) / (TW - 2), (op.rows + TH - 3) / (TH - 2), nimg);
-    auto kern = k_hessian_nms_c<O, TW, TH, NT>;
-    static bool attr_dev[64] = {false};                       // once per device (a process may hold contexts on several)
-    bool& attr_set = attr_dev[c->device & 63];
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kern, grid, dim3(NT), lds, c->stream, LA, w, h, op, thr);
-    return hipGetLastError();
-}
-
-// Geometry of the merged detection launch (all four octaves in one grid) for a w x h image
+// Geometry of the merged detection launch (every octave's tiles in one grid) from the octave table; an absent octave (zero-filled
+// entry) has no tiles
 struct MergedGrid { int nbx0, nb0, nbx1, nb1, nb23, total; P23Grid g; };
 static const int kMergedTW0 = 64, kMergedTH0 = 32, kMergedTW1 = 32;
 static MergedGrid merged_grid(const OctavePat* ops)
@@ -2531,16 +2413,7 @@ static MergedGrid merged_grid(const OctavePat* ops)
     m.nb23 = m.g.nb2 + m.g.nb3; m.total = m.nb0 + m.nb1 + m.nb23;
     return m;
 }
-static bool merged_launch(const Ctx* c)
-{
-    static const bool split_env = getenv("UVO_HESSIAN_SPLIT") != nullptr;       // diagnostic: one launch per octave
-    return c->p.SURF_OCTAVES_NUMBER == 4 && !split_env;
-}
 
-// Everything the detector keeps per image SIZE (and octave count) on this lane: the octave patterns for k_hessian_finish and the
-// block order of the merged detection launch.  Idempotent; surf_detect calls it for the image at hand, and the pipeline calls it
-// for every lane as soon as the stream's image size is known, so that a lane's first pair does not pay two allocations, two
-// uploads and four host syncs inside somebody's timed loop.
 // which detection kernels serve this lane's configuration (uvo_surf_set_detection_path; the master context's value)
 static bool general_path(const Ctx* c)
 {
@@ -2591,6 +2464,10 @@ static uvo_status general_prepare(Ctx* c, int w, int h)
     return UVO_OK;
 }
 
+// Everything the detector keeps per image SIZE (and octave count) on this lane: the octave patterns for k_hessian_finish and the
+// block order of the merged detection launch.  Idempotent; surf_detect calls it for the image at hand, and the pipeline calls it
+// for every lane as soon as the stream's image size is known, so that a lane's first pair does not pay two allocations, two
+// uploads and four host syncs inside somebody's timed loop.
 uvo_status surf_prepare(Ctx* c, int w, int h)
 {
     if (c->p.SURF_OCTAVES_NUMBER < 1 || c->p.SURF_OCTAVES_NUMBER > kGenMaxOctaves || c->p.SURF_OCTAVES_LAYERS < 1 || c->p.SURF_OCTAVES_LAYERS > kGenMaxLayers) {
@@ -2608,7 +2485,6 @@ uvo_status surf_prepare(Ctx* c, int w, int h)
         UVO_HIP_TRY(c, hipMemcpyAsync(c->d_octpat, c->h_octpat.data(), sizeof(ops), hipMemcpyHostToDevice, c->stream));
         UVO_HIP_TRY(c, hipStreamSynchronize(c->stream));
     }
-    if (!merged_launch(c)) return UVO_OK;
     const MergedGrid m = merged_grid(ops);
     const int nb0 = m.nb0, nb1 = m.nb1, nb23 = m.nb23, total = m.total;
     if (nb0 > 0x3FFF || nb1 > 0x3FFF || nb23 > 0x3FFF) { c->err = "SURF: image too large for the merged detection launch's tile table"; return UVO_INVALID_ARG; }
@@ -2644,184 +2520,131 @@ uvo_status surf_prepare(Ctx* c, int w, int h)
     return UVO_OK;
 }
 
-uvo_status surf_detect(Ctx* c, int nimg, int gate_min_features)
+// ------------------------------------------------------------------------------------------
+// surf_detect's steps after the integral image: each queues its launches on the lane's stream and returns a status
+// ------------------------------------------------------------------------------------------
+// every other scale space than the tuned kernels', and any under uvo_surf_set_detection_path(1)
+static uvo_status surf_detect_general(Ctx* c, const LaneArgs& LA, int nimg, float thr)
 {
     const int w = c->img_w, h = c->img_h;
-    UVO_TRY(surf_prepare(c, w, h));
-    const LaneArgs LA = lane_args(c, nimg, gate_min_features);
-    UVO_TRY(surf_integral_launch(c, LA, nimg));
-    const float thr = (float)c->p.SURF_MIN_HESSIAN;
-    if (general_path(c)) {
-        const int no = c->p.SURF_OCTAVES_NUMBER, nl = c->p.SURF_OCTAVES_LAYERS;
-        const GenLayer* tab = static_cast<const GenLayer*>(c->d_gen_tab);
-        const int gx = std::min(1024, (w * h + 255) / 256);
-        {
-            StageTimer t(c, ST_HESSIAN_O0);
-            hipLaunchKernelGGL(k_scale_space_det, dim3(gx, no * (nl + 2), nimg), dim3(256), 0, c->stream, LA, tab, c->d_gen_planes, c->gen_img_floats, w);
-            UVO_HIP_TRY(c, hipGetLastError());
-        }
-        {
-            StageTimer t(c, ST_HESSIAN_O0 + 1);
-            hipLaunchKernelGGL(k_scale_space_nms, dim3(gx, no * nl, nimg), dim3(256), 0, c->stream, LA, tab, c->d_gen_planes, c->gen_img_floats, nl, w, h, thr);
-            UVO_HIP_TRY(c, hipGetLastError());
-        }
-    } else {
-        OctavePat ops[4];
-        memset(ops, 0, sizeof(ops));
-        for (int o = 0; o < c->p.SURF_OCTAVES_NUMBER; o++) make_octave(o, c->p.SURF_OCTAVES_LAYERS, w, h, &ops[o]);
-        // four octaves (the shipped configuration): one launch for all of them
-        const bool merged = merged_launch(c);
-        if (merged) {
-            constexpr int TW0 = kMergedTW0, TH0 = kMergedTH0, TW1 = kMergedTW1, TH1 = kO1TileRows;
-            constexpr int THs0 = (TH0 - 1) * OctC<0>::STEP + (OctC<0>::HI - OctC<0>::LO) + 1, THs1 = (TH1 - 1) * OctC<1>::STEP + (OctC<1>::HI - OctC<1>::LO) + 1;
-            constexpr size_t lds0 = sizeof(float) * 3 * TW0 * TH0 + sizeof(int32_t) * (size_t)THs0 * OctC<0>::STEP * OctTile<0, TW0>::PW + sizeof(unsigned) * NmsLds<TW0, TH0>::kWords;
-            constexpr size_t lds1 = sizeof(float) * 3 * TW1 * TH1 + sizeof(int32_t) * (size_t)THs1 * OctC<1>::STEP * OctTile<1, TW1>::PW + sizeof(unsigned) * NmsLds<TW1, TH1>::kWords;
-            constexpr size_t lds = lds0 > lds1 ? lds0 : lds1;
-            static_assert(lds <= 54600, "three blocks of the merged detection launch must fit a CU's 160 KB of LDS");
-            const MergedGrid mg = merged_grid(ops);
-            const HessGrid hg = { mg.nbx0, mg.nb0, mg.nbx1, mg.nb1, mg.g };
-            const int total = mg.total;
-            auto kern = k_hessian_nms_all<TW0, TH0>;
-            static bool attr_dev[64] = {false};
-            bool& attr_set = attr_dev[c->device & 63];
-            if (!attr_set) { UVO_HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); attr_set = true; }
-            StageTimer t(c, ST_HESSIAN_O0);
-            static const size_t lds_pad = getenv("UVO_HESS_LDS") ? (size_t)atoi(getenv("UVO_HESS_LDS")) : 0;      // measurement: fewer blocks per CU
-            const size_t lds_launch = lds_pad > lds ? lds_pad : lds;
-            if (lds_pad > lds) { static bool once = false; if (!once) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_launch); once = true; } }
-            static const char* stamps_path = UVO_STAMPS ? getenv("UVO_HESS_STAMPS") : nullptr;
-            static long long* d_stamps = nullptr; static size_t stamps_n = 0;
-            if (stamps_path && c->lane_id == 0) {
-                if (!d_stamps) { stamps_n = (size_t)total * 4 * 8; (void)hipMalloc(reinterpret_cast<void**>(&d_stamps), sizeof(long long) * stamps_n); (void)hipMemcpyToSymbol(HIP_SYMBOL(g_hess_stamps), &d_stamps, sizeof(d_stamps)); }
-                (void)hipMemsetAsync(d_stamps, 0, sizeof(long long) * stamps_n, c->stream);
-            }
-            HessDims hd;
-            for (int o = 0; o < 4; o++) {
-                OctDims& d = hd.o[o];
-                for (int l = 0; l < 5; l++) { d.L[l].samples_i = ops[o].L[l].samples_i; d.L[l].samples_j = ops[o].L[l].samples_j; }
-                d.rows = ops[o].rows; d.cols = ops[o].cols; d.octave = ops[o].octave;
-                for (int l = 0; l < 3; l++) d.nms_margin[l] = ops[o].nms_margin[l];
-            }
-            Ctx::TraceRec* trh = (c->trace_on && c->trace_cur >= 0) ? &c->trace[c->trace_cur] : nullptr;      // uvo_trace_row::dev_ms[6], [7]
-            if (trh) (void)hipEventRecord(trh->ev[6], c->stream);
-            hipLaunchKernelGGL(kern, dim3(total, nimg), dim3(kP23Threads), lds_launch, c->stream, LA, w, h, hd, thr, c->d_hess_order);
-            if (trh) { (void)hipEventRecord(trh->ev[7], c->stream); trh->det_marked = true; }
-            if (stamps_path && d_stamps && c->lane_id == 0) {        // (measurement: synchronous, every launch rewrites the file)
-                std::vector<long long> hs(stamps_n);
-                (void)hipStreamSynchronize(c->stream);
-                (void)hipMemcpy(hs.data(), d_stamps, sizeof(long long) * stamps_n, hipMemcpyDeviceToHost);
-                if (FILE* f = fopen(stamps_path, "w")) {
-                    fprintf(f, "block,im,kind,t_start,t_filled,t_det,t_end,t_scan,t_scanbar,t_atomic\n");
-                    for (int y = 0; y < nimg; y++) for (int b = 0; b < total; b++) { const long long* r = hs.data() + ((size_t)y * total + b) * 8; fprintf(f, "%d,%d,%lld,%lld,%lld,%lld,%lld,%lld,%lld,%lld\n", b, y, r[4], r[0], r[1], r[2], r[3], r[5], r[6], r[7]); }
-                    fclose(f);
-                }
-            }
-            UVO_HIP_TRY(c, hipGetLastError());
-        }
-        for (int o = 0; o < c->p.SURF_OCTAVES_NUMBER && !merged; o++) {
-            StageTimer t(c, ST_HESSIAN_O0 + o);
-            const OctavePat& op = ops[o];
-            hipError_t e;
-            // tile shapes chosen by pipelined throughput (tools/probe/ab.sh): octave 0 64 x 24 samples = 40 KB of LDS (18 KB det planes,
-            // 19 KB integral tile, 3 KB survivor list), octave 1 32 x 24 = 59 KB (9 KB + 48 KB: the 54-pixel templates make the halo
-            // most of the tile)
-            if (o == 0)      e = launch_hessian_c<0, 64, 24, 512>(c, LA, nimg, op, thr);
-            else if (o == 1) e = launch_hessian_c<1, 32, 24, 512>(c, LA, nimg, op, thr);
-            else if (o == 2) e = launch_hessian_p<2, 32, 16, 512>(c, LA, nimg, op, thr);
-            else             e = launch_hessian_p<3, 16, 16, 256>(c, LA, nimg, op, thr);
-            UVO_HIP_TRY(c, e);
-        }
-        {   // the survivors of every octave: outer-layer determinants, last comparison, keypoints
-            StageTimer t(c, ST_HESSIAN_O0 + c->p.SURF_OCTAVES_NUMBER - 1);
-            hipLaunchKernelGGL(k_hessian_finish, dim3((c->surv_cap + kFinishPerWg - 1) / kFinishPerWg), dim3(256), 0, c->stream, LA, static_cast<const OctavePat*>(c->d_octpat), w, h);
-            UVO_HIP_TRY(c, hipGetLastError());
-        }
-        static const int probe_thin = getenv("UVO_PROBE_THIN_US") ? atoi(getenv("UVO_PROBE_THIN_US")) : 0, probe_fat = getenv("UVO_PROBE_FAT_US") ? atoi(getenv("UVO_PROBE_FAT_US")) : 0;
-        if (probe_thin > 0) hipLaunchKernelGGL(k_probe_hold, dim3(1), dim3(64), 64, c->stream, probe_thin * 100);           // wall_clock64: 100 MHz
-        if (probe_fat > 0) {
-            static bool once = false;
-            if (!once) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_probe_hold), hipFuncAttributeMaxDynamicSharedMemorySize, 53000); once = true; }
-            hipLaunchKernelGGL(k_probe_hold, dim3(768), dim3(256), 53000, c->stream, probe_fat * 100);
-        }
-    }
+    const int no = c->p.SURF_OCTAVES_NUMBER, nl = c->p.SURF_OCTAVES_LAYERS;
+    const GenLayer* tab = static_cast<const GenLayer*>(c->d_gen_tab);
+    const int gx = std::min(1024, (w * h + 255) / 256);
     {
-        StageTimer t(c, ST_SORT);
-        hipLaunchKernelGGL(k_order, dim3(1, nimg), dim3(kOrderThreads), 0, c->stream, LA, c->d_area_iscale);
-        if (c->cap > kOrderCap) {                              // the counts live on the device: each of these returns at once for an image k_order ordered
-            const int tiles_max = ((c->cap + 255) / 256) * ((c->cap + kSortChunk - 1) / kSortChunk);
-            hipLaunchKernelGGL(k_rank_partial, dim3(tiles_max < 512 ? tiles_max : 512, nimg), dim3(256), 0, c->stream, LA);
-            hipLaunchKernelGGL(k_rank_scatter, dim3((c->cap + 255) / 256, nimg), dim3(256), 0, c->stream, LA);
-            hipLaunchKernelGGL(k_big_sort, dim3(nimg), dim3(1024), 0, c->stream, LA, c->cap, c->d_area_iscale);
-        }
+        StageTimer t(c, ST_HESSIAN_O0);
+        hipLaunchKernelGGL(k_scale_space_det, dim3(gx, no * (nl + 2), nimg), dim3(256), 0, c->stream, LA, tab, c->d_gen_planes, c->gen_img_floats, w);
         UVO_HIP_TRY(c, hipGetLastError());
     }
     {
-        StageTimer t(c, ST_DESCRIPTOR);
-        const size_t lds_small = sizeof(float) * 21 * ((kSmallWin + 3) | 1), lds_big = sizeof(float) * 4 * kBigRow;
-        // windows wider than kMaxWin: only where the configuration and the image size can produce one (never for the shipped configuration), or
-        // under uvo_surf_set_detection_path(1); the launch walks the ordered keypoints and describes the wide ones
-        const bool wide = c->sh->surf_detection_path == 1 || widest_window(c, w, h) > kMaxWin;
-        const int kWideGrid = 128;                             // keypoints walked side by side (x 21 destination rows)
-        if (c->p.SURF_UPRIGHT) {
-            const int nbig = 1024;                             // 8192 persistent waves for the large-window tasks (512: 80 us, 768..2048: 66-69 us)
-            static const int desc_part = getenv("UVO_DESC_PART") ? atoi(getenv("UVO_DESC_PART")) : 0;      // measurement only
-            static const char* dstamps_path = UVO_STAMPS ? getenv("UVO_DESC_STAMPS") : nullptr;
-            static long long* d_dstamps = nullptr; const size_t dstamps_n = (size_t)4 * 16384 * 8;
-            const bool dstamp = dstamps_path && c->lane_id == 0 && nimg == 2;
-            if (dstamp) {
-                if (!d_dstamps) { (void)hipMalloc(reinterpret_cast<void**>(&d_dstamps), sizeof(long long) * dstamps_n); (void)hipMemcpyToSymbol(HIP_SYMBOL(g_desc_stamps), &d_dstamps, sizeof(d_dstamps)); }
-                (void)hipMemsetAsync(d_dstamps, 0, sizeof(long long) * dstamps_n, c->stream);
-            }
-            // small-window part: a workgroup per keypoint -- as many as the last pair whose counts reached the host had, plus a quarter
-            // (the workgroups walk the list when there are more: any grid gives the same descriptors); max_kpts of them before that
-            static const int fixed_grid = getenv("UVO_DESC_GRID") ? atoi(getenv("UVO_DESC_GRID")) : 0;              // measurement: 0 = by the hint, -1 = max_kpts, n = n
-            const int hint = c->sh->kp_hint;
-            int nsmall = hint > 0 ? ((hint + hint / 4 + 255) & ~255) : c->cap;
-            if (fixed_grid != 0) nsmall = fixed_grid < 0 ? c->cap : fixed_grid;
-            nsmall = nsmall < 512 ? 512 : (nsmall > c->cap ? c->cap : nsmall);
-            // order 2 + the hint-sized grid: 57.2 us; image by image on max_kpts workgroups (rounds 2-4): 60.5; large-window waves first,
-            // small-window workgroups image by image: 59.7; 512 / 2048 large-window workgroups per image: 58.1 / 58.9 (tools/probe/desc_order.sh)
-            static const int desc_order = getenv("UVO_DESC_ORDER") ? atoi(getenv("UVO_DESC_ORDER")) : 2;            // measurement
-            static const int nbig_env = getenv("UVO_DESC_NBIG") ? atoi(getenv("UVO_DESC_NBIG")) : 0;
-            const int nbig_l = nbig_env > 0 ? nbig_env : nbig;
-            hipLaunchKernelGGL(k_descriptor64, dim3((nbig_l + nsmall) * nimg), dim3(256), lds_small > lds_big ? lds_small : lds_big, c->stream, DescLane{ { LA } }, w, h, nbig_l, desc_part, nimg, desc_order);
-            if (dstamp && d_dstamps) {                        // (measurement: synchronous, every launch rewrites the file)
-                std::vector<long long> hs(dstamps_n);
-                (void)hipStreamSynchronize(c->stream);
-                (void)hipMemcpy(hs.data(), d_dstamps, sizeof(long long) * dstamps_n, hipMemcpyDeviceToHost);
-                if (FILE* f = fopen(dstamps_path, "w")) {
-                    fprintf(f, "im,k,t_start,t_kp,t_ready,t_horiz,t_vert,t_end,win,kind\n");
-                    for (int y = 0; y < 2; y++) for (int k = 0; k < 16384; k++) { const long long* r = hs.data() + ((size_t)y * 16384 + k) * 8; if (r[0]) fprintf(f, "%d,%d,%lld,%lld,%lld,%lld,%lld,%lld,%lld,%lld\n", y, k, r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7]); }
-                    fclose(f);
-                }
-                if (FILE* f = fopen((std::string(dstamps_path) + ".big").c_str(), "w")) {
-                    fprintf(f, "im,task,t_start,t_horiz,t_end,win,kind\n");
-                    for (int y = 0; y < 2; y++) for (int k = 0; k < 16384; k++) { const long long* r = hs.data() + ((size_t)(2 + y) * 16384 + k) * 8; if (r[0] && r[2]) fprintf(f, "%d,%d,%lld,%lld,%lld,%lld,%lld\n", y, k, r[0], r[1], r[2], r[6], r[7]); }
-                    fclose(f);
-                }
-            }
-            hipLaunchKernelGGL(k_descriptor64_big_finish, dim3(1024, nimg), dim3(256), 0, c->stream, LA);
-            if (wide) {
-                hipLaunchKernelGGL(k_descriptor_wide<false>, dim3(21 * kWideGrid, nimg), dim3(256), 0, c->stream, LA.da, w, h, LA.patch);
-                hipLaunchKernelGGL(k_descriptor_wide_finish, dim3(kWideGrid, nimg), dim3(256), 0, c->stream, LA.da, LA.patch);
-            }
-        } else {
-            // orientation assignment, then every descriptor from its rotated window (not the shipped configuration)
-            const DescArgs& da = LA.da;
-            const size_t lds_rot = sizeof(float) * 21 * (kMaxWin + 1);
-            static bool rot_attr_dev[64] = {false};
-            bool& rot_attr = rot_attr_dev[c->device & 63];
-            if (!rot_attr) { UVO_HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_descriptor_rot), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_rot)); rot_attr = true; }
-            hipLaunchKernelGGL(k_surf_orientation, dim3((c->cap + 3) / 4, nimg), dim3(256), 0, c->stream, da, w, h);
-            hipLaunchKernelGGL(k_descriptor_rot, dim3(2048, nimg), dim3(256), lds_rot, c->stream, da, w, h);
-            if (wide) {
-                hipLaunchKernelGGL(k_descriptor_wide<true>, dim3(21 * kWideGrid, nimg), dim3(256), 0, c->stream, da, w, h, LA.patch);
-                hipLaunchKernelGGL(k_descriptor_wide_finish, dim3(kWideGrid, nimg), dim3(256), 0, c->stream, da, LA.patch);
-            }
-        }
+        StageTimer t(c, ST_HESSIAN_O0 + 1);
+        hipLaunchKernelGGL(k_scale_space_nms, dim3(gx, no * nl, nimg), dim3(256), 0, c->stream, LA, tab, c->d_gen_planes, c->gen_img_floats, nl, w, h, thr);
         UVO_HIP_TRY(c, hipGetLastError());
     }
     return UVO_OK;
+}
+
+// three middle layers, one to four octaves: every octave's tiles in one launch, then the survivors of every octave
+static uvo_status surf_detect_tuned(Ctx* c, const LaneArgs& LA, int nimg, float thr)
+{
+    constexpr int TW0 = kMergedTW0, TH0 = kMergedTH0, TW1 = kMergedTW1, TH1 = kO1TileRows;
+    constexpr size_t lds0 = hessian_c_tile_lds<0, TW0, TH0>(), lds1 = hessian_c_tile_lds<1, TW1, TH1>(), lds = lds0 > lds1 ? lds0 : lds1;
+    static_assert(lds <= 54600, "three blocks of the merged detection launch must fit a CU's 160 KB of LDS");
+    const int w = c->img_w, h = c->img_h;
+    const OctavePat* ops = reinterpret_cast<const OctavePat*>(c->h_octpat.data());      // surf_prepare's table for this image size; an absent octave's entry is zero
+    const int total = merged_grid(ops).total;
+    if (total > 0) {
+        auto kern = k_hessian_nms_all<TW0, TH0>;
+        static bool lds_raised[64] = {false};
+        UVO_HIP_TRY(c, raise_dynamic_lds(c, kern, lds, lds_raised));
+        StageTimer t(c, ST_HESSIAN_O0);
+        HessDims hd;
+        for (int o = 0; o < 4; o++) {
+            OctDims& d = hd.o[o];
+            for (int l = 0; l < 5; l++) { d.L[l].samples_i = ops[o].L[l].samples_i; d.L[l].samples_j = ops[o].L[l].samples_j; }
+            d.rows = ops[o].rows; d.cols = ops[o].cols; d.octave = ops[o].octave;
+            for (int l = 0; l < 3; l++) d.nms_margin[l] = ops[o].nms_margin[l];
+        }
+        Ctx::TraceRec* trh = (c->trace_on && c->trace_cur >= 0) ? &c->trace[c->trace_cur] : nullptr;      // uvo_trace_row::dev_ms[6], [7]
+        if (trh) (void)hipEventRecord(trh->ev[6], c->stream);
+        hipLaunchKernelGGL(kern, dim3(total, nimg), dim3(kP23Threads), lds, c->stream, LA, w, h, hd, thr, c->d_hess_order);
+        if (trh) { (void)hipEventRecord(trh->ev[7], c->stream); trh->det_marked = true; }
+        UVO_HIP_TRY(c, hipGetLastError());
+    }
+    {   // outer-layer determinants, last comparison, keypoints
+        StageTimer t(c, ST_HESSIAN_O0 + c->p.SURF_OCTAVES_NUMBER - 1);
+        hipLaunchKernelGGL(k_hessian_finish, dim3((c->surv_cap + kFinishPerWg - 1) / kFinishPerWg), dim3(256), 0, c->stream, LA, static_cast<const OctavePat*>(c->d_octpat), w, h);
+        UVO_HIP_TRY(c, hipGetLastError());
+    }
+    return UVO_OK;
+}
+
+static uvo_status surf_order(Ctx* c, const LaneArgs& LA, int nimg)
+{
+    StageTimer t(c, ST_SORT);
+    hipLaunchKernelGGL(k_order, dim3(1, nimg), dim3(kOrderThreads), 0, c->stream, LA, c->d_area_iscale);
+    if (c->cap > kOrderCap) {                              // the counts live on the device: each of these returns at once for an image k_order ordered
+        const int tiles_max = ((c->cap + 255) / 256) * ((c->cap + kSortChunk - 1) / kSortChunk);
+        hipLaunchKernelGGL(k_rank_partial, dim3(tiles_max < 512 ? tiles_max : 512, nimg), dim3(256), 0, c->stream, LA);
+        hipLaunchKernelGGL(k_rank_scatter, dim3((c->cap + 255) / 256, nimg), dim3(256), 0, c->stream, LA);
+        hipLaunchKernelGGL(k_big_sort, dim3(nimg), dim3(1024), 0, c->stream, LA, c->cap, c->d_area_iscale);
+    }
+    UVO_HIP_TRY(c, hipGetLastError());
+    return UVO_OK;
+}
+
+static uvo_status surf_describe(Ctx* c, const LaneArgs& LA, int nimg)
+{
+    const int w = c->img_w, h = c->img_h;
+    StageTimer t(c, ST_DESCRIPTOR);
+    // windows wider than kMaxWin: only where the configuration and the image size can produce one (never for the shipped configuration), or
+    // under uvo_surf_set_detection_path(1); the launch walks the ordered keypoints and describes the wide ones
+    const bool wide = c->sh->surf_detection_path == 1 || widest_window(c, w, h) > kMaxWin;
+    const int kWideGrid = 128;                             // keypoints walked side by side (x 21 destination rows)
+    if (c->p.SURF_UPRIGHT) {
+        const size_t lds_small = sizeof(float) * 21 * ((kSmallWin + 3) | 1), lds_big = sizeof(float) * 4 * kBigRow;
+        // large-window part: 8192 persistent waves (1024 workgroups per image) for the tasks (512: 80 us, 768..2048: 66-69 us)
+        const int nbig = 1024;
+        // small-window part: a workgroup per keypoint -- as many as the last pair whose counts reached the host had, plus a quarter
+        // (the workgroups walk the list when there are more: any grid gives the same descriptors); max_kpts of them before that
+        const int hint = c->sh->kp_hint;
+        int nsmall = hint > 0 ? ((hint + hint / 4 + 255) & ~255) : c->cap;
+        nsmall = nsmall < 512 ? 512 : (nsmall > c->cap ? c->cap : nsmall);
+        // Measured, descriptor launch alone: every image's large-window workgroups first, then the small-window workgroups with the
+        // images alternating, on the hint-sized grid (what k_descriptor64 does): 57.2 us; image by image on max_kpts workgroups
+        // (rounds 2-4): 60.5; large-window workgroups first, small-window workgroups image by image: 59.7; 512 / 2048 large-window
+        // workgroups per image: 58.1 / 58.9
+        hipLaunchKernelGGL(k_descriptor64, dim3((nbig + nsmall) * nimg), dim3(256), lds_small > lds_big ? lds_small : lds_big, c->stream, DescLane{ { LA } }, w, h, nbig, nimg);
+        hipLaunchKernelGGL(k_descriptor64_big_finish, dim3(1024, nimg), dim3(256), 0, c->stream, LA);
+        if (wide) {
+            hipLaunchKernelGGL(k_descriptor_wide<false>, dim3(21 * kWideGrid, nimg), dim3(256), 0, c->stream, LA.da, w, h, LA.patch);
+            hipLaunchKernelGGL(k_descriptor_wide_finish, dim3(kWideGrid, nimg), dim3(256), 0, c->stream, LA.da, LA.patch);
+        }
+    } else {
+        // orientation assignment, then every descriptor from its rotated window (not the shipped configuration)
+        const DescArgs& da = LA.da;
+        const size_t lds_rot = sizeof(float) * 21 * (kMaxWin + 1);
+        static bool lds_raised[64] = {false};
+        UVO_HIP_TRY(c, raise_dynamic_lds(c, k_descriptor_rot, lds_rot, lds_raised));
+        hipLaunchKernelGGL(k_surf_orientation, dim3((c->cap + 3) / 4, nimg), dim3(256), 0, c->stream, da, w, h);
+        hipLaunchKernelGGL(k_descriptor_rot, dim3(2048, nimg), dim3(256), lds_rot, c->stream, da, w, h);
+        if (wide) {
+            hipLaunchKernelGGL(k_descriptor_wide<true>, dim3(21 * kWideGrid, nimg), dim3(256), 0, c->stream, da, w, h, LA.patch);
+            hipLaunchKernelGGL(k_descriptor_wide_finish, dim3(kWideGrid, nimg), dim3(256), 0, c->stream, da, LA.patch);
+        }
+    }
+    UVO_HIP_TRY(c, hipGetLastError());
+    return UVO_OK;
+}
+
+uvo_status surf_detect(Ctx* c, int nimg, int gate_min_features)
+{
+    UVO_TRY(surf_prepare(c, c->img_w, c->img_h));
+    const LaneArgs LA = lane_args(c, nimg, gate_min_features);
+    const float thr = (float)c->p.SURF_MIN_HESSIAN;
+    UVO_TRY(surf_integral_launch(c, LA, nimg));
+    UVO_TRY(general_path(c) ? surf_detect_general(c, LA, nimg, thr) : surf_detect_tuned(c, LA, nimg, thr));
+    UVO_TRY(surf_order(c, LA, nimg));
+    return surf_describe(c, LA, nimg);
 }
 
 uvo_status surf_hessian_layer_debug(Ctx* c, int octave, int layer, float* det, float* trace)

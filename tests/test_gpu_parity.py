@@ -51,7 +51,7 @@ def test_integral_wider_than_one_pass_and_ragged(oracle):
 @pytest.mark.parametrize("octave,layer", [(0, 0), (0, 4), (1, 2), (2, 1), (3, 0), (3, 4)])
 def test_hessian_layer_debug_hook_bit_exact(ctx, oracle, octave, layer):
     """uvo_hessian_layer is the parity hook (k_hessian_layer_debug: calcLayerDetAndTrace from the run-time box patterns, the
-    arithmetic k_hessian_finish uses); the fused detection kernels k_hessian_nms_c / _p are covered by the keypoint equality of
+    arithmetic k_hessian_finish uses); the fused detection launch k_hessian_nms_all is covered by the keypoint equality of
     the SURF tests below, which any wrong determinant near a maximum breaks."""
     img = _rand_img(2, 360, 640)
     s = ctx.integral(img)
@@ -88,7 +88,7 @@ def test_surf_detect_describe_bit_exact(ctx, oracle, shape, thr):
 @pytest.mark.parametrize("n_octaves", [1, 2, 3, 4])
 @pytest.mark.parametrize("shape", [(48, 48), (36, 300), (240, 320)])
 def test_surf_octave_counts_and_tiny_images_bit_exact(ctx, oracle, shape, n_octaves):
-    """nOctaves 1..4 (four takes the launch that carries octaves 0, 2 and 3 together, fewer the per-octave kernels) on images so
+    """nOctaves 1..4 (every count takes the one launch that carries all its octaves' tiles together) on images so
     small that the upper octaves have few or no samples: same keypoints and descriptors as the oracle, or none on both sides."""
     import ergo_uvo_amd as uvo
     img = _rand_img(5, *shape)

@@ -8,11 +8,8 @@
 #   ab <steps>                  previous build (ergo_uvo_amd/lib_ab/libuvo_hip_old.so) against the current one, interleaved
 #   sweep <steps>               overlap / depth / PnP-slot settings of the one-pair pipeline
 #   prof <tag> [sync|pipe]      rocprofv3 --kernel-trace --stats of a synchronous run / the pipelined bench
-#   hess-split <tag>            per-octave detection kernels (UVO_HESSIAN_SPLIT=1) and the merged launch, old build and new
-#   pmc <tag> <kernel pattern> [split]   counter passes (separate --pmc runs: SQ set 1, SQ set 2, FETCH_SIZE, WRITE_SIZE) of a synchronous run
+#   pmc <tag> <kernel pattern>   counter passes (separate --pmc runs: SQ set 1, SQ set 2, FETCH_SIZE, WRITE_SIZE) of a synchronous run
 #   ctx-reuse [pairs]           five contexts in a row, stream pool on and off
-#   sens [steps]                a kernel of known duration added to stage A (one wave / chip-filling): how the cadence follows thin and fat time
-#   stamps                      phases of the detection launch's workgroups (UVO_HESS_STAMPS -> tools/probe/hess_stamps.py)
 #   rates                       issue-rate probe (built by hipcc here if missing)
 #   topo                        what the rank pinning reads on this box
 #   configs                     tools/bench_configs.py
@@ -47,29 +44,13 @@ step() {
                sync)   rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_${t}_sync -- python3 tools/prof_stereo.py 24 > gpurun_out/prof_${t}_sync.log 2>&1 || return 1; python tools/probe/kstats.py prof_${t}_sync 26 ;;
                pipe)   rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_${t}_pipe -- python3 bench.py --steps 200 --blocks 1 --timed-only > gpurun_out/prof_${t}_pipe.log 2>&1 || return 1; python tools/probe/kstats.py prof_${t}_pipe 26 ;;
              esac ;;
-    hess-split) t=$1
-             for v in old new; do
-               if [ $v = old ]; then export UVO_HIP_LIB=$OLD; else unset UVO_HIP_LIB; fi
-               UVO_HESSIAN_SPLIT=1 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_${t}_${v}_split -- python3 tools/prof_stereo.py 24 > gpurun_out/prof_${t}_${v}_split.log 2>&1 || return 1
-               rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_${t}_${v}_merged -- python3 tools/prof_stereo.py 24 > gpurun_out/prof_${t}_${v}_merged.log 2>&1 || return 1
-               echo "== $v, one launch per octave"; python tools/probe/kstats.py prof_${t}_${v}_split 30 | grep -i hessian
-               echo "== $v, merged launch"; python tools/probe/kstats.py prof_${t}_${v}_merged 30 | grep -i hessian
-             done; unset UVO_HIP_LIB ;;
-    pmc)     t=$1; pat=$2; [ "$3" = split ] && export UVO_HESSIAN_SPLIT=1
+    pmc)     t=$1; pat=$2
              rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAVES --output-format csv -d gpurun_out/pmc_${t}_sq1 -- python3 tools/prof_stereo.py 6 > gpurun_out/pmc_${t}_sq1.log 2>&1 || return 1
              rocprofv3 --kernel-trace --pmc SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_LDS SQ_INSTS_SALU SQ_INSTS_VALU_CVT SQ_INSTS_VMEM_RD SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS --output-format csv -d gpurun_out/pmc_${t}_sq2 -- python3 tools/prof_stereo.py 6 > gpurun_out/pmc_${t}_sq2.log 2>&1 || return 1
              rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d gpurun_out/pmc_${t}_fetch -- python3 tools/prof_stereo.py 6 > gpurun_out/pmc_${t}_fetch.log 2>&1 || return 1
              rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d gpurun_out/pmc_${t}_write -- python3 tools/prof_stereo.py 6 > gpurun_out/pmc_${t}_write.log 2>&1 || return 1
-             unset UVO_HESSIAN_SPLIT
              for p in sq1 sq2 fetch write; do python tools/probe/pmc_quick.py pmc_${t}_${p} "$pat" 2; done ;;
     ctx-reuse) python tools/probe/ctx_reuse.py ${1:-400} 2>/dev/null | grep pool; UVO_STREAM_POOL=0 python tools/probe/ctx_reuse.py ${1:-400} 2>/dev/null | grep pool ;;
-    sens)    n=${1:-300}; LBL=base brun --steps $n || return 1
-             for us in 20 40; do UVO_PROBE_THIN_US=$us LBL="one wave held +$us us per pair" brun --steps $n; UVO_PROBE_FAT_US=$us LBL="768 LDS-filling blocks +$us us" brun --steps $n; done
-             LBL=base brun --steps $n ;;
-    stamps)  # the measurement build (make STAMPS=1 BUILD=build_stamps OUT=../lib_ab/libuvo_hip_stamps.so in ergo_uvo_amd/csrc): stamps cost time when compiled in
-             make -C ergo_uvo_amd/csrc -s -j8 STAMPS=1 BUILD=build_stamps OUT=../lib_ab/libuvo_hip_stamps.so || return 1
-             UVO_HIP_LIB=$PWD/ergo_uvo_amd/lib_ab/libuvo_hip_stamps.so UVO_HESS_STAMPS=gpurun_out/${TAG}_hess_stamps.csv python tools/prof_stereo.py 8 > /dev/null 2>&1; python tools/probe/hess_stamps.py gpurun_out/${TAG}_hess_stamps.csv
-             UVO_HIP_LIB=$PWD/ergo_uvo_amd/lib_ab/libuvo_hip_stamps.so UVO_DESC_STAMPS=gpurun_out/${TAG}_desc_stamps.csv python tools/prof_stereo.py 8 > /dev/null 2>&1; python tools/probe/desc_stamps.py gpurun_out/${TAG}_desc_stamps.csv ;;
     rates)   [ tools/probe/issue_rate_probe -nt tools/probe/issue_rate_probe.hip ] || /opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 tools/probe/issue_rate_probe.hip -o tools/probe/issue_rate_probe || return 1
              tools/probe/issue_rate_probe ;;
     topo)    for n in /sys/class/kfd/kfd/topology/nodes/*; do echo "== $n"; grep -E "simd_count|cpu_cores_count|location_id|domain|drm_render_minor" $n/properties 2>&1; done

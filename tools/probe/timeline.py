@@ -13,10 +13,10 @@ def main(d):
     f = sorted(glob.glob(d + "/**/*_kernel_trace.csv", recursive=True))[0]
     rows = [(short(r["Kernel_Name"]), int(r["Start_Timestamp"]), int(r["End_Timestamp"]), int(r["Queue_Id"])) for r in csv.DictReader(open(f))]
     rows.sort(key=lambda r: r[1])
-    hs = [r for r in rows if r[0].startswith("k_hessian_nms_c<0")]
+    hs = [r for r in rows if r[0].startswith("k_hessian_nms_all")]       # one detection launch per pair
     st = np.array([r[1] for r in hs])
     gaps = np.diff(st)
-    # pipelined region: consecutive o0 launches closer than 0.6 ms; the synchronous legs are ~0.9 ms apart
+    # pipelined region: consecutive detection launches closer than 0.6 ms; the synchronous legs are ~0.9 ms apart
     dense = gaps < 600_000
     # longest dense run(s)
     runs, i = [], 0

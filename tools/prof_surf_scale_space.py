@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """SURF scale spaces other than the shipped 4 x 3 (surf.hip: the general scale-space path, k_descriptor_wide) on the C3 frames, 1920x1080:
   python tools/prof_surf_scale_space.py detect [frames]        detection + description ms per frame (wall clock, image resident in HBM) and the
-                                                              library's stage timers, for (4,3) tuned, (4,3) forced general, (4,2), (4,4), (5,3), (3,5)
+                                                              library's stage timers, for (4,3) tuned, (4,3) forced general, (3,3), (2,3), (1,3) tuned, (4,2), (4,4), (5,3), (3,5)
   python tools/prof_surf_scale_space.py loops [pairs]          the stereo loop's pairs/s, synchronous and with six in flight, for (4,3) and (4,2)
   python tools/prof_surf_scale_space.py one NO NL PATH [frames]  one configuration only, for rocprofv3 --kernel-trace --stats
 Prints one JSON object."""
@@ -16,7 +16,8 @@ for _v in ("OMP_NUM_THREADS", "OPENBLAS_NUM_THREADS", "MKL_NUM_THREADS"):
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 W, H, THR = 1920, 1080, 6387
-CONFIGS = [("4x3_tuned", 4, 3, 0), ("4x3_general", 4, 3, 1), ("4x2", 4, 2, 0), ("4x4", 4, 4, 0), ("5x3", 5, 3, 0), ("3x5", 3, 5, 0)]
+CONFIGS = [("4x3_tuned", 4, 3, 0), ("4x3_general", 4, 3, 1), ("3x3_tuned", 3, 3, 0), ("2x3_tuned", 2, 3, 0), ("1x3_tuned", 1, 3, 0),
+           ("4x2", 4, 2, 0), ("4x4", 4, 4, 0), ("5x3", 5, 3, 0), ("3x5", 3, 5, 0)]
 
 
 def detect(configs, frames):
@@ -38,7 +39,7 @@ def detect(configs, frames):
         ctx.timing_enable(True); ctx.timing_reset()
         for _ in range(frames):
             ctx.detect_features(img)
-        stages = {k: round(ms / max(n, 1), 4) for k, (ms, n) in ctx.timing().items() if n > 0}
+        stages = {k: round(ms / frames, 4) for k, (ms, n) in ctx.timing().items() if n > 0}      # per frame: two launches may share a slot
         ctx.timing_enable(False)
         win = (21.0 * (kps["size"] * 1.2 / 9.0)).astype(int)
         out[name] = {"kpts": int(len(kps)), "windows_over_740": int((win > 740).sum()), "detect_and_describe_ms_per_frame": round(wall * 1e3, 3),
