@@ -838,6 +838,16 @@ class Context:
         self._check(self._lib.uvo_homography_models(self._h, _p(src), _p(dst), len(src), _p(sub), len(sub), _p(models), _p(nm)))
         return models.reshape(-1, 3, 3), nm
 
+    def homography_fit_all(self, src, dst, where=1):
+        """Test hook (uvo_homography_fit_all): findHomography's method-0 fit alone on pixel points src, dst (n x 2 float32).  where 0: the
+        host policy, 1: the kernel as the resident chain launches it.  Returns (ok, H float64 [3, 3]); H is zeros when not ok."""
+        src, dst = _np(src, np.float32), _np(dst, np.float32)
+        if src.shape != dst.shape or src.ndim != 2 or src.shape[1] != 2:
+            raise ValueError("homography_fit_all: src, dst n x 2")
+        H = np.zeros((3, 3)); ok = C.c_int(0)
+        self._check(self._lib.uvo_homography_fit_all(self._h, _p(src), _p(dst), len(src), int(where), _p(H), C.byref(ok)))
+        return bool(ok.value), H
+
     def recoverPose(self, E, pts1, pts2, K, mask):
         E, p1, p2, K = _np(E, np.float64), _np(pts1, np.float32), _np(pts2, np.float32), _np(K, np.float64)
         m = _np(mask, np.uint8).copy(); R = np.empty((3, 3)); t = np.empty(3); good = C.c_int(0)

@@ -22,7 +22,7 @@ EXPORTS = [
     "uvo_match_knn2_ratio", "uvo_match_knn2", "uvo_match_knn2_ratio_dim", "uvo_match_knn2_dim", "uvo_match_knn2_ratio_hamming", "uvo_match_knn2_hamming", "uvo_match_loop_knn2", "uvo_triangulate_points", "uvo_extract_3d_points",
     "uvo_solve_pnp_ransac", "uvo_reproject_errors", "uvo_rodrigues", "uvo_stereo_set_rig", "uvo_stereo_reset", "uvo_stereo_step",
     "uvo_stereo_set_depth", "uvo_stereo_submit", "uvo_stereo_collect",
-    "uvo_stereo_get", "uvo_find_essential_mat", "uvo_five_point_models", "uvo_solve_poly10", "uvo_homography_models", "uvo_recover_pose", "uvo_find_homography", "uvo_decompose_homography_mat",
+    "uvo_stereo_get", "uvo_find_essential_mat", "uvo_five_point_models", "uvo_solve_poly10", "uvo_homography_models", "uvo_homography_fit_all", "uvo_mono_method_refusal", "uvo_recover_pose", "uvo_find_homography", "uvo_decompose_homography_mat",
     "uvo_recover_pose_homography", "uvo_select_estimation_method", "uvo_estimate_relative_pose", "uvo_mono_set_camera",
     "uvo_mono_reset", "uvo_mono_step", "uvo_mono_submit", "uvo_mono_collect", "uvo_mono_get", "uvo_mono_set_pose_stage", "uvo_mono_pose_stats", "uvo_get_image",
     "uvo_ctx_set_camera", "uvo_stereo_step_frames", "uvo_stereo_submit_frames", "uvo_mono_step_frames", "uvo_mono_submit_frames",

@@ -751,15 +751,19 @@ static uvo_status stereo_submit_refusal(uvo_ctx* c, const char* who)
     if (c->timing && c->sh->n_pending > 0) return fail(c, UVO_INVALID_ARG, "timing mode measures one pair at a time: collect before submitting");
     return UVO_OK;
 }
+// the two estimators' methods, checked where they are run and never at context creation (stereo contexts carry anything there)
+static const char* bad_outlier_methods(const uvo_params& p);
 static uvo_status mono_step_refusal(uvo_ctx* c)
 {
     if (!c->sh->mono_cam_set) return fail(c, UVO_INVALID_ARG, "uvo_mono_set_camera has not been called");
+    if (const char* why = bad_outlier_methods(c->p)) return fail(c, UVO_INVALID_ARG, why);
     if (c->sh->mono_pipelined) return fail(c, UVO_INVALID_ARG, "uvo_mono_step after uvo_mono_submit: call uvo_mono_reset first (the previous frame is held by the pipeline)");
     return need_loop_table(c);
 }
 static uvo_status mono_submit_refusal(uvo_ctx* c, const char* who)
 {
     if (!c->sh->mono_cam_set) return fail(c, UVO_INVALID_ARG, "uvo_mono_set_camera has not been called");
+    if (const char* why = bad_outlier_methods(c->p)) return fail(c, UVO_INVALID_ARG, why);
     if (c->sh->lanes.size() < 2) return fail(c, UVO_INVALID_ARG, "uvo_mono_submit needs at least two lanes (uvo_stereo_set_depth): a frame is matched against the previous lane's buffers");
     UVO_TRY(need_loop_table(c));
     if (c->sh->n_pending >= (int)c->sh->lanes.size()) { c->err = std::string(who) + ": the pipeline is full; collect a frame first (uvo_stereo_set_depth)"; return UVO_INVALID_ARG; }
@@ -1928,7 +1932,8 @@ try {
 extern "C" uvo_status uvo_find_essential_mat(uvo_ctx* c, const uvo_point2f* p1, const uvo_point2f* p2, int n, const double* K, int method,
                                              double prob, double threshold, int max_iters, double* E, uint8_t* mask, int* ok)
 try {
-    if (!c || !p1 || !p2 || !K || !E || !mask || !ok || n < 0 || (method != 4 && method != 8)) return UVO_INVALID_ARG;
+    if (!c || !p1 || !p2 || !K || !E || !mask || !ok || n < 0) return UVO_INVALID_ARG;
+    if (const char* why = mono_essential_method_refusal(method)) return fail(c, UVO_INVALID_ARG, why);      // 8 RANSAC, anything else LMedS, as OpenCV
     (void)hipSetDevice(c->device);
     return mono_find_essential(c, p1, p2, n, K, method, prob, threshold, max_iters, E, mask, ok);
 } UVO_ABI_CATCH(c)
@@ -1958,6 +1963,14 @@ try {
     UVO_TRY(need_idle(c, "uvo_homography_models"));
     return mono_homography_models(c, src, dst, n, subsets, nsub, models, nmodels);
 } UVO_ABI_CATCH(c)
+// test hook: findHomography's method-0 fit alone (uvo_h_fit.h) -- where 0: the host policy, where 1: k_h_fit_all as the resident chain launches it
+extern "C" uvo_status uvo_homography_fit_all(uvo_ctx* c, const float* src, const float* dst, int n, int where, double* H, int* ok)
+try {
+    if (!c || !src || !dst || !H || !ok || n < 1 || (where != 0 && where != 1)) return UVO_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    UVO_TRY(need_idle(c, "uvo_homography_fit_all"));
+    return mono_homography_fit_all(c, src, dst, n, where, H, ok);
+} UVO_ABI_CATCH(c)
 extern "C" uvo_status uvo_recover_pose(uvo_ctx* c, const double* E, const uvo_point2f* p1, const uvo_point2f* p2, int n, const double* K,
                                        double* R, double* t, uint8_t* mask, int* good)
 try {
@@ -1968,7 +1981,8 @@ try {
 extern "C" uvo_status uvo_find_homography(uvo_ctx* c, const uvo_point2f* p1, const uvo_point2f* p2, int n, int method, double threshold,
                                           int max_iters, double confidence, double* H, uint8_t* mask, int* ok)
 try {
-    if (!c || !p1 || !p2 || !H || !mask || !ok || n < 0 || (method != 4 && method != 8)) return UVO_INVALID_ARG;
+    if (!c || !p1 || !p2 || !H || !mask || !ok || n < 0) return UVO_INVALID_ARG;
+    if (const char* why = mono_homography_method_refusal(method)) return fail(c, UVO_INVALID_ARG, why);
     (void)hipSetDevice(c->device);
     return mono_find_homography(c, p1, p2, n, method, threshold, max_iters, confidence, H, mask, ok);
 } UVO_ABI_CATCH(c)
@@ -2049,11 +2063,15 @@ static bool estimate_accepted(const uvo_params& p, int valid_inliers, int n)
     const double valid_point_fraction = (double)valid_inliers / n;
     return valid_point_fraction >= p.VPF_THRESHOLD && valid_inliers >= p.MIN_NUM_INLIERS;
 }
+extern "C" const char* uvo_mono_method_refusal(int essential_method, int homography_method)
+try {
+    if (const char* why = mono_essential_method_refusal(essential_method)) return why;
+    return mono_homography_method_refusal(homography_method);
+} UVO_ABI_CATCH_RET(nullptr, nullptr)
 static const char* bad_outlier_methods(const uvo_params& p)
 {
-    if ((p.ESSENTIAL_OUTLIER_METHOD != 4 && p.ESSENTIAL_OUTLIER_METHOD != 8) || (p.HOMOGRAPHY_OUTLIER_METHOD != 4 && p.HOMOGRAPHY_OUTLIER_METHOD != 8))
-        return "outlier methods must be 4 (LMEDS) or 8 (RANSAC)";
-    return nullptr;
+    if (const char* why = mono_essential_method_refusal(p.ESSENTIAL_OUTLIER_METHOD)) return why;
+    return mono_homography_method_refusal(p.HOMOGRAPHY_OUTLIER_METHOD);
 }
 // estimate_relative_pose (VOU:134-180) on host points through the device-resident chains (pose stage 1): the points are staged once
 // (mono_stage_points: what k_mono_prep leaves behind a frame's stage A), then each attempt is the chain the loop's stage B runs

@@ -18,6 +18,7 @@
 #include "uvo_ctx.h"
 #include "uvo_h_vote.h"
 #include "uvo_mono.h"
+#include "uvo_h_fit.h"
 #include "uvo_epnp.h"
 #include <string.h>
 #include <math.h>
@@ -1312,6 +1313,77 @@ static int h_compact_refit(const float* in1, const float* in2, int n, const uint
     return k;
 }
 
+// ---- findHomography with method 0: every point fits, nothing is sampled (uvo_h_fit.h carries the arithmetic and its summation order) ----
+// One workgroup per fit: the statistics, LtL, the eigen-solve (thread 0, on LDS) and the LM iterations inside the launch, workgroup
+// barriers only.  M / m: the float pairs where the caller has them on the device; H (9 doubles) and the status word (1 fitted, 0 not:
+// H is zeros) go where the host reads them after its next wait -- pinned memory.
+__global__ __launch_bounds__(kHfLanes) void k_h_fit_all(const float* __restrict__ M, const float* __restrict__ m, int n, double* __restrict__ H_out, int* __restrict__ status_out)
+{
+    __shared__ HFitWs ws;
+    HFitDev p{(int)threadIdx.x};
+    const int ok = hf_fit_all(p, M, m, n, &ws);
+    if (threadIdx.x == 0) { for (int k = 0; k < 9; k++) H_out[k] = ws.H[k]; *status_out = ok; }
+}
+// the launch, for the resident chain and the hook alike: H in h_models[0..8], the status in h_counts[0] (-1 until the kernel has written it)
+static uvo_status queue_h_fit_all(Ctx* c, MonoWs* w, const float* dM, const float* dm, int n)
+{
+    w->h_counts[0] = -1;
+    hipLaunchKernelGGL(k_h_fit_all, dim3(1), dim3(kHfLanes), 0, c->stream, dM, dm, n, w->h_models.data(), w->h_counts.data());
+    UVO_HIP_TRY(c, hipGetLastError());
+    return UVO_OK;
+}
+static int h_fit_all_host(const float* M, const float* m, int n, double* H)
+{
+    HFitWs ws; HFitHost p;
+    const int ok = hf_fit_all(p, M, m, n, &ws);
+    memcpy(H, ws.H, sizeof(double) * 9);
+    return ok;
+}
+// findHomography's method, where it is run: 0 (all points), 4 (LMedS) and 8 (RANSAC) are served; the rest is refused by name -- the
+// method's and the parameter's (the operator's `method` argument is that parameter in the reference, VOU:152)
+const char* mono_homography_method_refusal(int method)
+{
+    if (method == 0 || method == 4 || method == 8) return nullptr;
+    if (method == 16) return "HOMOGRAPHY_OUTLIER_METHOD 16: RHO is not implemented (findHomography serves 0 all points, 4 LMEDS, 8 RANSAC)";
+    if (method >= 32 && method <= 38) return "HOMOGRAPHY_OUTLIER_METHOD 32..38: USAC is not implemented (findHomography serves 0 all points, 4 LMEDS, 8 RANSAC)";
+    return "HOMOGRAPHY_OUTLIER_METHOD: unknown estimation method (findHomography serves 0 all points, 4 LMEDS, 8 RANSAC)";
+}
+// findEssentialMat's: 8 is RANSAC and every other value LMedS, as in OpenCV; only the USAC family is refused
+const char* mono_essential_method_refusal(int method)
+{
+    if (method >= 32 && method <= 38) return "ESSENTIAL_OUTLIER_METHOD 32..38: USAC is not implemented (findEssentialMat: 8 is RANSAC, any other value LMEDS)";
+    return nullptr;
+}
+
+// test hook (uvo_homography_fit_all): the all-point fit alone on the caller's pairs.  where 0: the host policy on the pinned mirrors;
+// where 1: the points uploaded, then the very launch the resident chain queues.  n == 4 is findHomography's four-point route on either
+// side (homography_kernel on the host, no refinement), as the operator and the chain take it.
+uvo_status mono_homography_fit_all(Ctx* c, const float* src, const float* dst, int n, int where, double* H, int* ok)
+{
+    *ok = 0;
+    for (int k = 0; k < 9; k++) H[k] = 0;
+    if (n > c->cap) { c->err = "point count exceeds the context's max_kpts"; return UVO_CAPACITY; }
+    MonoWs* w = mono_ws(c);
+    if (!w) { c->err = "mono workspace allocation failed"; return UVO_HIP_ERROR; }
+    if (n < 4) return UVO_OK;
+    memcpy(w->h_src.data(), src, sizeof(float) * 2 * n); memcpy(w->h_dst.data(), dst, sizeof(float) * 2 * n);
+    if (n == 4) {
+        double scratch[171]; int iscratch[18];
+        *ok = homography_kernel(w->h_src.data(), w->h_dst.data(), n, H, SArr<1>{scratch}, SArr<1>{scratch + 81}, SArr<1>{scratch + 90}, iscratch) > 0;
+        return UVO_OK;
+    }
+    if (where == 0) { *ok = h_fit_all_host(w->h_src.data(), w->h_dst.data(), n, H); return UVO_OK; }
+    hipStream_t st = c->stream;
+    UVO_HIP_TRY(c, hipMemcpyAsync(w->src, w->h_src.data(), sizeof(float) * 2 * n, hipMemcpyHostToDevice, st));
+    UVO_HIP_TRY(c, hipMemcpyAsync(w->dst, w->h_dst.data(), sizeof(float) * 2 * n, hipMemcpyHostToDevice, st));
+    UVO_TRY(queue_h_fit_all(c, w, w->src, w->dst, n));
+    UVO_HIP_TRY(c, host_sync(c, st));
+    if (w->h_counts[0] < 0) { c->err = "k_h_fit_all did not report"; return UVO_HIP_ERROR; }
+    *ok = w->h_counts[0];
+    memcpy(H, w->h_models.data(), sizeof(double) * 9);
+    return UVO_OK;
+}
+
 // cv::findHomography (VOU:152)
 uvo_status mono_find_homography(Ctx* c, const uvo_point2f* p1, const uvo_point2f* p2, int n, int method, double thr, int maxIters,
                                 double confidence, double* H, uint8_t* mask, int* ok)
@@ -1331,6 +1403,11 @@ uvo_status mono_find_homography(Ctx* c, const uvo_point2f* p1, const uvo_point2f
     if (n == 4) {
         memset(mask, 1, n);
         result = homography_kernel(src.data(), dst.data(), n, H, SArr<1>{scratch}, SArr<1>{scratch + 81}, SArr<1>{scratch + 90}, iscratch) > 0;
+    } else if (method == 0) {                    // all points: the host policy of uvo_h_fit.h on the pinned mirrors; nothing is launched or waited for
+        result = h_fit_all_host(src.data(), dst.data(), n, H);
+        memset(mask, result ? 1 : 0, n);
+        *ok = result;
+        return UVO_OK;
     } else {
         hipStream_t st = c->stream;
         const bool lmeds = method != 8;
@@ -1930,6 +2007,8 @@ __global__ __launch_bounds__(1024) void k_h_pick(const uvo_point2f* __restrict__
 // operator, and so is a vote no candidate won (R, t stay unwritten): the caller runs the host-pointer pose tail, as the definition does
 // (three uploads of the compacted inliers and two waits when the attempt is accepted).  "No upload, at most four waits" holds for the
 // attempts that are not handed over; uvo_mono_pose_stats counts the others as fallbacks with their waits and uploads.
+// Method 0 (all points; uvo_h_fit.h): k_h_fit_all and a memset in place of the hypothesis rounds, the mask and the host refit; TWO host waits
+// per attempt -- for H, which decomposeHomographyMat still takes on the host, and the end of the chain -- and no upload.
 uvo_status mono_homography_resident(Ctx* c, int n, const double* K, int method, double thr, int maxIters, double confidence, double HOMOGRAPHY_DISTANCE,
                                     MonoResident* out)
 {
@@ -1954,6 +2033,17 @@ uvo_status mono_homography_resident(Ctx* c, int n, const double* K, int method, 
         memset(mask, 1, n);
         UVO_HIP_TRY(c, hipMemsetAsync(hmask, 1, n, st));
         result = homography_kernel(hx1, hx2, n, H, SArr<1>{scratch}, SArr<1>{scratch + 81}, SArr<1>{scratch + 90}, iscratch) > 0;
+    } else if (method == 0) {
+        // all points: the fit is one launch on d_x1 / d_x2 and the mask a memset; no hypotheses, no scores, no mask to read.  The one
+        // wait here is for H, which decomposeHomographyMat takes on the host -- it stands where methods 4 and 8 wait for their scores
+        // and again for their mask, so a method-0 attempt has TWO host waits (this one and the end of the chain) against their three or four.
+        UVO_TRY(queue_h_fit_all(c, w, dx1, dx2, n));
+        UVO_HIP_TRY(c, hipMemsetAsync(hmask, 1, n, st));
+        UVO_HIP_TRY(c, host_sync(c, st));
+        if (w->h_counts[0] < 0) { c->err = "mono pose stage: k_h_fit_all did not report"; return UVO_HIP_ERROR; }
+        result = w->h_counts[0];
+        memcpy(H, w->h_models.data(), sizeof(H));
+        if (result) memset(mask, 1, (size_t)n);
     } else {
         const bool lmeds = method != 8;
         const int niters = h_niters(lmeds, confidence, maxIters);
@@ -2005,8 +2095,8 @@ uvo_status mono_homography_resident(Ctx* c, int n, const double* K, int method, 
         }
     }
     int k = 0;
-    if (result && n > 4) k = h_compact_refit(hx1, hx2, n, mask, w->h_src.data(), w->h_dst.data(), H);      // on the pinned mirror, which stays as it is
-    else if (result) k = n;
+    if (result && n > 4 && method != 0) k = h_compact_refit(hx1, hx2, n, mask, w->h_src.data(), w->h_dst.data(), H);      // on the pinned mirror, which stays as it is
+    else if (result) k = n;                                                  // four points, or method 0: H is final and every pair an inlier
     if (!result) { memset(mask, 0, (size_t)n); return UVO_OK; }
     out->ok = 1;
     out->n_in = out->valid_inliers = k;                                      // extract_inliers' count = countNonZero(mask) (VOU:154-157)

@@ -476,6 +476,9 @@ uvo_status mono_find_essential(Ctx* c, const uvo_point2f* p1, const uvo_point2f*
 uvo_status mono_five_point_models(Ctx* c, const double* q1, const double* q2, int n, const int* subsets, int nsub, double* models, int* nmodels);
 uvo_status mono_solve_poly10(Ctx* c, const double* coeffs, int npoly, double* roots_re, double* roots_im, int* stats);
 uvo_status mono_homography_models(Ctx* c, const float* src, const float* dst, int n, const int* subsets, int nsub, double* models, int* nmodels);
+uvo_status mono_homography_fit_all(Ctx* c, const float* src, const float* dst, int n, int where, double* H, int* ok);   // method 0's fit alone: 0 host policy, 1 k_h_fit_all
+const char* mono_homography_method_refusal(int method);      // nullptr when findHomography's method is served (0, 4, 8), else the refusal by name
+const char* mono_essential_method_refusal(int method);       // nullptr unless findEssentialMat's method is USAC (32..38)
 uvo_status mono_recover_pose(Ctx* c, const double* E, const uvo_point2f* p1, const uvo_point2f* p2, int n, const double* K,
                              double* R, double* t, uint8_t* mask, int* good);
 uvo_status mono_find_homography(Ctx* c, const uvo_point2f* p1, const uvo_point2f* p2, int n, int method, double thr, int maxIters,

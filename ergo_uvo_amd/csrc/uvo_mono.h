@@ -74,6 +74,26 @@ __host__ __device__ void jacobi_eigen(A Am, int n, A W, A V, IA indR, IA indC)
     }
 }
 
+// runKernel's scalar tail, shared with the all-point fit (uvo_h_fit.h): LtL's upper triangle mirrored, the eigenvector of the smallest
+// eigenvalue, denormalised by the two point sets' centroids (c..) and scales (s.. = count / sum of absolute deviations), H / H[8].
+template <class A, class IA>
+__host__ __device__ void homography_tail(double cMx, double cMy, double cmx, double cmy, double sMx, double sMy, double smx, double smy,
+                                         double* Hout, A LtL, A W, A V, IA ind)
+{
+    const double invHnorm[9] = { 1./smx, 0, cmx, 0, 1./smy, cmy, 0, 0, 1 };
+    const double Hnorm2[9] = { sMx, 0, -cMx*sMx, 0, sMy, -cMy*sMy, 0, 0, 1 };
+    for (int j = 0; j < 9; j++) for (int k = 0; k < j; k++) LtL[j*9 + k] = LtL[k*9 + j];
+    jacobi_eigen(LtL, 9, W, V, ind, ind + 9);
+    double H0[9], Ht[9], H1[9];
+    for (int k = 0; k < 9; k++) H0[k] = V[8*9 + k];
+    for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++)
+        Ht[r*3 + c] = invHnorm[r*3]*H0[c] + invHnorm[r*3+1]*H0[3 + c] + invHnorm[r*3+2]*H0[6 + c];
+    for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++)
+        H1[r*3 + c] = Ht[r*3]*Hnorm2[c] + Ht[r*3+1]*Hnorm2[3 + c] + Ht[r*3+2]*Hnorm2[6 + c];
+    double sc = 1./H1[8];
+    for (int k = 0; k < 9; k++) Hout[k] = H1[k]*sc;
+}
+
 // HomographyEstimatorCallback::runKernel: M -> m, `count` Point2f pairs (interleaved x,y floats).
 // scratch: LtL(81) W(9) V(81) doubles + 18 ints.  Returns 0 when the points are degenerate.
 template <class A, class IA>
@@ -89,8 +109,6 @@ __host__ __device__ int homography_kernel(const float* M, const float* m, int co
     }
     if (fabs(smx) < DBL_EPSILON || fabs(smy) < DBL_EPSILON || fabs(sMx) < DBL_EPSILON || fabs(sMy) < DBL_EPSILON) return 0;
     smx = count/smx; smy = count/smy; sMx = count/sMx; sMy = count/sMy;
-    const double invHnorm[9] = { 1./smx, 0, cmx, 0, 1./smy, cmy, 0, 0, 1 };
-    const double Hnorm2[9] = { sMx, 0, -cMx*sMx, 0, sMy, -cMy*sMy, 0, 0, 1 };
     for (i = 0; i < 81; i++) LtL[i] = 0;
     for (i = 0; i < count; i++) {
         double x = (m[2*i] - cmx)*smx, y = (m[2*i+1] - cmy)*smy;
@@ -99,16 +117,7 @@ __host__ __device__ int homography_kernel(const float* M, const float* m, int co
         const double Ly[9] = { 0, 0, 0, X, Y, 1, -y*X, -y*Y, -y };
         for (int j = 0; j < 9; j++) for (int k = j; k < 9; k++) LtL[j*9 + k] += Lx[j]*Lx[k] + Ly[j]*Ly[k];
     }
-    for (int j = 0; j < 9; j++) for (int k = 0; k < j; k++) LtL[j*9 + k] = LtL[k*9 + j];
-    jacobi_eigen(LtL, 9, W, V, ind, ind + 9);
-    double H0[9], Ht[9], H1[9];
-    for (int k = 0; k < 9; k++) H0[k] = V[8*9 + k];
-    for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++)
-        Ht[r*3 + c] = invHnorm[r*3]*H0[c] + invHnorm[r*3+1]*H0[3 + c] + invHnorm[r*3+2]*H0[6 + c];
-    for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++)
-        H1[r*3 + c] = Ht[r*3]*Hnorm2[c] + Ht[r*3+1]*Hnorm2[3 + c] + Ht[r*3+2]*Hnorm2[6 + c];
-    double sc = 1./H1[8];
-    for (int k = 0; k < 9; k++) Hout[k] = H1[k]*sc;
+    homography_tail(cMx, cMy, cmx, cmy, sMx, sMy, smx, smy, Hout, LtL, W, V, ind);
     return 1;
 }
 

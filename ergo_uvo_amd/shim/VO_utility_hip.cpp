@@ -185,6 +185,10 @@ void set_akaze_suppression(int where)
     g.akaze_suppression = where;
     g.akaze_suppression_sent = false;
 }
+void check_outlier_methods()
+{
+    if (const char* why = uvo_mono_method_refusal(ESSENTIAL_OUTLIER_METHOD, HOMOGRAPHY_OUTLIER_METHOD)) throw Error(UVO_INVALID_ARG, why);
+}
 void set_mono_pose_stage(int where)
 {
     if (where != 0 && where != 1) throw Error(UVO_INVALID_ARG, "set_mono_pose_stage: 0 (essential-first resident, the rest through the host-pointer operators) or 1 (every attempt resident)");

@@ -346,10 +346,26 @@ uvo_status uvo_solve_poly10(uvo_ctx* c, const double* coeffs, int npoly, double*
  * subset check.  src, dst: n x 2 f32 pixel points (host), subsets: nsub x 4 indices into them (any indices in [0, n)), nsub <= 2048
  * (UVO_CAPACITY beyond).  models: nsub x 9 f64, nmodels: nsub (host), 0 or 1; row i of models is written only when nmodels[i] is 1. */
 uvo_status uvo_homography_models(uvo_ctx* c, const float* src, const float* dst, int n, const int* subsets, int nsub, double* models, int* nmodels);
+/* test hook: findHomography's method-0 fit on its own (idle contexts only).  src, dst: n x 2 f32 pixel points (host), n <= max_kpts.
+ * where 0: the host policy of uvo_h_fit.h, as uvo_find_homography runs it; where 1: the one-workgroup kernel, launched as the
+ * device-resident chain launches it.  H: 9 f64, zeros when *ok = 0.  The two give the same bits.  n == 4 is the four-point route of
+ * every method (no refinement) on either side; n < 4 is *ok = 0. */
+uvo_status uvo_homography_fit_all(uvo_ctx* c, const float* src, const float* dst, int n, int where, double* H, int* ok);
 /* cv::recoverPose(E, p1, p2, K, R, t, mask), distance threshold 50 (VO_utility.cpp:149); mask is in/out */
 uvo_status uvo_recover_pose(uvo_ctx* c, const double* E, const uvo_point2f* p1, const uvo_point2f* p2, int n, const double* K,
                             double* R, double* t, uint8_t* mask, int* good);
-/* cv::findHomography(p1, p2, method, threshold, mask, maxIters, confidence)  (VO_utility.cpp:152) */
+/* cv::findHomography(p1, p2, method, threshold, mask, maxIters, confidence)  (VO_utility.cpp:152).  The method, checked here, in
+ * uvo_estimate_relative_pose and in the mono step / submit entries (before anything is queued), never at context creation:
+ *   0  all points (OpenCV's default): the normalised DLT over the n pairs, then ten LM iterations over all of them; the mask is all
+ *      ones.  Its sums are taken in the order ergo_uvo_amd/csrc/uvo_h_fit.h writes down, the same on host and device; H is not pinned
+ *      to OpenCV's last bits.  A degenerate or non-finite fit is *ok = 0 with a zero mask.
+ *   4  LMEDS, 8  RANSAC: hypotheses, mask, refit on the inliers, sums in sequential order (bit for bit the CPU restatement's).
+ *   16 (RHO) and 32..38 (USAC) are UVO_INVALID_ARG by name, every other value UVO_INVALID_ARG "unknown estimation method", as OpenCV
+ *   raises: no method is ever replaced silently.
+ * uvo_find_essential_mat: 8 is RANSAC and every other value LMEDS, as in OpenCV; only 32..38 (USAC) are refused.
+ * uvo_mono_method_refusal: NULL when the two methods are served, else the refusal's text (static; it names the parameter), for callers
+ * that want to know before their first frame. */
+const char* uvo_mono_method_refusal(int essential_method, int homography_method);
 uvo_status uvo_find_homography(uvo_ctx* c, const uvo_point2f* p1, const uvo_point2f* p2, int n, int method, double threshold,
                                int max_iters, double confidence, double* H, uint8_t* mask, int* ok);
 /* cv::decomposeHomographyMat(H, K, Rs, ts, ns)  (VO_utility.cpp:585): up to 4 solutions, Rs 4x9, ts 4x3, ns 4x3 (host) */
@@ -398,7 +414,9 @@ int        uvo_mono_get(uvo_ctx* c, const char* what, void* out, int cap_bytes);
  *      a host wait in between; at most four waits per homography attempt, nothing uploaded.  checkSubset, the refit with its LM
  *      refinement and decomposeHomographyMat stay on the host.  A single-solution decomposition and a vote without a winner are
  *      finished by route 0 from that point (counted as fallbacks).  uvo_estimate_relative_pose on host pointers then stages its points
- *      once and takes the same chains.
+ *      once and takes the same chains.  With HOMOGRAPHY_OUTLIER_METHOD 0 (all points) the hypothesis rounds, the mask and the host refit
+ *      are one launch (k_h_fit_all) and a memset: TWO waits per homography attempt -- for H, which decomposeHomographyMat takes on the
+ *      host, and at the end of the chain -- nothing uploaded.
  * Results do not depend on the value.  1 is faster wherever a frame takes a homography attempt, synchronously and with fourteen frames
  * in flight, and level with 0 on essential-only sequences; with six frames in flight at the shipped 0.1-px thresholds it measured level
  * too (profiles/mono_pose_resident.json), which is why it is not the default.  Refused with UVO_INVALID_ARG for other values, and while frames are in flight.  The master

@@ -97,6 +97,9 @@ void     set_akaze_suppression(int where);
 // 0 only a first attempt with the essential matrix, the rest through the host-pointer operators (the definition, the library's default); results do not depend
 // on it.  Sent to the context at its next use (refused there while frames are in flight).  Kept across a rebuilt context.
 void     set_mono_pose_stage(int where);
+// ESSENTIAL_OUTLIER_METHOD / HOMOGRAPHY_OUTLIER_METHOD as the globals hold them: throws Error naming the parameter when the library would refuse
+// one at the first estimate (uvo_mono_method_refusal); the mono node class asks once, at start-up
+void     check_outlier_methods();
 
 // Replacements for the cv:: functions the node loops call directly (visual_odometry.h:355, 631, 647-648, 673).
 void triangulatePoints(const uvocv::Mat& projMatr1, const uvocv::Mat& projMatr2, const std::vector<uvocv::Point2f>& projPoints1,

@@ -52,6 +52,7 @@ public:
     {
         if (mode_ != "mono" && mode_ != "stereo") throw Error(UVO_INVALID_ARG, "WRONG SELECTION OF VISUAL ODOMETRY NODE - CHOOSE BETWEEN mono AND stereo");   // VO:789
         get_VO_parameters(params);                                                       // VO:757
+        if (mode_ == "mono") check_outlier_methods();                                    // an unserved estimator method ends the node here, by name, not at its first estimate
         if (mode_ == "stereo") get_stereo_camera_parameters(params, CAMERA_NAME);        // VO:776
         else get_mono_camera_parameters(params, CAMERA_NAME);                            // VO:787
         R_currCam_prevCam_ = uvocv::Mat::eye(3, 3, uvocv::CV_64FC1); t_currCam_prevCam_ = uvocv::Mat::zeros(3, 1, uvocv::CV_64FC1);
