@@ -274,6 +274,20 @@ class Context:
         where = {"host": 0, "device": 1}.get(where, where)
         self._check(self._lib.uvo_orb_set_ranking(self._h, int(where)))
 
+    def orb_set_counts(self, where):
+        """Where the counts between ORB's launches are read while the rankings run on the device: "device" / 1 (they stay there: the fused
+        steps queue a detection without a host wait, orb_detect waits once for the count) or "host" / 0 (read back twice per image).  Not
+        consulted with the rankings on the host.  The results do not depend on it; the fused steps take the master context's value."""
+        where = {"host": 0, "device": 1}.get(where, where)
+        self._check(self._lib.uvo_orb_set_counts(self._h, int(where)))
+
+    def orb_stats(self):
+        """Figures of the ORB branch: dict(host_waits (stream waits of ORB detection on any lane since the previous call; read and cleared),
+        n_fast, n_ranked, n_keypoints (the last detection of this context's own lane whose counts reached the host; -1 where none did))."""
+        v = [C.c_int(0) for _ in range(4)]
+        self._check(self._lib.uvo_orb_stats(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("host_waits", "n_fast", "n_ranked", "n_keypoints"), (x.value for x in v)))
+
     def akaze_set_suppression(self, where):
         """Where AKAZE's sequential stages (contrast factor, duplicate suppression, refinement) run: "host" / 0 (the host scans of the
         candidate list) or "device" / 1 (k_ak_scan, k_ak_refine; the fused steps then queue their detection without a host wait).  The

@@ -671,7 +671,8 @@ static uvo_status check_cand_overflow(uvo_ctx* c, int nimg)
 
 // detect_features' AKAZE / ORB branch (VOU:93-105) inside the fused steps: each image through the lane's detector in turn (their host stages
 // -- AKAZE's contrast factor and duplicate suppression under uvo_akaze_set_suppression 0, ORB's retainBest rankings under
-// uvo_orb_set_ranking 0 -- run on this thread and wait for the device; AKAZE under setting 1 queues everything and hands back device counts), then the
+// uvo_orb_set_ranking 0, ORB's count readbacks under uvo_orb_set_counts 0 -- run on this thread and wait for the device; AKAZE under setting 1 and
+// ORB with rankings and counts on the device queue everything and hand back device counts), then the
 // counts are published where the SURF detector leaves its own: min(n, max_kpts) in d_counts[CN_NL + i], n in d_counts[CN_CAND0 + i] (more
 // than max_kpts is reported by the caller's overflow check; no list is cut), and the VO:556 gate evaluated on the device
 __global__ void k_binary_publish(int n0, int n1, int* cn, int cap, int nimg, int gate_min_features)
@@ -686,8 +687,9 @@ __global__ void k_binary_publish(int n0, int n1, int* cn, int cap, int nimg, int
     if (gate_min_features >= 0 && nimg == 2)                           // VO:556: both images need >= MIN_NUM_FEATURES keypoints, else no stereo matching
         cn[CN_NQA] = (cn[CN_NL] >= gate_min_features && cn[CN_NR] >= gate_min_features) ? cn[CN_NL] : 0;
 }
-// the same with the counts where AKAZE's device suppression leaves them (uvo_akaze_set_suppression 1): nothing of the detection came back to the host
-// (a candidate-list overflow -- d_ovf -- publishes no keypoints at all and leaves kCandListOverflow for the host's count check)
+// the same with the counts where AKAZE's device suppression (uvo_akaze_set_suppression 1) or ORB's counted kernels (uvo_orb_set_counts 1) leave them:
+// nothing of the detection came back to the host (a list overflow -- d_ovf -- publishes no keypoints at all and leaves kCandListOverflow for the
+// host's count check, which names AKAZE's candidate list or, for ORB, max_kpts as before)
 __global__ void k_binary_publish_dev(const int* d_n0, const int* d_n1, const int* d_ovf0, const int* d_ovf1, int* cn, int cap, int nimg, int gate_min_features)
 {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
@@ -705,7 +707,7 @@ static uvo_status binary_detect_lane(Ctx* c, int nimg, int gate_min_features)
 {
     int n[2] = {0, 0};
     const int* d_n[2] = {nullptr, nullptr}; const int* d_ovf[2] = {nullptr, nullptr};
-    for (int i = 0; i < nimg; i++) UVO_TRY(c->loop_detector() == 2 ? akaze_detect_lane(c, i, &n[i], &d_n[i], &d_ovf[i]) : orb_detect_lane(c, i, &n[i]));
+    for (int i = 0; i < nimg; i++) UVO_TRY(c->loop_detector() == 2 ? akaze_detect_lane(c, i, &n[i], &d_n[i], &d_ovf[i]) : orb_detect_lane(c, i, &n[i], &d_n[i], &d_ovf[i]));
     if (d_n[0]) hipLaunchKernelGGL(k_binary_publish_dev, dim3(1), dim3(64), 0, c->stream, d_n[0], d_n[nimg - 1], d_ovf[0], d_ovf[nimg - 1], c->d_counts, c->cap, nimg, gate_min_features);
     else hipLaunchKernelGGL(k_binary_publish, dim3(1), dim3(64), 0, c->stream, n[0], n[1], c->d_counts, c->cap, nimg, gate_min_features);
     UVO_HIP_TRY(c, hipGetLastError());
@@ -916,6 +918,22 @@ try {
     (void)hipSetDevice(c->device);
     UVO_TRY(need_idle(c, "uvo_orb_set_ranking"));
     return orb_set_ranking(c, where);
+} UVO_ABI_CATCH(c)
+// where the counts between ORB's launches are read when the rankings run on the device: 0 the host (two waits per image), 1 the kernels themselves
+// (none); the master context's value serves the lanes
+extern "C" uvo_status uvo_orb_set_counts(uvo_ctx* c, int where)
+try {
+    if (!c) return UVO_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    UVO_TRY(need_idle(c, "uvo_orb_set_counts"));
+    return orb_set_counts(c, where);
+} UVO_ABI_CATCH(c)
+extern "C" uvo_status uvo_orb_stats(uvo_ctx* c, int* host_waits, int* n_fast, int* n_ranked, int* n_keypoints)
+try {
+    if (!c) return UVO_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    UVO_TRY(need_idle(c, "uvo_orb_stats"));
+    return orb_stats(c, host_waits, n_fast, n_ranked, n_keypoints);
 } UVO_ABI_CATCH(c)
 // which detection kernels serve SURF: 0 the tuned ones where they apply and the general scale-space path otherwise, 1 the general path (and the
 // wide-window descriptor launch) for every configuration; the master context's value serves the lanes

@@ -21,6 +21,9 @@
 // keypoints -- is that of libstdc++'s std::nth_element + std::partition, a sequential algorithm stated pass by pass:
 //   k_rb_rank          both rankings, one launch each for all levels (uvo_orb_set_ranking 1, the default): introselect's Hoare passes
 //                      as stopper lists + independent swaps + a closed-form cut (uvo_retain_best_dev.h), the tail partition likewise
+//   k_orb_harris_cnt, k_orb_keypoints_cnt, k_orb_describe_cnt   with the rankings on the device and uvo_orb_set_counts 1 (the default) the
+//                      counts between the launches stay on the device too: fixed grids sized from capacities walk the lists grid-stride up
+//                      to lengths read from device memory, and a detection is queued without a stream wait
 // or, with uvo_orb_set_ranking 0, the host replays it on the response arrays (uvo_retain_best.h: 4 bytes per keypoint down, 4 bytes per
 // survivor up; the images never leave the device), like the RANSAC scans of the pose stages.
 // THE SAMPLING TABLE IS AN INPUT (uvo_orb_set_pattern): OpenCV's bit_pattern_31_ (1024 integers learned offline) cannot be restated
@@ -52,6 +55,11 @@ struct OrbPrefix { int n; int start[kOrbMaxLevels + 1]; };          // list posi
 static const int kOrbRankDefault = 1;                               // device: profiles/orb_device_rank.json
 // d_rank, in ints: k_rb_rank's ticket, counts and flags; the Harris list's OrbPrefix (n, start[17]); the final list's starts; both rankings' flags
 enum { RK_META = 0, RK_P1 = 48, RK_P2 = 68, RK_HIT1 = 88, RK_HIT2 = 104, RK_BACK_END = 120, RK_INTS = 128 };
+// ... and, past RK_BACK_END, what k_orb_keypoints_cnt leaves (uvo_orb_set_counts 1): per image slot the keypoint count and "more keypoints than the
+// list holds" (read by k_binary_publish_dev and the host only), the depth-limit flags summed since the workspace was planned, the FAST corners' count
+enum { RK_N = 120, RK_OVF = 122, RK_HITS = 124, RK_NFAST = 125 };
+static const int kOrbCountsDefault = 1;                             // the device: profiles/orb_device_counts.json
+static const int kOrbGridCap = 1024;                                // the counted launches' largest grid: four workgroups a CU on 256 CUs; the lists are walked grid-stride
 struct OrbWs {
     OrbParams p;
     bool has_pattern = false;
@@ -75,6 +83,10 @@ struct OrbWs {
     RbdItem* d_items = nullptr; int* d_la = nullptr; int* d_lb = nullptr;      // k_rb_rank's items and stopper lists, fast_cap each
     int* d_rank = nullptr;                                          // RK_INTS words: k_rb_rank's own, then what it leaves (level starts, depth-limit flags)
     long depth_limit_hits = 0;                                      // segments that reached introselect's depth limit on the device, since the context was made
+    // uvo_orb_set_counts: 1 = with the rankings on the device the counts stay there too and nothing waits, 0 = the host reads them between launches
+    int counts_dev = kOrbCountsDefault;
+    int hits_seen = 0;                                              // d_rank[RK_HITS] as last added to depth_limit_hits
+    int stat_waits = 0, stat_fast = -1, stat_ranked = -1, stat_kps = -1;      // uvo_orb_stats: stream waits since the last call; the last counts that reached the host
 };
 static int orb_rank_from_env()                                      // UVO_ORB_RANK=host|device: the initial setting, for measurements (tools/probe/README.md)
 {
@@ -82,6 +94,13 @@ static int orb_rank_from_env()                                      // UVO_ORB_R
     if (e && strcmp(e, "host") == 0) return 0;
     if (e && strcmp(e, "device") == 0) return 1;
     return kOrbRankDefault;
+}
+static int orb_counts_from_env()                                    // UVO_ORB_COUNTS=host|device, likewise
+{
+    const char* e = getenv("UVO_ORB_COUNTS");
+    if (e && strcmp(e, "host") == 0) return 0;
+    if (e && strcmp(e, "device") == 0) return 1;
+    return kOrbCountsDefault;
 }
 static const char* const kOrbNoTable = "uvo_orb_detect: descriptors need the sampling table -- OpenCV's bit_pattern_31_ (orb.cpp), 256 x (x0, y0, x1, y1) -- through uvo_orb_set_pattern; pass desc = NULL for keypoints only";
 const char* const kOrbLoopNoTable = "ORB in the fused steps: the descriptors need the sampling table -- OpenCV's bit_pattern_31_ (orb.cpp), 256 x (x0, y0, x1, y1) -- through uvo_orb_set_pattern";
@@ -221,6 +240,14 @@ __global__ __launch_bounds__(256) void k_orb_harris_dev(OrbLevels L, const OrbPr
     if (j >= P.start[P.n]) return;
     orb_harris_at(L, P, sel, pos, resp, j);
 }
+// the same with nothing of the list known to the host (uvo_orb_set_counts 1): a grid sized from the list's capacity walks it up to the end
+// k_rb_rank left, which every wave reads for itself (one address for the whole wave: the loop's exit does not diverge)
+__global__ __launch_bounds__(256) void k_orb_harris_cnt(OrbLevels L, const OrbPrefix* __restrict__ Pd, const int* __restrict__ sel, const uint32_t* __restrict__ pos, float* __restrict__ resp)
+{
+    const OrbPrefix P = *Pd;
+    const int n = P.start[P.n];
+    for (int j = blockIdx.x * 256 + threadIdx.x; j < n; j += gridDim.x * 256) orb_harris_at(L, P, sel, pos, resp, j);
+}
 
 __device__ __forceinline__ float orb_atan2_deg(float y, float x)     // cv::fastAtan2 (as surf.hip's fast_atan2_deg)
 {
@@ -281,6 +308,26 @@ __global__ __launch_bounds__(256) void k_orb_keypoints_dev(OrbLevels L, const Or
     if (i >= n) return;
     orb_keypoint_at(L, P, um, half_k, patch, fin, i, lane, sel, pos, resp, kps);
 }
+// How many keypoints a counted launch writes: all n of the final list, the first out_cap of them when the output holds fewer (the count
+// published downstream is then out_cap, and the caller's overflow check reports n), none when n exceeds the list itself
+__device__ __forceinline__ int orb_written(int n, int list_cap, int out_cap) { return n > list_cap ? 0 : min(n, out_cap); }
+// k_orb_keypoints_dev with the final list's length read where the second ranking left it (rk[RK_P2 + L.n]), grid-stride; the first thread also
+// leaves the count and the overflow flag of image `slot`, the FAST corners' count and the rankings' depth-limit flags for whoever reads them
+__global__ __launch_bounds__(256) void k_orb_keypoints_cnt(OrbLevels L, int* rk, OrbUmax um, int half_k, int patch, const int* __restrict__ fin, int list_cap, int out_cap, int slot,
+                                                           const int* __restrict__ n_fast, const int* __restrict__ sel, const uint32_t* __restrict__ pos, const float* __restrict__ resp,
+                                                           uvo_keypoint* __restrict__ kps)
+{
+    const OrbPrefix P = *reinterpret_cast<const OrbPrefix*>(rk + RK_P1);
+    const int n = rk[RK_P2 + L.n], nw = orb_written(n, list_cap, out_cap), lane = threadIdx.x & 31;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        int hits = 0;
+        for (int l = 0; l < L.n; l++) hits += rk[RK_HIT1 + l] + rk[RK_HIT2 + l];
+        rk[RK_N + slot] = n; rk[RK_OVF + slot] = n > list_cap ? 1 : 0;
+        rk[RK_HITS] += hits; rk[RK_NFAST] = *n_fast;
+    }
+    for (int i = blockIdx.x * 8 + (threadIdx.x >> 5); i < nw; i += gridDim.x * 8)      // (a whole 32-lane group stays or leaves together)
+        orb_keypoint_at(L, P, um, half_k, patch, fin, i, lane, sel, pos, resp, kps);
+}
 
 struct OrbTaps { int k[7]; };
 __device__ __forceinline__ int orb_reflect101(int p, int n) { while (p < 0 || p >= n) p = p < 0 ? -p : 2 * n - 2 - p; return p; }
@@ -314,15 +361,8 @@ __global__ __launch_bounds__(256) void k_orb_blur(const uint8_t* __restrict__ sr
 }
 
 // computeOrbDescriptors, WTA_K 2: lane = descriptor byte; bit b = I(p[16 byte + 2 b]) < I(p[16 byte + 2 b + 1]) on the blurred level
-__global__ __launch_bounds__(256) void k_orb_describe(OrbLevels L, const int8_t* __restrict__ pattern, const uvo_keypoint* __restrict__ kps, int n, uint8_t* __restrict__ desc)
+__device__ __forceinline__ int orb_describe_at(const OrbLevels& L, const int8_t* pat, const uvo_keypoint& k, int lane)
 {
-    __shared__ int pat32[256];                                      // the table's 1024 signed bytes, copied a word per thread
-    pat32[threadIdx.x] = reinterpret_cast<const int*>(pattern)[threadIdx.x];
-    const int8_t* pat = reinterpret_cast<const int8_t*>(pat32);
-    __syncthreads();
-    const int i = blockIdx.x * 8 + (threadIdx.x >> 5), lane = threadIdx.x & 31;
-    if (i >= n) return;
-    const uvo_keypoint k = kps[i];
     const int l = k.octave, step = L.w[l];
     const float s = 1.f / L.scale[l];
     float angle = k.angle;
@@ -344,7 +384,33 @@ __global__ __launch_bounds__(256) void k_orb_describe(OrbLevels L, const int8_t*
         }
         val |= (t[0] < t[1]) << bit;
     }
-    desc[(size_t)i * kOrbDescBytes + lane] = (uint8_t)val;
+    return val;
+}
+__global__ __launch_bounds__(256) void k_orb_describe(OrbLevels L, const int8_t* __restrict__ pattern, const uvo_keypoint* __restrict__ kps, int n, uint8_t* __restrict__ desc)
+{
+    __shared__ int pat32[256];                                      // the table's 1024 signed bytes, copied a word per thread
+    pat32[threadIdx.x] = reinterpret_cast<const int*>(pattern)[threadIdx.x];
+    const int8_t* pat = reinterpret_cast<const int8_t*>(pat32);
+    __syncthreads();
+    const int i = blockIdx.x * 8 + (threadIdx.x >> 5), lane = threadIdx.x & 31;
+    if (i >= n) return;
+    desc[(size_t)i * kOrbDescBytes + lane] = (uint8_t)orb_describe_at(L, pat, kps[i], lane);
+}
+// the same for the keypoints k_orb_keypoints_cnt wrote (*n_p: the final list's length), grid-stride, into rows of row_bytes: 32, or the fused
+// steps' 64 with the second half zeroed (what k_pad_binary_rows makes of a 32-byte row)
+__global__ __launch_bounds__(256) void k_orb_describe_cnt(OrbLevels L, const int8_t* __restrict__ pattern, const uvo_keypoint* __restrict__ kps, const int* __restrict__ n_p,
+                                                          int list_cap, int out_cap, uint8_t* __restrict__ desc, int row_bytes)
+{
+    __shared__ int pat32[256];
+    pat32[threadIdx.x] = reinterpret_cast<const int*>(pattern)[threadIdx.x];
+    const int8_t* pat = reinterpret_cast<const int8_t*>(pat32);
+    __syncthreads();
+    const int nw = orb_written(*n_p, list_cap, out_cap), lane = threadIdx.x & 31;
+    for (int i = blockIdx.x * 8 + (threadIdx.x >> 5); i < nw; i += gridDim.x * 8) {
+        uint8_t* row = desc + (size_t)i * row_bytes;
+        row[lane] = (uint8_t)orb_describe_at(L, pat, kps[i], lane);
+        if (row_bytes > kOrbDescBytes) row[kOrbDescBytes + lane] = 0;
+    }
 }
 
 // ------------------------------------------------------------------------------------------------ retainBest on the device
@@ -482,6 +548,9 @@ void linear_exact_table(int ssize, int dsize, uint16_t* ofs, uint16_t* c1)
 
 static void orb_free_sized(OrbWs* s)
 {
+    int hits = 0;                                                   // (idle here) the depth-limit flags no count readback has carried to the host yet
+    if (s->d_rank && hipMemcpy(&hits, s->d_rank + RK_HITS, sizeof(int), hipMemcpyDeviceToHost) == hipSuccess) s->depth_limit_hits += hits - s->hits_seen;
+    s->hits_seen = 0;
     (void)hipFree(s->d_pix); (void)hipFree(s->d_tab); (void)hipFree(s->d_rows); (void)hipFree(s->d_pos); (void)hipFree(s->d_score); (void)hipFree(s->d_sel);
     (void)hipFree(s->d_resp); (void)hipFree(s->d_fin); (void)hipFree(s->d_kps); (void)hipFree(s->d_desc); (void)hipHostFree(s->h_int); (void)hipHostFree(s->h_f);
     (void)hipFree(s->d_items); (void)hipFree(s->d_la); (void)hipFree(s->d_lb); (void)hipFree(s->d_rank);
@@ -501,7 +570,7 @@ void orb_ws_free(Ctx* c)
 }
 static OrbWs* orb_state(Ctx* c)
 {
-    if (!c->orb_ws) { c->orb_ws = new OrbWs(); static_cast<OrbWs*>(c->orb_ws)->rank_dev = orb_rank_from_env(); }
+    if (!c->orb_ws) { c->orb_ws = new OrbWs(); static_cast<OrbWs*>(c->orb_ws)->rank_dev = orb_rank_from_env(); static_cast<OrbWs*>(c->orb_ws)->counts_dev = orb_counts_from_env(); }
     return static_cast<OrbWs*>(c->orb_ws);
 }
 // ORB_Impl::detectAndCompute's level geometry and computeKeyPoints' shares (orb.cpp), tables and buffers for one image size
@@ -638,7 +707,7 @@ static uvo_status rb_launch(Ctx* c, hipStream_t st, const float* resp, const int
 static uvo_status orb_run_device(Ctx* c, OrbWs* s, hipStream_t st, const OrbLevels& L, int n_fast, const int8_t* pattern, int* n_out)
 {
     const OrbParams& p = s->p;
-    if (n_fast == 0) return UVO_OK;
+    if (n_fast == 0) { s->stat_fast = s->stat_ranked = s->stat_kps = 0; return UVO_OK; }
     const int margin = std::max(p.edgeThreshold, 3), R = s->total_rows;
     int* d_cnt = s->d_rows; int* d_off = s->d_rows + R; int* d_lvl = s->d_rows + 2 * R + 1;
     int* rk = s->d_rank;
@@ -658,12 +727,14 @@ static uvo_status orb_run_device(Ctx* c, OrbWs* s, hipStream_t st, const OrbLeve
         for (int l = 0; l < L.n; l++)
             hipLaunchKernelGGL(k_orb_blur, dim3((L.w[l] + 63) / 64, (L.h[l] + 15) / 16), dim3(256), 0, st, L.img[l], L.w[l], L.h[l], L.stride[l], kk, L.blur[l]);
     }
+    s->stat_waits++;
     UVO_HIP_TRY(c, hipStreamSynchronize(st));
     UVO_HIP_TRY(c, hipGetLastError());
     const int* back = s->h_int;
     for (int l = 0; l < L.n; l++) s->depth_limit_hits += back[RK_HIT1 - RK_P1 + l] + back[RK_HIT2 - RK_P1 + l];
     const int n = back[RK_P2 - RK_P1 + L.n];
     *n_out = n;
+    s->stat_fast = n_fast; s->stat_ranked = back[1 + L.n]; s->stat_kps = n;
     static const bool dbg = getenv("UVO_DBG_PHASE") != nullptr;      // (as AKAZE's host-clock phases: tools/probe/README.md)
     if (dbg) fprintf(stderr, "orb: %d FAST corners, %d after the first ranking, %d keypoints; %ld ranking segments past the depth limit so far\n", n_fast, back[1 + L.n], n, s->depth_limit_hits);
     if (n > s->cap || n == 0) return UVO_OK;
@@ -674,7 +745,63 @@ static uvo_status orb_run_device(Ctx* c, OrbWs* s, hipStream_t st, const OrbLeve
     return UVO_OK;
 }
 
-static uvo_status orb_run(Ctx* c, OrbWs* s, hipStream_t st, const uint8_t* gray, int w, int h, int stride, int mem, const int8_t* pattern, int rank_dev, int* n_out)
+// Where a detection whose counts stay on the device (uvo_orb_set_counts 1 with the rankings there) leaves its keypoints and rows: the
+// workspace's own lists (the operator: 32-byte rows, wait = true: ONE wait, for the counts that size the caller's copies) or image `slot`
+// of a lane (det[slot]: 64-byte zero-padded rows, at most the lane's max_kpts; nothing waits)
+struct OrbOut { uvo_keypoint* kps; uint8_t* rows; int row_bytes, cap, slot; bool wait; };
+// d_rank as it came back (from RK_P1 on): the counts, the depth-limit flags k_orb_keypoints_cnt summed, UVO_DBG_PHASE's line
+static void orb_counts_arrived(OrbWs* s, const int* back, int nlevels)
+{
+    s->depth_limit_hits += back[RK_HITS - RK_P1] - s->hits_seen;
+    s->hits_seen = back[RK_HITS - RK_P1];
+    s->stat_fast = back[RK_NFAST - RK_P1]; s->stat_ranked = back[1 + nlevels]; s->stat_kps = back[RK_P2 - RK_P1 + nlevels];
+    static const bool dbg = getenv("UVO_DBG_PHASE") != nullptr;
+    if (dbg) fprintf(stderr, "orb: %d FAST corners, %d after the first ranking, %d keypoints; %ld ranking segments past the depth limit so far\n", s->stat_fast, s->stat_ranked, s->stat_kps, s->depth_limit_hits);
+}
+// orb_run from the row scan on with every count left on the device: the ordered maxima, both rankings, the Harris responses, the
+// keypoints and their rows are queued with launch shapes that depend on capacities only.  An empty list (no FAST corner, or none
+// inside the border on some level) is no special case: k_rb_rank leaves empty segments empty and the grid-stride loops do not start.
+// *n_out = the count with out.wait, else -1 (k_orb_keypoints_cnt left it in d_rank[RK_N + out.slot], the overflow flag in RK_OVF + out.slot)
+static uvo_status orb_run_counted(Ctx* c, OrbWs* s, hipStream_t st, const OrbLevels& L, const int8_t* pattern, const OrbOut& out, int* n_out)
+{
+    const OrbParams& p = s->p;
+    const int margin = std::max(p.edgeThreshold, 3), R = s->total_rows;
+    int* d_cnt = s->d_rows; int* d_off = s->d_rows + R; int* d_lvl = s->d_rows + 2 * R + 1;
+    int* rk = s->d_rank;
+    OrbPrefix* d_P1 = reinterpret_cast<OrbPrefix*>(rk + RK_P1);
+    hipLaunchKernelGGL(k_orb_nms_rows<true>, dim3((R + 3) / 4), dim3(256), 0, st, L, margin, d_cnt, d_off, s->d_pos, s->d_score);
+    int keep[kOrbMaxLevels];
+    long listed = 0;                                                // the Harris list: twice every level's share, ties at the cuts aside
+    for (int l = 0; l < L.n; l++) { keep[l] = 2 * s->want[l]; listed += keep[l]; }
+    UVO_TRY(rb_launch(c, st, s->d_score, d_lvl, keep, L.n, s->d_items, s->d_la, s->d_lb, rk + RK_META, s->d_sel, s->fast_cap, d_P1->start, rk + RK_HIT1));
+    const int harris_grid = std::max(1, std::min(kOrbGridCap, (int)((std::min<long>(s->fast_cap, listed + 1024) + 255) / 256)));
+    hipLaunchKernelGGL(k_orb_harris_cnt, dim3(harris_grid), dim3(256), 0, st, L, d_P1, s->d_sel, s->d_pos, s->d_resp);
+    for (int l = 0; l < L.n; l++) keep[l] = s->want[l];
+    UVO_TRY(rb_launch(c, st, s->d_resp, d_P1->start, keep, L.n, s->d_items, s->d_la, s->d_lb, rk + RK_META, s->d_fin, s->fast_cap, rk + RK_P2, rk + RK_HIT2));
+    if (pattern) {
+        const OrbTaps kk = orb_blur_taps();
+        for (int l = 0; l < L.n; l++)
+            hipLaunchKernelGGL(k_orb_blur, dim3((L.w[l] + 63) / 64, (L.h[l] + 15) / 16), dim3(256), 0, st, L.img[l], L.w[l], L.h[l], L.stride[l], kk, L.blur[l]);
+    }
+    OrbUmax um; memcpy(um.u, s->umax, sizeof(um.u));
+    const int list_cap = s->cap, out_cap = std::min(out.cap, s->cap);
+    const int kp_grid = std::max(1, std::min(kOrbGridCap, (out_cap + 7) / 8));
+    hipLaunchKernelGGL(k_orb_keypoints_cnt, dim3(kp_grid), dim3(256), 0, st, L, rk, um, p.patchSize / 2, p.patchSize, s->d_fin, list_cap, out_cap, out.slot, d_lvl + L.n,
+                       s->d_sel, s->d_pos, s->d_resp, out.kps);
+    if (pattern) hipLaunchKernelGGL(k_orb_describe_cnt, dim3(kp_grid), dim3(256), 0, st, L, pattern, out.kps, rk + RK_P2 + L.n, list_cap, out_cap, out.rows, out.row_bytes);
+    UVO_HIP_TRY(c, hipGetLastError());
+    *n_out = -1;
+    static const bool dbg = getenv("UVO_DBG_PHASE") != nullptr;      // (the line needs the counts: with the variable set a lane reads them back too)
+    if (!out.wait && !dbg) return UVO_OK;
+    UVO_HIP_TRY(c, hipMemcpyAsync(s->h_int, rk + RK_P1, sizeof(int) * (RK_INTS - RK_P1), hipMemcpyDeviceToHost, st));
+    s->stat_waits++;
+    UVO_HIP_TRY(c, hipStreamSynchronize(st));
+    orb_counts_arrived(s, s->h_int, L.n);
+    if (out.wait) *n_out = s->stat_kps;
+    return UVO_OK;
+}
+
+static uvo_status orb_run(Ctx* c, OrbWs* s, hipStream_t st, const uint8_t* gray, int w, int h, int stride, int mem, const int8_t* pattern, int rank_dev, const OrbOut* counted, int* n_out)
 {
     *n_out = 0;
     OrbLevels L = s->L;
@@ -694,7 +821,9 @@ static uvo_status orb_run(Ctx* c, OrbWs* s, hipStream_t st, const uint8_t* gray,
     int* d_cnt = s->d_rows; int* d_off = s->d_rows + R; int* d_lvl = s->d_rows + 2 * R + 1;
     hipLaunchKernelGGL(k_orb_nms_rows<false>, dim3((R + 3) / 4), dim3(256), 0, st, L, margin, d_cnt, d_off, s->d_pos, s->d_score);
     hipLaunchKernelGGL(k_orb_row_scan, dim3(1), dim3(1024), 0, st, d_cnt, R, d_off, L, d_lvl);
+    if (rank_dev && counted) return orb_run_counted(c, s, st, L, pattern, *counted, n_out);
     UVO_HIP_TRY(c, hipMemcpyAsync(s->h_int, d_lvl, sizeof(int) * (L.n + 1), hipMemcpyDeviceToHost, st));
+    s->stat_waits++;
     UVO_HIP_TRY(c, hipStreamSynchronize(st));
     int lvl[kOrbMaxLevels + 1];
     memcpy(lvl, s->h_int, sizeof(int) * (L.n + 1));
@@ -707,6 +836,7 @@ static uvo_status orb_run(Ctx* c, OrbWs* s, hipStream_t st, const uint8_t* gray,
     if (n_fast > 0) {
         hipLaunchKernelGGL(k_orb_nms_rows<true>, dim3((R + 3) / 4), dim3(256), 0, st, L, margin, d_cnt, d_off, s->d_pos, s->d_score);
         UVO_HIP_TRY(c, hipMemcpyAsync(s->h_f, s->d_score, sizeof(float) * n_fast, hipMemcpyDeviceToHost, st));
+        s->stat_waits++;
         UVO_HIP_TRY(c, hipStreamSynchronize(st));
         // retainBest(keypoints, 2 * featuresNum) on the FAST scores (HARRIS_SCORE keeps twice the share for the second ranking)
         for (int l = 0; l < L.n; l++) { P1.start[l] = (int)sel.size(); retain_best_order(s->h_f + lvl[l], lvl[l + 1] - lvl[l], 2 * s->want[l], lvl[l], &tmp, &sel); }
@@ -719,6 +849,7 @@ static uvo_status orb_run(Ctx* c, OrbWs* s, hipStream_t st, const uint8_t* gray,
         UVO_HIP_TRY(c, hipMemcpyAsync(s->d_sel, sel.data(), sizeof(int) * n1, hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(k_orb_harris, dim3((n1 + 255) / 256), dim3(256), 0, st, L, P1, s->d_sel, n1, s->d_pos, s->d_resp);
         UVO_HIP_TRY(c, hipMemcpyAsync(s->h_f, s->d_resp, sizeof(float) * n1, hipMemcpyDeviceToHost, st));
+        s->stat_waits++;
         UVO_HIP_TRY(c, hipStreamSynchronize(st));
         // retainBest(keypoints, featuresNum) on the Harris responses, level by level
         for (int l = 0; l < L.n; l++) retain_best_order(s->h_f + P1.start[l], P1.start[l + 1] - P1.start[l], s->want[l], P1.start[l], &tmp, &fin);
@@ -726,6 +857,7 @@ static uvo_status orb_run(Ctx* c, OrbWs* s, hipStream_t st, const uint8_t* gray,
     UVO_HIP_TRY(c, hipGetLastError());
     const int n = (int)fin.size();
     *n_out = n;
+    s->stat_fast = n_fast; s->stat_ranked = n1; s->stat_kps = n;
     if (n > s->cap || n == 0) return UVO_OK;
     // ---- ICAngles + the KeyPoint fields; blur; descriptors ----
     OrbUmax um; memcpy(um.u, s->umax, sizeof(um.u));
@@ -749,20 +881,26 @@ uvo_status orb_detect(Ctx* c, const uint8_t* gray, int w, int h, int stride, int
     if (desc && !s->has_pattern) { c->err = kOrbNoTable; return UVO_INVALID_ARG; }
     UVO_TRY(orb_plan(c, s, w, h));
     hipStream_t st = c->stream;
-    UVO_TRY(orb_run(c, s, st, gray, w, h, stride, mem, desc ? s->d_pattern : nullptr, s->rank_dev, n_out));
+    const OrbOut own = { s->d_kps, s->d_desc, kOrbDescBytes, s->cap, 0, true };
+    UVO_TRY(orb_run(c, s, st, gray, w, h, stride, mem, desc ? s->d_pattern : nullptr, s->rank_dev, s->counts_dev ? &own : nullptr, n_out));
     const int n = *n_out;
     if (n > s->cap) { c->err = "ORB: more keypoints tie at the per-level cuts than the output list has room for"; return UVO_CAPACITY; }
     if ((kps || desc) && n > cap) { c->err = "uvo_orb_detect: output capacity too small"; return UVO_CAPACITY; }
     if (n == 0) return UVO_OK;
     if (kps) UVO_HIP_TRY(c, hipMemcpyAsync(kps, s->d_kps, sizeof(uvo_keypoint) * n, hipMemcpyDeviceToHost, st));
     if (desc) UVO_HIP_TRY(c, hipMemcpyAsync(desc, s->d_desc, (size_t)kOrbDescBytes * n, hipMemcpyDeviceToHost, st));
+    s->stat_waits++;
     UVO_HIP_TRY(c, hipStreamSynchronize(st));
     return UVO_OK;
 }
 
 // ---- detect_features' ORB branch inside the fused steps.  The parameters and the sampling table are lane 0's (uvo_orb_configure /
-// uvo_orb_set_pattern); each lane keeps its own level buffers, made when a sequence starts.  Both images of a pair go through them in turn:
-// the two retainBest rankings between the launches wait for the device.
+// uvo_orb_set_pattern); each lane keeps its own level buffers, made when a sequence starts.  Both images of a pair go through them in turn.
+// With the rankings on the device and the counts there too (uvo_orb_set_ranking 1, uvo_orb_set_counts 1) the whole detection is queued and
+// nothing waits: the keypoints and the padded rows go straight to det[slot], the count stays in the workspace's d_rank (*d_n, possibly
+// past max_kpts; *d_ovf raised when more keypoints tie at the cuts than the workspace's list holds -- nothing is written past either list)
+// and *n = -1: k_binary_publish_dev and the step's count readback report UVO_CAPACITY for either, as they do for AKAZE's device count.
+// With counts 0 the submitting thread waits twice per image, for the level counts; with the rankings on the host, three times.
 bool orb_has_pattern(Ctx* c)
 {
     const OrbWs* s = static_cast<const OrbWs*>(c->sh->lanes[0]->orb_ws);
@@ -775,16 +913,22 @@ uvo_status orb_prepare_lane(Ctx* c, int w, int h)
     if (s != ms && memcmp(&s->p, &ms->p, sizeof(OrbParams)) != 0) { s->p = ms->p; orb_free_sized(s); }     // lane 0's configuration
     return orb_plan(c, s, w, h);
 }
-uvo_status orb_detect_lane(Ctx* c, int slot, int* n)
+uvo_status orb_detect_lane(Ctx* c, int slot, int* n, const int** d_n, const int** d_ovf)
 {
     const int w = c->img_w, h = c->img_h;
-    *n = 0;
+    *n = 0; *d_n = nullptr; *d_ovf = nullptr;
     if (w < 16 || h < 16 || w > 65535 || h > 65535) { c->err = "ORB: image size outside the detector's limits"; return UVO_INVALID_ARG; }
     if (!orb_has_pattern(c)) { c->err = kOrbLoopNoTable; return UVO_INVALID_ARG; }
     UVO_TRY(orb_prepare_lane(c, w, h));                                       // (a no-op once the lane is primed)
     OrbWs* s = static_cast<OrbWs*>(c->orb_ws);
     const OrbWs* ms = static_cast<const OrbWs*>(c->sh->lanes[0]->orb_ws);
-    UVO_TRY(orb_run(c, s, c->stream, c->img[slot], w, h, w, UVO_MEM_DEVICE, ms->d_pattern, ms->rank_dev, n));
+    if (ms->rank_dev && ms->counts_dev) {                                     // the master context's values serve every lane
+        const OrbOut lo = { c->det[slot].kps, reinterpret_cast<uint8_t*>(c->det[slot].desc), 4 * kBinRowWords, c->cap, slot, false };
+        UVO_TRY(orb_run(c, s, c->stream, c->img[slot], w, h, w, UVO_MEM_DEVICE, ms->d_pattern, 1, &lo, n));
+        *d_n = s->d_rank + RK_N + slot; *d_ovf = s->d_rank + RK_OVF + slot;
+        return UVO_OK;
+    }
+    UVO_TRY(orb_run(c, s, c->stream, c->img[slot], w, h, w, UVO_MEM_DEVICE, ms->d_pattern, ms->rank_dev, nullptr, n));
     if (*n > c->cap || *n == 0) return UVO_OK;
     UVO_HIP_TRY(c, hipMemcpyAsync(c->det[slot].kps, s->d_kps, sizeof(uvo_keypoint) * (size_t)*n, hipMemcpyDeviceToDevice, c->stream));
     return pad_binary_rows(c, c->stream, s->d_desc, *n, kOrbDescBytes, reinterpret_cast<uint8_t*>(c->det[slot].desc));
@@ -809,6 +953,26 @@ uvo_status orb_set_ranking(Ctx* c, int where)
 {
     if (where != 0 && where != 1) { c->err = "uvo_orb_set_ranking: 0 (the host replays retainBest's order) or 1 (k_rb_rank on the device)"; return UVO_INVALID_ARG; }
     orb_state(c)->rank_dev = where;
+    return UVO_OK;
+}
+uvo_status orb_set_counts(Ctx* c, int where)
+{
+    if (where != 0 && where != 1) { c->err = "uvo_orb_set_counts: 0 (the host reads the counts back between launches) or 1 (they stay on the device)"; return UVO_INVALID_ARG; }
+    orb_state(c)->counts_dev = where;
+    return UVO_OK;
+}
+// uvo_orb_stats: the stream waits of every lane's ORB detections since the last call (read and cleared); the counts of this context's own
+// workspace as they last reached the host
+uvo_status orb_stats(Ctx* c, int* host_waits, int* n_fast, int* n_ranked, int* n_keypoints)
+{
+    int waits = 0;
+    for (Ctx* l : c->sh->lanes)
+        if (OrbWs* ls = static_cast<OrbWs*>(l->orb_ws)) { waits += ls->stat_waits; ls->stat_waits = 0; }
+    const OrbWs* s = static_cast<const OrbWs*>(c->orb_ws);
+    if (host_waits) *host_waits = waits;
+    if (n_fast) *n_fast = s ? s->stat_fast : -1;
+    if (n_ranked) *n_ranked = s ? s->stat_ranked : -1;
+    if (n_keypoints) *n_keypoints = s ? s->stat_kps : -1;
     return UVO_OK;
 }
 // the test hook behind uvo_retain_best: host buffers in and out; where = 1 is the launch orb_run_device makes

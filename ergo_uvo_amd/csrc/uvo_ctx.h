@@ -442,6 +442,8 @@ void orb_ws_free(Ctx* c);
 uvo_status orb_configure(Ctx* c, int nfeatures, float scaleFactor, int nlevels, int edgeThreshold, int patchSize, int fastThreshold);
 uvo_status orb_set_pattern(Ctx* c, const int* pattern);
 uvo_status orb_set_ranking(Ctx* c, int where);
+uvo_status orb_set_counts(Ctx* c, int where);
+uvo_status orb_stats(Ctx* c, int* host_waits, int* n_fast, int* n_ranked, int* n_keypoints);
 uvo_status orb_retain_best(Ctx* c, const float* responses, const int* start, const int* keep, int nseg, int where, int* order, int cap, int* out_start, int* hits);
 uvo_status orb_detect(Ctx* c, const uint8_t* gray, int w, int h, int stride, int mem, uvo_keypoint* kps, uint8_t* desc, int cap, int* n_out);
 uvo_status orb_level_plane(Ctx* c, int level, int what, uint8_t* out, int cap_bytes, int* ow, int* oh);
@@ -450,7 +452,7 @@ extern const char* const kOrbLoopNoTable;
 // detect_features' ORB / AKAZE branch inside the fused steps, image `slot` of the lane (c->img[slot]): keypoints to det[slot].kps, rows
 // to det[slot].desc (kBinRowWords words each); *n = the detector's count (> max_kpts: nothing is copied, the caller reports it)
 uvo_status orb_prepare_lane(Ctx* c, int w, int h);
-uvo_status orb_detect_lane(Ctx* c, int slot, int* n);
+uvo_status orb_detect_lane(Ctx* c, int slot, int* n, const int** d_n, const int** d_ovf);        // *d_n != null: the count and the list-overflow flag are on the device (counts setting 1 with the rankings there), *n = -1
 // akaze.hip
 void akaze_ws_free(Ctx* c);
 uvo_status akaze_detect(Ctx* c, const uint8_t* gray, int w, int h, int stride, int mem, uvo_keypoint* kps, uint8_t* desc, int cap, int* n_out);

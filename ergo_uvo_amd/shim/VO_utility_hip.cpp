@@ -77,6 +77,8 @@ struct State {
     bool orb_pattern_sent = false;                // ... and handed to the current context
     int orb_ranking = -1;                         // set_orb_ranking: 0 host, 1 device; -1 = the library's default
     bool orb_ranking_sent = false;
+    int orb_counts = -1;                          // set_orb_counts: 0 host, 1 device; -1 = the library's default
+    bool orb_counts_sent = false;
     int akaze_suppression = -1;                   // set_akaze_suppression: 0 host, 1 device; -1 = the library's default
     bool akaze_suppression_sent = false;
     int mono_pose_stage = -1;                     // set_mono_pose_stage: 0 the definition's routes, 1 every attempt resident; -1 = the library's default
@@ -169,7 +171,7 @@ void shutdown()
 {
     std::lock_guard<std::mutex> lk(g.mu);
     if (g.ctx) { uvo_ctx_destroy(g.ctx); g.ctx = nullptr; }
-    g.orb_pattern_sent = false; g.orb_ranking_sent = false; g.akaze_suppression_sent = false; g.mono_pose_stage_sent = false; g.pnp_method = 1;
+    g.orb_pattern_sent = false; g.orb_ranking_sent = false; g.orb_counts_sent = false; g.akaze_suppression_sent = false; g.mono_pose_stage_sent = false; g.pnp_method = 1;
 }
 void set_orb_ranking(int where)
 {
@@ -177,6 +179,13 @@ void set_orb_ranking(int where)
     std::lock_guard<std::mutex> lk(g.mu);
     g.orb_ranking = where;
     g.orb_ranking_sent = false;
+}
+void set_orb_counts(int where)
+{
+    if (where != 0 && where != 1) throw Error(UVO_INVALID_ARG, "set_orb_counts: 0 (host) or 1 (device)");
+    std::lock_guard<std::mutex> lk(g.mu);
+    g.orb_counts = where;
+    g.orb_counts_sent = false;
 }
 void set_akaze_suppression(int where)
 {
@@ -366,6 +375,7 @@ static void orb_pattern_to(uvo_ctx* c)
 {
     std::lock_guard<std::mutex> lk(g.mu);
     if (g.orb_ranking >= 0 && !g.orb_ranking_sent) { SHIM_TRY(uvo_orb_set_ranking(c, g.orb_ranking), "uvo_orb_set_ranking"); g.orb_ranking_sent = true; }
+    if (g.orb_counts >= 0 && !g.orb_counts_sent) { SHIM_TRY(uvo_orb_set_counts(c, g.orb_counts), "uvo_orb_set_counts"); g.orb_counts_sent = true; }
     if (g.orb_pattern.empty())
         if (const char* path = getenv("UVO_ORB_PATTERN_FILE"))
             if (FILE* f = fopen(path, "r")) {

@@ -118,7 +118,8 @@ uvo_status uvo_ctx_set_feature_detector(uvo_ctx* c, const char* name);
  * uvo_akaze_set_suppression puts them.  On the host (0) they run on the thread that calls uvo_stereo_submit /
  * uvo_mono_submit, which waits three times per image: with several pairs in flight they serialise the submissions' detection.  On the
  * device (1, the default) the whole detection is queued without a wait and its counts stay on the device, as the SURF branch's.  ORB has no host stage with the rankings on
- * the device (uvo_orb_set_ranking, the default): the submitting thread waits twice per image, for the FAST corners' level counts and for
+ * the device (uvo_orb_set_ranking, the default), and with its counts there too (uvo_orb_set_counts, the default) it is queued without a
+ * wait likewise; with uvo_orb_set_counts(c, 0) the submitting thread waits twice per image, for the FAST corners' level counts and for
  * the final counts; with the rankings on the host it replays retainBest there, and the submissions' detection serialises likewise.  Each
  * lane keeps its own detector workspace, made by the first (synchronous) pair of a sequence; uvo_stereo_get("desc_left" / "desc_right")
  * returns the rows' bytes (61 or 32 per row).  Refused while pairs are in flight, and a change of detector while a VO sequence is running
@@ -216,6 +217,20 @@ uvo_status uvo_orb_set_pattern(uvo_ctx* c, const int* pattern /* 1024 ints or NU
  * survivor up, twice).  The results do not depend on the value.  Anything else is UVO_INVALID_ARG; refused while entries are in flight.
  * The fused steps take the master context's value, as they take its uvo_orb_configure. */
 uvo_status uvo_orb_set_ranking(uvo_ctx* c, int where);
+/* Where the counts between ORB's launches are read while the rankings run on the device: 0 = the host reads them back (the FAST corners'
+ * level starts, then the final list's: two waits per image), 1 = they stay on the device (default): every launch behind the rankings
+ * takes its bound from device memory and has a shape sized from capacities, the fused steps queue a detection without a wait (its count
+ * is published where AKAZE's device count is; more than max_kpts keypoints is the count readback's UVO_CAPACITY, as before) and
+ * uvo_orb_detect waits once for the count that sizes its copies.  Consulted only with uvo_orb_set_ranking 1: the host rankings need
+ * their counts.  The results do not depend on the value.  Anything else is UVO_INVALID_ARG; refused while entries are in flight.  The
+ * fused steps take the master context's value, as for uvo_orb_set_ranking. */
+uvo_status uvo_orb_set_counts(uvo_ctx* c, int where);
+/* Figures of the ORB branch: host_waits = the stream waits ORB detection made its calling threads perform, on any lane of the context,
+ * since the previous call (read and cleared; the fused steps' own count readback is not ORB's): per image 2 with the counts on the
+ * host, 0 on the device, 3 with the rankings on the host; uvo_orb_detect adds the wait of its final copy.  n_fast / n_ranked /
+ * n_keypoints = the FAST corners, the Harris list and the keypoints of the last detection of the context's own lane whose counts
+ * reached the host, -1 where none did.  Any pointer may be NULL.  Idle contexts only. */
+uvo_status uvo_orb_stats(uvo_ctx* c, int* host_waits, int* n_fast, int* n_ranked, int* n_keypoints);
 /* test hook: KeyPointsFilter::retainBest's order on nseg (1 .. 16) segments of a response array: segment l is
  * responses[start[l] .. start[l + 1]) ranked for keep[l].  order[out_start[l] .. out_start[l + 1]) receives the positions in `responses`
  * (start[l] + index) that segment l keeps, in the order std::nth_element + std::partition leave; out_start is the running sum of the

@@ -90,6 +90,9 @@ void     set_orb_pattern(const int* pattern1024);
 // where the "ORB" branch's retainBest rankings run: 1 the device, 0 the host replay (uvo_orb_set_ranking); results do not depend on it.
 // Kept across a rebuilt context, as the table is.
 void     set_orb_ranking(int where);
+// where the "ORB" branch's counts are read while its rankings run on the device: 1 they stay on the device (no host wait in a detection),
+// 0 the host reads them back between launches (uvo_orb_set_counts); results do not depend on it.  Kept across a rebuilt context.
+void     set_orb_counts(int where);
 // where the "AKAZE" branch's contrast factor, duplicate suppression and refinement run: 1 the device, 0 the host scans
 // (uvo_akaze_set_suppression); results do not depend on it.  Kept across a rebuilt context.
 void     set_akaze_suppression(int where);
