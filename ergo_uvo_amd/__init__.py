@@ -103,6 +103,37 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+PIXEL_FORMATS = {"bgr8": 0, "bgra8": 1, "bayer_bggr8": 2}      # UVO_PIX_BGR8, UVO_PIX_BGRA8, UVO_PIX_BAYER_BGGR8
+_PIX_BPP = {0: 3, 1: 4, 2: 1}
+
+
+def _pix(fmt) -> int:
+    """a pixel format by name or by its UVO_PIX_* value; unknown names raise, unknown values are the library's to refuse"""
+    if isinstance(fmt, str):
+        if fmt.lower() not in PIXEL_FORMATS:
+            raise ValueError(f"unknown pixel format {fmt!r}: one of {sorted(PIXEL_FORMATS)}")
+        return PIXEL_FORMATS[fmt.lower()]
+    return int(fmt)
+
+
+def _frame_layout(a, fmt: int):
+    """(w, h, row stride in bytes) of a frame in pixel format fmt: HxWx3 (bgr8), HxWx4 (bgra8) or HxW (bayer_bggr8) uint8; the rows of a
+    CUDA tensor may be padded, a numpy array is made contiguous by the caller."""
+    bpp = _PIX_BPP[fmt]
+    want = "HxW" if bpp == 1 else f"HxWx{bpp}"
+    if a.ndim != (2 if bpp == 1 else 3) or (bpp != 1 and a.shape[2] != bpp):
+        raise ValueError(f"frames must be {want} uint8" if bpp == 3 else f"{'bgra8' if bpp == 4 else 'bayer_bggr8'} frames must be {want} uint8 (got shape {tuple(a.shape)})")
+    h, w = int(a.shape[0]), int(a.shape[1])
+    if _is_device(a):
+        if str(a.dtype) != "torch.uint8":
+            raise ValueError(f"device frames must be {want} uint8")
+        inner = (int(a.stride(1)), int(a.stride(2))) if bpp != 1 else (int(a.stride(1)),)
+        if inner != ((bpp, 1) if bpp != 1 else (1,)) or int(a.stride(0)) < bpp * w:
+            raise ValueError(f"device frames must be {want} uint8 with interleaved channels (rows may be padded)")
+        return w, h, int(a.stride(0))
+    return w, h, bpp * w
+
+
 TRACE_DTYPE = np.dtype([("pair", "i8"), ("lane", "i4"), ("b_used", "i4"), ("dev_ms", "f4", 8), ("host_ms", "f8", 6)], align=True)   # uvo_trace_row
 
 
@@ -122,6 +153,7 @@ class Context:
         self._h = h
         self._inflight = collections.deque()       # tensors handed to submit: kept alive until the matching collect
         self._producer = None
+        self._cam_fmt = [0, 0]                      # the cameras' pixel formats as the library holds them (set_camera_format)
         self.set_producer_stream("torch")           # device tensors are ordered after the torch stream that is current at each call
 
     # ------------------------------------------------------------------ plumbing
@@ -572,12 +604,20 @@ class Context:
         self._check(self._lib.uvo_stereo_step(self._h, pl, pr, w, h, w, ml, C.c_double(dt), C.byref(r)))
         return r
 
-    def get_image(self, rgb, desired_width, K, dist4, newK, clahe=True, clip_limit=3, device_out=False):
+    def get_image(self, rgb, desired_width, K, dist4, newK, clahe=True, clip_limit=3, device_out=False, pixel_format="bgr8"):
         """get_image (VO_utility.cpp:337-379): resize INTER_AREA -> RGB2GRAY -> undistort -> optional CLAHE.
-        rgb: HxWx3 uint8 numpy array, or a CUDA torch tensor of that shape.  Returns a numpy array, or a CUDA tensor
-        when device_out is set."""
+        rgb: HxWx3 uint8 numpy array, or a CUDA torch tensor of that shape; with pixel_format "bgra8" HxWx4 (the first three channels
+        count), with "bayer_bggr8" an HxW mosaic (demosaiced as bayer_bggr2bgr does).  Returns a numpy array, or a CUDA tensor when
+        device_out is set."""
         K, dist4, newK = _np(K, np.float64), _np(dist4, np.float64), _np(newK, np.float64)
-        if hasattr(rgb, "data_ptr"):
+        fmt = _pix(pixel_format)
+        if fmt != 0:
+            if not _is_device(rgb):
+                rgb = _np(rgb, np.uint8)
+            w, h, stride = _frame_layout(rgb, fmt if fmt in _PIX_BPP else 0)           # an unknown value is the library's to refuse
+            src, mem = (C.c_void_p(rgb.data_ptr()), 1) if _is_device(rgb) else (_p(rgb), 0)
+            self._order_after_producer(rgb)
+        elif hasattr(rgb, "data_ptr"):
             h, w, _ = rgb.shape
             src, mem, stride = C.c_void_p(rgb.data_ptr()), 1, int(rgb.stride(0))
         else:
@@ -592,37 +632,51 @@ class Context:
         else:
             out = np.empty((dh, desired_width), np.uint8)
             dst, omem = _p(out), 0
-        self._check(self._lib.uvo_get_image(self._h, src, w, h, stride, mem, _p(K), _p(dist4), _p(newK), int(desired_width),
-                                            int(bool(clahe)), int(clip_limit), dst, omem, C.byref(ow), C.byref(oh)))
+        if fmt != 0:
+            self._check(self._lib.uvo_get_image_fmt(self._h, src, fmt, w, h, stride, mem, _p(K), _p(dist4), _p(newK), int(desired_width),
+                                                    int(bool(clahe)), int(clip_limit), dst, omem, C.byref(ow), C.byref(oh)))
+        else:
+            self._check(self._lib.uvo_get_image(self._h, src, w, h, stride, mem, _p(K), _p(dist4), _p(newK), int(desired_width),
+                                                int(bool(clahe)), int(clip_limit), dst, omem, C.byref(ow), C.byref(oh)))
         assert (ow.value, oh.value) == (desired_width, dh)
         return out
 
     # ------------------------------------------------------------------ camera frames into the loops (uvo_*_frames)
-    def set_camera(self, cam, K, dist4, newK, desired_width, clahe=True, clip_limit=3):
+    def set_camera(self, cam, K, dist4, newK, desired_width, clahe=True, clip_limit=3, pixel_format=None):
         """get_image's arguments for camera `cam` (0 = left or mono, 1 = right), kept by the context for the *_frames calls.
+        pixel_format: "bgr8", "bgra8" or "bayer_bggr8" (set_camera_format); None leaves the camera's format as it is (initially "bgr8").
         Raises UvoError with pairs / frames in flight."""
         K, dist4, newK = _np(K, np.float64), _np(dist4, np.float64), _np(newK, np.float64)
         self._check(self._lib.uvo_ctx_set_camera(self._h, int(cam), _p(K), _p(dist4), _p(newK), int(desired_width), int(bool(clahe)), int(clip_limit)))
+        if pixel_format is not None:
+            self.set_camera_format(cam, pixel_format)
 
-    @staticmethod
-    def _frame(rgb):
-        """(pointer, w, h, stride, mem, keepalive) of an HxWx3 uint8 frame: a numpy array, or a CUDA tensor whose rows may be padded."""
+    def set_camera_format(self, cam, fmt):
+        """The layout the *_frames calls read camera `cam`'s frames in: "bgr8" (HxWx3, the default), "bgra8" (HxWx4, the first three
+        channels count) or "bayer_bggr8" (an HxW mosaic, demosaiced inside the resize launch).  May precede set_camera.  Raises UvoError
+        for an unknown value, a camera outside 0..1, or with pairs / frames in flight."""
+        v = _pix(fmt)
+        self._check(self._lib.uvo_ctx_set_camera_format(self._h, int(cam), v))
+        self._cam_fmt[int(cam)] = v
+
+    def _frame(self, rgb, cam=0):
+        """(pointer, w, h, stride, mem, keepalive) of a uint8 frame in camera `cam`'s pixel format: a numpy array, or a CUDA tensor
+        whose rows may be padded."""
+        fmt = self._cam_fmt[cam]
         if _is_device(rgb):
-            h, w, ch = rgb.shape
-            if ch != 3 or rgb.stride(2) != 1 or rgb.stride(1) != 3:
-                raise ValueError("device frames must be HxWx3 uint8 with interleaved channels (rows may be padded)")
-            return C.c_void_p(rgb.data_ptr()), w, h, int(rgb.stride(0)), MEM_DEVICE, rgb
+            w, h, stride = _frame_layout(rgb, fmt)
+            return C.c_void_p(rgb.data_ptr()), w, h, stride, MEM_DEVICE, rgb
         arr = _np(rgb, np.uint8)
-        h, w, ch = arr.shape
-        if ch != 3:
-            raise ValueError("frames must be HxWx3 uint8")
-        return _p(arr), w, h, 3 * w, MEM_HOST, arr
+        w, h, stride = _frame_layout(arr, fmt)
+        return _p(arr), w, h, stride, MEM_HOST, arr
 
     def _frame_pair(self, left_rgb, right_rgb):
-        pl, w, h, sl, ml, kl = self._frame(left_rgb)
-        pr, wr, hr, sr, mr, kr = self._frame(right_rgb)
+        pl, w, h, sl, ml, kl = self._frame(left_rgb, 0)
+        pr, wr, hr, sr, mr, kr = self._frame(right_rgb, 1)
         if ml != mr:
             raise ValueError("left and right must live in the same memory space")
+        if self._cam_fmt[0] != self._cam_fmt[1]:
+            sr = sl                             # cameras of two formats: the library refuses the entry, in its own words, before it reads a frame
         if (w, h, sl) != (wr, hr, sr):
             raise ValueError("left and right frames must have the same size and row stride")
         return pl, pr, w, h, sl, ml, (kl, kr)

@@ -25,7 +25,7 @@ EXPORTS = [
     "uvo_stereo_get", "uvo_find_essential_mat", "uvo_five_point_models", "uvo_solve_poly10", "uvo_homography_models", "uvo_homography_fit_all", "uvo_mono_method_refusal", "uvo_recover_pose", "uvo_find_homography", "uvo_decompose_homography_mat",
     "uvo_recover_pose_homography", "uvo_select_estimation_method", "uvo_estimate_relative_pose", "uvo_mono_set_camera",
     "uvo_mono_reset", "uvo_mono_step", "uvo_mono_submit", "uvo_mono_collect", "uvo_mono_get", "uvo_mono_set_pose_stage", "uvo_mono_pose_stats", "uvo_get_image",
-    "uvo_ctx_set_camera", "uvo_stereo_step_frames", "uvo_stereo_submit_frames", "uvo_mono_step_frames", "uvo_mono_submit_frames",
+    "uvo_ctx_set_camera", "uvo_ctx_set_camera_format", "uvo_get_image_fmt", "uvo_stereo_step_frames", "uvo_stereo_submit_frames", "uvo_mono_step_frames", "uvo_mono_submit_frames",
     "uvo_ctx_set_jpeg_entropy", "uvo_stereo_step_compressed", "uvo_stereo_submit_compressed", "uvo_mono_step_compressed", "uvo_mono_submit_compressed",
     "uvo_jpeg_coefficients", "uvo_jpeg_entropy_stats",
     "uvo_decode_image", "uvo_bayer_bggr2bgr", "uvo_resize_camera_matrix", "uvo_timing_enable", "uvo_timing_count", "uvo_timing_name", "uvo_timing_get", "uvo_timing_reset", "uvo_trace_enable", "uvo_trace_read",
@@ -95,6 +95,8 @@ def lib() -> C.CDLL:
         _lib.uvo_device_alloc.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
         _lib.uvo_device_free.argtypes = [C.c_void_p, C.c_void_p]
         _lib.uvo_device_download.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        if "uvo_ctx_set_camera_format" not in LACKS:
+            _lib.uvo_ctx_set_camera_format.argtypes = [C.c_void_p, C.c_int, C.c_int]
         _lib.uvo_ctx_pending.restype = C.c_int
         _lib.uvo_ctx_pending.argtypes = [C.c_void_p]
         _lib.uvo_ctx_destroy.argtypes = [C.c_void_p]

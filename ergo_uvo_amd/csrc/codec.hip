@@ -20,6 +20,7 @@
 #include "uvo_ctx.h"
 #include "uvo_png.h"
 #include "uvo_jhuff.h"
+#include "uvo_pix.h"
 #include <string.h>
 #include <vector>
 
@@ -381,17 +382,8 @@ __global__ __launch_bounds__(256) void k_bayer_bggr(const uint8_t* __restrict__ 
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (x >= w || y >= h) return;
     uint8_t* o = dst + ((size_t)y * w + x) * 3;
-    if (w < 3 || h < 3) { o[0] = o[1] = o[2] = 0; return; }
-    const int yy = y < 1 ? 1 : (y > h - 2 ? h - 2 : y), xx = x < 1 ? 1 : (x > w - 2 ? w - 2 : x);      // the border copies the nearest interior pixel
-    const uint8_t* r0 = bayer + (size_t)(yy - 1) * stride; const uint8_t* r1 = r0 + stride; const uint8_t* r2 = r1 + stride;
-    const bool ey = (yy & 1) == 0, ex = (xx & 1) == 0;
     int B, G, R;
-    const int cross = (r0[xx] + r1[xx - 1] + r1[xx + 1] + r2[xx] + 2) >> 2, diag = (r0[xx - 1] + r0[xx + 1] + r2[xx - 1] + r2[xx + 1] + 2) >> 2;
-    const int horz = (r1[xx - 1] + r1[xx + 1] + 1) >> 1, vert = (r0[xx] + r2[xx] + 1) >> 1;
-    if (ey && ex) { B = r1[xx]; G = cross; R = diag; }
-    else if (!ey && !ex) { R = r1[xx]; G = cross; B = diag; }
-    else if (ey) { G = r1[xx]; B = horz; R = vert; }
-    else { G = r1[xx]; R = horz; B = vert; }
+    pix_bayer_bggr(bayer, w, h, stride, x, y, B, G, R);                 // uvo_pix.h: the statement the frames entries' Bayer instance shares
     o[0] = (uint8_t)B; o[1] = (uint8_t)G; o[2] = (uint8_t)R;
 }
 

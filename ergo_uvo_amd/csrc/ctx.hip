@@ -2,6 +2,7 @@
 // fused stereo step (visual_odometry_node::stereo_VO, visual_odometry.h:474-739) with every
 // intermediate kept in HBM.
 #include "uvo_ctx.h"
+#include "uvo_pix.h"
 #include <pthread.h>
 #include "uvo_epnp.h"
 #include <string.h>
@@ -1901,18 +1902,44 @@ try {
     return UVO_OK;
 } UVO_ABI_CATCH(nullptr)
 
-extern "C" uvo_status uvo_get_image(uvo_ctx* c, const uint8_t* rgb, int w, int h, int stride, int mem, const double* K, const double* dist4,
-                                    const double* newK, int desired_width, int clahe, int clip_limit, uint8_t* out, int out_mem,
-                                    int* out_w, int* out_h)
-try {
-    if (!c || !rgb || !K || !dist4 || !newK || !out || !out_w || !out_h) return UVO_INVALID_ARG;
-    (void)hipSetDevice(c->device);
+// the one body of uvo_get_image and uvo_get_image_fmt: get_image on an h x w x 3 frame, the result copied out
+static uvo_status get_image_body(uvo_ctx* c, const uint8_t* rgb, int w, int h, int stride, int mem, const double* K, const double* dist4,
+                                 const double* newK, int desired_width, int clahe, int clip_limit, uint8_t* out, int out_mem, int* out_w, int* out_h)
+{
     const uint8_t* d_res = nullptr;
     UVO_TRY(pre_get_image(c, rgb, w, h, stride, mem, K, dist4, newK, desired_width, clahe, clip_limit, &d_res, out_w, out_h));
     const size_t n = (size_t)*out_w * *out_h;
     UVO_HIP_TRY(c, hipMemcpyAsync(out, d_res, n, out_mem == UVO_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
     UVO_HIP_TRY(c, hipStreamSynchronize(c->stream));
     return UVO_OK;
+}
+extern "C" uvo_status uvo_get_image(uvo_ctx* c, const uint8_t* rgb, int w, int h, int stride, int mem, const double* K, const double* dist4,
+                                    const double* newK, int desired_width, int clahe, int clip_limit, uint8_t* out, int out_mem,
+                                    int* out_w, int* out_h)
+try {
+    if (!c || !rgb || !K || !dist4 || !newK || !out || !out_w || !out_h) return UVO_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    return get_image_body(c, rgb, w, h, stride, mem, K, dist4, newK, desired_width, clahe, clip_limit, out, out_mem, out_w, out_h);
+} UVO_ABI_CATCH(c)
+
+// get_image on a frame of any served layout.  BGR8 is uvo_get_image itself; for the other two the operator composes existing kernels
+// into the defined result (BGRA8: the first three channels; BAYER_BGGR8: uvo_bayer_bggr2bgr's picture), then runs the same body.
+extern "C" uvo_status uvo_get_image_fmt(uvo_ctx* c, const uint8_t* pixels, int pixel_format, int w, int h, int stride, int mem, const double* K,
+                                        const double* dist4, const double* newK, int desired_width, int clahe, int clip_limit, uint8_t* out,
+                                        int out_mem, int* out_w, int* out_h)
+try {
+    if (!c || !pixels || !K || !dist4 || !newK || !out || !out_w || !out_h) return UVO_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (pixel_format == kPixBGR8) return get_image_body(c, pixels, w, h, stride, mem, K, dist4, newK, desired_width, clahe, clip_limit, out, out_mem, out_w, out_h);
+    if (!pix_known(pixel_format)) return fail(c, UVO_INVALID_ARG, "uvo_get_image_fmt: unknown pixel format (UVO_PIX_BGR8, UVO_PIX_BGRA8 or UVO_PIX_BAYER_BGGR8)");
+    if (w <= 0 || h <= 0 || stride < pix_bpp(pixel_format) * w)
+        return fail(c, UVO_INVALID_ARG, pixel_format == kPixBGRA8 ? "get_image: bad geometry (BGRA8 frames: stride < 4 * w?)" : "get_image: bad geometry (Bayer mosaics: stride < w?)");
+    UVO_TRY(need_idle(c, "uvo_get_image_fmt"));                          // the composed picture lives in lane 0's codec / preprocessing workspace
+    UVO_TRY(wait_for_producer(c, c, mem));
+    const uint8_t* d_bgr = nullptr;
+    if (pixel_format == kPixBayerBGGR8) { UVO_TRY(codec_bayer(c, pixels, w, h, stride, mem, &d_bgr)); }
+    else { UVO_TRY(pre_drop_alpha(c, pixels, w, h, stride, mem, &d_bgr)); }
+    return get_image_body(c, d_bgr, w, h, 3 * w, UVO_MEM_DEVICE, K, dist4, newK, desired_width, clahe, clip_limit, out, out_mem, out_w, out_h);
 } UVO_ABI_CATCH(c)
 
 // ------------------------------------------------------------------------------------------ compressed-image ingest
@@ -2582,17 +2609,27 @@ try {
     if (c->sh->n_pending != 0) return fail(c, UVO_INVALID_ARG, "uvo_ctx_set_camera: a camera cannot change while pairs / frames are in flight (collect first)");
     return frames_set_camera(c, cam, K, dist4, newK, desired_width, clahe, clip_limit);
 } UVO_ABI_CATCH(c)
+// the layout the *_frames entries read camera `cam`'s frames in; kept beside the camera's other get_image arguments, set or not yet
+extern "C" uvo_status uvo_ctx_set_camera_format(uvo_ctx* c, int cam, int pixel_format)
+try {
+    if (!c) return UVO_INVALID_ARG;
+    if (cam < 0 || cam > 1) return fail(c, UVO_INVALID_ARG, "uvo_ctx_set_camera_format: cam is 0 (left or mono) or 1 (right)");
+    if (!pix_known(pixel_format)) return fail(c, UVO_INVALID_ARG, "uvo_ctx_set_camera_format: unknown pixel format (UVO_PIX_BGR8, UVO_PIX_BGRA8 or UVO_PIX_BAYER_BGGR8)");
+    if (c->sh->n_pending != 0) return fail(c, UVO_INVALID_ARG, "uvo_ctx_set_camera_format: a camera's pixel format cannot change while pairs / frames are in flight (collect first)");
+    return frames_set_camera_format(c, cam, pixel_format);
+} UVO_ABI_CATCH(c)
 
 // the entry's frames (one, or left and right) to the detector images, dw x dh, of the lane *L that the body will pick, behind the producer
 static uvo_status frames_to_lane(uvo_ctx* c, bool loop_initialized, const uint8_t* rgb0, const uint8_t* rgb1, int w, int h, int stride, int mem, uvo_ctx** L, int* dw, int* dh)
 {
     const uint8_t* rgb[2] = { rgb0, rgb1 };
     const int ncam = rgb1 ? 2 : 1;
-    UVO_TRY(frames_plan(c, ncam, w, h, stride, mem, dw, dh));
+    int fmt = kPixOfCamera;                                             // the cameras' own layout (uvo_ctx_set_camera_format)
+    UVO_TRY(frames_plan(c, ncam, &fmt, w, h, stride, mem, dw, dh));
     *L = loop_initialized ? static_cast<uvo_ctx*>(c->sh->lanes[c->sh->next_lane]) : c;
     if (loop_initialized) assign_entry_streams(c, *L, ncam == 2);       // the entry's handles now: get_image and the body's stage A share a stream
     UVO_TRY(wait_for_producer(c, *L, mem));
-    const uvo_status st = frames_queue(c, *L, ncam, rgb, w, h, stride, mem, *dw, *dh);
+    const uvo_status st = frames_queue(c, *L, ncam, fmt, rgb, w, h, stride, mem, *dw, *dh);
     if (st != UVO_OK && *L != c) c->err = (*L)->err;
     return st;
 }
@@ -2657,13 +2694,14 @@ static uvo_status compressed_to_lane(uvo_ctx* c, bool loop_initialized, const uv
     }
     int w = 0, h = 0;
     UVO_TRY(codec_compressed_plan(c, ncam, data, n, bayer, &w, &h));
-    UVO_TRY(frames_plan(c, ncam, w, h, 3 * w, UVO_MEM_DEVICE, dw, dh));
+    int fmt = kPixBGR8;                                                 // the decoders' output, whatever layout the cameras' raw frames have
+    UVO_TRY(frames_plan(c, ncam, &fmt, w, h, 3 * w, UVO_MEM_DEVICE, dw, dh));
     UVO_TRY(codec_compressed_workspaces(c, ncam));
     *L = loop_initialized ? static_cast<uvo_ctx*>(c->sh->lanes[c->sh->next_lane]) : c;
     if (loop_initialized) assign_entry_streams(c, *L, ncam == 2);       // (as frames_to_lane)
     const uint8_t* rgb[2] = { nullptr, nullptr };
     for (int i = 0; i < ncam; i++) UVO_TRY(codec_compressed_queue(c, *L, i, &rgb[i]));
-    const uvo_status st = frames_queue(c, *L, ncam, rgb, w, h, 3 * w, UVO_MEM_DEVICE, *dw, *dh);
+    const uvo_status st = frames_queue(c, *L, ncam, fmt, rgb, w, h, 3 * w, UVO_MEM_DEVICE, *dw, *dh);
     if (st != UVO_OK && *L != c) c->err = (*L)->err;
     return st;
 }

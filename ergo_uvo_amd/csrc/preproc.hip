@@ -14,6 +14,7 @@
 //   k_clahe_apply      : bilinear blend of the four neighbouring tile LUTs
 #include "uvo_ctx.h"
 #include "uvo_math.h"
+#include "uvo_pix.h"
 #include <string.h>
 #include <math.h>
 
@@ -23,6 +24,7 @@ struct PreWs {
     uint8_t *rgb = nullptr, *small = nullptr, *gray = nullptr, *und = nullptr, *out = nullptr;
     int16_t* map1 = nullptr; uint16_t* map2 = nullptr; uint8_t* lut = nullptr;
     size_t cap_in = 0, cap_out = 0;
+    uint8_t *raw = nullptr, *bgr3 = nullptr; size_t cap_raw = 0, cap_bgr3 = 0;      // uvo_get_image_fmt(BGRA8): the staged frame, its three channels
     double mapK[9], mapD[4], mapN[9]; int map_w = 0, map_h = 0; bool map_valid = false;
 };
 
@@ -227,7 +229,7 @@ void pre_ws_free(Ctx* c)
 {
     PreWs* p = static_cast<PreWs*>(c->pre_ws);
     if (!p) return;
-    void* ptrs[] = { p->rgb, p->small, p->gray, p->und, p->out, p->map1, p->map2, p->lut };
+    void* ptrs[] = { p->rgb, p->small, p->gray, p->und, p->out, p->map1, p->map2, p->lut, p->raw, p->bgr3 };
     for (void* q : ptrs) (void)hipFree(q);
     delete p;
     c->pre_ws = nullptr;
@@ -311,13 +313,51 @@ uvo_status pre_get_image(Ctx* c, const uint8_t* rgb, int w, int h, int stride, i
     return UVO_OK;
 }
 
+// uvo_get_image_fmt's BGRA8 frames: the operator composes -- every fourth byte dropped into a tight w x h x 3 picture, then pre_get_image
+// (the loop entries read BGRA8 in place instead: k_fr_resize_gray<kPixBGRA8>)
+__global__ __launch_bounds__(256) void k_bgra_drop_alpha(const uint8_t* __restrict__ src, int w, int h, int stride, uint8_t* __restrict__ dst)
+{
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+    if (x >= w) return;
+    const uint8_t* s = src + (size_t)y * stride + 4 * (size_t)x;
+    uint8_t* o = dst + ((size_t)y * w + x) * 3;
+    o[0] = s[0]; o[1] = s[1]; o[2] = s[2];
+}
+uvo_status pre_drop_alpha(Ctx* c, const uint8_t* bgra, int w, int h, int stride, int mem, const uint8_t** d_bgr)
+{
+    PreWs* p = static_cast<PreWs*>(c->pre_ws);
+    if (!p) { p = new PreWs(); c->pre_ws = p; }
+    const size_t n_raw = mem == UVO_MEM_DEVICE ? 0 : (size_t)h * stride, n3 = (size_t)w * h * 3;
+    if (n_raw > p->cap_raw) {
+        (void)hipFree(p->raw); p->raw = nullptr; p->cap_raw = 0;
+        UVO_HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&p->raw), n_raw));
+        p->cap_raw = n_raw;
+    }
+    if (n3 > p->cap_bgr3) {
+        (void)hipFree(p->bgr3); p->bgr3 = nullptr; p->cap_bgr3 = 0;
+        UVO_HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&p->bgr3), n3));
+        p->cap_bgr3 = n3;
+    }
+    const uint8_t* d_src = bgra;
+    if (mem != UVO_MEM_DEVICE) {
+        UVO_HIP_TRY(c, hipMemcpyAsync(p->raw, bgra, n_raw, hipMemcpyHostToDevice, c->stream));
+        d_src = p->raw;
+    }
+    hipLaunchKernelGGL(k_bgra_drop_alpha, dim3((w + 255) / 256, h), dim3(256), 0, c->stream, d_src, w, h, stride, p->bgr3);
+    UVO_HIP_TRY(c, hipGetLastError());
+    *d_bgr = p->bgr3;
+    return UVO_OK;
+}
+
 // ------------------------------------------------------------------------------------------ camera frames into the loops' lanes
 // get_image in front of detect_features INSIDE a loop entry (uvo_stereo_*_frames / uvo_mono_*_frames): the same four stages, queued on
 // the entry's lane's stage-A stream, both cameras of a pair per launch (blockIdx.y = image, as the detector's ImgPair), the last
 // kernel writing the lane's detector image (Ctx::d_img).  Every image is addressed as a flat array of w * h bytes and a thread
 // owns four consecutive ones, so each store is one aligned dword whatever the width (the buffers come from hipMalloc; the last,
 // partial quad of an image is stored bytewise).  Arithmetic per pixel is the single-image kernels' above, statement for statement:
-//   k_fr_resize_gray : k_resize_area_c3's three channel values (fast / table path, saturated to u8), then k_rgb2gray's fixed point
+//   k_fr_resize_gray : k_resize_area_c3's three channel values (fast / table path, saturated to u8), then k_rgb2gray's fixed point;
+//                      one instance per pixel layout of the frame (uvo_ctx_set_camera_format): BGR8, BGRA8 (three of four bytes) and
+//                      BAYER_BGGR8 (the three values of a source pixel demosaiced from the mosaic's 3 x 3 neighbourhood, uvo_pix.h)
 //   k_fr_remap       : k_remap_bilinear, maps of the image's camera
 //   k_fr_clahe_lut   : k_clahe_lut, 64 workgroups per image
 //   k_fr_clahe_apply : k_clahe_apply
@@ -335,6 +375,7 @@ struct FrPair { FrImg im[2]; };
 struct FrCam {
     bool set = false;
     double K[9], D[4], N[9]; int desired_width = 0, clahe = 0, clip = 0;
+    int fmt = kPixBGR8;                           // the layout of this camera's frames (uvo_ctx_set_camera_format); kept whether or not the camera is set
     int16_t* map1 = nullptr; uint16_t* map2 = nullptr; size_t map_cap = 0; int map_w = 0, map_h = 0; bool map_valid = false;
 };
 struct FramesWs {
@@ -350,7 +391,22 @@ __device__ __forceinline__ void fr_store4(uint8_t* dst, size_t o0, size_t n, con
 }
 __device__ __forceinline__ uint8_t fr_gray(int r, int g, int b) { return (uint8_t)((r * 9798 + g * 19235 + b * 3735 + (1 << 14)) >> 15); }
 
-// mode 0: no resize, 1: resizeAreaFast_ (integer scale), 2: the table path
+// The three source samples of source pixel (x, y) that get_image's grey weights 9798 / 19235 / 3735 multiply (channels 0, 1, 2), per
+// pixel layout: BGR8 and BGRA8 read them (BGRA8 skips every fourth byte), BAYER_BGGR8 computes them from the mosaic's 3 x 3
+// neighbourhood with k_bayer_bggr's own statement (uvo_pix.h) -- no w x h x 3 picture exists on that route.
+template <int F> __device__ __forceinline__ void fr_fetch(const uint8_t* __restrict__ src, int sw, int sh, int stride, int x, int y, int& c0, int& c1, int& c2)
+{
+    if constexpr (F == kPixBayerBGGR8) pix_bayer_bggr(src, sw, sh, stride, x, y, c0, c1, c2);
+    else {
+        const uint8_t* s = src + (size_t)y * stride + (F == kPixBGRA8 ? 4 : 3) * x;
+        c0 = s[0]; c1 = s[1]; c2 = s[2];
+    }
+}
+
+// mode 0: no resize, 1: resizeAreaFast_ (integer scale), 2: the table path.  One instance per pixel layout F (UVO_PIX_*).  The BGR8
+// instance keeps the statements the kernel had before it took a layout (its code is the former kernel's, instruction for instruction);
+// the other two go through fr_fetch.
+template <int F>
 __global__ __launch_bounds__(256) void k_fr_resize_gray(FrPair fp, int sw, int sh, int stride, int dw, int dh, double scale_x, double scale_y,
                                                         int iscale_x, int iscale_y, int mode)
 {
@@ -359,30 +415,52 @@ __global__ __launch_bounds__(256) void k_fr_resize_gray(FrPair fp, int sw, int s
     if (o0 >= n) return;
     int dy = (int)(o0 / dw), dx = (int)(o0 - (size_t)dy * dw);
     uint8_t g[4] = {0, 0, 0, 0};
-    if (mode == 0 && dx + 4 <= dw && ((reinterpret_cast<uintptr_t>(im.src) | (unsigned)stride) & 3u) == 0 && (dx & 3) == 0) {
-        // twelve bytes of one row, dword aligned
-        const uint32_t* s = reinterpret_cast<const uint32_t*>(im.src + (size_t)dy * stride + 3 * dx);
-        const uint32_t a = s[0], b = s[1], c = s[2];
-        g[0] = fr_gray(a & 255, (a >> 8) & 255, (a >> 16) & 255);
-        g[1] = fr_gray(a >> 24, b & 255, (b >> 8) & 255);
-        g[2] = fr_gray((b >> 16) & 255, b >> 24, c & 255);
-        g[3] = fr_gray((c >> 8) & 255, (c >> 16) & 255, c >> 24);
-        fr_store4(im.gray, o0, n, g);
-        return;
+    if constexpr (F == kPixBGR8) {
+        if (mode == 0 && dx + 4 <= dw && ((reinterpret_cast<uintptr_t>(im.src) | (unsigned)stride) & 3u) == 0 && (dx & 3) == 0) {
+            // twelve bytes of one row, dword aligned
+            const uint32_t* s = reinterpret_cast<const uint32_t*>(im.src + (size_t)dy * stride + 3 * dx);
+            const uint32_t a = s[0], b = s[1], c = s[2];
+            g[0] = fr_gray(a & 255, (a >> 8) & 255, (a >> 16) & 255);
+            g[1] = fr_gray(a >> 24, b & 255, (b >> 8) & 255);
+            g[2] = fr_gray((b >> 16) & 255, b >> 24, c & 255);
+            g[3] = fr_gray((c >> 8) & 255, (c >> 16) & 255, c >> 24);
+            fr_store4(im.gray, o0, n, g);
+            return;
+        }
+    }
+    if constexpr (F == kPixBGRA8) {
+        if (mode == 0 && dx + 4 <= dw && ((reinterpret_cast<uintptr_t>(im.src) | (unsigned)stride) & 3u) == 0) {
+            // sixteen bytes of one row, one dword per pixel (4 * dx is a multiple of four whatever dx is)
+            const uint32_t* s = reinterpret_cast<const uint32_t*>(im.src + (size_t)dy * stride + 4 * dx);
+            for (int k = 0; k < 4; k++) { const uint32_t a = s[k]; g[k] = fr_gray(a & 255, (a >> 8) & 255, (a >> 16) & 255); }
+            fr_store4(im.gray, o0, n, g);
+            return;
+        }
     }
     PTab ty = {};
     int ty_row = -1;
     for (int k = 0; k < 4 && o0 + k < n; k++) {
         int ch3[3];
         if (mode == 0) {
-            const uint8_t* s = im.src + (size_t)dy * stride + 3 * dx;
-            ch3[0] = s[0]; ch3[1] = s[1]; ch3[2] = s[2];
+            if constexpr (F == kPixBGR8) {
+                const uint8_t* s = im.src + (size_t)dy * stride + 3 * dx;
+                ch3[0] = s[0]; ch3[1] = s[1]; ch3[2] = s[2];
+            } else fr_fetch<F>(im.src, sw, sh, stride, dx, dy, ch3[0], ch3[1], ch3[2]);
         } else if (mode == 1) {                                  // resizeAreaFast_: integer block sums
-            const uint8_t* S = im.src + (size_t)(dy * iscale_y) * stride + (size_t)(dx * iscale_x) * 3;
             int sum[3] = {0, 0, 0};
-            for (int sy = 0; sy < iscale_y; sy++) for (int sx = 0; sx < iscale_x; sx++) {
-                const uint8_t* q = S + (size_t)sy * stride + sx * 3;
-                sum[0] += q[0]; sum[1] += q[1]; sum[2] += q[2];
+            if constexpr (F == kPixBGR8) {
+                const uint8_t* S = im.src + (size_t)(dy * iscale_y) * stride + (size_t)(dx * iscale_x) * 3;
+                for (int sy = 0; sy < iscale_y; sy++) for (int sx = 0; sx < iscale_x; sx++) {
+                    const uint8_t* q = S + (size_t)sy * stride + sx * 3;
+                    sum[0] += q[0]; sum[1] += q[1]; sum[2] += q[2];
+                }
+            } else {
+                const int x0 = dx * iscale_x, y0 = dy * iscale_y;
+                for (int sy = 0; sy < iscale_y; sy++) for (int sx = 0; sx < iscale_x; sx++) {
+                    int q0, q1, q2;
+                    fr_fetch<F>(im.src, sw, sh, stride, x0 + sx, y0 + sy, q0, q1, q2);
+                    sum[0] += q0; sum[1] += q1; sum[2] += q2;
+                }
             }
             if (iscale_x == 2 && iscale_y == 2) for (int ch = 0; ch < 3; ch++) ch3[ch] = (uint8_t)((sum[ch] + 2) >> 2);
             else { const float sc = 1.f / (iscale_x * iscale_y); for (int ch = 0; ch < 3; ch++) ch3[ch] = p_sat_u8(sum[ch] * sc); }
@@ -393,11 +471,20 @@ __global__ __launch_bounds__(256) void k_fr_resize_gray(FrPair fp, int sw, int s
             const int r_begin = ty.has_first ? ty.sx1 - 1 : ty.sx1, r_end = ty.has_last ? ty.sx2 + 1 : ty.sx2;
             float sum[3] = {0.f, 0.f, 0.f};
             for (int r = r_begin; r < r_end; r++) {
-                const uint8_t* S = im.src + (size_t)r * stride;
                 float buf[3] = {0.f, 0.f, 0.f};
-                for (int cc = c_begin; cc < c_end; cc++) {
-                    const float alpha = cc < tx.sx1 ? tx.a_first : (cc < tx.sx2 ? tx.a_mid : tx.a_last);
-                    buf[0] += S[cc * 3] * alpha; buf[1] += S[cc * 3 + 1] * alpha; buf[2] += S[cc * 3 + 2] * alpha;
+                if constexpr (F == kPixBGR8) {
+                    const uint8_t* S = im.src + (size_t)r * stride;
+                    for (int cc = c_begin; cc < c_end; cc++) {
+                        const float alpha = cc < tx.sx1 ? tx.a_first : (cc < tx.sx2 ? tx.a_mid : tx.a_last);
+                        buf[0] += S[cc * 3] * alpha; buf[1] += S[cc * 3 + 1] * alpha; buf[2] += S[cc * 3 + 2] * alpha;
+                    }
+                } else {
+                    for (int cc = c_begin; cc < c_end; cc++) {
+                        const float alpha = cc < tx.sx1 ? tx.a_first : (cc < tx.sx2 ? tx.a_mid : tx.a_last);
+                        int q0, q1, q2;
+                        fr_fetch<F>(im.src, sw, sh, stride, cc, r, q0, q1, q2);
+                        buf[0] += q0 * alpha; buf[1] += q1 * alpha; buf[2] += q2 * alpha;
+                    }
                 }
                 const float beta = r < ty.sx1 ? ty.a_first : (r < ty.sx2 ? ty.a_mid : ty.a_last);
                 sum[0] += beta * buf[0]; sum[1] += beta * buf[1]; sum[2] += beta * buf[2];
@@ -530,20 +617,34 @@ uvo_status frames_set_camera(Ctx* m, int cam, const double* K, const double* dis
     fc.set = true;
     return UVO_OK;
 }
+uvo_status frames_set_camera_format(Ctx* m, int cam, int fmt)
+{
+    frames_ws(m)->cam[cam].fmt = fmt;
+    return UVO_OK;
+}
 
 // What a frames entry needs before anything is queued: the cameras (ncam = 1: camera 0 only), get_image's geometry, the output
 // against the context's limits, the cameras' maps and every lane's workspace.  Maps and workspaces are made when the first frame of
 // a size arrives -- a sequence's synchronous init entry, where prime_lanes makes the lanes' other per-size state -- and never while
 // entries are in flight: lanes read the maps.
-uvo_status frames_plan(Ctx* m, int ncam, int w, int h, int stride, int mem, int* out_w, int* out_h)
+// *fmt: the layout the frames are read in; kPixOfCamera on entry asks for the cameras' own (one for both cameras of a stereo entry).
+uvo_status frames_plan(Ctx* m, int ncam, int* fmt, int w, int h, int stride, int mem, int* out_w, int* out_h)
 {
     FramesWs* f = frames_ws(m);
     for (int i = 0; i < ncam; i++)
         if (!f->cam[i].set) { m->err = i == 0 ? "camera 0 is not set (uvo_ctx_set_camera)" : "camera 1 (right) is not set (uvo_ctx_set_camera): the stereo frames calls need both"; return UVO_INVALID_ARG; }
+    if (*fmt == kPixOfCamera) {
+        if (ncam == 2 && f->cam[0].fmt != f->cam[1].fmt) { m->err = "the two cameras have different pixel formats (uvo_ctx_set_camera_format): a stereo entry reads both frames in one layout"; return UVO_INVALID_ARG; }
+        *fmt = f->cam[0].fmt;
+    }
+    const int bpp = pix_bpp(*fmt);
     int dw = 0, dh = 0;
     for (int i = 0; i < ncam; i++) {
         const int desired_width = f->cam[i].desired_width;
-        if (w <= 0 || h <= 0 || desired_width <= 0 || stride < 3 * w) { m->err = "get_image: bad geometry (stride < 3 * w?)"; return UVO_INVALID_ARG; }
+        if (w <= 0 || h <= 0 || desired_width <= 0 || stride < bpp * w) {
+            m->err = bpp == 3 ? "get_image: bad geometry (stride < 3 * w?)" : bpp == 4 ? "get_image: bad geometry (BGRA8 frames: stride < 4 * w?)" : "get_image: bad geometry (Bayer mosaics: stride < w?)";
+            return UVO_INVALID_ARG;
+        }
         const double ratio = (double)w / (double)desired_width;
         const int cw = desired_width, ch = (int)(h / ratio);
         if (cw > w || ch > h || ch <= 0) { m->err = "get_image: enlarging (desired_width > w; OpenCV switches INTER_AREA to bilinear there) is not provided"; return UVO_INVALID_ARG; }
@@ -609,7 +710,7 @@ uvo_status frames_plan(Ctx* m, int ncam, int w, int h, int stride, int mem, int*
 }
 
 // get_image of the entry's ncam frames on lane L's stream, into L->d_img[0 .. ncam-1]: at most four launches, no host sync
-uvo_status frames_queue(Ctx* m, Ctx* L, int ncam, const uint8_t* const* rgb, int w, int h, int stride, int mem, int dw, int dh)
+uvo_status frames_queue(Ctx* m, Ctx* L, int ncam, int fmt, const uint8_t* const* rgb, int w, int h, int stride, int mem, int dw, int dh)
 {
     const FramesWs* f = static_cast<const FramesWs*>(m->frames_ws);
     const FramesWs* lf = static_cast<const FramesWs*>(L->frames_ws);
@@ -646,7 +747,8 @@ uvo_status frames_queue(Ctx* m, Ctx* L, int ncam, const uint8_t* const* rgb, int
         iscale_x = cv_round_d(scale_x); iscale_y = cv_round_d(scale_y);
         mode = (fabs(scale_x - iscale_x) < DBL_EPSILON && fabs(scale_y - iscale_y) < DBL_EPSILON) ? 1 : 2;
     }
-    hipLaunchKernelGGL(k_fr_resize_gray, dim3(gx, ncam), dim3(256), 0, st, fp, w, h, stride, dw, dh, scale_x, scale_y, iscale_x, iscale_y, mode);
+    auto k_resize_gray = fmt == kPixBayerBGGR8 ? k_fr_resize_gray<kPixBayerBGGR8> : fmt == kPixBGRA8 ? k_fr_resize_gray<kPixBGRA8> : k_fr_resize_gray<kPixBGR8>;
+    hipLaunchKernelGGL(k_resize_gray, dim3(gx, ncam), dim3(256), 0, st, fp, w, h, stride, dw, dh, scale_x, scale_y, iscale_x, iscale_y, mode);
     hipLaunchKernelGGL(k_fr_remap, dim3(gx, ncam), dim3(256), 0, st, fp, dw, dh);
     if (any_clahe) {
         hipLaunchKernelGGL(k_fr_clahe_lut, dim3(64, ncam), dim3(256), 0, st, fp, dw, dh, tw, th, lutScale);

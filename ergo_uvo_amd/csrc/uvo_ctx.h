@@ -422,8 +422,11 @@ uvo_status pre_get_image(Ctx* c, const uint8_t* rgb, int w, int h, int stride, i
 // camera frames into the loops' lanes (preproc.hip, "camera frames"): lane 0 (m) keeps the cameras, every lane its buffers
 void frames_ws_free(Ctx* c);
 uvo_status frames_set_camera(Ctx* m, int cam, const double* K, const double* dist4, const double* newK, int desired_width, int clahe, int clip_limit);
-uvo_status frames_plan(Ctx* m, int ncam, int w, int h, int stride, int mem, int* out_w, int* out_h);
-uvo_status frames_queue(Ctx* m, Ctx* L, int ncam, const uint8_t* const* rgb, int w, int h, int stride, int mem, int dw, int dh);
+uvo_status frames_set_camera_format(Ctx* m, int cam, int fmt);
+constexpr int kPixOfCamera = -1;                    // frames_plan: read the frames in the cameras' own layout (else a UVO_PIX_* value)
+uvo_status frames_plan(Ctx* m, int ncam, int* fmt, int w, int h, int stride, int mem, int* out_w, int* out_h);
+uvo_status pre_drop_alpha(Ctx* c, const uint8_t* bgra, int w, int h, int stride, int mem, const uint8_t** d_bgr);
+uvo_status frames_queue(Ctx* m, Ctx* L, int ncam, int fmt, const uint8_t* const* rgb, int w, int h, int stride, int mem, int dw, int dh);
 // codec.hip
 void codec_ws_free(Ctx* c);
 uvo_status codec_decode(Ctx* c, const uint8_t* data, size_t n, int bayer, const uint8_t** d_out, int* w, int* h, int* channels);

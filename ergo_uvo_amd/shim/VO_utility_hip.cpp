@@ -338,10 +338,10 @@ void resize_camera_matrix(Mat original_image, Mat& cameraMatrix, Mat distortionC
     for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) { cameraMatrix.at<double>(i, j) = K[3*i + j]; newCamMatrix.at<double>(i, j) = newK[3*i + j]; }
 }
 
-// VOU:337-379: resize INTER_AREA to DESIRED_WIDTH -> RGB2GRAY -> undistort -> CLAHE(CLIP_LIMIT) when CLAHE_CORRECTION
-Mat get_image(const Mat& current_img, const Mat& cameraMatrix, const Mat& distortionCoeff, const Mat& newCamMatrix)
+// VOU:337-379: resize INTER_AREA to DESIRED_WIDTH -> RGB2GRAY -> undistort -> CLAHE(CLIP_LIMIT) when CLAHE_CORRECTION; the frame in
+// pixel layout `fmt` (UVO_PIX_*), `bpp` bytes per pixel
+static Mat get_image_of(const Mat& current_img, int fmt, int bpp, const Mat& cameraMatrix, const Mat& distortionCoeff, const Mat& newCamMatrix)
 {
-    require(!current_img.empty() && current_img.type() == CV_8UC3, "get_image: CV_8UC3 image expected");
     double K[9], newK[9], d4[4] = {0, 0, 0, 0};
     doubles_of(cameraMatrix, 3, 3, K, "get_image: cameraMatrix must be 3x3 CV_64F");
     doubles_of(newCamMatrix, 3, 3, newK, "get_image: newCamMatrix must be 3x3 CV_64F");
@@ -349,16 +349,34 @@ Mat get_image(const Mat& current_img, const Mat& cameraMatrix, const Mat& distor
             "get_image: distortion must be (k1, k2, p1, p2) CV_64F");
     for (int i = 0, k = 0; i < distortionCoeff.rows; i++) for (int j = 0; j < distortionCoeff.cols; j++) d4[k++] = distortionCoeff.at<double>(i, j);
     const int w = current_img.cols, h = current_img.rows;
-    const int stride = h > 1 ? (int)(current_img.ptr<uint8_t>(1) - current_img.ptr<uint8_t>(0)) : w * 3;
+    const int stride = h > 1 ? (int)(current_img.ptr<uint8_t>(1) - current_img.ptr<uint8_t>(0)) : w * bpp;
     const int dh = (int)(h / ((double)w / (double)DESIRED_WIDTH));
     require(dh > 0, "get_image: DESIRED_WIDTH");
     Mat out(dh, DESIRED_WIDTH, CV_8UC1);
     std::vector<uint8_t> tight((size_t)dh * DESIRED_WIDTH);
     int ow = 0, oh = 0;
-    SHIM_TRY(uvo_get_image(ctx_now(), current_img.ptr<uint8_t>(0), w, h, stride, UVO_MEM_HOST, K, d4, newK, DESIRED_WIDTH, CLAHE_CORRECTION ? 1 : 0,
-                           CLIP_LIMIT, tight.data(), UVO_MEM_HOST, &ow, &oh), "uvo_get_image");
+    if (fmt == UVO_PIX_BGR8)
+        SHIM_TRY(uvo_get_image(ctx_now(), current_img.ptr<uint8_t>(0), w, h, stride, UVO_MEM_HOST, K, d4, newK, DESIRED_WIDTH, CLAHE_CORRECTION ? 1 : 0,
+                               CLIP_LIMIT, tight.data(), UVO_MEM_HOST, &ow, &oh), "uvo_get_image");
+    else
+        SHIM_TRY(uvo_get_image_fmt(ctx_now(), current_img.ptr<uint8_t>(0), fmt, w, h, stride, UVO_MEM_HOST, K, d4, newK, DESIRED_WIDTH, CLAHE_CORRECTION ? 1 : 0,
+                                   CLIP_LIMIT, tight.data(), UVO_MEM_HOST, &ow, &oh), "uvo_get_image_fmt");
     for (int y = 0; y < oh; y++) memcpy(out.ptr<uint8_t>(y), tight.data() + (size_t)y * ow, (size_t)ow);
     return out;
+}
+// a 3-channel Mat as before; a 4-channel Mat (cv_bridge's BGRA for an RGBA PNG topic) by its first three channels, as the reference's
+// cvtColor(COLOR_RGB2GRAY) reads it
+Mat get_image(const Mat& current_img, const Mat& cameraMatrix, const Mat& distortionCoeff, const Mat& newCamMatrix)
+{
+    require(!current_img.empty() && (current_img.type() == CV_8UC3 || current_img.type() == CV_8UC4), "get_image: CV_8UC3 or CV_8UC4 image expected");
+    const bool bgra = current_img.type() == CV_8UC4;
+    return get_image_of(current_img, bgra ? UVO_PIX_BGRA8 : UVO_PIX_BGR8, bgra ? 4 : 3, cameraMatrix, distortionCoeff, newCamMatrix);
+}
+// a BGGR mosaic: what cvtColor(COLOR_BayerBGGR2BGR) followed by get_image gives
+Mat uvo_hip::get_image_bayer(const Mat& mosaic, const Mat& cameraMatrix, const Mat& distortionCoeff, const Mat& newCamMatrix)
+{
+    require(!mosaic.empty() && mosaic.type() == CV_8UC1, "get_image_bayer: CV_8UC1 mosaic expected");
+    return get_image_of(mosaic, UVO_PIX_BAYER_BGGR8, 1, cameraMatrix, distortionCoeff, newCamMatrix);
 }
 
 // VOU:91-126: the "SURF" branch (SURF::create(...)->detectAndCompute), the "SIFT" branch (SIFT::create(10000, 3, 0.03, 10, 1.6)->
@@ -713,6 +731,7 @@ void loop_set_camera(int cam, const Mat& cameraMatrix, const Mat& distortionCoef
     for (int i = 0, k = 0; i < distortionCoeff.rows; i++) for (int j = 0; j < distortionCoeff.cols; j++) d4[k++] = distortionCoeff.at<double>(i, j);
     SHIM_TRY(uvo_ctx_set_camera(ctx_now(), cam, K, d4, newK, DESIRED_WIDTH, CLAHE_CORRECTION ? 1 : 0, CLIP_LIMIT), "uvo_ctx_set_camera");
 }
+void loop_set_camera_format(int cam, int pixel_format) { SHIM_TRY(uvo_ctx_set_camera_format(ctx_now(), cam, pixel_format), "uvo_ctx_set_camera_format"); }
 void loop_set_rig(const Mat& newK_left, const Mat& newK_right, const Mat& R_right, const Mat& t_right)
 {
     double KL[9], KR[9], R[9], t[3];

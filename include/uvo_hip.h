@@ -455,6 +455,31 @@ uvo_status uvo_get_image(uvo_ctx* c, const uint8_t* rgb, int w, int h, int strid
                          const double* newK, int desired_width, int clahe, int clip_limit, uint8_t* out, int out_mem,
                          int* out_w, int* out_h);
 
+/* ---- pixel layouts of a camera frame.  The reference's get_image (VO_utility.cpp:337-379) runs resize + cvtColor(COLOR_RGB2GRAY)
+ * on any 3- or 4-channel Mat, using the first three channels; cv_bridge::toCvCopy hands it BGRA for an RGBA PNG topic, and its
+ * "bayer" messages are demosaiced with COLOR_BayerBGGR2BGR in front of it (math_utility.cpp:154-173).
+ *   UVO_PIX_BGR8         h x w x 3 interleaved u8, stride >= 3 * w: what uvo_get_image and the *_frames entries have always read
+ *   UVO_PIX_BGRA8        h x w x 4 interleaved u8, stride >= 4 * w.  Defined result: what the BGR8 path gives on the same pixels with
+ *                        every fourth byte dropped (channels 0, 1, 2 take the grey weights 9798 / 19235 / 3735, as BGR8's do)
+ *   UVO_PIX_BAYER_BGGR8  h x w u8 mosaic (even row, even column: B; odd row, odd column: R; otherwise G), stride >= w.  Defined result:
+ *                        what uvo_bayer_bggr2bgr followed by the BGR8 path gives, byte for byte -- its border rule (a border pixel is
+ *                        the nearest interior pixel's value), its all-zero picture for w < 3 or h < 3, odd widths and heights included
+ * uvo_get_image_fmt is uvo_get_image on `pixels` in layout `pixel_format` (UVO_PIX_BGR8: the same body).  For the other two layouts
+ * the operator composes kernels into the defined result and, because it uses lane 0's workspaces, is refused while entries are in flight.
+ * uvo_ctx_set_camera_format keeps the layout of camera `cam`'s frames beside the camera's other get_image arguments (it may be called
+ * before uvo_ctx_set_camera; the default is UVO_PIX_BGR8): the *_frames entries below then read their frame pointers in that layout,
+ * with stride >= bytes-per-pixel * w.  The loop entries do not compose: their first launch (k_fr_resize_gray, one instance per layout)
+ * reads the frame in place -- a mosaic is demosaiced from its 3 x 3 neighbourhoods inside the resize, by the statement
+ * uvo_bayer_bggr2bgr's kernel runs, and no w x h x 3 picture is written or read; host-memory frames are staged as they are, so a
+ * mosaic costs a third of the copy.  An entry stays at four launches at most.  Refused with UVO_INVALID_ARG and a message: an unknown
+ * format, cam outside 0..1, a change while entries are in flight; by the stereo frames entries, before anything is queued and with
+ * uvo_ctx_pending unchanged: two cameras of different formats.  The compressed entries decode to BGR and are not affected. */
+enum { UVO_PIX_BGR8 = 0, UVO_PIX_BGRA8 = 1, UVO_PIX_BAYER_BGGR8 = 2 };
+uvo_status uvo_ctx_set_camera_format(uvo_ctx* c, int cam, int pixel_format);
+uvo_status uvo_get_image_fmt(uvo_ctx* c, const uint8_t* pixels, int pixel_format, int w, int h, int stride, int mem, const double* K,
+                             const double* dist4, const double* newK, int desired_width, int clahe, int clip_limit, uint8_t* out,
+                             int out_mem, int* out_w, int* out_h);
+
 /* ---- camera frames into the loops: get_image in front of detect_features as the reference's nodes run it (visual_odometry.h:235/260
  * mono, 482-483/542-543 stereo), inside the loop entry.  uvo_ctx_set_camera keeps get_image's arguments for camera `cam` (0 = left or
  * mono, 1 = right) in the context; the *_frames calls take h x w x 3 interleaved u8 frames, `stride` bytes per row, host or device per

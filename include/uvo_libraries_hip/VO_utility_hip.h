@@ -44,7 +44,7 @@ uvocv::Mat convert_from_homogeneous_coords(const uvocv::Mat& points4d);         
 // VO_utility.h:112: scales cameraMatrix in place by original width / DESIRED_WIDTH, newCamMatrix = getOptimalNewCameraMatrix(alpha = 0)
 void resize_camera_matrix(uvocv::Mat original_image, uvocv::Mat& cameraMatrix, uvocv::Mat distortionCoeff, uvocv::Mat& newCamMatrix);
 uvocv::Mat get_image(const uvocv::Mat& current_img, const uvocv::Mat& cameraMatrix, const uvocv::Mat& distortionCoeff,
-                     const uvocv::Mat& newCamMatrix);                                                                  // VOU:337-379
+                     const uvocv::Mat& newCamMatrix);                                                                  // VOU:337-379: CV_8UC3, or CV_8UC4 by its first three channels
 void detect_features(uvocv::Mat img, std::vector<uvocv::KeyPoint>& keypoints, uvocv::Mat& descriptors);                 // VOU:91-126
 void estimate_relative_pose(std::vector<uvocv::Point2f> keypoints1_conv, std::vector<uvocv::Point2f> keypoints2_conv,
                             uvocv::Mat cameraMatrix, uvocv::Mat& R_currCam_prevCam, uvocv::Mat& t_currCam_prevCam,
@@ -135,6 +135,10 @@ private:
     std::shared_ptr<void> mem_;
 };
 
+// get_image on a CV_8UC1 BGGR mosaic: what cvtColor(COLOR_BayerBGGR2BGR) (math_utility.cpp:154-173, the "bayer" step) and get_image give
+uvocv::Mat get_image_bayer(const uvocv::Mat& mosaic, const uvocv::Mat& cameraMatrix, const uvocv::Mat& distortionCoeff,
+                           const uvocv::Mat& newCamMatrix);
+void loop_set_camera_format(int cam, int pixel_format);        // UVO_PIX_*: the layout the frames entries read camera `cam`'s frames in (uvo_ctx_set_camera_format)
 void loop_set_camera(int cam, const uvocv::Mat& cameraMatrix, const uvocv::Mat& distortionCoeff, const uvocv::Mat& newCamMatrix);   // + DESIRED_WIDTH, CLAHE_CORRECTION, CLIP_LIMIT
 void loop_set_rig(const uvocv::Mat& newK_left, const uvocv::Mat& newK_right, const uvocv::Mat& R_right, const uvocv::Mat& t_right);
 void loop_set_mono_camera(const uvocv::Mat& newCamMatrix);

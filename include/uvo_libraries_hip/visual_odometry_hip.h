@@ -98,6 +98,17 @@ public:
     }
     // compressed messages that went through decode_compressed_image_device and the frames entry because the compressed entry refused their kind
     int compressed_fallbacks() const { return compressed_fallbacks_; }
+    // What a 1-channel frame (Mat or DeviceImage) is: UVO_PIX_BAYER_BGGR8 makes it a BGGR mosaic, demosaiced inside get_image in all
+    // three execution modes; under the default, UVO_PIX_BGR8, 1-channel frames are refused as before.  3-channel frames are always BGR8
+    // and 4-channel frames BGRA8 (cv_bridge's Mat for an RGBA PNG topic: the first three channels count).  Both cameras of a pair share
+    // one layout, and the layout of a topic cannot change while frames are in flight (spin_collect first).
+    void set_pixel_format(int fmt)
+    {
+        if (fmt != UVO_PIX_BGR8 && fmt != UVO_PIX_BAYER_BGGR8) throw Error(UVO_INVALID_ARG, "set_pixel_format: UVO_PIX_BGR8 (colour frames by their channel count) or UVO_PIX_BAYER_BGGR8 (1-channel frames are mosaics)");
+        if (!fifo_.empty()) throw Error(UVO_INVALID_ARG, "set_pixel_format: frames are in flight (spin_collect first)");
+        pixel_format_ = fmt;
+    }
+    int pixel_format() const { return pixel_format_; }
 
     // ---- one iteration of the node's loop (after ros::spinOnce(); loop_rate.sleep()) ----
     Published spin_once()
@@ -177,8 +188,29 @@ private:
         CompressedMessage msg[2];                                        // a compressed frame: the payloads, until its entry has consumed them
         const unsigned char* p[2] = {nullptr, nullptr};
         int w = 0, h = 0, stride = 0, mem = UVO_MEM_HOST;
+        int fmt = UVO_PIX_BGR8;                                          // the pixels' layout, from their channel count (layout_of)
         double stamp = 0, range = 0;
     };
+    int pixel_format_ = UVO_PIX_BGR8;                                    // set_pixel_format: what a 1-channel frame is
+    int ctx_format_ = -1;                                                // the layout the context's cameras were last given (-1: not yet)
+    // the layout of a frame with `channels` channels, -1 when the node does not take it
+    int layout_of(int channels) const
+    { return channels == 3 ? UVO_PIX_BGR8 : channels == 4 ? UVO_PIX_BGRA8 : (channels == 1 && pixel_format_ == UVO_PIX_BAYER_BGGR8) ? UVO_PIX_BAYER_BGGR8 : -1; }
+    static int bytes_per_pixel(int fmt) { return fmt == UVO_PIX_BGRA8 ? 4 : fmt == UVO_PIX_BAYER_BGGR8 ? 1 : 3; }
+    // the context's cameras read frames in layout fmt from now on (refused by the library while frames are in flight)
+    void cameras_read(int fmt)
+    {
+        if (fmt == ctx_format_) return;
+        loop_set_camera_format(0, fmt);
+        if (mode_ == "stereo") loop_set_camera_format(1, fmt);
+        ctx_format_ = fmt;
+    }
+    // get_image of the operator loops on whatever layout the node takes
+    Mat get_image_any(const Mat& img, const Mat& K, const Mat& dist, const Mat& newK) const
+    {
+        if (img.type() == uvocv::CV_8UC1 && pixel_format_ == UVO_PIX_BAYER_BGGR8) return get_image_bayer(img, K, dist, newK);
+        return get_image(img, K, dist, newK);
+    }
     DeviceImage dev_img_, dev_left_, dev_right_;
     CompressedMessage msg_[2];                                           // the compressed message(s) the callbacks last delivered (fused execution)
     int compressed_fallbacks_ = 0;
@@ -206,7 +238,7 @@ private:
         if (!new_img_available_) return out;
         new_img_available_ = false;
         const double curr_time = stamp_;
-        Mat curr_img = get_image(camera_img_, camera_matrix_, distortion_, new_camera_matrix_);          // VO:235 / VO:260
+        Mat curr_img = get_image_any(camera_img_, camera_matrix_, distortion_, new_camera_matrix_);          // VO:235 / VO:260
         std::vector<uvocv::KeyPoint> curr_keypoints; Mat curr_descriptors;
         detect_features(curr_img, curr_keypoints, curr_descriptors);                      // VO:238 / VO:274
         out.n_kps = (int)curr_keypoints.size();
@@ -272,7 +304,7 @@ private:
         if (!new_img_available_) return out;
         new_img_available_ = false;
         const double curr_time = stamp_;
-        Mat L = get_image(camera_left_, K_left_, dist_left_, newK_left_), R = get_image(camera_right_, K_right_, dist_right_, newK_right_);     // VO:482-483 / 542-543
+        Mat L = get_image_any(camera_left_, K_left_, dist_left_, newK_left_), R = get_image_any(camera_right_, K_right_, dist_right_, newK_right_);     // VO:482-483 / 542-543
         std::vector<uvocv::KeyPoint> kL, kR; Mat dL, dR;
         detect_features(L, kL, dL); detect_features(R, kR, dR);                            // VO:486-487 / 548-549
         out.n_kps = (int)kL.size();
@@ -357,23 +389,33 @@ private:
         }
         if (!(stereo ? dev_left_ : dev_img_).empty()) {
             f.dev[0] = stereo ? dev_left_ : dev_img_; if (stereo) f.dev[1] = dev_right_;
-            for (int i = 0; i < ncam; i++) {
-                if (f.dev[i].empty() || f.dev[i].channels != 3 || f.dev[i].cols != f.dev[0].cols || f.dev[i].rows != f.dev[0].rows)
-                    throw Error(UVO_INVALID_ARG, "fused iteration: 3-channel device images of one size expected");
-                f.p[i] = f.dev[i].data();
-            }
-            f.w = f.dev[0].cols; f.h = f.dev[0].rows; f.stride = f.w * 3; f.mem = UVO_MEM_DEVICE;
+            take_device(f, ncam);
             return f;
         }
         f.host[0] = stereo ? camera_left_ : camera_img_; if (stereo) f.host[1] = camera_right_;
-        auto pitch = [](const Mat& m) { return m.rows > 1 ? (int)(m.ptr<unsigned char>(1) - m.ptr<unsigned char>(0)) : m.cols * 3; };     // rows may be padded in a real cv::Mat
+        auto channels_of = [](const Mat& m) { return m.type() == uvocv::CV_8UC3 ? 3 : m.type() == uvocv::CV_8UC4 ? 4 : m.type() == uvocv::CV_8UC1 ? 1 : 0; };
+        f.fmt = f.host[0].empty() ? -1 : layout_of(channels_of(f.host[0]));
+        const int bpp = bytes_per_pixel(f.fmt);
+        auto pitch = [bpp](const Mat& m) { return m.rows > 1 ? (int)(m.ptr<unsigned char>(1) - m.ptr<unsigned char>(0)) : m.cols * bpp; };     // rows may be padded in a real cv::Mat
         for (int i = 0; i < ncam; i++)
-            if (f.host[i].empty() || f.host[i].type() != uvocv::CV_8UC3 || f.host[i].cols != f.host[0].cols || f.host[i].rows != f.host[0].rows)
-                throw Error(UVO_INVALID_ARG, "fused iteration: CV_8UC3 images of one size expected");
+            if (f.fmt < 0 || f.host[i].empty() || f.host[i].type() != f.host[0].type() || f.host[i].cols != f.host[0].cols || f.host[i].rows != f.host[0].rows)
+                throw Error(UVO_INVALID_ARG, "fused iteration: CV_8UC3 or CV_8UC4 images (CV_8UC1 mosaics under set_pixel_format) of one size and type expected");
         if (stereo && pitch(f.host[0]) != pitch(f.host[1])) { f.host[0] = f.host[0].clone(); f.host[1] = f.host[1].clone(); }       // the entry takes one pitch for the pair: clone() packs the rows
         for (int i = 0; i < ncam; i++) f.p[i] = f.host[i].ptr<unsigned char>(0);
         f.w = f.host[0].cols; f.h = f.host[0].rows; f.stride = pitch(f.host[0]); f.mem = UVO_MEM_HOST;
         return f;
+    }
+
+    // the frame's device images, as the frames entries take them: one size, one layout
+    void take_device(Frame& f, int ncam) const
+    {
+        f.fmt = f.dev[0].empty() ? -1 : layout_of(f.dev[0].channels);
+        for (int i = 0; i < ncam; i++) {
+            if (f.fmt < 0 || f.dev[i].empty() || f.dev[i].channels != f.dev[0].channels || f.dev[i].cols != f.dev[0].cols || f.dev[i].rows != f.dev[0].rows)
+                throw Error(UVO_INVALID_ARG, "fused iteration: 3- or 4-channel device images (1-channel mosaics under set_pixel_format) of one size and layout expected");
+            f.p[i] = f.dev[i].data();
+        }
+        f.w = f.dev[0].cols; f.h = f.dev[0].rows; f.stride = f.w * bytes_per_pixel(f.fmt); f.mem = UVO_MEM_DEVICE;
     }
 
     // A frame into its loop entry: `frames` for pixels; for compressed messages `compressed`, and when that entry refuses the payload
@@ -382,18 +424,14 @@ private:
     template <class Compressed, class Frames>
     void enter(Frame& f, Compressed&& compressed, Frames&& frames)
     {
-        if (f.msg[0].data.empty()) { frames(); return; }
+        if (f.msg[0].data.empty()) { cameras_read(f.fmt); frames(); return; }
         try { compressed(); return; }
         catch (const Error& e) { if (e.status != UVO_INVALID_ARG || std::string(e.what()).find("compressed entry:") == std::string::npos) throw; }
         const int ncam = mode_ == "stereo" ? 2 : 1;
-        for (int i = 0; i < ncam; i++) {
-            f.dev[i] = decode_compressed_image_device(f.msg[i].data.data(), f.msg[i].data.size(), f.msg[i].format);
-            if (f.dev[i].empty() || f.dev[i].channels != 3 || f.dev[i].cols != f.dev[0].cols || f.dev[i].rows != f.dev[0].rows)
-                throw Error(UVO_INVALID_ARG, "fused iteration: 3-channel device images of one size expected");
-            f.p[i] = f.dev[i].data();
-        }
-        f.w = f.dev[0].cols; f.h = f.dev[0].rows; f.stride = f.w * 3; f.mem = UVO_MEM_DEVICE;
+        for (int i = 0; i < ncam; i++) f.dev[i] = decode_compressed_image_device(f.msg[i].data.data(), f.msg[i].data.size(), f.msg[i].format);
+        take_device(f, ncam);                                            // an RGBA PNG decodes to four channels: BGRA8
         compressed_fallbacks_++;
+        cameras_read(f.fmt);
         frames();
     }
     // the size of a compressed message's picture, from its headers
@@ -432,6 +470,7 @@ private:
             loop_set_mono_camera(new_camera_matrix_);
         }
         loop_reset(stereo);                                              // the shared context may hold an earlier node's sequence
+        ctx_format_ = -1; cameras_read(UVO_PIX_BGR8);                    // ... and its cameras' layout
         loop_set_detector();
         cameras_ready_ = true;
     }
