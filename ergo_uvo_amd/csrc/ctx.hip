@@ -658,16 +658,25 @@ static uvo_status read_counts(uvo_ctx* c)
     return UVO_OK;
 }
 
+// what a counts mirror of nimg detected images refuses, as (status, message); UVO_OK when nothing
+static uvo_status count_refusal(const uvo_ctx* c, const int* counts, int nimg, const char** why)
+{
+    *why = nullptr;
+    if (counts[CN_ORI_DROP] != 0) {
+        *why = "SURF orientation: a keypoint had no gradient sample inside the image; OpenCV drops such keypoints, which this build does not do";
+        return UVO_INVALID_ARG;
+    }
+    for (int i = 0; i < nimg; i++)
+        if (counts[CN_CAND0 + i] == kCandListOverflow && c->loop_detector() == 2) { *why = kAkazeCandOverflow; return UVO_CAPACITY; }
+    for (int i = 0; i < nimg; i++)
+        if (counts[CN_CAND0 + i] > c->cap) { *why = "SURF found more keypoints than the context's max_kpts; results would be order-dependent"; return UVO_CAPACITY; }
+    return UVO_OK;
+}
 static uvo_status check_cand_overflow(uvo_ctx* c, int nimg)
 {
-    if (c->h_counts[CN_ORI_DROP] != 0)
-        return fail(c, UVO_INVALID_ARG, "SURF orientation: a keypoint had no gradient sample inside the image; OpenCV drops such keypoints, which this build does not do");
-    for (int i = 0; i < nimg; i++)
-        if (c->h_counts[CN_CAND0 + i] == kCandListOverflow && c->loop_detector() == 2) return fail(c, UVO_CAPACITY, kAkazeCandOverflow);
-    for (int i = 0; i < nimg; i++)
-        if (c->h_counts[CN_CAND0 + i] > c->cap)
-            return fail(c, UVO_CAPACITY, "SURF found more keypoints than the context's max_kpts; results would be order-dependent");
-    return UVO_OK;
+    const char* why = nullptr;
+    const uvo_status st = count_refusal(c, c->h_counts, nimg, &why);
+    return st == UVO_OK ? UVO_OK : fail(c, st, why);
 }
 
 // detect_features' AKAZE / ORB branch (VOU:93-105) inside the fused steps: each image through the lane's detector in turn (their host stages
@@ -2118,40 +2127,62 @@ static const char* bad_outlier_methods(const uvo_params& p)
     if (const char* why = mono_essential_method_refusal(p.ESSENTIAL_OUTLIER_METHOD)) return why;
     return mono_homography_method_refusal(p.HOMOGRAPHY_OUTLIER_METHOD);
 }
-// estimate_relative_pose (VOU:134-180) on host points through the device-resident chains (pose stage 1): the points are staged once
-// (mono_stage_points: what k_mono_prep leaves behind a frame's stage A), then each attempt is the chain the loop's stage B runs
-static uvo_status estimate_relative_pose_resident(uvo_ctx* c, const uvo_point2f* k1, const uvo_point2f* k2, int n, const double* K, int* use_essential, double* R, double* t,
-                                                  uvo_point2f* in1, uvo_point2f* in2, int* n_in, uint8_t* mask, int* success, Ctx::MonoPoseStats* ps)
+// Which attempts of estimate_relative_pose take a device-resident chain (mono.hip) and which the host-pointer route (estimate_once):
+//   the loop at pose stage 0      { true,  false }   a first attempt with the essential matrix resident, the rest host-pointer
+//   the loop at pose stage 1      { true,  true  }   everything resident
+//   the operator at pose stage 0  { false, false }   everything host-pointer
+//   the operator at pose stage 1  { false, true  }   everything resident
+struct MonoRoutes { bool essential_first_resident, all_resident; };
+// What the attempts leave behind them.  The last attempt is the accepted one on success.
+struct MonoAttempts {
+    int success = 0, use_essential = 0, n_in = 0;
+    bool resident = false;                       // the last attempt was a chain that ran to its end: triangulation and scale are done (mr), and
+    MonoResident mr;                             // extract_inliers' output is on the device (mono_resident_inliers)
+    uvo_point2f *in1 = nullptr, *in2 = nullptr;  // otherwise extract_inliers' output of the host-pointer attempt, or of the chain that was handed over,
+    std::vector<uvo_point2f> own[2];             // is here: in the caller's arrays, or (in1 null on entry) in `own`, sized when first needed
+    void need_lists(int n) { if (!in1) { own[0].resize(n); own[1].resize(n); in1 = own[0].data(); in2 = own[1].data(); } }
+};
+// estimate_relative_pose's attempts (VOU:134-180) on the lane's n matched points as k_mono_prep / mono_stage_points leave them (d_x1 / d_x2,
+// q1 / q2, and k1 / k2: the pinned mirrors) or, when every route is host-pointer, on any host points k1 / k2.  R, t are in/out as in the
+// reference (kept when no estimator writes them); mask: n bytes.  Either chain reads the device points and the mirrors and leaves their
+// content as it is, so a failed attempt leaves the other method what it needs (mono.hip lists what the chains overwrite).
+static uvo_status estimate_attempts(uvo_ctx* c, const uvo_point2f* k1, const uvo_point2f* k2, int n, const double* K, int use_essential, MonoRoutes routes,
+                                    double* R, double* t, uint8_t* mask, Ctx::MonoPoseStats* ps, MonoAttempts* a)
 {
     const uvo_params& p = c->p;
-    const uvo_point2f *h1 = nullptr, *h2 = nullptr;
-    UVO_TRY(mono_stage_points(c, k1, k2, n, K, &h1, &h2));
-    for (int attempt = 0; attempt < 2 && !*success; attempt++) {
-        MonoResident mr;
+    for (int attempt = 0; attempt < 2 && !a->success; attempt++) {
         int valid_inliers = 0;
-        bool fetch = true;
-        if (*use_essential) {
-            ps->attempts[0]++;
-            UVO_TRY(mono_essential_resident(c, n, K, p.ESSENTIAL_OUTLIER_METHOD, p.ESSENTIAL_CONFIDENCE, p.ESSENTIAL_THRESHOLD, (int)p.ESSENTIAL_MAX_ITERS, &mr));
-            if (mr.ok) { memcpy(R, mr.R, sizeof(double) * 9); memcpy(t, mr.t, sizeof(double) * 3); memcpy(mask, mr.mask, (size_t)n); valid_inliers = mr.valid_inliers; }
-            else memset(mask, 0, (size_t)n);
-        } else {
-            ps->attempts[1]++;
-            UVO_TRY(mono_homography_resident(c, n, K, p.HOMOGRAPHY_OUTLIER_METHOD, p.HOMOGRAPHY_THRESHOLD, (int)p.HOMOGRAPHY_MAX_ITERS, p.HOMOGRAPHY_CONFIDENCE,
-                                             p.HOMOGRAPHY_DISTANCE, &mr));
-            memcpy(mask, mr.mask, (size_t)n);
-            valid_inliers = mr.valid_inliers;
+        const bool resident = routes.all_resident || (routes.essential_first_resident && use_essential && attempt == 0);
+        ps->attempts[(resident ? 0 : 2) + (use_essential ? 0 : 1)]++;
+        a->resident = resident;
+        if (resident) {
+            MonoResident& mr = a->mr;
+            if (use_essential) UVO_TRY(mono_essential_resident(c, n, K, p.ESSENTIAL_OUTLIER_METHOD, p.ESSENTIAL_CONFIDENCE, p.ESSENTIAL_THRESHOLD, (int)p.ESSENTIAL_MAX_ITERS, &mr));
+            else UVO_TRY(mono_homography_resident(c, n, K, p.HOMOGRAPHY_OUTLIER_METHOD, p.HOMOGRAPHY_THRESHOLD, (int)p.HOMOGRAPHY_MAX_ITERS, p.HOMOGRAPHY_CONFIDENCE,
+                                                  p.HOMOGRAPHY_DISTANCE, &mr));
+            a->n_in = mr.n_in;
+            if (mr.ok) { memcpy(mask, mr.mask, (size_t)n); valid_inliers = mr.valid_inliers; }
+            else memset(mask, 0, (size_t)n);                                               // no model (LMedS: too few inliers): the attempt simply fails
             if (mr.pose) { memcpy(R, mr.R, sizeof(double) * 9); memcpy(t, mr.t, sizeof(double) * 3); }
-            if (mr.fallback) { ps->fallbacks++; fetch = false; }
+            if (mr.fallback) {                                                             // the definition's route from here: extract_inliers on the host, the caller's host-pointer pose tail
+                ps->fallbacks++;
+                a->resident = false;
+                a->need_lists(n);
+                a->n_in = extract_inliers(k1, k2, mask, n, a->in1, a->in2);
+            }
+        } else {
+            a->need_lists(n);
+            UVO_TRY(estimate_once(c, k1, k2, n, K, use_essential, R, t, a->in1, a->in2, &a->n_in, mask, &valid_inliers));
         }
-        if (fetch) { *n_in = mr.n_in; UVO_TRY(mono_resident_inliers(c, mr.n_in, in1, in2)); }
-        else *n_in = extract_inliers(h1, h2, mask, n, in1, in2);
-        if (estimate_accepted(p, valid_inliers, n)) *success = 1;
-        else if (attempt == 0) *use_essential = !*use_essential;
+        if (estimate_accepted(p, valid_inliers, n)) a->success = 1;
+        else if (attempt == 0) use_essential = !use_essential;                             // VOU:165-178: the other method, once
     }
+    a->use_essential = use_essential;
     return UVO_OK;
 }
-// estimate_relative_pose (VOU:134-180).  use_essential is the reference's global (in/out); R, t are in/out.
+// estimate_relative_pose (VOU:134-180).  use_essential is the reference's global (in/out); R, t are in/out.  At pose stage 1 the points are
+// staged once (mono_stage_points: what k_mono_prep leaves behind a frame's stage A) and every attempt is the chain the loop's stage B
+// runs; the inliers of the last one are fetched once, after the attempts.
 extern "C" uvo_status uvo_estimate_relative_pose(uvo_ctx* c, const uvo_point2f* k1, const uvo_point2f* k2, int n, const double* K,
                                                  int* use_essential, double* R, double* t, uvo_point2f* in1, uvo_point2f* in2, int* n_in,
                                                  uint8_t* mask, int* success)
@@ -2159,29 +2190,19 @@ try {
     if (!c || !k1 || !k2 || !K || !use_essential || !R || !t || !in1 || !in2 || !n_in || !mask || !success || n <= 0) return UVO_INVALID_ARG;
     (void)hipSetDevice(c->device);
     Range r_erp("uvo:estimate_relative_pose");
-    const uvo_params& p = c->p;
-    if (const char* why = bad_outlier_methods(p)) return fail(c, UVO_INVALID_ARG, why);
-    bool estimate_completed = false, switch_method = false;
+    if (const char* why = bad_outlier_methods(c->p)) return fail(c, UVO_INVALID_ARG, why);
     *success = 0;
     Ctx::MonoPoseStats ps;                                 // uvo_mono_pose_stats after an operator call speaks of that call
     ps.first_method = *use_essential ? 1 : 0;
     const unsigned waits0 = c->stat_waits, uploads0 = c->stat_uploads;
     struct StatsAtExit { uvo_ctx* c; Ctx::MonoPoseStats& ps; unsigned w0, u0; ~StatsAtExit() { ps.host_waits = (int)(c->stat_waits - w0); ps.uploads = (int)(c->stat_uploads - u0); c->mono_pstats = ps; } } stats_at_exit{c, ps, waits0, uploads0};
-    if (c->sh->mono_pose_stage == 1) {
-        *n_in = 0;
-        return estimate_relative_pose_resident(c, k1, k2, n, K, use_essential, R, t, in1, in2, n_in, mask, success, &ps);
-    }
-    while (!estimate_completed) {
-        int valid_inliers = 0;
-        ps.attempts[*use_essential ? 2 : 3]++;
-        UVO_TRY(estimate_once(c, k1, k2, n, K, *use_essential, R, t, in1, in2, n_in, mask, &valid_inliers));
-        if (estimate_accepted(p, valid_inliers, n)) { *success = 1; estimate_completed = true; }
-        else {
-            if (switch_method) break;
-            switch_method = true;
-            *use_essential = !*use_essential;
-        }
-    }
+    const bool all_resident = c->sh->mono_pose_stage == 1;
+    if (all_resident) { *n_in = 0; UVO_TRY(mono_stage_points(c, k1, k2, n, K, &k1, &k2)); }
+    MonoAttempts a;
+    a.in1 = in1; a.in2 = in2;
+    UVO_TRY(estimate_attempts(c, k1, k2, n, K, *use_essential, MonoRoutes{false, all_resident}, R, t, mask, &ps, &a));
+    *use_essential = a.use_essential; *success = a.success; *n_in = a.n_in;
+    if (a.resident) UVO_TRY(mono_resident_inliers(c, a.n_in, in1, in2));
     return UVO_OK;
 } UVO_ABI_CATCH(c)
 
@@ -2249,15 +2270,46 @@ __global__ __launch_bounds__(256) void k_gather_mono_pairs(const uvo_dmatch* __r
     x1[i] = uvo_point2f{a.x, a.y}; x2[i] = uvo_point2f{b.x, b.y};
 }
 
+// The host-pointer pose tail of an accepted attempt (VO:351-357): the n_in compacted inlier pairs uploaded, triangulatePoints +
+// extract_3Dpoints, the good points to the host (L->mono_good_pts; *G of them), and convert_3Dpoints_camera's z list (VOU:46-63) --
+// three uploads and two host waits when there are inliers
+static uvo_status mono_pose_tail_host(uvo_ctx* L, const double* K, const double* R, const double* t, const uvo_point2f* in1, const uvo_point2f* in2, int n_in,
+                                      int* G_out, std::vector<double>* zs)
+{
+    hipStream_t st = L->stream;
+    const double I[9] = {1,0,0,0,1,0,0,0,1}, z[3] = {0,0,0};
+    double P_prev[12], P_curr[12];
+    projection_matrix(I, z, K, P_prev);
+    projection_matrix(R, t, K, P_curr);
+    int G = 0;
+    if (n_in > 0) {
+        UVO_HIP_TRY(L, hipMemcpyAsync(L->d_x1, in1, sizeof(uvo_point2f) * n_in, hipMemcpyHostToDevice, st));
+        UVO_HIP_TRY(L, hipMemcpyAsync(L->d_x2, in2, sizeof(uvo_point2f) * n_in, hipMemcpyHostToDevice, st));
+        UVO_HIP_TRY(L, hipMemcpyAsync(L->d_xc, in2, sizeof(uvo_point2f) * n_in, hipMemcpyHostToDevice, st));
+        L->stat_uploads += 3;
+        UVO_TRY(pose_triangulate_extract3d(L, 0, P_prev, P_curr, I, z, R, t, K, K, nullptr, n_in));                       // VO:355-356
+        UVO_TRY(read_counts(L));
+        G = L->h_counts[CN_G];
+        L->mono_good_pts.resize((size_t)3 * G);
+        if (G) UVO_HIP_TRY(L, hipMemcpyAsync(L->mono_good_pts.data(), L->d_good_pts[0], sizeof(double) * 3 * G, hipMemcpyDeviceToHost, st));
+        UVO_HIP_TRY(L, host_sync(L, st));
+    }
+    L->mono_good_on_host = true;
+    for (int i = 0; i < G; i++) {                                                          // convert_3Dpoints_camera (VOU:46-63)
+        const double* q = &L->mono_good_pts[3 * (size_t)i];
+        double zt = (R[6]*q[0] + R[7]*q[1] + R[8]*q[2]) * 1.0 + t[2] * 1.0;
+        if (zt > 0) zs->push_back(q[2]);
+    }
+    *G_out = G;
+    return UVO_OK;
+}
 // Stage B of one mono frame (VO:276-376 after the matching) on lane L's buffers and stream -- the lane's worker for a pipelined frame,
 // the calling thread for uvo_mono_step: fills job.mres / pose_written / sf_written.  The matched points are on the device (d_x1 / d_x2,
 // mirrored in pinned memory by k_mono_prep together with select_estimation_method's decision).  With the pose stage at 1
 // (uvo_mono_set_pose_stage) every attempt of estimate_relative_pose takes a device-resident chain (mono.hip:
 // mono_essential_resident, two host syncs; mono_homography_resident, three or four; nothing uploaded).  At 0 -- the definition, and the default -- only a
 // first attempt with the essential matrix does; homography-first frames and second attempts (VOU:165-178) take the host-pointer
-// operators on the pinned mirrors.  Either chain reads d_x1 / d_x2, q1 / q2 and the pinned mirrors and leaves their content as it is (the
-// homography chain's single-solution hand-over uploads the mirrors into d_x1 / d_x2 again: the same bytes), so a failed attempt leaves
-// the other method what it needs (mono.hip lists what the chains overwrite).  Keypoints, matches and good points are NOT
+// operators on the pinned mirrors (estimate_attempts).  Keypoints, matches and good points are NOT
 // copied to the host: uvo_mono_get reads them from the lane's buffers when asked.
 static void run_mono_stage_b(uvo_ctx* L, bool stage_a_ok)
 {
@@ -2273,105 +2325,46 @@ static void run_mono_stage_b(uvo_ctx* L, bool stage_a_ok)
     L->mono_dev_n = L->mono_dev_M = L->mono_dev_G = 0; L->mono_good_on_host = false;
     if (!stage_a_ok) { j.st = UVO_HIP_ERROR; j.err = "stage A of the frame failed"; return; }
     Range r_b("uvo:mono estimate_relative_pose + triangulation + scale");
-    auto hip_ok = [&](hipError_t e) { if (e != hipSuccess && j.st == UVO_OK) { j.st = UVO_HIP_ERROR; j.err = hipGetErrorString(e); } return e == hipSuccess; };
+    // the gates on the counts
     const int* hc = L->h_countsA[0];
-    const int cap = L->cap;
-    if (hc[CN_CAND0] == kCandListOverflow && L->loop_detector() == 2) { j.st = UVO_CAPACITY; j.err = kAkazeCandOverflow; return; }
-    if (hc[CN_CAND0] > cap) { j.st = UVO_CAPACITY; j.err = "SURF found more keypoints than the context's max_kpts; results would be order-dependent"; return; }
-    if (hc[CN_ORI_DROP] != 0) { j.st = UVO_INVALID_ARG; j.err = "SURF orientation: a keypoint had no gradient sample inside the image; OpenCV drops such keypoints, which this build does not do"; return; }
+    const char* why = nullptr;
+    if ((j.st = count_refusal(L, hc, 1, &why)) != UVO_OK) { j.err = why; return; }
     const int n = hc[CN_NL], M = L->mono_matched ? hc[CN_M] : 0;
     j.mres.initialized = 1; j.mres.n_kps = n;
     L->mono_dev_n = n;
-    hipStream_t st = L->stream;
     if (n < p.MIN_NUM_FEATURES) return;                                                    // VO:276-284
-    if (M > cap) { j.st = UVO_CAPACITY; j.err = "match count exceeds max_kpts"; return; }
+    if (M > L->cap) { j.st = UVO_CAPACITY; j.err = "match count exceeds max_kpts"; return; }
     j.mres.n_matches = M; L->mono_dev_M = M;
     if (M < p.MIN_NUM_FEATURES) return;                                                    // VO:299-307
-    if (const char* why = bad_outlier_methods(p)) { j.st = UVO_INVALID_ARG; j.err = why; return; }
+    if (const char* bad = bad_outlier_methods(p)) { j.st = UVO_INVALID_ARG; j.err = bad; return; }
     const uvo_point2f *k1 = nullptr, *k2 = nullptr;
-    int use_essential = mono_prep_method(L, M, &k1, &k2);                                  // VO:310-317 (select_estimation_method, on the device)
-    if (use_essential < 0) { j.st = UVO_HIP_ERROR; j.err = "mono pose stage: select_estimation_method's kernel did not report"; return; }
+    const int first_method = mono_prep_method(L, M, &k1, &k2);                             // VO:310-317 (select_estimation_method, on the device)
+    if (first_method < 0) { j.st = UVO_HIP_ERROR; j.err = "mono pose stage: select_estimation_method's kernel did not report"; return; }
     L->mono_mask.assign(M, 0);
-    j.pstats.first_method = use_essential;
-    const bool all_resident = L->sh->mono_pose_stage == 1;
-    // R, t are in/out in the reference (kept when no estimator writes them): run on a sentinel and report whether they were written
+    j.pstats.first_method = first_method;
+    // estimate_relative_pose.  R, t are in/out in the reference (kept when no estimator writes them): run on a sentinel and report whether they were written
     double R[9], t[3];
     const double kSentinel = -7.0e300;
     for (int i = 0; i < 9; i++) R[i] = kSentinel;
     for (int i = 0; i < 3; i++) t[i] = kSentinel;
-    int n_in = 0, success = 0;
-    bool resident = false;                       // the accepted estimate came from the device-resident chain: triangulation and scale are done
-    MonoResident mr;
-    std::vector<uvo_point2f> in1, in2;           // extract_inliers' output of a host-pointer attempt
-    for (int attempt = 0; attempt < 2 && !success; attempt++) {                            // estimate_relative_pose (VOU:134-180)
-        int valid_inliers = 0;
-        if (use_essential && (attempt == 0 || all_resident)) {
-            j.pstats.attempts[0]++;
-            j.st = mono_essential_resident(L, M, K, p.ESSENTIAL_OUTLIER_METHOD, p.ESSENTIAL_CONFIDENCE, p.ESSENTIAL_THRESHOLD, (int)p.ESSENTIAL_MAX_ITERS, &mr);
-            if (j.st != UVO_OK) { j.err = L->err; return; }
-            n_in = mr.n_in;
-            if (mr.ok) { memcpy(R, mr.R, sizeof(R)); memcpy(t, mr.t, sizeof(t)); memcpy(L->mono_mask.data(), mr.mask, (size_t)M); valid_inliers = mr.valid_inliers; }
-            else memset(L->mono_mask.data(), 0, (size_t)M);
-            resident = true;
-        } else if (!use_essential && all_resident) {
-            j.pstats.attempts[1]++;
-            j.st = mono_homography_resident(L, M, K, p.HOMOGRAPHY_OUTLIER_METHOD, p.HOMOGRAPHY_THRESHOLD, (int)p.HOMOGRAPHY_MAX_ITERS, p.HOMOGRAPHY_CONFIDENCE,
-                                            p.HOMOGRAPHY_DISTANCE, &mr);
-            if (j.st != UVO_OK) { j.err = L->err; return; }
-            n_in = mr.n_in; valid_inliers = mr.valid_inliers;
-            memcpy(L->mono_mask.data(), mr.mask, (size_t)M);                               // (zeros when findHomography produced nothing)
-            if (mr.pose) { memcpy(R, mr.R, sizeof(R)); memcpy(t, mr.t, sizeof(t)); }
-            resident = !mr.fallback;
-            if (mr.fallback) {                                                             // the definition's route from here: extract_inliers on the host, its pose tail below
-                j.pstats.fallbacks++;
-                in1.resize(M); in2.resize(M);
-                n_in = extract_inliers(k1, k2, L->mono_mask.data(), M, in1.data(), in2.data());
-            }
-        } else {
-            j.pstats.attempts[use_essential ? 2 : 3]++;
-            in1.resize(M); in2.resize(M);
-            j.st = estimate_once(L, k1, k2, M, K, use_essential, R, t, in1.data(), in2.data(), &n_in, L->mono_mask.data(), &valid_inliers);
-            if (j.st != UVO_OK) { j.err = L->err; return; }
-            resident = false;
-        }
-        if (estimate_accepted(p, valid_inliers, M)) success = 1;
-        else if (attempt == 0) use_essential = !use_essential;                             // VOU:165-178: the other method, once
-    }
+    MonoAttempts a;
+    j.st = estimate_attempts(L, k1, k2, M, K, first_method, MonoRoutes{true, L->sh->mono_pose_stage == 1}, R, t, L->mono_mask.data(), &j.pstats, &a);
+    if (j.st != UVO_OK) { j.err = L->err; return; }
     j.pose_written = R[0] != kSentinel;
     if (j.pose_written) { memcpy(j.R, R, sizeof(R)); memcpy(j.t, t, sizeof(t)); }
-    j.mres.success = success; j.mres.used_essential = use_essential; j.mres.n_inliers = n_in;
+    j.mres.success = a.success; j.mres.used_essential = a.use_essential; j.mres.n_inliers = a.n_in;
     j.mres.published = 1;
-    int valid = success ? 1 : 0;                                                           // VO:335-344
-    if (success) {                                                                         // VO:351-376 (success implies the pose was written)
+    int valid = a.success ? 1 : 0;                                                         // VO:335-344
+    if (a.success) {                                                                       // VO:351-376 (success implies the pose was written)
         int G = 0, n_front = 0;
         std::vector<double> zs;
-        if (resident) {                                                                    // triangulated, filtered and projected on the device already
-            G = mr.G; n_front = mr.n_front;
+        if (a.resident) {                                                                  // triangulated, filtered and projected on the device already
+            G = a.mr.G; n_front = a.mr.n_front;
             L->mono_dev_G = G;
-            zs.assign(mr.zs, mr.zs + n_front);
+            zs.assign(a.mr.zs, a.mr.zs + n_front);
         } else {
-            const double I[9] = {1,0,0,0,1,0,0,0,1}, z[3] = {0,0,0};
-            double P_prev[12], P_curr[12];
-            projection_matrix(I, z, K, P_prev);
-            projection_matrix(R, t, K, P_curr);
-            if (n_in > 0) {
-                if (!hip_ok(hipMemcpyAsync(L->d_x1, in1.data(), sizeof(uvo_point2f) * n_in, hipMemcpyHostToDevice, st))) return;
-                if (!hip_ok(hipMemcpyAsync(L->d_x2, in2.data(), sizeof(uvo_point2f) * n_in, hipMemcpyHostToDevice, st))) return;
-                if (!hip_ok(hipMemcpyAsync(L->d_xc, in2.data(), sizeof(uvo_point2f) * n_in, hipMemcpyHostToDevice, st))) return;
-                L->stat_uploads += 3;
-                if ((j.st = pose_triangulate_extract3d(L, 0, P_prev, P_curr, I, z, R, t, K, K, nullptr, n_in)) != UVO_OK) { j.err = L->err; return; }   // VO:355-356
-                if ((j.st = read_counts(L)) != UVO_OK) { j.err = L->err; return; }
-                G = L->h_counts[CN_G];
-                L->mono_good_pts.resize((size_t)3 * G);
-                if (G && !hip_ok(hipMemcpyAsync(L->mono_good_pts.data(), L->d_good_pts[0], sizeof(double) * 3 * G, hipMemcpyDeviceToHost, st))) return;
-                if (!hip_ok(host_sync(L, st))) return;
-            }
-            L->mono_good_on_host = true;
-            for (int i = 0; i < G; i++) {                                                  // convert_3Dpoints_camera (VOU:46-63)
-                const double* q = &L->mono_good_pts[3 * (size_t)i];
-                double zt = (R[6]*q[0] + R[7]*q[1] + R[8]*q[2]) * 1.0 + t[2] * 1.0;
-                if (zt > 0) zs.push_back(q[2]);
-            }
+            j.st = mono_pose_tail_host(L, K, R, t, a.in1, a.in2, a.n_in, &G, &zs);
+            if (j.st != UVO_OK) { j.err = L->err; return; }
             n_front = (int)zs.size();
         }
         j.mres.n_good3d = G;

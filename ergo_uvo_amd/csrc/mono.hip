@@ -743,10 +743,10 @@ struct Pinned {
 struct MonoWs {                       // device workspace of the mono stage, owned by the context
     double *q1 = nullptr, *q2 = nullptr;           // normalised points (cap x 2)
     float *src = nullptr, *dst = nullptr;          // pixel points (cap x 2)
-    int* subsets = nullptr;                        // kMaxHyp x 5
+    int* subsets = nullptr;                        // kMaxHyp x 5 (the model hooks' subsets; the estimators' kernels read h_subsets)
     double* models = nullptr;                      // kMaxHyp x 10 x 9
     int* nmodels = nullptr;                        // kMaxHyp
-    int* counts = nullptr;  double* medians = nullptr;   // kMaxHyp x 10
+    int* counts = nullptr;                         // kMaxHyp x 10 (uvo_solve_poly10's path counts; the estimators' scores go to h_counts / h_medians)
     uint8_t* masks = nullptr;                      // 5 x cap
     int* good = nullptr;                           // 4
     double* best = nullptr;                        // 9
@@ -781,7 +781,6 @@ static MonoWs* mono_ws(Ctx* c)
               hipMalloc((void**)&w->models, sizeof(double) * kMaxHyp * 90) == hipSuccess &&
               hipMalloc((void**)&w->nmodels, sizeof(int) * kMaxHyp) == hipSuccess &&
               hipMalloc((void**)&w->counts, sizeof(int) * kMaxHyp * 10) == hipSuccess &&
-              hipMalloc((void**)&w->medians, sizeof(double) * kMaxHyp * 10) == hipSuccess &&
               hipMalloc((void**)&w->masks, 5 * cap) == hipSuccess && hipMalloc((void**)&w->good, sizeof(int) * 4) == hipSuccess &&
               hipMalloc((void**)&w->best, sizeof(double) * 9) == hipSuccess &&
               hipMalloc((void**)&w->in1, sizeof(uvo_point2f) * cap) == hipSuccess && hipMalloc((void**)&w->in2, sizeof(uvo_point2f) * cap) == hipSuccess &&
@@ -800,7 +799,7 @@ void mono_ws_free(Ctx* c)
 {
     MonoWs* w = static_cast<MonoWs*>(c->mono_ws);
     if (!w) return;
-    void* ptrs[] = { w->q1, w->q2, w->src, w->dst, w->subsets, w->models, w->nmodels, w->counts, w->medians, w->masks, w->good, w->best, w->in1, w->in2, w->pick, w->zrows };
+    void* ptrs[] = { w->q1, w->q2, w->src, w->dst, w->subsets, w->models, w->nmodels, w->counts, w->masks, w->good, w->best, w->in1, w->in2, w->pick, w->zrows };
     for (void* p : ptrs) (void)hipFree(p);
     w->h_subsets.release(); w->h_nmodels.release(); w->h_counts.release(); w->h_medians.release(); w->h_models.release();
     w->h_q1.release(); w->h_q2.release(); w->h_src.release(); w->h_dst.release(); w->h_mask.release(); w->h_good.release();
@@ -927,6 +926,120 @@ static Winner replay_lmeds(const int* nmodels, const double* medians, int stride
     return w;
 }
 
+// findEssentialMat's normalisation of a pixel point, (p - c) / f in double, as p * a + b per axis
+struct KNorm { double ax, bx, ay, by; };
+static KNorm k_norm(const double* K)
+{
+    const double fx = K[0], fy = K[4], cx = K[2], cy = K[5];
+    const double ax = 1. / fx, bx = -cx * ax, ay = 1. / fy, by = -cy * ay;
+    return KNorm{ ax, bx, ay, by };
+}
+
+// The threshold of the winner's mask: RANSAC keeps the caller's; LMedS derives it from the winning median (sigma rule of
+// LMeDSPointSetRegistrator::run)
+static double final_threshold(bool lmeds, double thr, int n, int modelPoints, double min_median)
+{
+    if (!lmeds) return thr;
+    const double sigma = 2.5 * 1.4826 * (1 + 5. / (n - modelPoints)) * sqrt(min_median);
+    return sigma > 0.001 ? sigma : 0.001;
+}
+
+// ---- the hypothesis search of the robust estimators (RANSACPointSetRegistrator::run / LMeDSPointSetRegistrator::run) ----
+// What the search has to know about an estimator.  There are two: findEssentialMat and findHomography.
+struct Estimator {
+    int modelPoints;                               // 5 (five-point) / 4
+    int stride;                                    // models per hypothesis: 10 / 1, nine doubles each
+    const float *h1, *h2;                          // homography: the pinned float pairs the sampler's checkSubset reads; essential: null, it has no check
+    const float *d1, *d2;                          // homography: the same pairs on the device; essential: null, its kernels read the workspace's q1 / q2
+};
+struct Search { Winner win; double final_thr = 0; int nsub = 0; };     // win.hyp < 0: no model
+
+__global__ __launch_bounds__(256) void k_mirror_words(const int* __restrict__ src, int* __restrict__ dst, int n);
+// One round: hypotheses [from, from + cnt) solved and scored, then ONE host wait.  The kernels read the subsets from pinned memory and
+// write counts / medians / model counts to it (k_mirror_words where a kernel has no such output); the essential models are mirrored as
+// well, for decomposeEssentialMat on the host.
+static uvo_status search_round(Ctx* c, MonoWs* w, const Estimator& est, int n, bool lmeds, float thr2, int from, int cnt)
+{
+    hipStream_t st = c->stream;
+    const int npow2 = next_pow2(n);
+    const size_t lds = lmeds ? sizeof(float) * npow2 : 0;
+    const int* subsets = w->h_subsets.data() + (size_t)est.modelPoints * from;
+    double* models = w->models + (size_t)9 * est.stride * from;
+    int* counts = w->h_counts.data() + (size_t)est.stride * from; double* medians = w->h_medians.data() + (size_t)est.stride * from;
+    if (est.stride == 10) {
+        hipLaunchKernelGGL(k_fivepoint_hyp, dim3((cnt + kFpPerWg - 1) / kFpPerWg), dim3(64), 0, st, w->q1, w->q2, subsets, cnt, models, w->nmodels + from);
+        if (n != est.modelPoints)
+            hipLaunchKernelGGL(k_e_score, dim3(10, cnt), dim3(256), lds, st, w->q1, w->q2, n, models, w->nmodels + from, lmeds ? 1 : 0, thr2, npow2, counts, medians,
+                               w->h_nmodels.data() + from);
+        else hipLaunchKernelGGL(k_mirror_words, dim3(1), dim3(256), 0, st, w->nmodels, w->h_nmodels.data(), 1);      // exactly five points: nothing to score
+        hipLaunchKernelGGL(k_mirror_words, dim3(std::min(64, (cnt * 180 + 255) / 256)), dim3(256), 0, st, reinterpret_cast<const int*>(models),
+                           reinterpret_cast<int*>(w->h_models.data() + (size_t)90 * from), cnt * 180);
+    } else {
+        hipLaunchKernelGGL(k_h_hyp, dim3((cnt + kHPerWg - 1) / kHPerWg), dim3(64), 0, st, est.d1, est.d2, subsets, cnt, models, w->nmodels + from);
+        hipLaunchKernelGGL(k_h_score, dim3(cnt), dim3(256), lds, st, est.d1, est.d2, n, models, w->nmodels + from, lmeds ? 1 : 0, thr2, npow2, counts, medians);
+        hipLaunchKernelGGL(k_mirror_words, dim3(std::min(64, (cnt + 255) / 256)), dim3(256), 0, st, w->nmodels + from, w->h_nmodels.data() + from, cnt);
+    }
+    UVO_HIP_TRY(c, hipGetLastError());
+    UVO_HIP_TRY(c, host_sync(c, st));
+    return UVO_OK;
+}
+// The search on the n points the caller has put where the estimator's kernels read them (`thr` in the estimator's units): the iteration
+// count, the subsets by the cv::RNG replay, the hypotheses solved and scored on the device, the sequential scan replayed on the host.
+// Leaves every model on the device (w->models; essential: mirrored in h_models) and returns the winner, the threshold of its mask and
+// the number of subsets.  n == modelPoints: the one model of the points themselves, every point an inlier (run(), count == modelPoints).
+static uvo_status hypothesis_search(Ctx* c, MonoWs* w, const Estimator& est, int n, bool lmeds, double confidence, double thr, int maxIters, Search* out)
+{
+    *out = Search();
+    const int modelPoints = est.modelPoints, stride = est.stride;
+    const bool essential = stride == 10, exact = n == modelPoints;
+    int niters;
+    if (exact) niters = 1;
+    else if (lmeds) { niters = ransac_update_num_iters(confidence, 0.45, modelPoints, maxIters); niters = niters > 3 ? niters : 3; }
+    else niters = maxIters > 1 ? maxIters : 1;
+    if (niters > kMaxHyp) { c->err = "max_iters exceeds the compiled hypothesis capacity (2048)"; return UVO_CAPACITY; }
+    if (lmeds && !exact) UVO_TRY(lmeds_capacity(c, w, n));
+    bool failed_first = false;
+    int nsub = 1;
+    if (exact) for (int i = 0; i < modelPoints; i++) w->h_subsets[i] = i;
+    else nsub = make_subsets(w->h_subsets.data(), niters, modelPoints, n, lmeds ? 1000 : 10000, est.h1, est.h2, &failed_first);
+    out->nsub = nsub;
+    if (nsub <= 0) return UVO_OK;
+    // RANSAC hypotheses are solved and scored in rounds: the first kFirstRound subsets, then -- only if the adaptive iteration count
+    // still reaches past them after the replayed scan -- the rest.  The scan visits the same counts in the same order either
+    // way.  (A five-point solve keeps a SIMD busy for 0.85 ms whether 32 or 500 waves run, so the first round's latency is the
+    // same, but it leaves the chip to the other frames of a pipeline and scores 16x fewer models.)  LMedS needs all of them.
+    // The homography remembers what its last scan needed: at the shipped 0.1-px threshold the scan of a low-inlier frame never settles
+    // inside the first round, and the second launch costs the frame another 0.35 ms and a synchronisation, so the next call solves
+    // everything in one launch (h_one_round; the scan's result is the same either way).
+    const int kFirstRound = 128;
+    const int first = (!lmeds && !exact && nsub > kFirstRound && !(!essential && w->h_one_round)) ? kFirstRound : nsub;
+    const float thr2 = (float)(thr * thr);
+    UVO_TRY(search_round(c, w, est, n, lmeds, thr2, 0, first));
+    if (essential && getenv("UVO_DBG_PHASE")) {
+        long long clk[8];
+        UVO_HIP_TRY(c, hipMemcpyFromSymbol(clk, HIP_SYMBOL(g_fp_clk), sizeof(clk)));
+        fprintf(stderr, "[uvo] five-point phases (us): svd %.1f polys %.1f lu %.1f detB %.1f roots %.1f solveZ %.1f | nsub %d\n",
+                (clk[1]-clk[0])*0.01, (clk[2]-clk[1])*0.01, (clk[3]-clk[2])*0.01, (clk[4]-clk[3])*0.01, (clk[5]-clk[4])*0.01,
+                (clk[6]-clk[5])*0.01, nsub);
+    }
+    if (exact) {
+        if (w->h_nmodels[0] > 0) { out->win.hyp = 0; out->win.model = 0; out->final_thr = DBL_MAX; }
+        return UVO_OK;
+    }
+    if (lmeds) out->win = replay_lmeds(w->h_nmodels.data(), w->h_medians.data(), stride, nsub);
+    else
+        for (int have = first; ; have = nsub) {                   // the scan over what is scored; once more, over everything, when it goes on past that
+            int settled = niters;
+            out->win = replay_ransac(w->h_nmodels.data(), w->h_counts.data(), stride, have, niters, n, modelPoints, confidence, &settled);
+            if (have == first && !essential && nsub > kFirstRound) w->h_one_round = settled > kFirstRound;
+            if (have == nsub || settled <= have) break;
+            UVO_TRY(search_round(c, w, est, n, lmeds, thr2, have, nsub - have));
+        }
+    if (out->win.hyp >= 0) out->final_thr = final_threshold(lmeds, thr, n, modelPoints, out->win.min_median);
+    return UVO_OK;
+}
+static const Estimator kEssential = { 5, 10, nullptr, nullptr, nullptr, nullptr };
+
 // cv::findEssentialMat on host points (VOU:147)
 uvo_status mono_find_essential(Ctx* c, const uvo_point2f* p1, const uvo_point2f* p2, int n, const double* K, int method,
                                double prob, double threshold, int maxIters, double* E, uint8_t* mask, int* ok)
@@ -938,96 +1051,30 @@ uvo_status mono_find_essential(Ctx* c, const uvo_point2f* p1, const uvo_point2f*
     if (!w) { c->err = "mono workspace allocation failed"; return UVO_HIP_ERROR; }
     const int modelPoints = 5;
     if (n < modelPoints) return UVO_OK;
-    const double fx = K[0], fy = K[4], cx = K[2], cy = K[5];
-    const double ax = 1. / fx, bx = -cx * ax, ay = 1. / fy, by = -cy * ay;
+    const KNorm kn = k_norm(K);
     Pinned<double>& q1 = w->h_q1; Pinned<double>& q2 = w->h_q2;
     for (int i = 0; i < n; i++) {
-        q1[2*i] = p1[i].x * ax + bx; q1[2*i+1] = p1[i].y * ay + by;
-        q2[2*i] = p2[i].x * ax + bx; q2[2*i+1] = p2[i].y * ay + by;
+        q1[2*i] = p1[i].x * kn.ax + kn.bx; q1[2*i+1] = p1[i].y * kn.ay + kn.by;
+        q2[2*i] = p2[i].x * kn.ax + kn.bx; q2[2*i+1] = p2[i].y * kn.ay + kn.by;
     }
-    threshold /= (fx + fy) / 2;
+    threshold /= (K[0] + K[4]) / 2;
     hipStream_t st = c->stream;
     UVO_HIP_TRY(c, hipMemcpyAsync(w->q1, q1.data(), sizeof(double) * 2 * n, hipMemcpyHostToDevice, st));
     UVO_HIP_TRY(c, hipMemcpyAsync(w->q2, q2.data(), sizeof(double) * 2 * n, hipMemcpyHostToDevice, st));
     c->stat_uploads += 2;
     const bool lmeds = method != 8;
-    int niters;
-    if (n == modelPoints) niters = 1;
-    else if (lmeds) { niters = ransac_update_num_iters(prob, 0.45, modelPoints, maxIters); niters = niters > 3 ? niters : 3; }
-    else niters = maxIters > 1 ? maxIters : 1;
-    if (niters > kMaxHyp) { c->err = "max_iters exceeds the compiled hypothesis capacity (2048)"; return UVO_CAPACITY; }
-    if (lmeds && n != modelPoints) UVO_TRY(lmeds_capacity(c, w, n));
-    bool failed_first = false;
-    int nsub;
-    if (n == modelPoints) { for (int i = 0; i < 5; i++) w->h_subsets[i] = i; nsub = 1; }
-    else nsub = make_subsets(w->h_subsets.data(), niters, modelPoints, n, lmeds ? 1000 : 10000, nullptr, nullptr, &failed_first);
-    UVO_HIP_TRY(c, hipMemcpyAsync(w->subsets, w->h_subsets.data(), sizeof(int) * 5 * nsub, hipMemcpyHostToDevice, st));
-    // RANSAC hypotheses are solved and scored in rounds: the first kFirstRound subsets, then -- only if the adaptive iteration count
-    // still reaches past them after the replayed scan -- the rest.  The scan visits the same counts in the same order either
-    // way.  (A five-point solve keeps a SIMD busy for 0.85 ms whether 32 or 500 waves run, so the first round's latency is the
-    // same, but it leaves the chip to the other frames of a pipeline and scores 16x fewer models.)  LMedS needs all of them.
-    const int kFirstRound = 128;
-    const int first = (!lmeds && n != modelPoints && nsub > kFirstRound) ? kFirstRound : nsub;
-    hipLaunchKernelGGL(k_fivepoint_hyp, dim3((first + kFpPerWg - 1) / kFpPerWg), dim3(64), 0, st, w->q1, w->q2, w->subsets, first, w->models, w->nmodels);
-    UVO_HIP_TRY(c, hipGetLastError());
-    if (getenv("UVO_DBG_PHASE")) {
-        long long clk[8];
-        UVO_HIP_TRY(c, host_sync(c, st));
-        UVO_HIP_TRY(c, hipMemcpyFromSymbol(clk, HIP_SYMBOL(g_fp_clk), sizeof(clk)));
-        fprintf(stderr, "[uvo] five-point phases (us): svd %.1f polys %.1f lu %.1f detB %.1f roots %.1f solveZ %.1f | nsub %d\n",
-                (clk[1]-clk[0])*0.01, (clk[2]-clk[1])*0.01, (clk[3]-clk[2])*0.01, (clk[4]-clk[3])*0.01, (clk[5]-clk[4])*0.01,
-                (clk[6]-clk[5])*0.01, nsub);
-    }
-    if (n == modelPoints) {
-        UVO_HIP_TRY(c, hipMemcpyAsync(w->h_nmodels.data(), w->nmodels, sizeof(int), hipMemcpyDeviceToHost, st));
-        UVO_HIP_TRY(c, hipMemcpyAsync(w->h_models.data(), w->models, sizeof(double) * 9, hipMemcpyDeviceToHost, st));
-        UVO_HIP_TRY(c, host_sync(c, st));
-        memcpy(E, w->h_models.data(), sizeof(double) * 9);
-        if (w->h_nmodels[0] <= 0) return UVO_OK;
-        memset(mask, 1, n); *ok = 1;
-        return UVO_OK;
-    }
-    const int npow2 = next_pow2(n);
-    const float thr2 = (float)(threshold * threshold);
-    hipLaunchKernelGGL(k_e_score, dim3(10, first), dim3(256), lmeds ? sizeof(float) * npow2 : 0, st, w->q1, w->q2, n, w->models, w->nmodels,
-                       lmeds ? 1 : 0, thr2, npow2, w->counts, w->medians);
-    UVO_HIP_TRY(c, hipGetLastError());
-    UVO_HIP_TRY(c, hipMemcpyAsync(w->h_nmodels.data(), w->nmodels, sizeof(int) * first, hipMemcpyDeviceToHost, st));
-    if (lmeds) UVO_HIP_TRY(c, hipMemcpyAsync(w->h_medians.data(), w->medians, sizeof(double) * 10 * first, hipMemcpyDeviceToHost, st));
-    else UVO_HIP_TRY(c, hipMemcpyAsync(w->h_counts.data(), w->counts, sizeof(int) * 10 * first, hipMemcpyDeviceToHost, st));
-    UVO_HIP_TRY(c, host_sync(c, st));
-    Winner win;
-    if (lmeds) win = replay_lmeds(w->h_nmodels.data(), w->h_medians.data(), 10, nsub);
-    else {
-        int settled = niters;
-        win = replay_ransac(w->h_nmodels.data(), w->h_counts.data(), 10, first, niters, n, modelPoints, prob, &settled);
-        if (first < nsub && settled > first) {                 // the scan goes on past the first round: solve and score the rest, rescan
-            const int rest = nsub - first;
-            hipLaunchKernelGGL(k_fivepoint_hyp, dim3((rest + kFpPerWg - 1) / kFpPerWg), dim3(64), 0, st, w->q1, w->q2, w->subsets + (size_t)5 * first, rest,
-                               w->models + (size_t)90 * first, w->nmodels + first);
-            hipLaunchKernelGGL(k_e_score, dim3(10, rest), dim3(256), 0, st, w->q1, w->q2, n, w->models + (size_t)90 * first, w->nmodels + first,
-                               0, thr2, npow2, w->counts + (size_t)10 * first, w->medians + (size_t)10 * first);
-            UVO_HIP_TRY(c, hipGetLastError());
-            UVO_HIP_TRY(c, hipMemcpyAsync(w->h_nmodels.data() + first, w->nmodels + first, sizeof(int) * rest, hipMemcpyDeviceToHost, st));
-            UVO_HIP_TRY(c, hipMemcpyAsync(w->h_counts.data() + (size_t)10 * first, w->counts + (size_t)10 * first, sizeof(int) * 10 * rest, hipMemcpyDeviceToHost, st));
-            UVO_HIP_TRY(c, host_sync(c, st));
-            win = replay_ransac(w->h_nmodels.data(), w->h_counts.data(), 10, nsub, niters, n, modelPoints, prob);
-        }
-    }
-    if (win.hyp < 0) return UVO_OK;
-    double final_thr = threshold;
-    if (lmeds) {
-        double sigma = 2.5 * 1.4826 * (1 + 5. / (n - modelPoints)) * sqrt(win.min_median);
-        final_thr = sigma > 0.001 ? sigma : 0.001;
-    }
-    const double* best = w->models + (size_t)win.hyp * 90 + win.model * 9;
-    hipLaunchKernelGGL(k_model_mask, dim3((n + 255) / 256), dim3(256), 0, st, 0, w->q1, w->q2, nullptr, nullptr, n, best,
-                       (float)(final_thr * final_thr), w->masks);
+    Search s;
+    UVO_TRY(hypothesis_search(c, w, kEssential, n, lmeds, prob, threshold, maxIters, &s));
+    if (n == modelPoints) memcpy(E, w->h_models.data(), sizeof(double) * 9);       // (written whether or not the five points had a model)
+    if (s.win.hyp < 0) return UVO_OK;
+    if (n == modelPoints) { memset(mask, 1, n); *ok = 1; return UVO_OK; }
+    const size_t best = (size_t)s.win.hyp * 90 + s.win.model * 9;
+    hipLaunchKernelGGL(k_model_mask, dim3((n + 255) / 256), dim3(256), 0, st, 0, w->q1, w->q2, nullptr, nullptr, n, w->models + best,
+                       (float)(s.final_thr * s.final_thr), w->masks);
     UVO_HIP_TRY(c, hipGetLastError());
     UVO_HIP_TRY(c, hipMemcpyAsync(w->h_mask.data(), w->masks, n, hipMemcpyDeviceToHost, st));
-    UVO_HIP_TRY(c, hipMemcpyAsync(w->h_models.data(), best, sizeof(double) * 9, hipMemcpyDeviceToHost, st));
     UVO_HIP_TRY(c, host_sync(c, st));
-    memcpy(mask, w->h_mask.data(), (size_t)n); memcpy(E, w->h_models.data(), sizeof(double) * 9);
+    memcpy(mask, w->h_mask.data(), (size_t)n); memcpy(E, w->h_models.data() + best, sizeof(double) * 9);
     if (lmeds) { int good = 0; for (int i = 0; i < n; i++) good += mask[i]; *ok = good >= modelPoints; }
     else *ok = 1;
     return UVO_OK;
@@ -1288,17 +1335,6 @@ static void lm_refine_homography(const float* M, const float* m, int count, doub
 }
 
 // findHomography's host pieces, shared by the host-pointer operator and the resident chain (mono_homography_resident)
-static int h_niters(bool lmeds, double confidence, int maxIters)
-{
-    if (lmeds) { int niters = ransac_update_num_iters(confidence, 0.45, 4, maxIters); return niters > 3 ? niters : 3; }
-    return maxIters > 1 ? maxIters : 1;
-}
-static double h_final_threshold(bool lmeds, double thr, int n, double min_median)
-{
-    if (!lmeds) return thr;
-    double sigma = 2.5 * 1.4826 * (1 + 5. / (n - 4)) * sqrt(min_median);
-    return sigma > 0.001 ? sigma : 0.001;
-}
 // compressElems by the mask (in1 / in2 -> src / dst, which may be the same arrays) and the refit on the k inliers: homography_kernel,
 // then the LM refinement.  Returns k; H is left alone when k == 0.
 static int h_compact_refit(const float* in1, const float* in2, int n, const uint8_t* mask, float* src, float* dst, double* H)
@@ -1384,6 +1420,30 @@ uvo_status mono_homography_fit_all(Ctx* c, const float* src, const float* dst, i
     return UVO_OK;
 }
 
+// findHomography's sampled methods (4 LMedS, 8 RANSAC) up to the refit: the search, then the winner's mask (device: dmask; host: h_mask)
+// and model (H) behind one more wait.  *result: a model stands (LMedS: with at least four inliers); h_mask is not cleared when none does.
+static uvo_status h_search_mask(Ctx* c, MonoWs* w, const Estimator& est, int n, int method, double thr, int maxIters, double confidence,
+                                uint8_t* dmask, double* H, int* result)
+{
+    *result = 0;
+    hipStream_t st = c->stream;
+    const bool lmeds = method != 8;
+    Search s;
+    UVO_TRY(hypothesis_search(c, w, est, n, lmeds, confidence, thr, maxIters, &s));
+    if (s.win.hyp < 0) return UVO_OK;
+    const double* best = w->models + (size_t)s.win.hyp * 9;
+    hipLaunchKernelGGL(k_model_mask, dim3((n + 255) / 256), dim3(256), 0, st, 1, nullptr, nullptr, est.d1, est.d2, n, best,
+                       (float)(s.final_thr * s.final_thr), dmask);
+    UVO_HIP_TRY(c, hipGetLastError());
+    UVO_HIP_TRY(c, hipMemcpyAsync(w->h_mask.data(), dmask, n, hipMemcpyDeviceToHost, st));
+    UVO_HIP_TRY(c, hipMemcpyAsync(w->h_models.data(), best, sizeof(double) * 9, hipMemcpyDeviceToHost, st));
+    UVO_HIP_TRY(c, host_sync(c, st));
+    memcpy(H, w->h_models.data(), sizeof(double) * 9);
+    if (lmeds) { int good = 0; for (int i = 0; i < n; i++) good += w->h_mask[i]; *result = good >= est.modelPoints; }
+    else *result = 1;
+    return UVO_OK;
+}
+
 // cv::findHomography (VOU:152)
 uvo_status mono_find_homography(Ctx* c, const uvo_point2f* p1, const uvo_point2f* p2, int n, int method, double thr, int maxIters,
                                 double confidence, double* H, uint8_t* mask, int* ok)
@@ -1410,66 +1470,12 @@ uvo_status mono_find_homography(Ctx* c, const uvo_point2f* p1, const uvo_point2f
         return UVO_OK;
     } else {
         hipStream_t st = c->stream;
-        const bool lmeds = method != 8;
-        const int niters = h_niters(lmeds, confidence, maxIters);
-        if (niters > kMaxHyp) { c->err = "max_iters exceeds the compiled hypothesis capacity (2048)"; return UVO_CAPACITY; }
-        if (lmeds) UVO_TRY(lmeds_capacity(c, w, n));
-        bool failed_first = false;
-        int nsub = make_subsets(w->h_subsets.data(), niters, modelPoints, n, lmeds ? 1000 : 10000, src.data(), dst.data(), &failed_first);
-        if (nsub > 0) {
-            UVO_HIP_TRY(c, hipMemcpyAsync(w->src, src.data(), sizeof(float) * 2 * n, hipMemcpyHostToDevice, st));
-            UVO_HIP_TRY(c, hipMemcpyAsync(w->dst, dst.data(), sizeof(float) * 2 * n, hipMemcpyHostToDevice, st));
-            c->stat_uploads += 2;
-            UVO_HIP_TRY(c, hipMemcpyAsync(w->subsets, w->h_subsets.data(), sizeof(int) * 4 * nsub, hipMemcpyHostToDevice, st));
-            // RANSAC in rounds, as mono_find_essential: the first kFirstRound subsets, the rest only if the adaptive count reaches past them
-            // (at the shipped 0.1-px threshold the scan of a low-inlier frame never settles inside the first round, and the second launch
-            //  costs the frame another 0.35 ms and a synchronisation: the workspace remembers what the last scan needed)
-            const int kFirstRound = 128;
-            const int first = (!lmeds && nsub > kFirstRound && !w->h_one_round) ? kFirstRound : nsub;
-            hipLaunchKernelGGL(k_h_hyp, dim3((first + kHPerWg - 1) / kHPerWg), dim3(64), 0, st, w->src, w->dst, w->subsets, first,
-                               w->models, w->nmodels);
-            const int npow2 = next_pow2(n);
-            const float thr2 = (float)(thr * thr);
-            hipLaunchKernelGGL(k_h_score, dim3(first), dim3(256), lmeds ? sizeof(float) * npow2 : 0, st, w->src, w->dst, n, w->models, w->nmodels,
-                               lmeds ? 1 : 0, thr2, npow2, w->counts, w->medians);
-            UVO_HIP_TRY(c, hipGetLastError());
-            UVO_HIP_TRY(c, hipMemcpyAsync(w->h_nmodels.data(), w->nmodels, sizeof(int) * first, hipMemcpyDeviceToHost, st));
-            if (lmeds) UVO_HIP_TRY(c, hipMemcpyAsync(w->h_medians.data(), w->medians, sizeof(double) * first, hipMemcpyDeviceToHost, st));
-            else UVO_HIP_TRY(c, hipMemcpyAsync(w->h_counts.data(), w->counts, sizeof(int) * first, hipMemcpyDeviceToHost, st));
-            UVO_HIP_TRY(c, host_sync(c, st));
-            Winner win;
-            if (lmeds) win = replay_lmeds(w->h_nmodels.data(), w->h_medians.data(), 1, nsub);
-            else {
-                int settled = niters;
-                win = replay_ransac(w->h_nmodels.data(), w->h_counts.data(), 1, first, niters, n, modelPoints, confidence, &settled);
-                if (nsub > kFirstRound) w->h_one_round = settled > kFirstRound;          // the scan's result is the same either way
-                if (first < nsub && settled > first) {
-                    const int rest = nsub - first;
-                    hipLaunchKernelGGL(k_h_hyp, dim3((rest + kHPerWg - 1) / kHPerWg), dim3(64), 0, st, w->src, w->dst,
-                                       w->subsets + (size_t)4 * first, rest, w->models + (size_t)9 * first, w->nmodels + first);
-                    hipLaunchKernelGGL(k_h_score, dim3(rest), dim3(256), 0, st, w->src, w->dst, n, w->models + (size_t)9 * first, w->nmodels + first,
-                                       0, thr2, npow2, w->counts + first, w->medians + first);
-                    UVO_HIP_TRY(c, hipGetLastError());
-                    UVO_HIP_TRY(c, hipMemcpyAsync(w->h_nmodels.data() + first, w->nmodels + first, sizeof(int) * rest, hipMemcpyDeviceToHost, st));
-                    UVO_HIP_TRY(c, hipMemcpyAsync(w->h_counts.data() + first, w->counts + first, sizeof(int) * rest, hipMemcpyDeviceToHost, st));
-                    UVO_HIP_TRY(c, host_sync(c, st));
-                    win = replay_ransac(w->h_nmodels.data(), w->h_counts.data(), 1, nsub, niters, n, modelPoints, confidence);
-                }
-            }
-            if (win.hyp >= 0) {
-                const double final_thr = h_final_threshold(lmeds, thr, n, win.min_median);
-                const double* best = w->models + (size_t)win.hyp * 9;
-                hipLaunchKernelGGL(k_model_mask, dim3((n + 255) / 256), dim3(256), 0, st, 1, nullptr, nullptr, w->src, w->dst, n, best,
-                                   (float)(final_thr * final_thr), w->masks);
-                UVO_HIP_TRY(c, hipGetLastError());
-                UVO_HIP_TRY(c, hipMemcpyAsync(w->h_mask.data(), w->masks, n, hipMemcpyDeviceToHost, st));
-                UVO_HIP_TRY(c, hipMemcpyAsync(w->h_models.data(), best, sizeof(double) * 9, hipMemcpyDeviceToHost, st));
-                UVO_HIP_TRY(c, host_sync(c, st));
-                memcpy(mask, w->h_mask.data(), (size_t)n); memcpy(H, w->h_models.data(), sizeof(double) * 9);
-                if (lmeds) { int good = 0; for (int i = 0; i < n; i++) good += mask[i]; result = good >= modelPoints; }
-                else result = 1;
-            }
-        }
+        UVO_HIP_TRY(c, hipMemcpyAsync(w->src, src.data(), sizeof(float) * 2 * n, hipMemcpyHostToDevice, st));
+        UVO_HIP_TRY(c, hipMemcpyAsync(w->dst, dst.data(), sizeof(float) * 2 * n, hipMemcpyHostToDevice, st));
+        c->stat_uploads += 2;
+        const Estimator est = { modelPoints, 1, src.data(), dst.data(), w->src, w->dst };
+        UVO_TRY(h_search_mask(c, w, est, n, method, thr, maxIters, confidence, w->masks, H, &result));
+        memcpy(mask, w->h_mask.data(), (size_t)n);
     }
     if (result && n > 4) h_compact_refit(src.data(), dst.data(), n, mask, src.data(), dst.data(), H);
     if (!result) memset(mask, 0, n);
@@ -1731,10 +1737,9 @@ uvo_status mono_prep_launch(Ctx* c, hipStream_t st, const double* K, int distanc
 {
     MonoWs* w = mono_ws(c);
     if (!w) { c->err = "mono workspace allocation failed"; return UVO_HIP_ERROR; }
-    const double fx = K[0], fy = K[4], cx = K[2], cy = K[5];
-    const double ax = 1. / fx, bx = -cx * ax, ay = 1. / fy, by = -cy * ay;
+    const KNorm kn = k_norm(K);
     w->h_prep[0] = -1;
-    hipLaunchKernelGGL(k_mono_prep, dim3(1), dim3(1024), 0, st, c->d_x1, c->d_x2, c->d_counts + CN_M, c->cap, ax, bx, ay, by, distance,
+    hipLaunchKernelGGL(k_mono_prep, dim3(1), dim3(1024), 0, st, c->d_x1, c->d_x2, c->d_counts + CN_M, c->cap, kn.ax, kn.bx, kn.ay, kn.by, distance,
                        w->q1, w->q2, w->h_x1.data(), w->h_x2.data(), w->h_prep.data());
     UVO_HIP_TRY(c, hipGetLastError());
     return UVO_OK;
@@ -1823,65 +1828,19 @@ uvo_status mono_essential_resident(Ctx* c, int n, const double* K, int method, d
     const int modelPoints = 5;
     out->mask = w->h_mask.data(); out->zs = w->h_zs.data();
     if (n < modelPoints) { memset(w->h_mask.data(), 0, (size_t)(n > 0 ? n : 0)); return UVO_OK; }
-    const double fx = K[0], fy = K[4];
-    threshold /= (fx + fy) / 2;
+    threshold /= (K[0] + K[4]) / 2;
     hipStream_t st = c->stream;
     const bool lmeds = method != 8;
-    int niters;
-    if (n == modelPoints) niters = 1;
-    else if (lmeds) { niters = ransac_update_num_iters(prob, 0.45, modelPoints, maxIters); niters = niters > 3 ? niters : 3; }
-    else niters = maxIters > 1 ? maxIters : 1;
-    if (niters > kMaxHyp) { c->err = "max_iters exceeds the compiled hypothesis capacity (2048)"; return UVO_CAPACITY; }
-    if (lmeds && n != modelPoints) UVO_TRY(lmeds_capacity(c, w, n));
-    bool failed_first = false;
-    int nsub;
-    if (n == modelPoints) { for (int i = 0; i < 5; i++) w->h_subsets[i] = i; nsub = 1; }
-    else nsub = make_subsets(w->h_subsets.data(), niters, modelPoints, n, lmeds ? 1000 : 10000, nullptr, nullptr, &failed_first);
-    const int kFirstRound = 128;
-    const int first = (!lmeds && n != modelPoints && nsub > kFirstRound) ? kFirstRound : nsub;
-    const int npow2 = next_pow2(n);
-    const float thr2 = (float)(threshold * threshold);
-    // round(s) of hypotheses: subsets read from pinned memory, counts / medians / model counts written to it, the models mirrored
-    auto round = [&](int from, int cnt) -> uvo_status {
-        hipLaunchKernelGGL(k_fivepoint_hyp, dim3((cnt + kFpPerWg - 1) / kFpPerWg), dim3(64), 0, st, w->q1, w->q2, w->h_subsets.data() + (size_t)5 * from, cnt,
-                           w->models + (size_t)90 * from, w->nmodels + from);
-        if (n != modelPoints)
-            hipLaunchKernelGGL(k_e_score, dim3(10, cnt), dim3(256), lmeds ? sizeof(float) * npow2 : 0, st, w->q1, w->q2, n, w->models + (size_t)90 * from, w->nmodels + from,
-                               lmeds ? 1 : 0, thr2, npow2, w->h_counts.data() + (size_t)10 * from, w->h_medians.data() + (size_t)10 * from, w->h_nmodels.data() + from);
-        else hipLaunchKernelGGL(k_mirror_words, dim3(1), dim3(256), 0, st, w->nmodels, w->h_nmodels.data(), 1);
-        hipLaunchKernelGGL(k_mirror_words, dim3(std::min(64, (cnt * 180 + 255) / 256)), dim3(256), 0, st, reinterpret_cast<const int*>(w->models + (size_t)90 * from),
-                           reinterpret_cast<int*>(w->h_models.data() + (size_t)90 * from), cnt * 180);
-        UVO_HIP_TRY(c, hipGetLastError());
-        UVO_HIP_TRY(c, host_sync(c, st));
-        return UVO_OK;
-    };
-    UVO_TRY(round(0, first));
-    Winner win;
-    double final_thr = threshold;
-    if (n == modelPoints) {
-        if (w->h_nmodels[0] <= 0) { memset(w->h_mask.data(), 0, (size_t)n); return UVO_OK; }
-        win.hyp = 0; win.model = 0;
-        final_thr = DBL_MAX;                                         // every point an inlier (RANSACPointSetRegistrator::run, count == modelPoints)
-    } else if (lmeds) win = replay_lmeds(w->h_nmodels.data(), w->h_medians.data(), 10, nsub);
-    else {
-        int settled = niters;
-        win = replay_ransac(w->h_nmodels.data(), w->h_counts.data(), 10, first, niters, n, modelPoints, prob, &settled);
-        if (first < nsub && settled > first) {
-            UVO_TRY(round(first, nsub - first));
-            win = replay_ransac(w->h_nmodels.data(), w->h_counts.data(), 10, nsub, niters, n, modelPoints, prob);
-        }
-    }
+    Search s;
+    UVO_TRY(hypothesis_search(c, w, kEssential, n, lmeds, prob, threshold, maxIters, &s));
+    const Winner win = s.win;
     if (win.hyp < 0) { memset(w->h_mask.data(), 0, (size_t)n); return UVO_OK; }
-    if (lmeds && n != modelPoints) {
-        const double sigma = 2.5 * 1.4826 * (1 + 5. / (n - modelPoints)) * sqrt(win.min_median);
-        final_thr = sigma > 0.001 ? sigma : 0.001;
-    }
     const double* E = w->h_models.data() + (size_t)win.hyp * 90 + win.model * 9;
     memcpy(out->E, E, sizeof(out->E));
     uint8_t* emask = w->masks + 4 * (size_t)c->cap;
     if (n == modelPoints) UVO_HIP_TRY(c, hipMemsetAsync(emask, 1, n, st));
     else hipLaunchKernelGGL(k_model_mask, dim3((n + 255) / 256), dim3(256), 0, st, 0, w->q1, w->q2, nullptr, nullptr, n,
-                            w->models + (size_t)win.hyp * 90 + win.model * 9, (float)(final_thr * final_thr), emask);
+                            w->models + (size_t)win.hyp * 90 + win.model * 9, (float)(s.final_thr * s.final_thr), emask);
     // recoverPose: the four candidates of decomposeEssentialMat, cheirality counts on the device
     double R1[9], R2[9], tt[3];
     decompose_essential(E, R1, R2, tt);
@@ -1928,10 +1887,9 @@ uvo_status mono_stage_points(Ctx* c, const uvo_point2f* p1, const uvo_point2f* p
     UVO_HIP_TRY(c, hipMemcpyAsync(c->d_x1, p1, sizeof(uvo_point2f) * n, hipMemcpyHostToDevice, st));
     UVO_HIP_TRY(c, hipMemcpyAsync(c->d_x2, p2, sizeof(uvo_point2f) * n, hipMemcpyHostToDevice, st));
     c->stat_uploads += 2;
-    const double fx = K[0], fy = K[4], cx = K[2], cy = K[5];
-    const double ax = 1. / fx, bx = -cx * ax, ay = 1. / fy, by = -cy * ay;
+    const KNorm kn = k_norm(K);
     w->h_prep[0] = -1;
-    hipLaunchKernelGGL(k_mono_prep, dim3(1), dim3(1024), 0, st, c->d_x1, c->d_x2, (const int*)nullptr, n, ax, bx, ay, by, 0,
+    hipLaunchKernelGGL(k_mono_prep, dim3(1), dim3(1024), 0, st, c->d_x1, c->d_x2, (const int*)nullptr, n, kn.ax, kn.bx, kn.ay, kn.by, 0,
                        w->q1, w->q2, w->h_x1.data(), w->h_x2.data(), w->h_prep.data());
     UVO_HIP_TRY(c, hipGetLastError());
     UVO_HIP_TRY(c, host_sync(c, st));
@@ -1992,7 +1950,7 @@ __global__ __launch_bounds__(1024) void k_h_pick(const uvo_point2f* __restrict__
 // findHomography + recover_pose_homography + triangulatePoints + extract_3Dpoints + convert_3Dpoints_camera on the n matched points
 // k_mono_prep left on the device (d_x1 / d_x2: uvo_point2f[n] is the float[2n] the homography kernels read) and mirrored in pinned
 // memory (h_x1 / h_x2).  Nothing is uploaded unless the attempt is handed over (below).  Host waits: the hypothesis scores (a second one when RANSAC's scan goes past the first
-// round, as mono_find_homography), the mask with the winning model, and the end of the chain -- three or four.
+// round: hypothesis_search), the mask with the winning model, and the end of the chain -- three or four.
 //   on the host, on the pinned mirrors: the sampler's checkSubset; the refit on the inliers (homography_kernel on k points, then the LM
 //       refinement: their sums over the points are sequential in the definition, and that order is what the bits are);
 //       decomposeHomographyMat.
@@ -2045,54 +2003,8 @@ uvo_status mono_homography_resident(Ctx* c, int n, const double* K, int method, 
         memcpy(H, w->h_models.data(), sizeof(H));
         if (result) memset(mask, 1, (size_t)n);
     } else {
-        const bool lmeds = method != 8;
-        const int niters = h_niters(lmeds, confidence, maxIters);
-        if (niters > kMaxHyp) { c->err = "max_iters exceeds the compiled hypothesis capacity (2048)"; return UVO_CAPACITY; }
-        if (lmeds) UVO_TRY(lmeds_capacity(c, w, n));
-        bool failed_first = false;
-        const int nsub = make_subsets(w->h_subsets.data(), niters, modelPoints, n, lmeds ? 1000 : 10000, hx1, hx2, &failed_first);
-        if (nsub > 0) {
-            const int kFirstRound = 128;
-            const int first = (!lmeds && nsub > kFirstRound && !w->h_one_round) ? kFirstRound : nsub;
-            const int npow2 = next_pow2(n);
-            const float thr2 = (float)(thr * thr);
-            // a round of hypotheses: subsets read from pinned memory, counts / medians written to it, the model counts mirrored
-            auto round = [&](int from, int cnt) -> uvo_status {
-                hipLaunchKernelGGL(k_h_hyp, dim3((cnt + kHPerWg - 1) / kHPerWg), dim3(64), 0, st, dx1, dx2, w->h_subsets.data() + (size_t)4 * from, cnt,
-                                   w->models + (size_t)9 * from, w->nmodels + from);
-                hipLaunchKernelGGL(k_h_score, dim3(cnt), dim3(256), lmeds ? sizeof(float) * npow2 : 0, st, dx1, dx2, n, w->models + (size_t)9 * from, w->nmodels + from,
-                                   lmeds ? 1 : 0, thr2, npow2, w->h_counts.data() + from, w->h_medians.data() + from);
-                hipLaunchKernelGGL(k_mirror_words, dim3(std::min(64, (cnt + 255) / 256)), dim3(256), 0, st, w->nmodels + from, w->h_nmodels.data() + from, cnt);
-                UVO_HIP_TRY(c, hipGetLastError());
-                UVO_HIP_TRY(c, host_sync(c, st));
-                return UVO_OK;
-            };
-            UVO_TRY(round(0, first));
-            Winner win;
-            if (lmeds) win = replay_lmeds(w->h_nmodels.data(), w->h_medians.data(), 1, nsub);
-            else {
-                int settled = niters;
-                win = replay_ransac(w->h_nmodels.data(), w->h_counts.data(), 1, first, niters, n, modelPoints, confidence, &settled);
-                if (nsub > kFirstRound) w->h_one_round = settled > kFirstRound;          // as mono_find_homography: the scan's result is the same either way
-                if (first < nsub && settled > first) {
-                    UVO_TRY(round(first, nsub - first));
-                    win = replay_ransac(w->h_nmodels.data(), w->h_counts.data(), 1, nsub, niters, n, modelPoints, confidence);
-                }
-            }
-            if (win.hyp >= 0) {
-                const double final_thr = h_final_threshold(lmeds, thr, n, win.min_median);
-                const double* best = w->models + (size_t)win.hyp * 9;
-                hipLaunchKernelGGL(k_model_mask, dim3((n + 255) / 256), dim3(256), 0, st, 1, nullptr, nullptr, dx1, dx2, n, best,
-                                   (float)(final_thr * final_thr), hmask);
-                UVO_HIP_TRY(c, hipGetLastError());
-                UVO_HIP_TRY(c, hipMemcpyAsync(mask, hmask, n, hipMemcpyDeviceToHost, st));
-                UVO_HIP_TRY(c, hipMemcpyAsync(w->h_models.data(), best, sizeof(double) * 9, hipMemcpyDeviceToHost, st));
-                UVO_HIP_TRY(c, host_sync(c, st));
-                memcpy(H, w->h_models.data(), sizeof(double) * 9);
-                if (lmeds) { int good = 0; for (int i = 0; i < n; i++) good += mask[i]; result = good >= modelPoints; }
-                else result = 1;
-            }
-        }
+        const Estimator est = { modelPoints, 1, hx1, hx2, dx1, dx2 };
+        UVO_TRY(h_search_mask(c, w, est, n, method, thr, maxIters, confidence, hmask, H, &result));      // (mask is h_mask)
     }
     int k = 0;
     if (result && n > 4 && method != 0) k = h_compact_refit(hx1, hx2, n, mask, w->h_src.data(), w->h_dst.data(), H);      // on the pinned mirror, which stays as it is

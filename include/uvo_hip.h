@@ -429,7 +429,7 @@ int        uvo_mono_get(uvo_ctx* c, const char* what, void* out, int cap_bytes);
  *      a host wait in between; at most four waits per homography attempt, nothing uploaded.  checkSubset, the refit with its LM
  *      refinement and decomposeHomographyMat stay on the host.  A single-solution decomposition and a vote without a winner are
  *      finished by route 0 from that point (counted as fallbacks).  uvo_estimate_relative_pose on host pointers then stages its points
- *      once and takes the same chains.  With HOMOGRAPHY_OUTLIER_METHOD 0 (all points) the hypothesis rounds, the mask and the host refit
+ *      once, takes the same chains and reads the inliers of its last attempt back (one wait per call).  With HOMOGRAPHY_OUTLIER_METHOD 0 (all points) the hypothesis rounds, the mask and the host refit
  *      are one launch (k_h_fit_all) and a memset: TWO waits per homography attempt -- for H, which decomposeHomographyMat takes on the
  *      host, and at the end of the chain -- nothing uploaded.
  * Results do not depend on the value.  1 is faster wherever a frame takes a homography attempt, synchronously and with fourteen frames

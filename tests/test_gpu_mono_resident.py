@@ -318,6 +318,66 @@ def test_operator_vote_without_a_winner_hands_over(oracle, op_ctx):
     assert s1["attempts"] == [0, 1, 0, 0] and s1["fallbacks"] == 1, s1
 
 
+def test_search_rounds_and_memory(oracle):
+    """The estimators' shared search (mono.hip: hypothesis_search) where it takes a second round, and the homography's memory of it.
+    RANSAC for both, 1000 iterations, on a planar set of 200 with few outliers (the scan settles after a handful of iterations: one
+    round of 128 hypotheses) and with 60 % (E settles near 350 iterations, H near 178: the rest is solved in a second round, one host
+    wait more).  Every call succeeds on its first attempt and equals the oracle bit for bit at stage 0 and at stage 1.  The waits are
+    compared as differences of the library's own counter at stage 1; a fresh context per case, because the memory lives in its workspace."""
+    import ergo_uvo_amd as uvo
+    kw = dict(_T1, ESSENTIAL_MAX_ITERS=1000, HOMOGRAPHY_MAX_ITERS=1000, VPF_THRESHOLD=0, MIN_NUM_INLIERS=5)
+    sets = {o: _planted(200, 4242, planar=True, noise=0.15, outliers=o) for o in (0.05, 0.6)}
+
+    def first_attempt(s1, start_e):
+        assert s1["attempts"] == ([1, 0, 0, 0] if start_e else [0, 1, 0, 0]), s1
+        assert s1["fallbacks"] == 0 and s1["uploads"] == 2, s1                  # the operator's own staging of its two point lists
+
+    def three_ways(c, o, start_e):
+        K, x1, x2 = sets[o]
+        want, s0, s1 = _erp_three_ways(oracle, c, kw, 8, K, x1, x2, start_e)
+        assert want[0] and bool(want[1]) == start_e, (o, start_e, want[:2])      # accepted with the method it started with
+        first_attempt(s1, start_e)
+        return want, s1["host_waits"]
+
+    def at_stage_1(c, o):
+        K, x1, x2 = sets[o]
+        c.set_params(_params(oracle, kw, 8)[0])
+        c.mono_set_pose_stage(1)
+        got = c.estimate_relative_pose(x1, x2, K, False)
+        s1 = c.mono_pose_stats()
+        first_attempt(s1, False)
+        return got, s1["host_waits"]
+
+    waits = {}
+    for o in sets:                                                               # the essential matrix: no memory
+        c = uvo.Context(uvo.Params.mono(), 0, W, H, 1024)
+        try:
+            waits[o] = three_ways(c, o, True)[1]
+        finally:
+            c.close()
+    print("essential: host waits", waits)
+    assert waits[0.6] == waits[0.05] + 1, waits
+
+    c = uvo.Context(uvo.Params.mono(), 0, W, H, 1024)                            # the homography, one round
+    try:
+        got, low = at_stage_1(c, 0.05)
+        assert _erp_equal(got, three_ways(c, 0.05, False)[0])
+    finally:
+        c.close()
+    c = uvo.Context(uvo.Params.mono(), 0, W, H, 1024)                            # two rounds on a fresh workspace, one from then on
+    try:
+        got1, w1 = at_stage_1(c, 0.6)
+        got2, w2 = at_stage_1(c, 0.6)
+        print("homography: host waits", low, w1, w2)
+        assert w1 == low + 1, (low, w1)
+        assert w2 == w1 - 1, (w1, w2)
+        assert _erp_equal(got1, got2)
+        assert _erp_equal(got1, three_ways(c, 0.6, False)[0])
+        three_ways(c, 0.05, False)                                               # whatever the workspace remembers, the bits are the oracle's
+    finally:
+        c.close()
+
+
 # ------------------------------------------------------------------ a binary-detector pair
 def test_orb_quarter_step_pair(oracle):
     import ergo_uvo_amd as uvo
