@@ -1,4 +1,5 @@
-"""numpy (float64) statements of the AKAZE and SIFT detector stages after their scale spaces, written from the published methods and the
+"""numpy (float64) statements of the AKAZE and SIFT detector stages after their scale spaces (the scale spaces themselves, and SIFT's
+extremum search: tests/scale_space_definitions_np.py), written from the published methods and the
 OpenCV 4.5 routines the oracle headers name -- NOT from `oracle/` or the HIP code (nothing here imports either).  Inputs are planes and
 keypoints, outputs float64; each statement also returns how close its own decisions came to a discontinuity, so that a check can tell an
 ambiguous case from a wrong one.
