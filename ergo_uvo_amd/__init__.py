@@ -320,6 +320,14 @@ class Context:
         self._check(self._lib.uvo_orb_stats(self._h, *[C.byref(x) for x in v]))
         return dict(zip(("host_waits", "n_fast", "n_ranked", "n_keypoints"), (x.value for x in v)))
 
+    def akaze_configure(self, descriptor_type=5, descriptor_size=0, descriptor_channels=3, threshold=0.001, nOctaves=4, nOctaveLayers=4, diffusivity=1):
+        """AKAZE::create's arguments, in its order, for akaze_detect, the AKAZE hooks and the loops after set_feature_detector("AKAZE").
+        Served: descriptor_type 5 (DESCRIPTOR_MLDB), descriptor_size 0 and descriptor_channels 3 only; threshold finite and > 0; nOctaves
+        1..4; nOctaveLayers 1..4; diffusivity 0 (DIFF_PM_G1), 1 (DIFF_PM_G2), 2 (DIFF_WEICKERT), 3 (DIFF_CHARBONNIER).  Anything else raises
+        UvoError with the argument's name, as does a call with pairs in flight; a refused call changes nothing.  Survives set_params."""
+        self._check(self._lib.uvo_akaze_configure(self._h, int(descriptor_type), int(descriptor_size), int(descriptor_channels), float(threshold),
+                                                  int(nOctaves), int(nOctaveLayers), int(diffusivity)))
+
     def akaze_set_suppression(self, where):
         """Where AKAZE's sequential stages (contrast factor, duplicate suppression, refinement) run: "host" / 0 (the host scans of the
         candidate list) or "device" / 1 (k_ak_scan, k_ak_refine; the fused steps then queue their detection without a host wait).  The

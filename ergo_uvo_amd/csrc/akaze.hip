@@ -1,6 +1,7 @@
 // akaze.hip -- the AKAZE branch of detect_features on gfx950 (uvo_libraries/src/VO_utility.cpp:93-98):
 //     Ptr<AKAZE> detector = AKAZE::create();  detector->detectAndCompute(img, noArray(), keypoints, descriptors);
-// DESCRIPTOR_MLDB, full length (486 bits = 61 bytes), 3 channels, threshold 0.001f, 4 octaves x 4 sublevels, DIFF_PM_G2 -- after
+// DESCRIPTOR_MLDB, full length (486 bits = 61 bytes), 3 channels; the detection arguments of AKAZE::create -- threshold, nOctaves,
+// nOctaveLayers, diffusivity -- are the context's (uvo_akaze_configure; 0.001f, 4 octaves x 4 sublevels, DIFF_PM_G2 until it is called) -- after
 // Alcantarilla, Nuevo, Bartoli, "Fast explicit diffusion for accelerated features in nonlinear scale spaces" (BMVC 2013) in the form
 // of OpenCV 4.5's features2d/src/kaze/AKAZEFeatures.cpp as far as it can be recalled (PARITY UNPINNED; the float operation order is
 // the scalar one of imgproc's separable filters).
@@ -10,7 +11,7 @@
 //   k_ak_blur_rows / _cols         GaussianBlur, BORDER_REPLICATE (9 taps for the base level, 5 for the smoothed copies)
 //   k_ak_scharr                    Scharr 3 x 3 (for the conductance), BORDER_REFLECT_101
 //   k_ak_gradmax / _gradhist       compute_kcontrast: maximum and 300-bin histogram of the gradient magnitude
-//   k_ak_pm_g2                     Perona-Malik g2 conductance
+//   k_ak_conductance<D>            the conductance of the configured diffusivity: Perona-Malik g1, g2 (the default), Weickert, Charbonnier
 //   k_ak_nld_step                  one FED step Lt + step * div(c grad Lt), five-point star, one-sided at the border
 //   k_ak_half / k_ak_area          resize INTER_AREA to the next octave (exact halving, or the general table form for odd sizes)
 //   k_ak_sep_deriv                 the stretched Scharr pair of compute_derivative_kernels (taps at +-sigma_size)
@@ -30,6 +31,7 @@
 #include "uvo_ctx.h"
 #include "uvo_math.h"
 #include "uvo_akaze_suppress.h"
+#include "uvo_akaze_plan.h"
 #include <float.h>
 #include <string.h>
 #include <math.h>
@@ -41,11 +43,11 @@ namespace uvo {
 double now_us();                                                  // pose.hip / ctx.hip: steady clock, microseconds
 static const int kAkMaxLevels = 16, kAkDescBytes = 61, kAkCandCap = 1 << 18;
 static const int kAkazeSuppressDefault = 1;                       // uvo_akaze_set_suppression's initial value: the device (124 against 66 stereo pairs/s at depth 6)
-struct AkLevel { int w, h, octave, sublevel, sigma_size, border, nsteps; float esigma, etime, octave_ratio; float tau[64]; };
 struct AkTab { int si; float alpha; };
 
 struct AkazeWs {
     int w = 0, h = 0, n = 0, cap = 0;
+    AkazeCfg cfg;                                             // what the plan, the tables and the captured graphs below were made for (uvo_akaze_configure)
     AkLevel lv[kAkMaxLevels];
     float* Lt[kAkMaxLevels] = {nullptr}; float* Lsmooth[kAkMaxLevels] = {nullptr}; float* Lx[kAkMaxLevels] = {nullptr};
     float* Ly[kAkMaxLevels] = {nullptr}; float* Ldet[kAkMaxLevels] = {nullptr};
@@ -74,61 +76,7 @@ struct AkazeWs {
 // keypoint count (what the kernels after the refinement consume: always a count of written keypoints) and, apart from it, the flag "more
 // candidates were found than the list holds" (read by k_binary_publish_dev and the host only), the largest round count per phase
 enum { SUP_FOUND = 0, SUP_N = 1, SUP_START = 2, SUP_NK = SUP_START + kAkMaxLevels + 1, SUP_OVF = SUP_NK + 2, SUP_ROUNDS = SUP_OVF + 2, SUP_INTS = SUP_ROUNDS + 3 };
-static_assert(sizeof(AksKp) == sizeof(uvo_keypoint) && kAksMaxLevels == kAkMaxLevels, "AksKp mirrors uvo_keypoint");
-
-// ---- fed.cpp: fed_tau_by_process_time(T, 1, 0.25f, true, tau) ----
-static bool fed_is_prime(int number)
-{
-    if (number <= 1) return false;
-    if (number == 1 || number == 2 || number == 3 || number == 5 || number == 7) return true;
-    if ((number % 2) == 0 || (number % 3) == 0 || (number % 5) == 0 || (number % 7) == 0) return false;
-    int upperLimit = (int)sqrt(1.0f + number), divisor = 11;
-    while (divisor <= upperLimit) { if (number % divisor == 0) return false; divisor += 2; }
-    return true;
-}
-static int fed_tau(float T, float tau_max, float* tau)
-{
-    const float t = T / 1.0f;
-    const int n = cv_ceil_d((double)(sqrtf(3.0f * t / tau_max + 0.25f) - 0.5f - 1.0e-8f));
-    const float scale = 3.0f * t / (tau_max * (float)(n * (n + 1)));
-    if (n <= 0) return 0;
-    float tauh[256];
-    const float c = 1.0f / (4.0f * (float)n + 2.0f), d = scale * tau_max / 2.0f;
-    for (int k = 0; k < n; ++k) { const float hh = cosf((float)3.14159265358979323846 * (2.0f * (float)k + 1.0f) * c); tauh[k] = d / (hh * hh); }
-    const int kappa = n / 2;
-    int prime = n + 1;
-    while (!fed_is_prime(prime)) prime++;
-    for (int k = 0, l = 0; l < n; ++k, ++l) {
-        int index = 0;
-        while ((index = ((k + 1) * kappa) % prime - 1) >= n) k++;
-        tau[l] = tauh[index];
-    }
-    return n;
-}
-// Allocate_Memory_Evolution with AKAZE::create()'s options
-static int akaze_plan(int img_w, int img_h, AkLevel* L)
-{
-    const int omax = 4, nsublevels = 4;
-    const float soffset = 1.6f, derivative_factor = 1.5f, smax = 10.0f * sqrtf(2.0f);
-    int n = 0;
-    for (int i = 0, power = 1; i <= omax - 1; i++, power *= 2) {
-        const float rfactor = 1.0f / power;
-        const int level_height = (int)(img_h * rfactor), level_width = (int)(img_w * rfactor);
-        if ((level_width < 80 || level_height < 40) && i != 0) break;
-        for (int j = 0; j < nsublevels; j++) {
-            AkLevel* s = &L[n++];
-            s->w = level_width; s->h = level_height;
-            s->esigma = soffset * powf(2.f, (float)(j) / (float)(nsublevels) + i);
-            s->sigma_size = cv_round_f(s->esigma * derivative_factor / power);
-            s->etime = 0.5f * (s->esigma * s->esigma);
-            s->octave = i; s->sublevel = j; s->octave_ratio = (float)power;
-            s->border = cv_round_f(smax * s->sigma_size) + 1;
-            s->nsteps = 0;
-        }
-    }
-    for (int i = 1; i < n; i++) L[i].nsteps = fed_tau(L[i].etime - L[i - 1].etime, 0.25f, L[i].tau);
-    return n;
-}
+static_assert(sizeof(AksKp) == sizeof(uvo_keypoint) && kAksMaxLevels == kAkMaxLevels && kAkPlanMaxLevels == kAkMaxLevels, "AksKp mirrors uvo_keypoint");
 
 // ------------------------------------------------------------------------------------------ kernels
 __device__ __forceinline__ int ak_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
@@ -238,15 +186,25 @@ __global__ __launch_bounds__(256) void k_ak_gradhist(const float* __restrict__ l
     for (int i = threadIdx.x; i < nbins; i += 256) if (s_h[i]) atomicAdd(&hist[1 + i], s_h[i]);
 }
 // (kcontrast of the frame from device memory -- the launch is part of a captured graph --, x 0.75f once per octave change as
-// Create_Nonlinear_Scale_Space does)
-__global__ __launch_bounds__(256) void k_ak_pm_g2(const float* __restrict__ lx, const float* __restrict__ ly, int n, const float* __restrict__ kc, int octave, float* __restrict__ dst)
+// Create_Nonlinear_Scale_Space does).  One instance per diffusivity of AKAZE::create (nldiffusion_functions.cpp's pm_g1, pm_g2,
+// weickert_diffusivity, charbonnier_diffusivity, recalled: DESIGN.md 6), with d = (Lx^2 + Ly^2) / k^2:
+//   DIFF_PM_G1 exp(-d) | DIFF_PM_G2 1 / (1 + d) | DIFF_WEICKERT 1 - exp(-3.315 / d^4), 1 where d^4 = 0 | DIFF_CHARBONNIER 1 / sqrt(1 + d)
+enum { kAkDiffPmG1 = 0, kAkDiffPmG2 = 1, kAkDiffWeickert = 2, kAkDiffCharbonnier = 3 };
+template <int DIFF>
+__global__ __launch_bounds__(256) void k_ak_conductance(const float* __restrict__ lx, const float* __restrict__ ly, int n, const float* __restrict__ kc, int octave, float* __restrict__ dst)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     float k = *kc;
     for (int o = 0; o < octave; o++) k *= 0.75f;
     const float k2inv = 1.0f / (k * k);
-    dst[i] = 1.0f / (1.0f + ((lx[i] * lx[i] + ly[i] * ly[i]) * k2inv));
+    if constexpr (DIFF == kAkDiffPmG2) dst[i] = 1.0f / (1.0f + ((lx[i] * lx[i] + ly[i] * ly[i]) * k2inv));
+    else {
+        const float d = (lx[i] * lx[i] + ly[i] * ly[i]) * k2inv;
+        if constexpr (DIFF == kAkDiffPmG1) dst[i] = expf(-d);
+        else if constexpr (DIFF == kAkDiffCharbonnier) dst[i] = 1.0f / sqrtf(1.0f + d);
+        else { const float d2 = d * d, d4 = d2 * d2; dst[i] = d4 > 0.0f ? 1.0f - expf(-3.315f / d4) : 1.0f; }
+    }
 }
 // non_linear_diffusion_step + add: out = Lt + step * div(c grad Lt).  Interior: the five-point star; image border: the one-sided stencil;
 // the four corners get a zero step.
@@ -645,12 +603,18 @@ static void area_tab(int ssize, int dsize, double scale, std::vector<AkTab>* tab
 static AkazeWs* akaze_ws(Ctx* c, int w, int h)
 {
     AkazeWs* s = static_cast<AkazeWs*>(c->akaze_ws);
-    if (s && s->w == w && s->h == h) return s;
+    const AkazeCfg cfg = c->sh->lanes[0]->akaze_cfg;                // the master context's configuration serves every lane
+    if (s && s->w == w && s->h == h && s->cfg == cfg) return s;
     akaze_ws_free(c);
     s = new AkazeWs();
     c->akaze_ws = s;
-    s->w = w; s->h = h; s->cap = c->cap;
-    s->n = akaze_plan(w, h, s->lv);
+    s->w = w; s->h = h; s->cap = c->cap; s->cfg = cfg;
+    s->n = akaze_plan(w, h, cfg.n_octaves, cfg.n_octave_layers, s->lv);
+    if (s->n < 1) {                                                 // (uvo_akaze_configure serves at most 4 x 4: 16 levels, cycles of at most 31 steps)
+        c->err = s->n == AK_PLAN_CYCLE_TOO_LONG ? "AKAZE: a FED cycle of the level plan has more steps than a level holds (64)" : "AKAZE: the level plan has more levels than the tables hold (16)";
+        akaze_ws_free(c);
+        return nullptr;
+    }
     if (const char* e = getenv("UVO_AKAZE_CAND_CAP")) s->cand_cap = std::min(std::max(atoi(e), 1), kAkCandCap);      // (read per workspace: tools/probe/README.md)
     bool ok = true;
     auto alloc = [&](float** p, size_t n) { ok = ok && hipMalloc(reinterpret_cast<void**>(p), sizeof(float) * n) == hipSuccess; };
@@ -693,7 +657,7 @@ static AkazeWs* akaze_ws(Ctx* c, int w, int h)
              hipMemcpy(s->xtab[i], xt.data(), sizeof(AkTab) * xt.size(), hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(s->ytab[i], yt.data(), sizeof(AkTab) * yt.size(), hipMemcpyHostToDevice) == hipSuccess &&
              hipMemcpy(s->xofs[i], xo.data(), sizeof(int) * xo.size(), hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(s->yofs[i], yo.data(), sizeof(int) * yo.size(), hipMemcpyHostToDevice) == hipSuccess;
     }
-    if (!ok) { akaze_ws_free(c); return nullptr; }
+    if (!ok) { akaze_ws_free(c); c->err = "AKAZE workspace allocation failed"; return nullptr; }
     return s;
 }
 static void gauss_kernel(int n, double sigma, AkKernel* kk)       // getGaussianKernel(n, sigma, CV_32F): double, normalised, cast
@@ -729,7 +693,9 @@ static uvo_status akaze_record(Ctx* c, AkazeWs* s, hipStream_t st, bool ordered)
     auto grid = [](int ww, int hh) { return dim3((ww + 255) / 256, hh); };
     AkKernel k5;
     gauss_kernel(5, (double)1.0f, &k5);
-        for (int i = 1; i < s->n; i++) {
+    const int diff = s->cfg.diffusivity;
+    auto k_cond = diff == kAkDiffPmG1 ? k_ak_conductance<kAkDiffPmG1> : diff == kAkDiffWeickert ? k_ak_conductance<kAkDiffWeickert> : diff == kAkDiffCharbonnier ? k_ak_conductance<kAkDiffCharbonnier> : k_ak_conductance<kAkDiffPmG2>;
+    for (int i = 1; i < s->n; i++) {
         const AkLevel& lv = s->lv[i];
         const int lw = lv.w, lh = lv.h;
         if (lv.octave > s->lv[i - 1].octave) {
@@ -741,7 +707,7 @@ static uvo_status akaze_record(Ctx* c, AkazeWs* s, hipStream_t st, bool ordered)
         hipLaunchKernelGGL(k_ak_blur_cols, grid(lw, lh), blk, 0, st, s->s[0], lw, lh, k5, s->Lsmooth[i]);
         hipLaunchKernelGGL(k_ak_scharr, grid(lw, lh), blk, 0, st, s->Lsmooth[i], lw, lh, 1, s->s[0]);
         hipLaunchKernelGGL(k_ak_scharr, grid(lw, lh), blk, 0, st, s->Lsmooth[i], lw, lh, 0, s->s[1]);
-        hipLaunchKernelGGL(k_ak_pm_g2, dim3((lw * lh + 255) / 256), blk, 0, st, s->s[0], s->s[1], lw * lh, s->d_kc, lv.octave, s->s[2]);
+        hipLaunchKernelGGL(k_cond, dim3((lw * lh + 255) / 256), blk, 0, st, s->s[0], s->s[1], lw * lh, s->d_kc, lv.octave, s->s[2]);
         // Fast Explicit Diffusion: the cycle's steps, ping-pong between Lt[i] and a scratch plane
         float* cur = s->Lt[i]; float* nxt = s->s[3];
         for (int j = 0; j < lv.nsteps; j++) {
@@ -762,14 +728,14 @@ static uvo_status akaze_record(Ctx* c, AkazeWs* s, hipStream_t st, bool ordered)
         hipLaunchKernelGGL(k_ak_det, dim3((lw * lh + 255) / 256), blk, 0, st, s->s[0], s->s[1], s->s[2], lw * lh, (float)(r * r * r * r), s->Ldet[i]);
         if (ordered || lv.border + 1 >= lh || lw - 2 * lv.border <= 0 || lh - 2 * lv.border <= 0) continue;   // "if border is too big we shouldn't search any keypoints"
         // every level appends to one list (the record carries its level); cand_n[0] counts them all
-        hipLaunchKernelGGL(k_ak_candidates, grid(lw - 2 * lv.border, lh - 2 * lv.border), blk, 0, st, s->Ldet[i], lw, lh, lv.border, 0.001f, i, s->cand, s->cand_n, s->cand_cap);
+        hipLaunchKernelGGL(k_ak_candidates, grid(lw - 2 * lv.border, lh - 2 * lv.border), blk, 0, st, s->Ldet[i], lw, lh, lv.border, s->cfg.threshold, i, s->cand, s->cand_n, s->cand_cap);
     }
     if (ordered) {
         AkCandPlan P;
         memset(&P, 0, sizeof(P));
         for (int i = 0; i < s->n; i++) { P.ldet[i] = s->Ldet[i]; P.w[i] = s->lv[i].w; P.h[i] = s->lv[i].h; P.border[i] = s->lv[i].border; P.gx[i] = std::max(1, (s->lv[i].w - 2 * s->lv[i].border + 255) / 256); }
         for (int i = 0; i <= s->n; i++) P.blk_base[i] = s->blk_base[i];
-        P.n = s->n; P.thr = 0.001f;
+        P.n = s->n; P.thr = s->cfg.threshold;
         const int nblk = s->blk_base[s->n];
         if (nblk > 0) hipLaunchKernelGGL(k_ak_cand_count, dim3(nblk), blk, 0, st, P, s->d_blk);
         hipLaunchKernelGGL(k_ak_cand_scan, dim3(1), dim3(1024), 0, st, P, s->d_blk, nblk, s->cand_cap, s->d_sup);
@@ -979,12 +945,36 @@ uvo_status akaze_set_suppression(Ctx* c, int where)
     c->akaze_suppress = where;
     return UVO_OK;
 }
+// uvo_akaze_configure.  Everything made for the previous value goes from every lane: the level plan, the INTER_AREA tables and the captured
+// evolution graphs (threshold and conductance kernel are launch arguments recorded in them); the next detection makes them again, as
+// for a new image size.  The caller holds an idle context whose streams have drained.
+uvo_status akaze_configure(Ctx* c, int descriptor_type, int descriptor_size, int descriptor_channels, float threshold, int n_octaves, int n_octave_layers, int diffusivity)
+{
+    if (descriptor_type >= 2 && descriptor_type <= 4) {
+        c->err = "uvo_akaze_configure: descriptor_type 2 (DESCRIPTOR_KAZE_UPRIGHT), 3 (DESCRIPTOR_KAZE) and 4 (DESCRIPTOR_MLDB_UPRIGHT) are not implemented; served is 5 (DESCRIPTOR_MLDB)";
+        return UVO_INVALID_ARG;
+    }
+    if (descriptor_type != 5) { c->err = "uvo_akaze_configure: descriptor_type: served is 5 (DESCRIPTOR_MLDB) only"; return UVO_INVALID_ARG; }
+    if (descriptor_size != 0) { c->err = "uvo_akaze_configure: descriptor_size: served is 0 (the full 486 bits) only; descriptor subsets are not implemented"; return UVO_INVALID_ARG; }
+    if (descriptor_channels != 3) { c->err = "uvo_akaze_configure: descriptor_channels: served is 3 only; 1- and 2-channel M-LDB are not implemented"; return UVO_INVALID_ARG; }
+    if (!(threshold > 0.0f) || !(threshold <= FLT_MAX)) { c->err = "uvo_akaze_configure: threshold: served is any finite value > 0"; return UVO_INVALID_ARG; }
+    if (n_octaves < 1 || n_octaves > 4) { c->err = "uvo_akaze_configure: n_octaves: served are 1..4"; return UVO_INVALID_ARG; }
+    if (n_octave_layers < 1 || n_octave_layers > 4) { c->err = "uvo_akaze_configure: n_octave_layers: served are 1..4"; return UVO_INVALID_ARG; }
+    if (diffusivity < 0 || diffusivity > 3) { c->err = "uvo_akaze_configure: diffusivity: served are 0 (DIFF_PM_G1), 1 (DIFF_PM_G2), 2 (DIFF_WEICKERT) and 3 (DIFF_CHARBONNIER)"; return UVO_INVALID_ARG; }
+    AkazeCfg cfg;
+    cfg.threshold = threshold; cfg.n_octaves = n_octaves; cfg.n_octave_layers = n_octave_layers; cfg.diffusivity = diffusivity;
+    Ctx* m = c->sh->lanes[0];                                        // where akaze_ws reads it, for every lane
+    if (cfg == m->akaze_cfg) return UVO_OK;
+    m->akaze_cfg = cfg;
+    for (Ctx* l : c->sh->lanes) { if (l->akaze_ws && l->stream) (void)hipStreamSynchronize(l->stream); akaze_ws_free(l); }
+    return UVO_OK;
+}
 uvo_status akaze_detect(Ctx* c, const uint8_t* gray, int w, int h, int stride, int mem, uvo_keypoint* kps, uint8_t* desc, int cap, int* n_out)
 {
     *n_out = 0;
     if (w < 16 || h < 16 || w > c->max_w || h > c->max_h || stride < w) { c->err = "uvo_akaze_detect: image size outside the context's limits"; return UVO_INVALID_ARG; }
     AkazeWs* s = akaze_ws(c, w, h);
-    if (!s) { c->err = "AKAZE workspace allocation failed"; return UVO_HIP_ERROR; }
+    if (!s) return UVO_HIP_ERROR;                                    // (akaze_ws says why)
     hipStream_t st = c->stream;
     UVO_TRY(akaze_run(c, s, st, gray, w, h, stride, mem, true, akaze_where(c), nullptr, n_out));
     const int n = *n_out;
@@ -1003,7 +993,7 @@ uvo_status akaze_detect(Ctx* c, const uint8_t* gray, int w, int h, int stride, i
 uvo_status akaze_prepare_lane(Ctx* c, int w, int h)
 {
     AkazeWs* s = akaze_ws(c, w, h);
-    if (!s) { c->err = "AKAZE workspace allocation failed"; return UVO_HIP_ERROR; }
+    if (!s) return UVO_HIP_ERROR;                                    // (akaze_ws says why)
     if (akaze_use_graph()) UVO_TRY(akaze_capture(c, s, c->stream, akaze_where(c->sh->lanes[0])));
     return UVO_OK;
 }
@@ -1036,7 +1026,7 @@ uvo_status akaze_suppress(Ctx* c, int w, int h, const int* level, const int* x, 
     if (n > kAkCandCap) { c->err = "uvo_akaze_suppress: more candidates than the candidate list holds (262144)"; return UVO_INVALID_ARG; }
     if (n > 0 && (!level || !x || !y || !v9)) { c->err = "uvo_akaze_suppress: level, x, y and v9 are required"; return UVO_INVALID_ARG; }
     AkazeWs* s = akaze_ws(c, w, h);
-    if (!s) { c->err = "AKAZE workspace allocation failed"; return UVO_HIP_ERROR; }
+    if (!s) return UVO_HIP_ERROR;                                    // (akaze_ws says why)
     std::vector<AkCand> list((size_t)n);
     for (int q = 0; q < n; q++) {
         if (level[q] < 0 || level[q] >= s->n) { c->err = "uvo_akaze_suppress: a candidate's level is outside the image's plan"; return UVO_INVALID_ARG; }

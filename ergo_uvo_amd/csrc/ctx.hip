@@ -888,6 +888,16 @@ try {
     UVO_TRY(need_idle(c, "uvo_akaze_set_suppression"));
     return akaze_set_suppression(c, where);
 } UVO_ABI_CATCH(c)
+// AKAZE::create's arguments, in its order, for every AKAZE detection of the context: the operator, the hooks and the loops' lanes (the master
+// context's value serves them all, and uvo_ctx_set_params leaves it alone).  Refused while entries are in flight; a refusal changes nothing.
+extern "C" uvo_status uvo_akaze_configure(uvo_ctx* c, int descriptor_type, int descriptor_size, int descriptor_channels, float threshold, int n_octaves, int n_octave_layers, int diffusivity)
+try {
+    if (!c) return UVO_INVALID_ARG;
+    if (c->sh->n_pending != 0) return fail(c, UVO_INVALID_ARG, "uvo_akaze_configure: the configuration cannot change while pairs / frames are in flight (collect them first)");
+    (void)hipSetDevice(c->device);
+    sync_owned_streams(c);                                                   // the lanes' workspaces and captured graphs go: nothing queued may still use them
+    return akaze_configure(c, descriptor_type, descriptor_size, descriptor_channels, threshold, n_octaves, n_octave_layers, diffusivity);
+} UVO_ABI_CATCH(c)
 extern "C" uvo_status uvo_akaze_suppress(uvo_ctx* c, int w, int h, const int* level, const int* x, const int* y, const float* v9, int n, int where, uint8_t* marks,
                                          uvo_keypoint* kps, int cap, int* n_kps)
 try {

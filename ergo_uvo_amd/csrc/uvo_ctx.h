@@ -56,6 +56,12 @@ struct DetectSet {                    // one image's detector outputs (device)
     float* desc;                      // cap rows of 512 bytes: 64 / 128 floats, or a binary row as kBinRowWords words
     int* n;                           // device count (clamped to cap)
 };
+// AKAZE::create's detection arguments as uvo_akaze_configure took them (the descriptor arguments are served at their defaults only);
+// diffusivity: 0 DIFF_PM_G1, 1 DIFF_PM_G2, 2 DIFF_WEICKERT, 3 DIFF_CHARBONNIER
+struct AkazeCfg {
+    float threshold = 0.001f; int n_octaves = 4, n_octave_layers = 4, diffusivity = 1;
+    bool operator==(const AkazeCfg& o) const { return threshold == o.threshold && n_octaves == o.n_octaves && n_octave_layers == o.n_octave_layers && diffusivity == o.diffusivity; }
+};
 
 // What exists once per caller-held context: the sequence state of both loops, the rig, the pipeline's plan and FIFO, its streams and
 // knobs.  Every lane of the context points to the same object (Ctx::sh); lane 0 creates it and deletes it last.  Written by the thread
@@ -302,6 +308,7 @@ struct Ctx {
     void* orb_ws = nullptr;                      // OrbWs* (uvo_orb_detect): parameters, sampling table, buffers of the last image size
     void* akaze_ws = nullptr;                    // AkazeWs* (uvo_akaze_detect), allocated on first use per image size
     int akaze_suppress = -1;                     // uvo_akaze_set_suppression: 0 the host scans, 1 the device form; -1 = not asked yet (akaze.hip: the default, or UVO_AKAZE_SUPPRESS)
+    AkazeCfg akaze_cfg;                          // uvo_akaze_configure: AKAZE::create's detection arguments (the master context's serve every lane)
     void* sift_ws[2] = {nullptr, nullptr};       // SiftWs* per image slot (uvo_sift_detect uses slot 0), allocated on first use
     // the last frame's intermediates for uvo_mono_get: keypoints (det[0].kps), matches (d_matches[0]) and, after the device-resident pose
     // chain, the good points (d_good_pts[0]) stay in the lane's device buffers -- counts here -- until someone asks
@@ -467,6 +474,9 @@ uvo_status akaze_detect_lane(Ctx* c, int slot, int* n, const int** d_n, const in
 static const int kCandListOverflow = 0x7fffffff;
 static const char* const kAkazeCandOverflow = "AKAZE: more local maxima than the candidate list holds (a larger max_kpts does not help)";
 uvo_status akaze_set_suppression(Ctx* c, int where);
+// uvo_akaze_configure on the master context (idle, its streams drained by the caller): refuses by argument name, else stores the value
+// and frees every lane's workspace -- plan, INTER_AREA tables, captured graphs -- when it changed; the next detection rebuilds them
+uvo_status akaze_configure(Ctx* c, int descriptor_type, int descriptor_size, int descriptor_channels, float threshold, int n_octaves, int n_octave_layers, int diffusivity);
 uvo_status akaze_suppress(Ctx* c, int w, int h, const int* level, const int* x, const int* y, const float* v9, int n, int where, uint8_t* marks, uvo_keypoint* kps, int cap, int* n_kps);
 uvo_status akaze_stats(Ctx* c, int* n_candidates, int* rounds, int* host_waits);
 uvo_status sift_detect(Ctx* c, const uint8_t* gray, int w, int h, int stride, int mem, int nfeatures, int nL, double contrastThreshold,

@@ -81,6 +81,9 @@ struct State {
     bool orb_counts_sent = false;
     int akaze_suppression = -1;                   // set_akaze_suppression: 0 host, 1 device; -1 = the library's default
     bool akaze_suppression_sent = false;
+    struct AkazeArgs { int descriptor_type, descriptor_size, descriptor_channels; float threshold; int n_octaves, n_octave_layers, diffusivity; };
+    AkazeArgs akaze_args = { 5, 0, 3, 0.001f, 4, 4, 1 };   // configure_akaze: AKAZE::create's arguments
+    bool akaze_args_set = false, akaze_args_sent = false;  // ... given at all (else the library's defaults stand); handed to the current context
     int mono_pose_stage = -1;                     // set_mono_pose_stage: 0 the definition's routes, 1 every attempt resident; -1 = the library's default
     bool mono_pose_stage_sent = false;
 } g;
@@ -171,7 +174,7 @@ void shutdown()
 {
     std::lock_guard<std::mutex> lk(g.mu);
     if (g.ctx) { uvo_ctx_destroy(g.ctx); g.ctx = nullptr; }
-    g.orb_pattern_sent = false; g.orb_ranking_sent = false; g.orb_counts_sent = false; g.akaze_suppression_sent = false; g.mono_pose_stage_sent = false; g.pnp_method = 1;
+    g.orb_pattern_sent = false; g.orb_ranking_sent = false; g.orb_counts_sent = false; g.akaze_suppression_sent = false; g.akaze_args_sent = false; g.mono_pose_stage_sent = false; g.pnp_method = 1;
 }
 void set_orb_ranking(int where)
 {
@@ -193,6 +196,16 @@ void set_akaze_suppression(int where)
     std::lock_guard<std::mutex> lk(g.mu);
     g.akaze_suppression = where;
     g.akaze_suppression_sent = false;
+}
+void configure_akaze(int descriptor_type, int descriptor_size, int descriptor_channels, float threshold, int nOctaves, int nOctaveLayers, int diffusivity)
+{
+    std::lock_guard<std::mutex> lk(g.mu);
+    const State::AkazeArgs a = { descriptor_type, descriptor_size, descriptor_channels, threshold, nOctaves, nOctaveLayers, diffusivity };
+    // a living context hears it now, so that a refusal (the library's, by argument name) comes from this call and leaves the kept value alone
+    if (g.ctx) SHIM_TRY(uvo_akaze_configure(g.ctx, a.descriptor_type, a.descriptor_size, a.descriptor_channels, a.threshold, a.n_octaves, a.n_octave_layers, a.diffusivity), "uvo_akaze_configure");
+    g.akaze_args = a;
+    g.akaze_args_set = true;
+    g.akaze_args_sent = g.ctx != nullptr;
 }
 void check_outlier_methods()
 {
@@ -388,6 +401,11 @@ static void akaze_suppression_to(uvo_ctx* c)
 {
     std::lock_guard<std::mutex> lk(g.mu);
     if (g.akaze_suppression >= 0 && !g.akaze_suppression_sent) { SHIM_TRY(uvo_akaze_set_suppression(c, g.akaze_suppression), "uvo_akaze_set_suppression"); g.akaze_suppression_sent = true; }
+    if (g.akaze_args_set && !g.akaze_args_sent) {
+        const State::AkazeArgs& a = g.akaze_args;
+        SHIM_TRY(uvo_akaze_configure(c, a.descriptor_type, a.descriptor_size, a.descriptor_channels, a.threshold, a.n_octaves, a.n_octave_layers, a.diffusivity), "uvo_akaze_configure");
+        g.akaze_args_sent = true;
+    }
 }
 static void orb_pattern_to(uvo_ctx* c)
 {

@@ -166,13 +166,25 @@ uvo_status uvo_surf_set_detection_path(uvo_ctx* c, int which);
 uvo_status uvo_sift_detect(uvo_ctx* c, const uint8_t* gray, int w, int h, int stride, int mem, int nfeatures, int n_octave_layers,
                            double contrast_threshold, double edge_threshold, double sigma, uvo_keypoint* kps, float* desc, int cap, int* n);
 /* detect_features, FEATURE_DETECTOR == "AKAZE" (VO_utility.cpp:93-98): AKAZE::create()->detectAndCompute(img, noArray(), keypoints,
- * descriptors) -- DESCRIPTOR_MLDB at full length (486 bits: rows of 61 bytes, for uvo_match_knn2_ratio_hamming), 3 channels, threshold
- * 0.001, 4 octaves of 4 sublevels, DIFF_PM_G2.  Keypoints in OpenCV's order (evolution level by level, row-major), `size` the diameter,
+ * descriptors) -- DESCRIPTOR_MLDB at full length (486 bits: rows of 61 bytes, for uvo_match_knn2_ratio_hamming), 3 channels; threshold
+ * 0.001, 4 octaves of 4 sublevels, DIFF_PM_G2 unless uvo_akaze_configure said otherwise.  Keypoints in OpenCV's order (evolution level by level, row-major), `size` the diameter,
  * `angle` in degrees, `class_id` the evolution level.  The non-linear scale space, the Hessian response, orientation and descriptors run
  * on the device; the contrast factor, the sequential duplicate suppression of Find_Scale_Space_Extrema and the sub-pixel refinement run
  * over the candidate list on the host or on the device (uvo_akaze_set_suppression; this operator then waits once, for the count that
  * sizes its buffers, instead of three times).  The fused steps take the same detector after uvo_ctx_set_loop_detector(c, "AKAZE"). */
 uvo_status uvo_akaze_detect(uvo_ctx* c, const uint8_t* gray, int w, int h, int stride, int mem, uvo_keypoint* kps, uint8_t* desc, int cap, int* n);
+/* AKAZE::create(descriptor_type, descriptor_size, descriptor_channels, threshold, nOctaves, nOctaveLayers, diffusivity), in its argument
+ * order, for every AKAZE detection of the context: uvo_akaze_detect, uvo_akaze_suppress, uvo_akaze_plane, uvo_akaze_stats and the fused,
+ * frames and compressed steps after uvo_ctx_set_loop_detector(c, "AKAZE") (the master context's value serves every pipeline lane).
+ * Served: descriptor_type 5 (DESCRIPTOR_MLDB), descriptor_size 0, descriptor_channels 3 and only these (types 2, 3 and 4 -- the KAZE
+ * and upright descriptors -- are not implemented); threshold finite and > 0; n_octaves 1..4; n_octave_layers 1..4; diffusivity 0
+ * (DIFF_PM_G1), 1 (DIFF_PM_G2), 2 (DIFF_WEICKERT), 3 (DIFF_CHARBONNIER).  Anything else is UVO_INVALID_ARG with a message that names the
+ * argument and what is served; nothing is replaced silently, and a refused call leaves the configuration as it was.  Refused while
+ * entries are in flight.  A new value drops the level plan, the INTER_AREA tables and the captured evolution graphs of every lane; the
+ * next detection makes them again, as for a new image size.  uvo_ctx_set_params leaves the value alone.  A context that was never
+ * configured behaves as one configured with (5, 0, 3, 0.001f, 4, 4, 1). */
+uvo_status uvo_akaze_configure(uvo_ctx* c, int descriptor_type, int descriptor_size, int descriptor_channels, float threshold,
+                               int n_octaves, int n_octave_layers, int diffusivity);
 /* Where AKAZE's sequential stages run: 0 = the host scans of the candidate list (the definition), 1 = the device (default): the contrast
  * factor by one small kernel, the candidates emitted in visiting order, the three suppression phases as rounds of one workgroup per level,
  * the refinement compacted in candidate order.  The results do not depend on the value.  Anything else is UVO_INVALID_ARG; refused while

@@ -96,6 +96,13 @@ void     set_orb_counts(int where);
 // where the "AKAZE" branch's contrast factor, duplicate suppression and refinement run: 1 the device, 0 the host scans
 // (uvo_akaze_set_suppression); results do not depend on it.  Kept across a rebuilt context.
 void     set_akaze_suppression(int where);
+// AKAZE::create's arguments, in its order (uvo_akaze_configure), for the "AKAZE" branch of detect_features, loop_set_detector and the node
+// classes: descriptor_type 5 (DESCRIPTOR_MLDB), descriptor_size 0 and descriptor_channels 3 only; threshold finite and > 0; nOctaves 1..4;
+// nOctaveLayers 1..4; diffusivity 0 (DIFF_PM_G1), 1 (DIFF_PM_G2), 2 (DIFF_WEICKERT), 3 (DIFF_CHARBONNIER).  Anything else throws uvo_hip::Error
+// with the library's message -- from this call when a context lives, else from the first call that makes one and takes the AKAZE branch.
+// Kept across a rebuilt context and sent before the first detection.  Not called: AKAZE::create()'s defaults.
+void     configure_akaze(int descriptor_type = 5, int descriptor_size = 0, int descriptor_channels = 3, float threshold = 0.001f,
+                         int nOctaves = 4, int nOctaveLayers = 4, int diffusivity = 1);
 // where estimate_relative_pose's attempts run (uvo_mono_set_pose_stage): 1 every attempt a device-resident chain,
 // 0 only a first attempt with the essential matrix, the rest through the host-pointer operators (the definition, the library's default); results do not depend
 // on it.  Sent to the context at its next use (refused there while frames are in flight).  Kept across a rebuilt context.
