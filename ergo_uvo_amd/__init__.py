@@ -561,6 +561,31 @@ class Context:
         self._check(self._lib.uvo_extract_3d_points(self._h, _p(k1), _p(k2), n, *[_p(x) for x in a], _p(p4), _p(pts), _p(idx), C.byref(g)))
         return pts[:g.value].copy(), idx[:g.value].copy()
 
+    EXTRACT3D_ROUTES = {0: "tree", 1: "ordered", -1: None}
+
+    def extract_3Dpoints_route(self):
+        """Test hook (uvo_extract_3d_route): which sums decided the +-3 sigma set of the last extract_3Dpoints / extract_3Dpoints_rows
+        call -- "tree", "ordered" (the sums in index order), or None when the filter did not run."""
+        r = C.c_int(0)
+        self._check(self._lib.uvo_extract_3d_route(self._h, C.byref(r)))
+        return self.EXTRACT3D_ROUTES[r.value]
+
+    def extract_3Dpoints_rows(self, points4D, k1, k2, R1, t1, R2, t2, K1, K2, matches, keypoints):
+        """Test hook (uvo_extract_3d_rows): extract_3Dpoints as the stereo loop runs it, on rows of the caller's.  points4D 4 x n_rows,
+        k1 / k2 the rows' image points; matches (DM_DTYPE): queryIdx a row, trainIdx an index into keypoints (KP_DTYPE).  Returns
+        (good_idx into matches, good_pts G x 3 f64, object points G x 3 f32, image points G x 2 f32, route)."""
+        k1, k2 = _np(k1, np.float32), _np(k2, np.float32)
+        p4 = _np(points4D, np.float32)
+        m, kp = _np(matches, DM_DTYPE), _np(keypoints, KP_DTYPE)
+        a = [_np(x, np.float64) for x in (R1, t1, R2, t2, K1, K2)]
+        n = max(len(m), 1)
+        idx, pts, opts, ipts = np.empty(n, np.int32), np.empty((n, 3)), np.empty((n, 3), np.float32), np.empty((n, 2), np.float32)
+        g, r = C.c_int(0), C.c_int(0)
+        self._check(self._lib.uvo_extract_3d_rows(self._h, _p(p4), _p(k1), _p(k2), len(k1), *[_p(x) for x in a], _p(m), len(m), _p(kp), len(kp),
+                                                  _p(idx), _p(pts), _p(opts), _p(ipts), C.byref(g), C.byref(r)))
+        G = g.value
+        return idx[:G].copy(), pts[:G].copy(), opts[:G].copy(), ipts[:G].copy(), self.EXTRACT3D_ROUTES[r.value]
+
     def reproject_errors(self, world_points, R, t, K, img_points):
         w, img = _np(world_points, np.float64), _np(img_points, np.float32)
         R, t, K = _np(R, np.float64), _np(t, np.float64), _np(K, np.float64)

@@ -19,7 +19,7 @@ LACKS = frozenset(n for n in os.environ.get("UVO_HIP_LIB_LACKS", "").split(",") 
 EXPORTS = [
     "uvo_params_default_stereo", "uvo_params_default_mono", "uvo_ctx_create", "uvo_ctx_destroy", "uvo_last_error",
     "uvo_ctx_stream", "uvo_ctx_set_params", "uvo_ctx_set_feature_detector", "uvo_ctx_set_loop_detector", "uvo_ctx_set_pnp_method", "uvo_ctx_set_producer_stream", "uvo_device_alloc", "uvo_device_free", "uvo_device_download", "uvo_ctx_warning", "uvo_ctx_pending", "uvo_ctx_host_policy", "uvo_surf_detect", "uvo_surf_set_detection_path", "uvo_sift_detect", "uvo_sift_layer", "uvo_akaze_detect", "uvo_akaze_configure", "uvo_akaze_plane", "uvo_akaze_set_suppression", "uvo_akaze_suppress", "uvo_akaze_stats", "uvo_orb_configure", "uvo_orb_set_pattern", "uvo_orb_set_ranking", "uvo_orb_set_counts", "uvo_orb_stats", "uvo_retain_best", "uvo_orb_detect", "uvo_orb_plane", "uvo_integral", "uvo_hessian_layer",
-    "uvo_match_knn2_ratio", "uvo_match_knn2", "uvo_match_knn2_ratio_dim", "uvo_match_knn2_dim", "uvo_match_knn2_ratio_hamming", "uvo_match_knn2_hamming", "uvo_match_loop_knn2", "uvo_triangulate_points", "uvo_extract_3d_points",
+    "uvo_match_knn2_ratio", "uvo_match_knn2", "uvo_match_knn2_ratio_dim", "uvo_match_knn2_dim", "uvo_match_knn2_ratio_hamming", "uvo_match_knn2_hamming", "uvo_match_loop_knn2", "uvo_triangulate_points", "uvo_extract_3d_points", "uvo_extract_3d_rows", "uvo_extract_3d_route",
     "uvo_solve_pnp_ransac", "uvo_reproject_errors", "uvo_rodrigues", "uvo_stereo_set_rig", "uvo_stereo_reset", "uvo_stereo_step",
     "uvo_stereo_set_depth", "uvo_stereo_submit", "uvo_stereo_collect",
     "uvo_stereo_get", "uvo_find_essential_mat", "uvo_five_point_models", "uvo_solve_poly10", "uvo_homography_models", "uvo_homography_fit_all", "uvo_mono_method_refusal", "uvo_recover_pose", "uvo_find_homography", "uvo_decompose_homography_mat",
@@ -90,6 +90,9 @@ def lib() -> C.CDLL:
         _lib.uvo_akaze_suppress.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         _lib.uvo_akaze_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         for name, sig in (("uvo_mono_set_pose_stage", [C.c_void_p, C.c_int]), ("uvo_mono_pose_stats", [C.c_void_p] * 6)):
+            if name not in LACKS:
+                getattr(_lib, name).argtypes = sig
+        for name, sig in (("uvo_extract_3d_rows", [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 7 + [C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 6), ("uvo_extract_3d_route", [C.c_void_p] * 2)):
             if name not in LACKS:
                 getattr(_lib, name).argtypes = sig
         _lib.uvo_retain_best.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]

@@ -282,7 +282,7 @@ static uvo_status create_one(const uvo_params* p, int device, int max_w, int max
     A(dalloc(&c->d_DW, 400)); A(dalloc(&c->d_rank, cap * 2)); A(dalloc(&c->d_big_par, cap * 4)); A(dalloc(&c->d_big_patch, cap * 2 * 448));
     A(dalloc(&c->d_mpart, 2 * nchunks * cap)); A(dalloc(&c->d_mscratch, 2 * (nchunks + 4))); A(dalloc(&c->d_knn_idx, 2 * cap * 2)); A(dalloc(&c->d_knn_dist, 2 * cap * 2));
     A(dalloc(&c->d_x1, cap)); A(dalloc(&c->d_x2, cap)); A(dalloc(&c->d_xc, cap)); A(dalloc(&c->d_pts4, cap));
-    A(dalloc(&c->d_cam1, cap * 3)); A(dalloc(&c->d_flag, cap)); A(dalloc(&c->d_tmp_idx, cap)); A(dalloc(&c->d_tmp_row, cap));
+    A(dalloc(&c->d_cam1, cap * 3)); A(dalloc(&c->d_flag, cap)); A(dalloc(&c->d_tmp_idx, cap)); A(dalloc(&c->d_tmp_row, cap)); A(dalloc(&c->d_ex3_route, (size_t)1));
     if (const char* ww = getenv("UVO_WORKER_WAIT")) c->worker_wait = !strcmp(ww, "spin") ? 0 : (!strcmp(ww, "block-all") ? 2 : ((!strcmp(ww, "sleep") || !strcmp(ww, "block")) ? 3 : 1));
     c->wait_eff.store(c->worker_wait == 0 ? 0 : (c->worker_wait == 2 ? 2 : 1), std::memory_order_relaxed);      // auto: decided by set_depth (apply_wait_policy)
     A(hipEventCreateWithFlags(&c->evBlock, hipEventDisableTiming | hipEventBlockingSync));
@@ -524,7 +524,7 @@ static void destroy_one(uvo_ctx* c)
     akaze_ws_free(c);
     orb_ws_free(c);
     void* ptrs[] = { c->d_hess_order, c->d_gen_tab, c->d_gen_planes, c->d_surv, c->d_octpat, c->d_colpart, c->d_DW, c->d_rank, c->d_big_par, c->d_big_patch, c->d_area_tabs, c->d_area_iscale, c->d_ori_w, c->d_mpart, c->d_mscratch, c->d_knn_idx, c->d_knn_dist, c->d_x1, c->d_x2, c->d_xc, c->d_pts4, c->d_cam1,
-                     c->d_flag, c->d_tmp_idx, c->d_tmp_row, c->d_good_pts[0], c->d_good_pts[1], c->d_good_idx[0], c->d_good_idx[1], c->d_opts[0], c->d_opts[1],
+                     c->d_flag, c->d_tmp_idx, c->d_tmp_row, c->d_ex3_route, c->d_good_pts[0], c->d_good_pts[1], c->d_good_idx[0], c->d_good_idx[1], c->d_opts[0], c->d_opts[1],
                      c->d_ipts[0], c->d_ipts[1], c->d_counts, c->d_countsB, c->d_subsets, c->d_models,
                      c->d_hcount, c->d_inliers, c->d_refit, c->d_pose };
     for (void* p : ptrs) (void)hipFree(p);
@@ -1208,6 +1208,7 @@ try {
     (void)hipSetDevice(c->device);
     *g = 0;
     UVO_TRY(need_idle(c, "uvo_extract_3d_points"));
+    c->ex3_route = -1;
     if (n == 0) return UVO_OK;
     if (n > c->cap) return fail(c, UVO_CAPACITY, "point count exceeds the context's max_kpts");
     std::vector<float4> tmp(n);
@@ -1216,7 +1217,9 @@ try {
     UVO_HIP_TRY(c, hipMemcpyAsync(c->d_x1, k1, sizeof(uvo_point2f) * n, hipMemcpyHostToDevice, c->stream));
     UVO_HIP_TRY(c, hipMemcpyAsync(c->d_x2, k2, sizeof(uvo_point2f) * n, hipMemcpyHostToDevice, c->stream));
     UVO_HIP_TRY(c, hipMemcpyAsync(c->d_xc, k1, sizeof(uvo_point2f) * n, hipMemcpyHostToDevice, c->stream));
-    UVO_TRY(pose_extract3d(c, 0, R1, t1, R2, t2, K1, K2, nullptr, n));
+    UVO_HIP_TRY(c, hipMemsetAsync(c->d_ex3_route, 0xff, sizeof(int), c->stream));      // -1: the filter did not run
+    UVO_TRY(pose_extract3d(c, 0, R1, t1, R2, t2, K1, K2, nullptr, n, c->d_ex3_route));
+    UVO_HIP_TRY(c, hipMemcpyAsync(&c->ex3_route, c->d_ex3_route, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     UVO_TRY(read_counts(c));
     int G = c->h_counts[CN_G];
     if (G) {
@@ -2034,6 +2037,53 @@ try {
     (void)hipSetDevice(c->device);
     UVO_TRY(need_idle(c, "uvo_homography_fit_all"));
     return mono_homography_fit_all(c, src, dst, n, where, H, ok);
+} UVO_ABI_CATCH(c)
+// test hook: the stereo loop's extract_3Dpoints (workgroup 0 of k_stereo_tail, launched as pose_stereo_tail launches it) on rows and matches of the caller's
+extern "C" uvo_status uvo_extract_3d_rows(uvo_ctx* c, const float* points4d, const uvo_point2f* k1, const uvo_point2f* k2, int n_rows,
+                                          const double* R1, const double* t1, const double* R2, const double* t2, const double* K1, const double* K2,
+                                          const uvo_dmatch* matches, int n_matches, const uvo_keypoint* kps, int n_kps,
+                                          int* idx, double* pts, float* opts, uvo_point2f* ipts, int* g, int* route)
+try {
+    if (!c || !points4d || !k1 || !k2 || !R1 || !t1 || !R2 || !t2 || !K1 || !K2 || !matches || !kps || !idx || !pts || !opts || !ipts || !g || !route ||
+        n_rows < 1 || n_matches < 1 || n_kps < 1) return UVO_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    *g = 0; *route = -1;
+    UVO_TRY(need_idle(c, "uvo_extract_3d_rows"));
+    if (const char* why = pose_extract3d_rows_refusal(c)) return fail(c, UVO_CAPACITY, why);      // before anything is staged in the loop's buffers
+    if (n_rows > c->cap || n_matches > c->cap || n_kps > c->cap) return fail(c, UVO_CAPACITY, "uvo_extract_3d_rows: a count exceeds the context's max_kpts");
+    for (int i = 0; i < n_matches; i++)
+        if (matches[i].queryIdx < 0 || matches[i].queryIdx >= n_rows || matches[i].trainIdx < 0 || matches[i].trainIdx >= n_kps)
+            return fail(c, UVO_INVALID_ARG, "uvo_extract_3d_rows: a match points outside the rows or the keypoints");
+    std::vector<float4> tmp(n_rows);
+    for (int i = 0; i < n_rows; i++) tmp[i] = make_float4(points4d[i], points4d[n_rows + i], points4d[2*n_rows + i], points4d[3*n_rows + i]);
+    UVO_HIP_TRY(c, hipMemcpyAsync(c->d_as_pts4[0], tmp.data(), sizeof(float4) * n_rows, hipMemcpyHostToDevice, c->stream));
+    UVO_HIP_TRY(c, hipMemcpyAsync(c->d_x1, k1, sizeof(uvo_point2f) * n_rows, hipMemcpyHostToDevice, c->stream));
+    UVO_HIP_TRY(c, hipMemcpyAsync(c->d_x2, k2, sizeof(uvo_point2f) * n_rows, hipMemcpyHostToDevice, c->stream));
+    UVO_HIP_TRY(c, hipMemcpyAsync(c->d_matches[1], matches, sizeof(uvo_dmatch) * n_matches, hipMemcpyHostToDevice, c->stream));
+    UVO_HIP_TRY(c, hipMemcpyAsync(c->det[0].kps, kps, sizeof(uvo_keypoint) * n_kps, hipMemcpyHostToDevice, c->stream));
+    UVO_HIP_TRY(c, hipMemcpyAsync(c->d_counts + CN_T, &n_matches, sizeof(int), hipMemcpyHostToDevice, c->stream));
+    UVO_HIP_TRY(c, hipMemsetAsync(c->d_ex3_route, 0xff, sizeof(int), c->stream));      // -1: the filter did not run
+    UVO_TRY(pose_extract3d_rows(c, n_rows, R1, t1, R2, t2, K1, K2, c->d_ex3_route));
+    UVO_HIP_TRY(c, hipMemcpyAsync(&c->ex3_route, c->d_ex3_route, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    UVO_TRY(read_counts(c));
+    const int G = c->h_counts[CN_G];
+    if (G < 0 || G > n_matches) return fail(c, UVO_HIP_ERROR, "uvo_extract_3d_rows: the kernel's count is outside the matches");
+    if (G) {
+        UVO_HIP_TRY(c, hipMemcpyAsync(idx, c->d_good_idx[0], sizeof(int) * G, hipMemcpyDeviceToHost, c->stream));
+        UVO_HIP_TRY(c, hipMemcpyAsync(pts, c->d_good_pts[0], sizeof(double) * 3 * G, hipMemcpyDeviceToHost, c->stream));
+        UVO_HIP_TRY(c, hipMemcpyAsync(opts, c->d_opts[0], sizeof(float) * 3 * G, hipMemcpyDeviceToHost, c->stream));
+        UVO_HIP_TRY(c, hipMemcpyAsync(ipts, c->d_ipts[0], sizeof(uvo_point2f) * G, hipMemcpyDeviceToHost, c->stream));
+        UVO_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    *g = G; *route = c->ex3_route;
+    return stereo_reset_body(c);                       // the staging went through the loop's buffers: whatever set it held is gone
+} UVO_ABI_CATCH(c)
+// which sums decided the +-3 sigma set of the context's last uvo_extract_3d_points / uvo_extract_3d_rows call
+extern "C" uvo_status uvo_extract_3d_route(uvo_ctx* c, int* route)
+try {
+    if (!c || !route) return UVO_INVALID_ARG;
+    *route = c->ex3_route;
+    return UVO_OK;
 } UVO_ABI_CATCH(c)
 extern "C" uvo_status uvo_recover_pose(uvo_ctx* c, const double* E, const uvo_point2f* p1, const uvo_point2f* p2, int n, const double* K,
                                        double* R, double* t, uint8_t* mask, int* good)

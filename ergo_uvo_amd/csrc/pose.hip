@@ -68,7 +68,10 @@ struct Ex3Lane { const double* cam1; const int* flag; const uvo_point2f* xc; con
                  uvo_point2f* ipts; int* counts /* [1] = G */; int* counts_host /* pinned mirror of all the step's counters, or null */;
                  // the stereo loop's tail (k_stereo_tail): point i is row map[i].queryIdx of cam1 / flag / pts4 (the previous pair's set, triangulated
                  // row by row in that pair's own tail) and its current-image point is keypoint map[i].trainIdx of cL; null: point i is row i
-                 const uvo_dmatch* map; const uvo_keypoint* cL; const float4* pts4; float4* out_pts4; int* tmp_row; };
+                 const uvo_dmatch* map; const uvo_keypoint* cL; const float4* pts4; float4* out_pts4; int* tmp_row;
+                 // which sums decided the +-3 sigma set: 0 the tree sums, 1 the ordered chains; left alone when the filter did not run
+                 // (too few points).  Null in the loops; the operator and the rows test entry pass a word (uvo_extract_3d_route)
+                 int* route; };
 // cv::triangulatePoints for one point pair, by thread threadIdx.x < TT of its workgroup (the 4x4 Jacobi SVD's operands live in
 // LDS, one column of `lds` per thread)
 static const int kTriLdsDoubles = (16 + 16 + 16 + 4 + 4) * kTriThreads;
@@ -242,6 +245,7 @@ __device__ __forceinline__ void extract3d_block(const Ex3Lane& LN, int n_imm, in
             if (near) sm.s_need_seq = 1;                     // (benign race: every writer stores 1, a late reader skips a scan that could only store 1)
         }
         __syncthreads();
+        if (LN.route && tid == 0) *LN.route = sm.s_need_seq;
     }
     if (sm.s_need_seq)
     {   // MU:35-56: sum and sum of squares in index order.  z and z*z are staged through LDS in chunks; the two sequential chains run
@@ -420,6 +424,7 @@ __device__ __forceinline__ void extract3d_rows(const Ex3Lane& LN, int min_pts, i
         if (near) sm.s_need_seq = 1;
         __syncthreads();
     }
+    if (LN.route && tid == 0) *LN.route = sm.s_need_seq;
     if (sm.s_need_seq) {
         // MU:35-56: the sum and the sum of squares in index order decide.  The members' depths go to scratch (the output buffer, not
         // yet written) in compaction order and through LDS in chunks; the two chains run on one lane of two different waves.
@@ -1087,7 +1092,7 @@ static Cam make_cam(const double* R, const double* t, const double* K)
 }
 
 uvo_status pose_extract3d(Ctx* c, int slot, const double* R1, const double* t1, const double* R2, const double* t2,
-                          const double* K1, const double* K2, const int* d_n, int n_max)
+                          const double* K1, const double* K2, const int* d_n, int n_max, int* d_route)
 {
     int* counts_host = nullptr;
     StageTimer t(c, ST_EXTRACT3D);
@@ -1095,7 +1100,38 @@ uvo_status pose_extract3d(Ctx* c, int slot, const double* R1, const double* t1, 
         hipLaunchKernelGGL(k_extract3d_a, dim3((n_max + 255) / 256), dim3(256), 0, c->stream, c->d_pts4, c->d_x1, c->d_x2,
                            make_cam(R1, t1, K1), make_cam(R2, t2, K2), c->p.REPROJECTION_TOLERANCE, d_n, n_max, c->d_cam1, c->d_flag);
     }
-    hipLaunchKernelGGL(k_extract3d_b, dim3(1), dim3(1024), 0, c->stream, ex3_lane(c, slot, d_n, counts_host), n_max, c->p.MIN_NUM_3DPOINTS, extract3d_force_seq());
+    Ex3Lane e = ex3_lane(c, slot, d_n, counts_host);
+    e.route = d_route;
+    hipLaunchKernelGGL(k_extract3d_b, dim3(1), dim3(1024), 0, c->stream, e, n_max, c->p.MIN_NUM_3DPOINTS, extract3d_force_seq());
+    UVO_HIP_TRY(c, hipGetLastError());
+    return UVO_OK;
+}
+
+// test hook (uvo_extract_3d_rows): the stereo loop's extract_3Dpoints -- workgroup 0 of k_stereo_tail, launched with that role alone -- on
+// rows of the caller's.  Staged by the caller on c->stream: the n_rows homogeneous points in d_as_pts4[0] and their image points in
+// d_x1 / d_x2, the n_matches matches in d_matches[1] with their count in d_counts[CN_T], the keypoints they name in det[0].kps.  The
+// per-row half runs as in the loop (extract3d_point, into d_as_cam1[0] / d_as_flag[0]); the lane is the one pose_stereo_tail builds,
+// plus the route word.  Outputs in slot 0 and d_counts[CN_G].
+const char* pose_extract3d_rows_refusal(const Ctx* c)
+{
+    return c->cap > kEx3Passes * kTailThreads ? "uvo_extract_3d_rows: the rows form serves contexts of up to 8192 keypoints (larger ones run k_extract3d_b)" : nullptr;
+}
+uvo_status pose_extract3d_rows(Ctx* c, int n_rows, const double* R1, const double* t1, const double* R2, const double* t2,
+                               const double* K1, const double* K2, int* d_route)
+{
+    if (const char* why = pose_extract3d_rows_refusal(c)) { c->err = why; return UVO_CAPACITY; }
+    const Cam c1 = make_cam(R1, t1, K1), c2 = make_cam(R2, t2, K2);
+    StageTimer t(c, ST_EXTRACT3D);
+    if (n_rows > 0)
+        hipLaunchKernelGGL(k_extract3d_a, dim3((n_rows + 255) / 256), dim3(256), 0, c->stream, c->d_as_pts4[0], c->d_x1, c->d_x2,
+                           c1, c2, c->p.REPROJECTION_TOLERANCE, nullptr, n_rows, c->d_as_cam1[0], c->d_as_flag[0]);
+    int* cn = c->d_counts;
+    TailArgs ta{};
+    ta.cn = cn; ta.fused = 1;                              // no triangulation, match-order or gather workgroups: the grid is workgroup 0
+    ta.ex = Ex3Lane{ c->d_as_cam1[0], c->d_as_flag[0], nullptr, cn + CN_T, c->d_tmp_idx, c->d_good_pts[0], c->d_good_idx[0], c->d_opts[0], c->d_ipts[0],
+                     cn, nullptr, c->d_matches[1], c->det[0].kps, c->d_as_pts4[0], nullptr, c->d_tmp_row, d_route };
+    hipLaunchKernelGGL(k_stereo_tail, dim3(1), dim3(kTailThreads), 0, c->stream, Mat34(), Mat34(), c1, c2, c->p.REPROJECTION_TOLERANCE, ta,
+                       c->p.MIN_NUM_3DPOINTS, extract3d_force_seq());
     UVO_HIP_TRY(c, hipGetLastError());
     return UVO_OK;
 }

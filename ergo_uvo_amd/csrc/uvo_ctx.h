@@ -213,7 +213,8 @@ struct Ctx {
     float* d_opts[2] = {nullptr, nullptr};  uvo_point2f* d_ipts[2] = {nullptr, nullptr};      // G x 3 f32 object points, G image points
     int* d_tmp_idx = nullptr;                    // extract_3Dpoints scratch
     int* d_tmp_row = nullptr;                    // the same, rows of the previous set (k_stereo_tail)
-    int* d_counts = nullptr;                     // misc device counters: [0]=T, [1]=G, [2]=n_inliers, ...
+    int* d_ex3_route = nullptr; int ex3_route = -1;   // which sums decided the last operator call's +-3 sigma set (uvo_extract_3d_route), device word / its value
+    int* d_counts = nullptr;                    // misc device counters: [0]=T, [1]=G, [2]=n_inliers, ...
     int* h_counts = nullptr;                     // pinned mirror
 
     // ---- PnP RANSAC ----
@@ -411,7 +412,10 @@ uvo_status pose_triangulate_extract3d_pick(Ctx* c, const double* P1, const doubl
                                            const int* d_best, const uvo_point2f* d_in1, const uvo_point2f* d_in2, const int* d_n, int n_max);
 uvo_status pose_h_vote(Ctx* c, const double* P1, const double* P2x4, int ncand, const uvo_point2f* d_x1, const uvo_point2f* d_x2, int n, float* d_zrows, int row_stride);
 uvo_status pose_extract3d(Ctx* c, int slot, const double* R1, const double* t1, const double* R2, const double* t2,
-                          const double* K1, const double* K2, const int* d_n, int n_max);
+                          const double* K1, const double* K2, const int* d_n, int n_max, int* d_route = nullptr);   // d_route: Ex3Lane::route
+const char* pose_extract3d_rows_refusal(const Ctx* c);      // why this context cannot run the rows form (its capacity), or null: asked before anything is staged
+uvo_status pose_extract3d_rows(Ctx* c, int n_rows, const double* R1, const double* t1, const double* R2, const double* t2,
+                               const double* K1, const double* K2, int* d_route);
 uvo_status pose_reproject_errors(Ctx* c, const double* world, int n, const double* R, const double* t, const double* K,
                                  const uvo_point2f* img, double* err);
 struct PnpResult { uvo_status st; int wrote, ok, ninl; double rvec[3], tvec[3]; };

@@ -304,6 +304,21 @@ uvo_status uvo_extract_3d_points(uvo_ctx* c, const uvo_point2f* k1, const uvo_po
                                  const double* K1, const double* K2, const float* points4d,
                                  double* pts, int* idx, int* g);
 
+/* test hook: extract_3Dpoints as the stereo loop runs it -- one small workgroup of the loop's tail launch, which reads its points through
+ * the triangular matches -- on rows of the caller's (idle contexts of at most 8192 keypoints; UVO_CAPACITY above).  points4d: 4 x n_rows
+ * f32, k1 / k2: the rows' two image points (host); R1 .. K2 and the thresholds as uvo_extract_3d_points.  matches: n_matches DMatch,
+ * queryIdx a row, trainIdx an index into kps (n_kps KeyPoint, host); point i of the filter is row matches[i].queryIdx.  Outputs (host,
+ * capacity n_matches): idx (positions in `matches`), pts g x 3 f64, opts g x 3 f32 (solvePnPRansac's object points), ipts g Point2f
+ * (the keypoints of trainIdx).  *route as uvo_extract_3d_route.  Resets the stereo loop (its buffers carry the rows). */
+uvo_status uvo_extract_3d_rows(uvo_ctx* c, const float* points4d, const uvo_point2f* k1, const uvo_point2f* k2, int n_rows,
+                               const double* R1, const double* t1, const double* R2, const double* t2, const double* K1, const double* K2,
+                               const uvo_dmatch* matches, int n_matches, const uvo_keypoint* kps, int n_kps,
+                               int* idx, double* pts, float* opts, uvo_point2f* ipts, int* g, int* route);
+/* test hook: which sums decided the +-3 sigma set of the context's last uvo_extract_3d_points / uvo_extract_3d_rows call: 0 the tree
+ * sums (no depth within their error radius of a threshold), 1 the sums in index order (math_utility.cpp:35-56), -1 the filter did
+ * not run (fewer than MIN_NUM_3DPOINTS points). */
+uvo_status uvo_extract_3d_route(uvo_ctx* c, int* route);
+
 /* ---- reproject_errors (VO_utility.h:112 -> VO_utility.cpp:632-651): cv::projectPoints without distortion,
  * then the pixel distance to img[i].  world: n x 3 f64, R: 3x3 f64, t: 3, K: 3x3 (host); err: n f64 (host). */
 uvo_status uvo_reproject_errors(uvo_ctx* c, const double* world, int n, const double* R, const double* t,

@@ -273,7 +273,9 @@ def test_extract_3dpoints_tree_sums_and_ordered_sums_agree(ctx, oracle):
     """extract_3Dpoints' +-3 sigma filter (MU:35-56): the kernel takes the sum and the sum of squares as tree sums, bounds their distance
     from the reference's ordered sums, and lets the ordered chains decide only when some depth lies within that radius of a
     threshold (pose.hip, k_extract3d_b).  Both routes (UVO_EXTRACT3D_SEQ forces the ordered one) and the oracle must keep the same
-    points -- also when all depths are equal (zero variance: the radius test cannot vouch for the tree sums), and for 6 to 3000 points."""
+    points -- also when all depths are equal (zero variance: the radius test cannot vouch for the tree sums), and for 6 to 3000 points.
+    On these inputs no depth is within a few ulps of a threshold, so ANY summation order keeps the same points: this test shows that
+    both routes run, not that the ordered route adds in the reference's order.  That is tests/test_gpu_extract3d_edges.py."""
     import os
     rig, X, x1, x2, P1, P2 = _synthetic_stereo_points(3000, 17, 0.5)
     p4_full = oracle.triangulate(P1, P2, x1, x2)

@@ -4,7 +4,9 @@ match that selects it) and runs extract_3Dpoints (VO:632, VOU:188-232) on the ro
 matches select -- on one small workgroup that keeps a bit per match between its sweeps (extract3d_rows).  What has to hold:
 the loop's results are those of the oracle and do not depend on which route the +-3 sigma filter's sums take (UVO_EXTRACT3D_SEQ
 forces the ordered chains, MU:35-56), nor on the context's capacity (above 8192 keypoints extract_3Dpoints runs as its any-size
-kernel in a launch of its own, reading the same rows through the matches)."""
+kernel in a launch of its own, reading the same rows through the matches).  The depths of these image pairs do not depend on the
+summation order (none lies within a few ulps of a threshold): that the ordered route adds in the reference's order, and that the
+radius test sends every close call there, is tested on chosen rows in tests/test_gpu_extract3d_edges.py."""
 import os
 
 import numpy as np
