@@ -7,7 +7,7 @@
 // Parallelism never changes a result: independent accumulators / matrix entries / the three beta
 // approximations go to different lanes, every floating-point SUM keeps the reference's sequential
 // order inside one lane, and the 12x12 Jacobi sweep runs its 66 rotations in 21 dependency levels
-// (rotations on disjoint row pairs commute exactly).
+// (rotations on disjoint row pairs commute exactly), a sweep starting 12 steps after the one before it.
 #pragma once
 #include "uvo_linalg.h"
 
@@ -169,7 +169,15 @@ __host__ __device__ __forceinline__ void project_point(double X, double Y, doubl
 // rotation that touched row i and the previous one that touched row j, which are (i,j-1)/(i-1,i) and
 // (i-1,j): level(i,j) = i + j.  All rotations of one level touch disjoint rows, so they run on
 // different lanes; levels run in order, which reproduces the sequential result bit for bit.
-// `flag` is one double of shared scratch.  Needs P::nth() >= N/2 lanes.
+// Consecutive sweeps overlap: the last levels of a sweep touch only the high rows and the first levels of
+// the next one only the low rows, so rotation (i,j) of sweep s runs at step T = N*s + i + j.  Every earlier
+// rotation on row i or row j -- (i,j-1) / (i-1,i) and (i-1,j) of the same sweep, (i,N-1) and (j,N-1) of the
+// sweep before -- has a strictly smaller step, the rotations of one step touch disjoint rows, and there are
+// never more than N/2 of them.  A sweep costs N steps instead of 2N-3; only the last one pays all 2N-3.
+// The convergence exit stays exact: when sweep s is known to have rotated nothing, sweep s+1 has already
+// run its first N-3 levels, but on the very state sweep s tested, so its tests failed too and it wrote
+// nothing.  No rotation of a sweep >= max_iter is evaluated.
+// `flag` is two doubles of shared scratch (one `changed` slot per sweep parity).  Needs P::nth() >= N/2 lanes.
 // ------------------------------------------------------------------------------------------
 template <class P, int M, int N>
 __device__ void jacobi_svd_u_levels(typename P::Arr At, typename P::Arr W_out, typename P::Arr W, typename P::Arr flag)
@@ -178,58 +186,68 @@ __device__ void jacobi_svd_u_levels(typename P::Arr At, typename P::Arr W_out, t
     const double minval = DBL_MIN, eps = DBL_EPSILON * 10;
     const int lane = P::tid();
     const int max_iter = M > 30 ? M : 30;
+    constexpr int t_fin = 2*N - 3;                         // last level of a sweep
     for (int i = lane; i < N; i += P::nth()) {
         double sd = 0;
 #pragma unroll
         for (int k = 0; k < M; k++) { double t = At[i*M + k]; sd += t*t; }
         W[i] = sd;
     }
+    if (lane == 0) flag[0] = 0;
     P::sync();
+    // step T = N*s_new + t_new, 1 <= t_new <= N: level t_new of sweep s_new and, on the lanes before it, level t_new + N of sweep s_new - 1
+    int s_new = 0, t_new = 1;
 #pragma unroll 1
-    for (int iter = 0; iter < max_iter; iter++) {
-        if (lane == 0) flag[0] = 0;
-        P::sync();
-#pragma unroll 1
-        for (int t = 1; t <= 2*N - 3; t++) {
-            const int i_lo = t - (N - 1) > 0 ? t - (N - 1) : 0, i_hi = (t - 1) / 2;
-            const int i = i_lo + lane, j = t - i;
-            if (i <= i_hi) {
-                A Ai = At + i*M, Aj = At + j*M;
-                double ai[M], aj[M];
+    for (;;) {
+        const int t_old = t_new + N;
+        const bool has_old = s_new > 0 && t_old <= t_fin;
+        const bool has_new = s_new < max_iter && t_new <= t_fin;
+        const int lo_old = t_old - (N - 1), hi_old = (t_old - 1) / 2;
+        const int lo_new = t_new - (N - 1) > 0 ? t_new - (N - 1) : 0, hi_new = (t_new - 1) / 2;
+        const int n_old = has_old ? hi_old - lo_old + 1 : 0;
+        const bool in_old = lane < n_old;
+        const int i = in_old ? lo_old + lane : lo_new + (lane - n_old);
+        const int j = (in_old ? t_old : t_new) - i;
+        const int slot = (in_old ? s_new - 1 : s_new) & 1;
+        // the slot of sweep s_new + 1 (last read when sweep s_new - 1 completed, at t_new = N - 3) is cleared a step before its first level
+        if (t_new == N && lane == 0) flag[(s_new + 1) & 1] = 0;
+        if (in_old || (has_new && i <= hi_new)) {
+            A Ai = At + i*M, Aj = At + j*M;
+            double ai[M], aj[M];
 #pragma unroll
-                for (int k = 0; k < M; k++) { ai[k] = Ai[k]; aj[k] = Aj[k]; }
-                double a = W[i], p = 0, b = W[j];
+            for (int k = 0; k < M; k++) { ai[k] = Ai[k]; aj[k] = Aj[k]; }
+            double a = W[i], p = 0, b = W[j];
 #pragma unroll
-                for (int k = 0; k < M; k++) p += ai[k]*aj[k];
-                if (!(fabs(p) <= eps*sqrt(a*b))) {
-                    double c, s;
-                    p *= 2;
-                    double beta = a - b, gamma = det_hypot(p, beta);
-                    if (beta < 0) {
-                        double delta = (gamma - beta)*0.5;
-                        s = sqrt(delta/gamma);
-                        c = p/(gamma*s*2);
-                    } else {
-                        c = sqrt((gamma + beta)/(gamma*2));
-                        s = p/(gamma*c*2);
-                    }
-                    a = b = 0;
-#pragma unroll
-                    for (int k = 0; k < M; k++) {
-                        double t0 = c*ai[k] + s*aj[k];
-                        double t1 = -s*ai[k] + c*aj[k];
-                        Ai[k] = t0; Aj[k] = t1;
-                        a += t0*t0; b += t1*t1;
-                    }
-                    W[i] = a; W[j] = b;
-                    flag[0] = 1;
+            for (int k = 0; k < M; k++) p += ai[k]*aj[k];
+            if (!(fabs(p) <= eps*sqrt(a*b))) {
+                double c, s;
+                p *= 2;
+                double beta = a - b, gamma = det_hypot(p, beta);
+                if (beta < 0) {
+                    double delta = (gamma - beta)*0.5;
+                    s = sqrt(delta/gamma);
+                    c = p/(gamma*s*2);
+                } else {
+                    c = sqrt((gamma + beta)/(gamma*2));
+                    s = p/(gamma*c*2);
                 }
+                a = b = 0;
+#pragma unroll
+                for (int k = 0; k < M; k++) {
+                    double t0 = c*ai[k] + s*aj[k];
+                    double t1 = -s*ai[k] + c*aj[k];
+                    Ai[k] = t0; Aj[k] = t1;
+                    a += t0*t0; b += t1*t1;
+                }
+                W[i] = a; W[j] = b;
+                flag[slot] = 1;
             }
-            P::sync();
         }
-        const bool changed = flag[0] != 0;
         P::sync();
-        if (!changed) break;
+        // the sweep this step completes, if any: it ends the loop when it rotated nothing or was the last one allowed
+        const int s_done = t_new == t_fin ? s_new : (has_old && t_old == t_fin) ? s_new - 1 : -1;
+        if (s_done >= 0 && (flag[s_done & 1] == 0 || s_done == max_iter - 1)) break;
+        if (++t_new > N) { t_new = 1; s_new++; }
     }
     for (int i = lane; i < N; i += P::nth()) {
         double sd = 0;
@@ -281,7 +299,7 @@ __device__ void jacobi_svd_u_levels(typename P::Arr At, typename P::Arr W_out, t
 // ------------------------------------------------------------------------------------------
 enum {
     EP_CWS = 0, EP_MTM = 12, EP_D = 156, EP_WT = 168, EP_FLAG = 180, EP_L = 181, EP_RHO = 241,
-    EP_PW0 = 247, EP_SC = 250,      // common scratch: 72 doubles
+    EP_PW0 = 247, EP_SC = 250,      // common scratch: 72 doubles (its first two are the Jacobi's `changed` slots; EP_FLAG is spare)
     EP_BR = 322,                    // per-branch blocks start here
     EPB_CCS = 0, EPB_BETAS = 12, EPB_REP = 16, EPB_RS = 17, EPB_TS = 26, EPB_PC0 = 29, EPB_ABT = 32, EPB_SC = 41,  // scratch: 100
     EPB_SIZE = 141,
@@ -501,6 +519,8 @@ struct Epnp {
     // find_betas_approx_{1,2,3}: cvSolve(L_6xK, Rho, B, CV_SVD) with K = 4, 3, 5 columns picked from L_6x10.
     // Written shape-generic so that lanes 0..2 run the three approximations in one instruction stream.
     // scratch: Ls(30) a(30) v(25) w(5) wt(5) b(5)
+    // (the decomposition is inlined: a function that makes no call of its own saves no registers to scratch memory, which is what
+    // the sequential refit, where the compiler keeps find_betas out of line, otherwise does)
     __device__ void find_betas(int which, Arr L, Arr rho, Arr betas, Arr sc)
     {
         Arr Ls = sc, a = sc + 30, v = sc + 60, w = sc + 85, wt = sc + 90, b = sc + 95;
@@ -512,8 +532,142 @@ struct Epnp {
             }
         // cv::solve(DECOMP_SVD): a = Ls^T, JacobiSVD, back-substitution
         for (int i = 0; i < 6; i++) for (int j = 0; j < K; j++) a[j*6 + i] = Ls[i*K + j];
-        jacobi_svd_rt6(a, w, v, wt, K);
+        [[clang::always_inline]] jacobi_svd_rt6(a, w, v, wt, K);
         svbksb_vec(6, K, w, a, 6, v, K, rho, b);
+        if (which == 1) {
+            if (b[0] < 0) { betas[0] = sqrt(-b[0]); betas[1] = -b[1] / betas[0]; betas[2] = -b[2] / betas[0]; betas[3] = -b[3] / betas[0]; }
+            else          { betas[0] = sqrt(b[0]);  betas[1] = b[1] / betas[0];  betas[2] = b[2] / betas[0];  betas[3] = b[3] / betas[0]; }
+        } else {
+            if (b[0] < 0) { betas[0] = sqrt(-b[0]); betas[1] = (b[2] < 0) ? sqrt(-b[2]) : 0.0; }
+            else          { betas[0] = sqrt(b[0]);  betas[1] = (b[2] > 0) ? sqrt(b[2]) : 0.0; }
+            if (b[1] < 0) betas[0] = -betas[0];
+            betas[2] = which == 2 ? 0.0 : b[3] / betas[0];
+            betas[3] = 0.0;
+        }
+    }
+
+    // find_betas on register arrays of the K = 5 shape: every index is a compile-time constant after unrolling and the
+    // indices >= K are predicated off, so lanes 0..2 still run the three approximations in one instruction stream, without
+    // an LDS round trip per element.  The operations and their order are those of find_betas (jacobi_svd_rt6: the pairs
+    // (i, j) of a sweep in cyclic order, skipping j >= K; svbksb_vec).  A vanishing singular value -- whose row the reference
+    // rebuilds from its random sequence -- is left to find_betas itself: the decision reads the same W the LDS path computes.
+    __device__ __forceinline__ void find_betas_reg(int which, Arr L, Arr rho, Arr betas, Arr sc)
+    {
+        constexpr int m = 6, NMAX = 5;
+        const double minval = DBL_MIN, eps = DBL_EPSILON * 10;
+        const int K = which == 1 ? 4 : which == 2 ? 3 : 5;
+        double a[NMAX][m], v[NMAX][NMAX], w[NMAX], rh[m];
+#pragma unroll
+        for (int j = 0; j < NMAX; j++) {
+            const int col = which == 1 ? (j == 0 ? 0 : j == 1 ? 1 : j == 2 ? 3 : 6) : j;
+#pragma unroll
+            for (int i = 0; i < m; i++) a[j][i] = j < K ? L[10*i + col] : 0.0;
+        }
+#pragma unroll
+        for (int i = 0; i < m; i++) rh[i] = rho[i];
+#pragma unroll
+        for (int i = 0; i < NMAX; i++) {
+            double sd = 0;
+#pragma unroll
+            for (int k = 0; k < m; k++) sd += a[i][k]*a[i][k];
+            w[i] = sd;
+#pragma unroll
+            for (int k = 0; k < NMAX; k++) v[i][k] = k == i ? 1.0 : 0.0;
+        }
+#pragma unroll 1
+        for (int iter = 0; iter < 30; iter++) {
+            bool changed = false;
+#pragma unroll
+            for (int i = 0; i < NMAX - 1; i++)
+#pragma unroll
+                for (int j = i + 1; j < NMAX; j++) {
+                    if (j >= K) continue;
+                    double p = 0;
+#pragma unroll
+                    for (int k = 0; k < m; k++) p += a[i][k]*a[j][k];
+                    if (fabs(p) <= eps*sqrt(w[i]*w[j])) continue;
+                    double c, s;
+                    p *= 2;
+                    const double beta = w[i] - w[j], gamma = det_hypot(p, beta);
+                    if (beta < 0) {
+                        double delta = (gamma - beta)*0.5;
+                        s = sqrt(delta/gamma);
+                        c = p/(gamma*s*2);
+                    } else {
+                        c = sqrt((gamma + beta)/(gamma*2));
+                        s = p/(gamma*c*2);
+                    }
+                    double wa = 0, wb = 0;
+#pragma unroll
+                    for (int k = 0; k < m; k++) {
+                        const double t0 = c*a[i][k] + s*a[j][k];
+                        const double t1 = -s*a[i][k] + c*a[j][k];
+                        a[i][k] = t0; a[j][k] = t1;
+                        wa += t0*t0; wb += t1*t1;
+                    }
+                    w[i] = wa; w[j] = wb;
+                    changed = true;
+#pragma unroll
+                    for (int k = 0; k < NMAX; k++) if (k < K) {
+                        const double t0 = c*v[i][k] + s*v[j][k];
+                        const double t1 = -s*v[i][k] + c*v[j][k];
+                        v[i][k] = t0; v[j][k] = t1;
+                    }
+                }
+            if (!changed) break;
+        }
+        bool tiny = false;
+#pragma unroll
+        for (int i = 0; i < NMAX; i++) {
+            double sd = 0;
+#pragma unroll
+            for (int k = 0; k < m; k++) sd += a[i][k]*a[i][k];
+            w[i] = sqrt(sd);
+            tiny = tiny || (i < K && w[i] <= minval);
+        }
+        if (tiny) { find_betas(which, L, rho, betas, sc); return; }
+        // descending selection sort of the singular values with their rows (W[j] < W[k] as the reference compares them)
+#pragma unroll
+        for (int i = 0; i < NMAX - 1; i++) {
+            if (i >= K - 1) continue;
+            int j = i; double wj = w[i];
+#pragma unroll
+            for (int k = i + 1; k < NMAX; k++) if (k < K && wj < w[k]) { j = k; wj = w[k]; }
+#pragma unroll
+            for (int jj = i + 1; jj < NMAX; jj++) if (j == jj) {
+                double t = w[i]; w[i] = w[jj]; w[jj] = t;
+#pragma unroll
+                for (int k = 0; k < m; k++) { t = a[i][k]; a[i][k] = a[jj][k]; a[jj][k] = t; }
+#pragma unroll
+                for (int k = 0; k < NMAX; k++) { t = v[i][k]; v[i][k] = v[jj][k]; v[jj][k] = t; }
+            }
+        }
+        // svbksb_vec's threshold is over the singular values; the rows are normalised afterwards in the reference too
+        // (W_out is copied before the rows are scaled), and all of them are above minval here
+        double threshold = 0;
+#pragma unroll
+        for (int i = 0; i < NMAX; i++) if (i < K) threshold += w[i];
+        threshold *= DBL_EPSILON * 2;
+#pragma unroll
+        for (int i = 0; i < NMAX; i++) {
+            const double s = w[i] > minval ? 1/w[i] : 0.;
+#pragma unroll
+            for (int k = 0; k < m; k++) a[i][k] *= s;
+        }
+        double b[NMAX] = {0, 0, 0, 0, 0};
+#pragma unroll
+        for (int i = 0; i < NMAX; i++) {
+            if (i >= K) continue;
+            double wi = w[i];
+            if (fabs(wi) <= threshold) continue;
+            wi = 1/wi;
+            double s = 0;
+#pragma unroll
+            for (int j = 0; j < m; j++) s += a[i][j]*rh[j];
+            s *= wi;
+#pragma unroll
+            for (int j = 0; j < NMAX; j++) if (j < K) b[j] = b[j] + s*v[i][j];
+        }
         if (which == 1) {
             if (b[0] < 0) { betas[0] = sqrt(-b[0]); betas[1] = -b[1] / betas[0]; betas[2] = -b[2] / betas[0]; betas[3] = -b[3] / betas[0]; }
             else          { betas[0] = sqrt(b[0]);  betas[1] = b[1] / betas[0];  betas[2] = b[2] / betas[0];  betas[3] = b[3] / betas[0]; }
@@ -672,10 +826,12 @@ struct Epnp {
         EP_STAMP(3);
         Arr mtm = s + EP_MTM, L = s + EP_L, rho = s + EP_RHO, cws = s + EP_CWS, pw0 = s + EP_PW0;
         // cvSVD(MtM, D, Ut, 0, MODIFY_A | U_T): MtM is symmetric so At = MtM^T is MtM itself; rows -> U^T
-        if constexpr (P::kStaged) {                   // block policy: 21 levels x ~8 sweeps of workgroup barriers cost more than they buy
-            if (P::tid() < 64) jacobi_svd_u_levels<WavePolicy, 12, 12>(mtm, s + EP_D, s + EP_WT, s + EP_FLAG);
+        // (the two `changed` slots are the first doubles of the common scratch, which is idle between the barycentric coordinates
+        // and compute_L_6x10: the fixed-size layout, which the parallel refit shares, keeps its size; EP_FLAG is no longer used)
+        if constexpr (P::kStaged) {                   // block policy: a workgroup barrier per step costs more than it buys
+            if (P::tid() < 64) jacobi_svd_u_levels<WavePolicy, 12, 12>(mtm, s + EP_D, s + EP_WT, s + EP_SC);
             P::sync();
-        } else jacobi_svd_u_levels<P, 12, 12>(mtm, s + EP_D, s + EP_WT, s + EP_FLAG);
+        } else jacobi_svd_u_levels<P, 12, 12>(mtm, s + EP_D, s + EP_WT, s + EP_SC);
         const int tid = P::tid();
         EP_STAMP(4);
         compute_L_6x10(mtm, L);
@@ -688,7 +844,9 @@ struct Epnp {
         // ---- the three beta approximations, one per lane: find_betas + gauss_newton + compute_ccs ----
         if (tid < 3) {
             Arr B = br(tid), betas = B + EPB_BETAS, ccs = B + EPB_CCS;
-            find_betas(tid + 1, L, rho, betas, B + EPB_SC);
+            // (the sequential refit keeps the LDS form: inlined into that much larger kernel the register form costs it scratch memory)
+            if constexpr (P::kStaged) find_betas(tid + 1, L, rho, betas, B + EPB_SC);
+            else find_betas_reg(tid + 1, L, rho, betas, B + EPB_SC);
             EP_STAMP(11);
             gauss_newton(L, rho, betas, B + EPB_SC);
             EP_STAMP(12);
@@ -777,7 +935,8 @@ struct Epnp {
             if (rep3 < repN) N = 3;
             Arr B = br(N - 1), ts = B + EPB_TS;
             tvec[0] = ts[0]; tvec[1] = ts[1]; tvec[2] = ts[2];
-            rodrigues_mat2vec(B + EPB_RS, B + EPB_SC, rvec);
+            // inlined here: as a call it takes rvec's address, which puts the caller's rvec into scratch memory (k_pnp_refit)
+            [[clang::always_inline]] rodrigues_mat2vec(B + EPB_RS, B + EPB_SC, rvec);
         }
         P::sync();
         EP_STAMP(9);
