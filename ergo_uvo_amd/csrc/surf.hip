@@ -1383,7 +1383,7 @@ __global__ __launch_bounds__(256) void k_rank_scatter(LaneArgs LA)
 }
 
 // ------------------------------------------------------------------------------------------
-// descriptor: one workgroup per keypoint
+// descriptor
 // ------------------------------------------------------------------------------------------
 struct AreaTab { int sx1, sx2; float a_first, a_mid, a_last; bool has_first, has_last; };
 
@@ -1470,8 +1470,7 @@ __device__ __forceinline__ void describe_tail(const DescArgs& a, int im, int k, 
 // taps all carry a_mid and run in batches of eight loads in flight, and the tail of the last batch is branched over rather than
 // loaded and masked.  Round 2's loop spent 16.7 VALU and 22 SALU instructions per useful tap (address add, two scalar selects
 // per tap for the weight, sixteen loads per batch whatever the tap count): the scalar unit -- one per CU -- was 73 % busy.
-// A lane owns PX adjacent pixels of each of Q chunks of 64 * PX columns: PX = 4 (aligned dword loads; Q = 1..3 covers the 739-pixel
-// windows), PX = 2 and PX = 1 for windows up to 127 / 64 pixels so that small windows do not idle three quarters of the lanes.
+// A lane owns PX = 4 adjacent pixels (an aligned dword load) of each of Q chunks of 256 columns; Q = 1..3 covers the 739-pixel windows.
 // ------------------------------------------------------------------------------------------
 static const int kTapBatch = 16;           // image rows a lane of descriptor64_big has in flight
 // (Round 4, measured and removed: staging a small window's bytes in LDS first -- every load of the workgroup in flight at once -- and
@@ -1491,8 +1490,6 @@ __device__ __forceinline__ float sgpr_f(float v) { return __int_as_float(__built
 struct ColTask { int y0, n, h1, w; float a_first, a_mid, a_last; };      // tap t reads row clamp(y0 - t, 0, h1); n >= 1 taps
 
 template <int PX> __device__ __forceinline__ unsigned px_load(ImgRsrc rs, int voff, int soff);
-template <> __device__ __forceinline__ unsigned px_load<1>(ImgRsrc rs, int voff, int soff) { return __builtin_amdgcn_raw_buffer_load_b8(rs, voff, soff, 0); }
-template <> __device__ __forceinline__ unsigned px_load<2>(ImgRsrc rs, int voff, int soff) { return __builtin_amdgcn_raw_buffer_load_b16(rs, voff, soff, 0); }
 template <> __device__ __forceinline__ unsigned px_load<4>(ImgRsrc rs, int voff, int soff) { return __builtin_amdgcn_raw_buffer_load_b32(rs, voff, soff, 0); }
 
 template <int PX, int Q>
@@ -1574,13 +1571,6 @@ struct AreaCol {
             case 13: taps_static<13>(t); break; case 14: taps_static<14>(t); break;
             default: taps_any(t); break;
             }
-        } else if (Q == 2 && PX == 1) {                 // the small-window part: up to 128 columns a pixel per lane, up to 8 taps
-            switch (t.n) {
-            case 1: taps_static<1>(t); break;   case 2: taps_static<2>(t); break;   case 3: taps_static<3>(t); break;
-            case 4: taps_static<4>(t); break;   case 5: taps_static<5>(t); break;   case 6: taps_static<6>(t); break;
-            case 7: taps_static<7>(t); break;   case 8: taps_static<8>(t); break;
-            default: taps_any(t); break;
-            }
         } else taps_any(t);
     }
     // The sums land at row[(x - start_x) + sh], sh = start_x & 3, which makes every lane's PX floats one aligned LDS store; window
@@ -1634,88 +1624,209 @@ __device__ __forceinline__ ColTask col_task(const AreaTab& ty, int dx, int start
     return t;
 }
 
-// One workgroup per keypoint.  PATCH = cv::resize(WIN, 21x21, INTER_AREA) with
-// WIN[i][j] = img(clamp(start_y - j), clamp(start_x + i)) is evaluated separably, exactly as
-// resizeArea_ does: buf[i][dx] = sum_j WIN[i][j]*alpha_j (lanes run along i = image x, coalesced),
-// then PATCH[dy][dx] = sum_i beta_i*buf[i][dx].  Windows up to kSmallWin = 128 samples (10.5 KB of LDS); larger
-// ones are skipped here and handled by descriptor64_big.
-__device__ __forceinline__ void describe_keypoint(const DescArgs& a, int w, int h, int k, int im)
+// ------------------------------------------------------------------------------------------
+// Small windows (up to kSmallWin = 128 samples): one WAVE per keypoint, the patch by gather.
+//   PATCH[dy][dx] = sat_u8( sum over rows r of dy: beta_r * ( sum over taps c of dx: alpha_c * WIN[r][c] ) ),
+//   WIN[r][c] = img(clamp(start_y - c), clamp(start_x + r)),
+// the inner sum from 0 in tap order, the outer sum from 0 in row order: the expression tree of resizeArea_'s two passes (area_column
+// into the row buffer, then the vertical loop), so every bit is the same, without the row buffer, the shared table and the workgroup
+// barriers between them.  A horizontal value that two destination rows share is evaluated by both.  A lane owns seven of the 441
+// entries, e = lane + 64 j with dy = e % 21 running along the lanes: the 21 lanes of one dx read the same image rows at x a
+// scale apart, so a load instruction touches a few cache lines.  A window's scale bounds an entry's rows and taps alike by
+// nt = ceil(win / 21) + 1 <= 8; the entry's rows are nt adjacent bytes of an image row, fetched per tap as two or three aligned
+// dwords and shifted into place (v_alignbyte), and rows or taps past the entry's own count carry weight +0, which leaves the
+// non-negative sums unchanged.  A window that crosses the image border clamps every pixel's coordinates and loads bytes.
+// ------------------------------------------------------------------------------------------
+static const int kWaveLds = kPatchStride + 128 * (int)sizeof(float);      // a wave's PATCH bytes and descriptor vector
+__device__ __forceinline__ void wave_sync() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
+
+// a table entry as its run of source cells: cell begin + i carries weight wf (i = 0), wm, or wl (i = n - 1); n >= 1
+struct AreaRun { int begin, n; float wf, wm, wl; };
+static_assert(21 * sizeof(AreaRun) <= 128 * sizeof(float), "a wave keeps its runs where its descriptor vector goes");
+__device__ __forceinline__ AreaRun area_run(const AreaTab& t, bool unit)
 {
-    const int tid = threadIdx.x;
+    AreaRun r;
+    const int end = t.has_last ? t.sx2 + 1 : t.sx2;
+    r.begin = t.has_first ? t.sx1 - 1 : t.sx1; r.n = end - r.begin;
+    // resizeArea_'s table entry of cell cc: cc < sx1 ? a_first : (cc < sx2 ? a_mid : a_last), selected on the bit patterns in registers
+    // (written over the floats of the loaded entry the compiler selects between their ADDRESSES and loads the winner: a second round trip)
+    int bf = __float_as_int(t.a_first), bm = __float_as_int(t.a_mid), bl = __float_as_int(t.a_last);
+    asm volatile("" : "+v"(bf), "+v"(bm), "+v"(bl));
+    r.wf = __int_as_float(r.begin < t.sx1 ? bf : (r.begin < t.sx2 ? bm : bl));
+    r.wl = __int_as_float(end - 1 < t.sx1 ? bf : (end - 1 < t.sx2 ? bm : bl));
+    r.wm = __int_as_float(bm);
+    if (unit) r.wf = r.wm = r.wl = 1.f;           // resizeAreaFast_: the block's plain sum (exact in float: at most 36 * 255)
+    return r;
+}
+__device__ __forceinline__ float run_weight(const AreaRun& r, int i) { return i >= r.n ? 0.f : (i == r.n - 1 ? r.wl : (i == 0 ? r.wf : r.wm)); }
+
+// The NT adjacent pixels of an entry's rows, per tap: two or three aligned dwords shifted into place (the bytes sit at any alignment: w may
+// be odd).  A dword that lies outside the buffer -- only where its bytes carry weight 0 -- reads as 0.  CLAMP (the window crosses the image
+// border): the bytes are fetched from column xc = clamp(x0, 0, w - NT) on and row i picks byte clamp(x0 + i, 0, w - 1) - xc of them
+// (v_perm_b32, the selectors once per entry), and the tap's row is clamped.
+template <int NT, bool CLAMP>
+struct RowFetch {
+    int xc, h1; unsigned sel_lo, sel_hi;
+    __device__ __forceinline__ RowFetch(int x0, int w, int h) : xc(x0), h1(h - 1), sel_lo(0), sel_hi(0)
+    {
+        if (CLAMP) {
+            xc = x0 < w - NT ? x0 : w - NT; xc = xc > 0 ? xc : 0;
+#pragma unroll
+            for (int i = 0; i < NT; i++) {
+                int x = x0 + i; x = x > 0 ? x : 0; x = x < w - 1 ? x : w - 1;
+                if (i < 4) sel_lo |= (unsigned)(x - xc) << (8 * i); else sel_hi |= (unsigned)(x - xc) << (8 * (i - 4));
+            }
+        }
+    }
+    // pixels of the rows at image row y, as bytes of lo (rows 0..3) and hi (4..7)
+    __device__ __forceinline__ void load(ImgRsrc rs, int w, int y, unsigned (&d)[3]) const
+    {
+        if (CLAMP) { y = y > 0 ? y : 0; y = y < h1 ? y : h1; }
+        const int oa = (y * w + xc) & ~3;
+        d[0] = __builtin_amdgcn_raw_buffer_load_b32(rs, oa, 0, 0); d[1] = __builtin_amdgcn_raw_buffer_load_b32(rs, oa + 4, 0, 0);
+        d[2] = NT <= 5 ? 0u : __builtin_amdgcn_raw_buffer_load_b32(rs, oa + 8, 0, 0);
+    }
+    __device__ __forceinline__ void bytes(int w, int y, const unsigned (&d)[3], unsigned& lo, unsigned& hi) const
+    {
+        if (CLAMP) { y = y > 0 ? y : 0; y = y < h1 ? y : h1; }
+        const int sh = (y * w + xc) & 3;
+        lo = __builtin_amdgcn_alignbyte(d[1], d[0], sh); hi = __builtin_amdgcn_alignbyte(d[2], d[1], sh);
+        if (CLAMP) { const unsigned l = __builtin_amdgcn_perm(hi, lo, sel_lo), u = __builtin_amdgcn_perm(hi, lo, sel_hi); lo = l; hi = u; }
+    }
+};
+// one entry: the taps of run tab[dx] over the rows of run tab[dy]; taps go up the image from start_y
+template <int NT, bool CLAMP>
+__device__ __forceinline__ float gather_entry(ImgRsrc rs, int w, int h, int start_x, int start_y, const AreaRun* __restrict__ tab, int dx, int dy)
+{
+    constexpr int B = NT <= 5 ? NT : 4;           // taps in flight
+    float H[NT];
+    {
+        const AreaRun c = tab[dx];
+        const RowFetch<NT, CLAMP> f(start_x + tab[dy].begin, w, h);
+        const int y0 = start_y - c.begin;
+#pragma unroll
+        for (int t0 = 0; t0 < NT; t0 += B) {
+            unsigned d[B][3];
+#pragma unroll
+            for (int b = 0; b < B; b++) if (t0 + b < NT) f.load(rs, w, y0 - (t0 + b), d[b]);
+#pragma unroll
+            for (int b = 0; b < B; b++) {
+                const int t = t0 + b;
+                if (t >= NT) continue;
+                unsigned lo, hi;
+                f.bytes(w, y0 - t, d[b], lo, hi);
+                const float alpha = run_weight(c, t);
+#pragma unroll
+                for (int i = 0; i < NT; i++) {
+                    const float p = (float)(int)(((i < 4 ? lo : hi) >> (8 * (i & 3))) & 255u) * alpha;
+                    H[i] = t == 0 ? p : H[i] + p;         // 0.f + v * a == v * a
+                }
+            }
+        }
+    }
+    const AreaRun r = tab[dy];
+    float sum = 0.f;
+#pragma unroll
+    for (int i = 0; i < NT; i++) sum += run_weight(r, i) * H[i];
+    return sum;
+}
+// a lane's seven entries into the wave's PATCH bytes
+template <int NT, bool CLAMP>
+__device__ __forceinline__ void gather_patch(ImgRsrc rs, int w, int h, int lane, int start_x, int start_y, const AreaRun* __restrict__ tab, int iscale, float sc, uint8_t* __restrict__ P)
+{
+    for (int j = 0; j < 7; j++) {
+        const int e = lane + 64 * j, ec = e < 441 ? e : 440;
+        const int dx = ec / 21, dy = ec - dx * 21;
+        const float sum = gather_entry<NT, CLAMP>(rs, w, h, start_x, start_y, tab, dx, dy);
+        int result;
+        if (iscale == 0) result = sat_u8(sum);
+        else {
+            // resizeAreaFast_: integer block sums; 2x2 -> (sum+2)>>2, else saturate(sum * (1.f/area))
+            const int isum = (int)sum;
+            if (iscale == 2) result = (isum + 2) >> 2;
+            else result = sat_u8(isum * sc);          // sc = 1.f / (iscale * iscale)
+        }
+        if (e < 441) P[dy * 21 + dx] = (uint8_t)result;
+    }
+}
+// describe_tail's element d of the descriptor row, from the wave's PATCH bytes: the cell's 25 gradients in (y, x) order
+template <bool EXT>
+__device__ __forceinline__ float cell_sum(const uint8_t* __restrict__ P, const float* __restrict__ DW, int d)
+{
+    const int cell = EXT ? d >> 3 : d >> 2, comp = EXT ? d & 7 : d & 3, ci = cell >> 2, cj = cell & 3;
+    float acc = 0.f;
+#pragma unroll 1
+    for (int yy = 0; yy < 5; yy++)
+#pragma unroll
+        for (int xx = 0; xx < 5; xx++) {
+            const int i = ci * 5 + yy, j = cj * 5 + xx;
+            const int p00 = P[i * 21 + j], p01 = P[i * 21 + j + 1], p10 = P[i * 21 + 21 + j], p11 = P[i * 21 + 21 + j + 1];
+            const float dw = DW[i * 20 + j];
+            const float tx = (p01 - p00 + p11 - p10) * dw;
+            const float ty = (p10 - p00 + p11 - p01) * dw;
+            if (!EXT) {
+                const float t = (comp & 1) ? ty : tx;
+                acc += (comp & 2) ? (float)fabs(t) : t;
+            } else {
+                // surf.cpp, extended: (sum tx, sum |tx|) over ty >= 0 and over ty < 0, then (sum ty, sum |ty|) over tx >= 0 and over tx < 0
+                const float val = comp < 4 ? tx : ty, sel = comp < 4 ? ty : tx;
+                const bool take = (comp & 2) ? sel < 0 : sel >= 0;
+                if (take) acc += (comp & 1) ? (float)fabs(val) : val;
+            }
+        }
+    return acc;
+}
+// keypoint k of image im by the calling wave; lds: the wave's kWaveLds bytes
+__device__ __forceinline__ void describe_keypoint(const DescArgs& a, ImgRsrc rs, int w, int h, int k, int im, int lane, unsigned char* __restrict__ lds)
+{
     const uvo_keypoint kp = a.kps[im][k];
     const float size = kp.size;
     const float s = size * 1.2f / 9.0f;
     const int win_size = (int)((20 + 1) * s);
     if (win_size > kSmallWin) return;                  // large windows: descriptor64_big
-    extern __shared__ __align__(16) unsigned char smem_desc[];
-    float* buf = reinterpret_cast<float*>(smem_desc);                 // [21][bp]
-    const int bp = (win_size + 3) | 1;                                // odd pitch: the vertical pass walks 21 columns bank-conflict-free (+3: area_column's alignment shift)
-    __shared__ AreaTab tab[21];
-    __shared__ int PATCH[21][21];
-    const uint8_t* __restrict__ img = a.img[im];
+    uint8_t* P = lds;
+    float* vec = reinterpret_cast<float*>(lds + kPatchStride);
     const float win_offset = -(float)(win_size - 1) / 2;
-    const int start_x = cv_round_f(kp.x + win_offset);
-    const int start_y = cv_round_f(kp.y - win_offset);
-    // (computed here rather than looked up in a.tabs / a.iscale: a second dependent fetch costs this latency-bound kernel more)
-    const double inv_scale = (double)21 / win_size;
-    const double scale = 1. / inv_scale;
-    const int iscale = cv_round_d(scale);
-    const bool area_fast = fabs(scale - iscale) < DBL_EPSILON;
-
-    if (area_fast) {
-        // resizeAreaFast_: integer block sums; 2x2 -> (sum+2)>>2, else saturate(sum * (1.f/area))
-        for (int o = tid; o < 441; o += 256) {
-            int dy = o / 21, dx = o - dy * 21;
-            int sum = 0;
-            for (int sx = 0; sx < iscale; sx++) {
-                int y = start_y - (dx * iscale + sx); y = y > 0 ? y : 0; y = y < h - 1 ? y : h - 1;
-                for (int sy = 0; sy < iscale; sy++) {
-                    int x = start_x + dy * iscale + sy; x = x > 0 ? x : 0; x = x < w - 1 ? x : w - 1;
-                    sum += img[(size_t)y * w + x];
-                }
-            }
-            int result;
-            if (iscale == 2) result = (sum + 2) >> 2;
-            else { float sc = 1.f / (iscale * iscale); result = sat_u8(sum * sc); }
-            PATCH[dy][dx] = result;
+    const int start_x = sgpr_i(cv_round_f(kp.x + win_offset));
+    const int start_y = sgpr_i(cv_round_f(kp.y - win_offset));
+    // (never negative, whatever the record holds: after a capacity overflow, which the host reports, the list's tail is not written, and the
+    // window size indexes the tables)
+    const int ws = sgpr_i(win_size > 0 ? win_size : 0);
+    // the window size's resize table as runs, in the wave's LDS (where the descriptor vector goes later), and its integer scale
+    // (non-zero: resizeAreaFast_)
+    const int iscale = sgpr_i(a.iscale[ws]);
+    AreaRun* tab = reinterpret_cast<AreaRun*>(vec);
+    int el = lane; asm volatile("" : "+v"(el));        // (what a keypoint derives from the lane is computed per keypoint, not kept in registers across the loop)
+    if (el < 21) tab[el] = area_run(a.tabs[ws * 21 + el], iscale != 0);
+    wave_sync();
+    const float sc = sgpr_f(1.f / (iscale * iscale));
+    const int nt = (ws + 20) / 21 + 1;                 // rows and taps of an entry: at most ceil(scale) + 1
+    const bool inside = start_x >= 0 && start_x + ws <= w && start_y <= h - 1 && start_y - (ws - 1) >= 0;
+    if (inside) {
+        switch (nt) {
+        case 4: gather_patch<4, false>(rs, w, h, lane, start_x, start_y, tab, iscale, sc, P); break;
+        case 5: gather_patch<5, false>(rs, w, h, lane, start_x, start_y, tab, iscale, sc, P); break;
+        case 6: gather_patch<6, false>(rs, w, h, lane, start_x, start_y, tab, iscale, sc, P); break;
+        case 7: gather_patch<7, false>(rs, w, h, lane, start_x, start_y, tab, iscale, sc, P); break;
+        case 8: gather_patch<8, false>(rs, w, h, lane, start_x, start_y, tab, iscale, sc, P); break;
+        default: gather_patch<3, false>(rs, w, h, lane, start_x, start_y, tab, iscale, sc, P); break;      // nt <= 3
         }
     } else {
-        if (tid < 21) tab[tid] = area_tab(tid, win_size, scale);
-        __syncthreads();
-        // horizontal pass of resizeArea_ (over WIN columns j = image rows), lanes along WIN rows i = image x: wave wv takes the
-        // destination columns dx = wv, wv + 4, .. through the shared column core (round 3): a column's taps are the same for
-        // every lane, so row clamps, offsets and weights are scalar work and a lane's pixel costs cvt + mul + add.  (Round 2 ran
-        // a column per half-wave with per-lane tap parameters: ~33 VALU instructions per load.)
-        {
-            const int wv = sgpr_i(tid >> 6), lane = tid & 63;
-            const AreaTab ty = tab[lane % 21];
-            const int xlo = start_x > 0 ? start_x : 0, xhi = start_x + win_size < w ? start_x + win_size : w;
-            const ImgRsrc rs = img_rsrc(img, w * h);
-            const int sx = sgpr_i(start_x), sy = sgpr_i(start_y), ws = sgpr_i(win_size);
-            if (xhi <= xlo) { for (int it = tid; it < 21 * bp; it += 256) buf[it] = 0.f; }        // cannot happen for a keypoint inside the image
-            else if (xhi - xlo <= 64) {
-                AreaCol<1, 1> c(rs, w, h, lane, xlo);
-                for (int dx = wv; dx < 21; dx += 4) { const ColTask ct = col_task(ty, dx, sy, w, h); c.taps(ct); c.store(lane, sx, ws, buf + dx * bp); }
-            } else {
-                AreaCol<1, 2> c(rs, w, h, lane, xlo);
-                for (int dx = wv; dx < 21; dx += 4) { const ColTask ct = col_task(ty, dx, sy, w, h); c.taps(ct); c.store(lane, sx, ws, buf + dx * bp); }
-            }
-        }
-        __syncthreads();
-        // vertical pass (over WIN rows i)
-        for (int o = tid; o < 441; o += 256) {
-            int dy = o / 21, dx = o - dy * 21;
-            const AreaTab ty = tab[dy];
-            const float* col = buf + dx * bp + (start_x & 3);
-            float sum = 0.f;
-            if (ty.has_first) sum += ty.a_first * col[ty.sx1 - 1];                    // the loop of resizeArea_'s table, split by weight
-            for (int r = ty.sx1; r < ty.sx2; r++) sum += ty.a_mid * col[r];
-            if (ty.has_last) sum += ty.a_last * col[ty.sx2];
-            PATCH[dy][dx] = sat_u8(sum);
-        }
+        if (nt <= 5) gather_patch<5, true>(rs, w, h, lane, start_x, start_y, tab, iscale, sc, P);
+        else gather_patch<8, true>(rs, w, h, lane, start_x, start_y, tab, iscale, sc, P);
     }
-    __syncthreads();
-    describe_tail(a, im, k, PATCH);
+    wave_sync();
+    // describe_tail, by one wave: a lane per element (extended: two), then the ordered double sum by every lane alike
+    const int dsize = a.extended ? 128 : 64;
+    int tl = lane; asm volatile("" : "+v"(tl));        // (what the tail derives from the lane is computed here, not kept in registers across the gather)
+    if (!a.extended) vec[tl] = cell_sum<false>(P, a.DW, tl);
+    else for (int d = tl; d < 128; d += 64) vec[d] = cell_sum<true>(P, a.DW, d);
+    wave_sync();
+    double square_mag = 0;
+    for (int kk = 0; kk < dsize; kk++) square_mag += vec[kk] * vec[kk];
+    const float scale = (float)(1. / (sqrt(square_mag) + FLT_EPSILON));
+    for (int d = tl; d < dsize; d += 64) a.desc[im][(size_t)k * dsize + d] = vec[d] * scale;
+    wave_sync();                                       // the wave's next keypoint reuses the buffers
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1935,7 +2046,7 @@ __global__ __launch_bounds__(256) void k_descriptor_rot(DescArgs a, int w, int h
 // The LDS does not grow with the window: a destination row only needs the window rows i of its own taps, staged kWideRows at a
 // time -- buf[dx][i] = sum over the taps j of column dx of WIN[i][j] * alpha_j (resizeArea_'s table order; integer block sums where
 // the scale is an integer to within DBL_EPSILON: resizeAreaFast_) -- and thread dx accumulates PATCH[dy][dx] over them in order.
-// The tables are evaluated here in double (area_tab, as describe_keypoint does).  ROT: thread i walks its row's running double
+// The tables are evaluated here in double (area_tab).  ROT: thread i walks its row's running double
 // sums over the whole window, as k_descriptor_rot does; a row's float start position is carried from row 0 by thread 0.
 static const int kWideRows = 128;
 template <bool ROT>
@@ -2099,16 +2210,15 @@ __global__ __launch_bounds__(256) void k_descriptor_wide_finish(DescArgs a, cons
     }
 }
 
-// small windows: one workgroup per keypoint (block bx of nbx of the launch's small-window part)
+// small windows: a wave per keypoint, four keypoints per workgroup (block bx of nbx of the launch's small-window part); the waves
+// walk the list when the grid is smaller than it.  No workgroup barrier: a wave that draws a large window goes on to its next keypoint.
 __device__ __forceinline__ void descriptor64_small(const DescArgs& a, int w, int h, int bx, int nbx, int im)
 {
+    __shared__ __align__(16) unsigned char s_wave[4][kWaveLds];
+    const int lane = threadIdx.x & 63, wv = sgpr_i(threadIdx.x >> 6);
     const int n = *a.n[im];
-    // one workgroup per keypoint when the grid has max_kpts of them (measured faster than a smaller grid walking the list:
-    // the hardware hands the next keypoint to whichever CU frees up); the loop covers smaller grids
-    for (int k = bx; k < n; k += nbx) {
-        describe_keypoint(a, w, h, k, im);
-        __syncthreads();                     // the LDS buffers are reused by the next keypoint
-    }
+    const ImgRsrc rs = img_rsrc(a.img[im], (w * h + 3) & ~3);      // whole dwords: the image starts 16-byte aligned (surf_upload)
+    for (int k = 4 * bx + wv; k < n; k += 4 * nbx) describe_keypoint(a, rs, w, h, k, im, lane, s_wave[wv]);
 }
 // Large windows (up to 739 samples: the keypoints of octaves 2 and 3).  One keypoint is 21 independent tasks, one per
 // destination column dx of the area resize: a task needs only the ~win/21 image rows of that column's taps, computes
@@ -2266,9 +2376,12 @@ __device__ __forceinline__ void descriptor64_big(const DescArgs& a, int w, int h
         __builtin_amdgcn_wave_barrier();
     }
 }
-// Both window classes in one launch: blocks [0, nbig) are the persistent waves of the large-window tasks, the rest take one
-// small-window keypoint each.  The large-window part stalls on its per-tap dependency chains, the small-window part on its
-// barriers; resident together they keep the VALU busier than one after the other (and a launch is saved).
+// Both window classes in one launch: blocks [0, nbig) are the persistent waves of the large-window tasks, the rest take four
+// small-window keypoints each, one per wave.  Neither part has a workgroup barrier; both stall on dependent memory round trips
+// (the large-window part on its per-tap chains, a small-window wave on its seven entries' fetches), and resident together they
+// keep the VALU busier than one after the other (and a launch is saved).  A small-window keypoint used to hold a whole workgroup
+// -- four waves parked through seven barriers, 10 us alone and 13.9 us beside the large-window waves; as one wave it holds a
+// quarter of the slots: 56.7 -> 50.5 us for the launch (the large-window part alone: 41.8; profiles/surf_small_window_waves.json).
 // (8 waves per SIMD: the compiler would settle at 66 VGPRs = 7 waves)
 // The lane's arguments arrive as a one-entry array that the kernel indexes with yy >> 1 (0: a launch has at most two images).  With the
 // fields at constant offsets of the argument block the compiler loads them at entry, spills 46 SGPRs instead of 37 and needs 24 bytes of
@@ -2601,19 +2714,20 @@ static uvo_status surf_describe(Ctx* c, const LaneArgs& LA, int nimg)
     const bool wide = c->sh->surf_detection_path == 1 || widest_window(c, w, h) > kMaxWin;
     const int kWideGrid = 128;                             // keypoints walked side by side (x 21 destination rows)
     if (c->p.SURF_UPRIGHT) {
-        const size_t lds_small = sizeof(float) * 21 * ((kSmallWin + 3) | 1), lds_big = sizeof(float) * 4 * kBigRow;
+        const size_t lds_big = sizeof(float) * 4 * kBigRow;          // dynamic LDS: the large-window part's row buffers (the small-window part's is static)
         // large-window part: 8192 persistent waves (1024 workgroups per image) for the tasks (512: 80 us, 768..2048: 66-69 us)
         const int nbig = 1024;
-        // small-window part: a workgroup per keypoint -- as many as the last pair whose counts reached the host had, plus a quarter
-        // (the workgroups walk the list when there are more: any grid gives the same descriptors); max_kpts of them before that
+        // small-window part: a wave per keypoint, four to a workgroup -- as many waves as the last pair whose counts reached the host had
+        // keypoints, plus a quarter (the waves walk the list when there are more: any grid gives the same descriptors); max_kpts of them before that
         const int hint = c->sh->kp_hint;
         int nsmall = hint > 0 ? ((hint + hint / 4 + 255) & ~255) : c->cap;
         nsmall = nsmall < 512 ? 512 : (nsmall > c->cap ? c->cap : nsmall);
+        nsmall = (nsmall + 3) / 4;
         // Measured, descriptor launch alone: every image's large-window workgroups first, then the small-window workgroups with the
         // images alternating, on the hint-sized grid (what k_descriptor64 does): 57.2 us; image by image on max_kpts workgroups
         // (rounds 2-4): 60.5; large-window workgroups first, small-window workgroups image by image: 59.7; 512 / 2048 large-window
         // workgroups per image: 58.1 / 58.9
-        hipLaunchKernelGGL(k_descriptor64, dim3((nbig + nsmall) * nimg), dim3(256), lds_small > lds_big ? lds_small : lds_big, c->stream, DescLane{ { LA } }, w, h, nbig, nimg);
+        hipLaunchKernelGGL(k_descriptor64, dim3((nbig + nsmall) * nimg), dim3(256), lds_big, c->stream, DescLane{ { LA } }, w, h, nbig, nimg);
         hipLaunchKernelGGL(k_descriptor64_big_finish, dim3(1024, nimg), dim3(256), 0, c->stream, LA);
         if (wide) {
             hipLaunchKernelGGL(k_descriptor_wide<false>, dim3(21 * kWideGrid, nimg), dim3(256), 0, c->stream, LA.da, w, h, LA.patch);
